@@ -8,7 +8,7 @@ configs[2], the configuration the metric is quoted on), inputs resident in HBM w
 timed region starts (they are regenerated on the device before every step, outside the
 timed region, because the solve overwrites A and B as the reference does).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--order 16384] [--problem gep|sep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--order 16384] [--problem gep|sep] [--dump-outputs DIR]
 
 For N > 1 there is one rank per GPU: either the driver launches them with torch.distributed.run, or --
 when no RANK is in the environment -- `python bench.py --gpus N` starts them itself as fresh child
@@ -47,6 +47,11 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                       (smaller N) of the same generator, rank 0 at N=1 only, with the GPU path timed
                       at that SAME order beside it ("gpu_same_order").
 Every extra runs after the headline exists and is caught on its own: none of them can take the line down.
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's, before any extra runs) as float64 .npy
+files: the eigenvalues, and a fixed, seeded sample of the eigenvector columns (all of them when they fit) with
+their column indices, at most 64 MB in all (dump_outputs()).  The inputs come from the seeded generator, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import numpy as np
@@ -378,6 +383,38 @@ def q2_traffic_record(n, ncols):
     return None, why
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 20261015            # the eigenvector columns sampled when they do not all fit
+
+
+def dump_outputs(out_dir, w, take_columns, n, cols):
+    """Writes a solve's outputs as a caller receives them: eigenvalues.npy (w), and eigenvectors.npy (n x m,
+    column c = eigenvector eigenvector_index[c] of the solve) with eigenvector_index.npy.  The solve holds
+    len(cols) eigenvector columns of length n, cols[j] the global index of its column j; take_columns(pick)
+    returns its columns pick as a host array of len(pick) rows.  When all columns do not fit in
+    DUMP_LIMIT_BYTES, m of them are drawn by a generator seeded with DUMP_SEED: the same n and cols give the same
+    sample in every run and every build.  Returns the file sizes."""
+    os.makedirs(out_dir, exist_ok=True)
+    nc = len(cols)
+    room = DUMP_LIMIT_BYTES - 3 * 4096 - 8 * len(w)       # (4 KB per file leaves room for the .npy headers)
+    m = min(nc, max(0, room // (8 * (n + 1))))
+    if m == nc:
+        pick = np.arange(nc)
+    else:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(nc, size=m, replace=False))
+    Z = take_columns(pick)                         # m x n: row c is eigenvector cols[pick[c]]
+    files = {"eigenvalues": np.asarray(w, dtype=np.float64),
+             "eigenvectors": np.ascontiguousarray(Z.T, dtype=np.float64),
+             "eigenvector_index": np.asarray(cols, dtype=np.float64)[pick]}
+    sizes = {}
+    for name, arr in files.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, arr)
+        sizes[name + ".npy"] = os.path.getsize(path)
+    assert sum(sizes.values()) <= DUMP_LIMIT_BYTES, sizes
+    return sizes
+
+
 _cpu_child = None    # the CPU baseline's mpiexec (leader of its own session) while it runs
 
 
@@ -443,7 +480,7 @@ def grid_probe(args, lib, solver, dist, torch, dev, cdev, rank, world, n, proble
     import threading
     from eigenkernel_amd import descriptor as dsc
     NB = 64
-    K, W = min(args.steps, 8), max(1, min(args.warmup, 2))      # a probe, not the headline: bounded whatever --steps says
+    K, W = args.steps, args.warmup      # --distribution auto may make this the headline: the run's own step counts
     res = {"distribution": "1 x %d process grid, replicated inputs; PDPOTRF/PDSYGST (from 3 ranks on) and PDSYTRD "
                            "distributed over %s, eigenvector columns sharded"
                            % (world, "the HOST communicator (one-GPU rehearsal: timings mean nothing)"
@@ -681,10 +718,15 @@ def main():
     ap.add_argument("--budget-seconds", type=int, default=480,
                     help="wall-clock budget of the whole run: the CPU baseline at the headline order (minutes on 64 cores) is "
                          "only started if its projection fits what is left")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's eigenvalues and a seeded "
+                         "sample of its eigenvector columns, float64 .npy, at most 64 MB) under DIR")
     ap.add_argument("--dry-launch", action="store_true",
                     help="start the ranks, join them in a gloo group, count them and print a line with n_gpus = the "
                          "number of ranks that answered -- no GPU call anywhere (the CPU test of the self-launch)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config:
         args.n, args.problem, args.n_vec = CONFIGS[args.config]
 
@@ -814,6 +856,11 @@ def main():
     # reference's own acceptance quantities (verifier.f90:75-204, 233-330) evaluated on the GPU
     # against freshly regenerated inputs (the solve destroyed its copies): outside the timed region.
     w = dw.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # dZ is column-major: row j of the tensor is eigenvector column j
+        sizes = dump_outputs(args.dump_outputs, w[:n_vec], lambda pick: dZ[torch.from_numpy(pick).to(dev)].cpu().numpy(),
+                             n, my_cols if columns else np.arange(n_vec))
+        sys.stderr.write("[bench] outputs of the last timed step: %s under %s\n" % (sizes, args.dump_outputs))
     assert (w[1:n_vec] >= w[:n_vec - 1]).all() and abs(w[:n_vec]).max() < 1e6
     parity = None
     if not args.no_parity_check and nc_loc > 0:

@@ -188,6 +188,32 @@ def test_device_resident_solve_and_synth(hip, oracle):
         lib.ek_hip_free(p)
 
 
+def test_bench_dumps_the_eigenpairs_of_its_last_timed_step(oracle, tmp_path):
+    """`bench.py --dump-outputs DIR` on one GPU: the line counts exactly --steps timed solves, and DIR holds the
+    eigenvalues and (all of them fit at this order) the eigenvectors of the seeded pencil, in column order."""
+    import json
+    import subprocess
+    import sys
+    import scipy.linalg as sl
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 1024
+    out = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+                          "--order", str(n), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-path",
+                          "--no-other-configs", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1
+    w = np.load(tmp_path / "out" / "eigenvalues.npy")
+    Z = np.load(tmp_path / "out" / "eigenvectors.npy")
+    assert np.array_equal(np.load(tmp_path / "out" / "eigenvector_index.npy"), np.arange(n))
+    assert w.dtype == Z.dtype == np.float64 and w.shape == (n,) and Z.shape == (n, n)
+    A, B = oracle.synth_matrix(n, 1), oracle.synth_matrix(n, 2)
+    w_ref = sl.eigh(A, B, eigvals_only=True)
+    assert np.abs(w - w_ref).max() <= 4 * n * EPS * np.abs(w_ref).max()
+    _check_pairs(A, B, w, Z)
+
+
 @pytest.mark.parametrize("name,n,gep", [("gep_n256_np4", 256, True), ("sep_n256_np4", 256, False),
                                          ("gep_n1000_np4", 1000, True)])
 def test_hip_vs_scalapack_goldens(hip, oracle, golden_dir, name, n, gep):

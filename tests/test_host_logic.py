@@ -26,6 +26,11 @@ from eigenkernel_amd.matrix_io import _fortran_e26
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# PyTorch is never imported into this (pytest) process.  Its libraries ask for the HIP runtime it bundles by a file
+# name that does not match the soname of the system runtime libek_hip.so loads, so both runtimes would end up in
+# one process; once the GPU tests of the same session have initialised the system's, the process aborts at exit.
+# What needs torch runs in a child process: the gloo ranks (the standard library's spawn) and the GPU probe.
+
 
 def test_layout_procs_matches_reference_rule():
     """processes.f90:56-65; SURVEY.md section 5: 1->1x1, 2->1x2, 4->2x2, 8->2x4."""
@@ -181,7 +186,7 @@ def _bench_agg_worker(rank, world, port, q):
 def test_multi_rank_aggregation_gloo():
     """bench.py --gpus N: independent problems are sharded over ranks with no data-path
     collective; value = all units / max-over-ranks time (world_size 2, gloo)."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp           # not torch.multiprocessing: see the note at the top of this file
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -240,7 +245,7 @@ def _grid_worker(rank, world, port, q):
 def test_column_sharding_of_eigenvectors_gloo():
     """Replicated-input mode on a 1 x P grid: the ranks' eigenvector columns partition
     [0, n_vec) with no overlap (world_size 2, gloo)."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp           # not torch.multiprocessing: see the note at the top of this file
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -370,7 +375,7 @@ def _gather_worker(rank, world, port, q):
 
 def test_gather_matrix_gloo_world2():
     """The exchange step of ek_hip_solve for distributed inputs, two real ranks over gloo."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp           # not torch.multiprocessing: see the note at the top of this file
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -432,6 +437,30 @@ def test_bench_configs_and_flop_counts_follow_baseline_and_survey():
     assert abs(bench.flops(1, 16384, 16384) - 3.079e13) <= 1e10        # GEP full: 7 N^3
     assert abs(bench.flops(1, 16384, 1024) - 1.255e13) <= 1e10         # partial GEP, k = 1024
     assert bench.FP64_MFMA_PEAK_TFLOPS == 78.6 and bench.HBM_PEAK_GBS == 8000.0
+
+
+def test_bench_dump_outputs_is_a_bounded_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files, 64 MB at most; column c of eigenvectors.npy is the
+    eigenvector whose global index is eigenvector_index.npy[c]; the sample is the same in every run."""
+    import bench
+    n, nc = 4096, 3000                                # 96 MB of eigenvectors: a sample has to be drawn
+    cols = np.arange(nc) * 3 + 1                      # global indices of the columns held (a grid rank's share)
+    Zt = np.arange(nc, dtype=np.float64)[:, None] * np.ones(n)[None, :]       # row j (column j of Z) holds j
+    take = lambda pick: Zt[pick]                      # noqa: E731
+    w = np.linspace(0.4, 2.6, nc)
+    sizes = bench.dump_outputs(str(tmp_path / "a"), w, take, n, cols)
+    assert sorted(sizes) == ["eigenvalues.npy", "eigenvector_index.npy", "eigenvectors.npy"]
+    assert sum(sizes.values()) <= 64 << 20
+    Z, idx = np.load(tmp_path / "a" / "eigenvectors.npy"), np.load(tmp_path / "a" / "eigenvector_index.npy")
+    assert Z.dtype == idx.dtype == np.float64 and Z.shape == (n, len(idx)) and 1000 < len(idx) < nc
+    assert np.array_equal(np.load(tmp_path / "a" / "eigenvalues.npy"), w)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(cols[(Z[0]).astype(int)], idx)
+    bench.dump_outputs(str(tmp_path / "b"), w, take, n, cols)
+    for name in sizes:
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
+    # all columns when they fit
+    bench.dump_outputs(str(tmp_path / "c"), w[:64], take, n, cols[:64])
+    assert np.array_equal(np.load(tmp_path / "c" / "eigenvector_index.npy"), cols[:64])
 
 
 def test_fortran_mpi_host_argument_contract(tmp_path):
@@ -515,11 +544,9 @@ def test_bench_host_path_child_reports_instead_of_raising():
     bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
     out = bench.host_path_child(1, 256, 256, timeout=120.0)
     assert isinstance(out, dict)
-    try:
-        import torch
-        has_gpu = torch.cuda.is_available()
-    except Exception:
-        has_gpu = False
+    import subprocess
+    has_gpu = subprocess.run([sys.executable, "-c", "import sys, torch; sys.exit(0 if torch.cuda.is_available() else 1)"],
+                             capture_output=True).returncode == 0       # asked in a child: see the note at the top
     if has_gpu:
         assert "error" in out or out.get("seconds", 0) > 0
     else:
