@@ -5,6 +5,8 @@
 // kernels on one HIP stream and hands results back.  No numerical work happens on the CPU.
 #include "ek_api_internal.h"
 
+#include <cfloat>
+
 namespace ek {
 namespace api {
 
@@ -239,7 +241,7 @@ using namespace ek::api;
 
 extern "C" {
 
-int ek_hip_version(void) { return 2; }
+int ek_hip_version(void) { return 3; }
 
 int ek_hip_init(int device) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -492,6 +494,42 @@ int ek_hip_stedc(int n, double *d, double *e, double *Z_loc, const int desc_Z[9]
   int info = 0;
   rc = fetch_info(&info); if (rc) return rc;
   return info;
+}
+
+int ek_hip_stebz(int n, const double *d, const double *e, int il, int iu, double *w) {
+  if (n < 0) return -1;
+  if (n > 0 && !d) return -2;
+  if (n > 1 && !e) return -3;
+  if (n > 0 && (il < 1 || il > n)) return -4;
+  if (n > 0 && (iu < il || iu > n)) return -5;
+  if (n > 0 && !w) return -6;
+  double tnorm = 0.0;                       // (NaN / Inf: illegal value of d or e, as for the whole path's A)
+  for (int i = 0; i < n; ++i) { const double v = fabs(d[i]); if (!(v <= DBL_MAX)) return -2; if (v > tnorm) tnorm = v; }
+  for (int i = 0; i + 1 < n; ++i) { const double v = fabs(e[i]); if (!(v <= DBL_MAX)) return -3; if (v > tnorm) tnorm = v; }
+  int rc = ensure_init(); if (rc) return rc;
+  if (n == 0) return 0;
+  // entries far from 1 are scaled by a power of two (exact) so that e^2 and the pivots stay in range
+  int ex = 0;
+  if (tnorm > 0.0) { (void)frexp(tnorm, &ex); ex = (ex > 400 || ex < -400) ? -ex : 0; }
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n), m = iu - il + 1;
+  void *ws;
+  rc = workspace(al(stebz_work_bytes(n)) + 3 * al((size_t)ld * 8), &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  char *work = a.get<char>(stebz_work_bytes(n));
+  double *dd = a.get<double>(ld), *de = a.get<double>(ld), *dw = a.get<double>(ld);
+  EK_HIP_CHECK(hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemsetAsync(de, 0, (size_t)ld * 8, s));
+  if (n > 1) EK_HIP_CHECK(hipMemcpyAsync(de, e, (size_t)(n - 1) * 8, hipMemcpyHostToDevice, s));
+  if (ex != 0) { scale_vector(s, n, ldexp(1.0, ex), dd); scale_vector(s, n, ldexp(1.0, ex), de); }
+  stebz(s, n, dd, de, il, iu, dw, work);
+  if (ex != 0) scale_vector(s, m, ldexp(1.0, -ex), dw);
+  EK_HIP_CHECK(hipGetLastError());
+  EK_HIP_CHECK(hipMemcpyAsync(w, dw, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
 }
 
 int ek_hip_ormtr(int n, int ncols, const double *A_loc, const int desc_A[9], const double *tau,

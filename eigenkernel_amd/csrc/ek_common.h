@@ -281,6 +281,13 @@ void stedc(hipStream_t s, int n, const double *d, const double *e, double *w, do
            int ldz, void *work, int *d_info, const StedcSelect *sel = nullptr, double *d_flops = nullptr,
            double *wscratch = nullptr, const StedcTeam *team = nullptr);
 
+// ---------------------------------------------------------------- tridiagonal eigenvalues by bisection (ek_stebz.hip)
+// w(0 : iu-il+1) <- eigenvalues il..iu (1-based, ascending) of the tridiagonal d(n), e(n-1): DSTEBZ with RANGE = 'I'.
+// The value of index k is bit-identical whatever [il, iu] is asked for; work >= stebz_work_bytes(n), 256-byte aligned.
+size_t stebz_work_bytes(int n);
+void stebz(hipStream_t s, int n, const double *d, const double *e, int il, int iu, double *w, void *work);
+int stebz_set_lanes(int lanes);                    // lanes per index: 1, 2, 4, 8 or 16 (<= 0: the default, 4)
+
 // ---------------------------------------------------------------- back-transformation (ek_ormtr.hip)
 size_t ormtr_work_bytes(int n, int ncols, int ncols_global = -1);   // ncols_global: columns of the whole Z (a grid cell holds ncols of them)
 // Z(:, 0:ncols) <- Q Z with Q = H(0)...H(n-2) given by explicit V (see sytrd_lower) and tau.

@@ -374,8 +374,12 @@ struct PathPlan {
   size_t mat, zmat, x0, x1, sygst_dbl, potrf_wb, wb_sytrd, wb_stedc, wb_ormtr, wb_sy2sb, wb_sb2st, wb_rec, wb_q1prep,
          trsm_work, inv256, total;
 };
+// values_only: the plan of an eigenvalues-only call (ek_hip_eigenvalues*): the stages up to the tridiagonalisation, then
+// the bisection -- no eigenvector array, no records of Q2, no scratch of Q1, of the D&C or of the back-transformation;
+// X1 is then [phase A | the bisection's scratch] (never distributed).
 PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /* 0: not distributed */,
-                   size_t exch_bytes = 0 /* X1's last life: the eigenvector pieces on their way between the cells of a process column */) {
+                   size_t exch_bytes = 0 /* X1's last life: the eigenvector pieces on their way between the cells of a process column */,
+                   bool values_only = false) {
   PathPlan p{};
   const bool dist = nranks_dist > 0;
   p.ld = pad_ld(n); p.nblk = ceil_div(n, kDiagNB);
@@ -408,6 +412,11 @@ PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /*
   p.x0 = p.mat;
   const size_t phase_a = al(p.sygst_dbl * 8) + p.potrf_wb + al(p.wb_sytrd) + 512;   // [reduction | Cholesky | one-stage scratch]
   p.x1 = phase_a;
+  if (values_only) {
+    p.zcols = 0; p.zmat = 0; p.wb_stedc = 0; p.wb_ormtr = 0; p.wb_rec = 0; p.wb_q1prep = 0;
+    if (al(stebz_work_bytes(n)) > p.x1) p.x1 = al(stebz_work_bytes(n));
+    if (p.x1 < 4096) p.x1 = 4096;          // (the stage-in's partial maxima)
+  }
   if (al(p.wb_stedc) > p.x1) p.x1 = al(p.wb_stedc);
   if (p.wb_rec > p.x1) p.x1 = p.wb_rec;
   if (al(p.wb_ormtr) > p.x1) p.x1 = al(p.wb_ormtr);
@@ -424,9 +433,14 @@ PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /*
 // and the tridiagonal eigenproblem are computed as usual (replicated on every rank) and only the
 // eigenvector columns this grid cell owns are back-transformed; dZ receives the local
 // block-cyclic piece numroc(n, nb, myrow, nprow) x numroc(n_vec, nb, mycol, npcol).
+//
+// vals != nullptr: an eigenvalues-only call (1 x 1, no pipeline): the same stages up to the tridiagonalisation, then the
+// bisection for eigenvalues vals->il..vals->iu into dw (iu - il + 1 doubles); n_vec, dZ and ldz are not referenced, and
+// dA / dB come back as after the full path's tridiagonalisation (A) and Cholesky factorisation (B).
+struct ValuesRange { int il, iu; };
 int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, double *dB, int ldb,
                         double *dw, double *dZ, int ldz, double *stage_seconds, int n_stages,
-                        const GridCell *cell = nullptr, HostPipe *pipe = nullptr) {
+                        const GridCell *cell = nullptr, HostPipe *pipe = nullptr, const ValuesRange *vals = nullptr) {
   hipStream_t s = g_ctx.stream;
   const int nc_out = cell ? numroc0(n_vec, cell->nb, cell->mycol, cell->npcol) : n_vec;    // columns of the piece of Z this call returns
   const int nr_loc = cell ? numroc0(n, cell->nb, cell->myrow, cell->nprow) : n;
@@ -446,7 +460,9 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   const int nc_loc = split_rows ? numroc0(n_vec, cell->nb, g_comm.rank, g_comm.nranks) : nc_out;   // columns this call FORMS
   size_t exch_bytes = 0;
   if (split_rows) exch_bytes = ((size_t)n * (nc_loc > 0 ? nc_loc : 1) + (size_t)(nr_loc > 0 ? nr_loc : 1) * (nc_out > 0 ? nc_out : 1)) * 8 + 4096;
-  const PathPlan pl = plan_path(problem, n, n_vec, nc_loc, dist ? g_comm.nranks : 0, exch_bytes);
+  const bool values_only = vals != nullptr;
+  if (values_only && (cell || pipe)) return -1;
+  const PathPlan pl = plan_path(problem, n, n_vec, nc_loc, dist ? g_comm.nranks : 0, exch_bytes, values_only);
   const int ld = pl.ld, nblk = pl.nblk, zcols = pl.zcols;
   const bool two_stage = pl.two_stage, potrf_rl = pl.potrf_rl;
   const size_t wb_sytrd = pl.wb_sytrd;
@@ -467,10 +483,10 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
     return alias_env && p && n % 128 == 0 && ldu == ld && (((size_t)p) & 255) == 0;
   };
   const bool aliasA = alias_ok(dA, lda), aliasB = problem == 1 && alias_ok(dB, ldb);
-  const bool aliasZ = !cell && nc_loc == n && zcols == ld && alias_ok(dZ, ldz);
+  const bool aliasZ = !values_only && !cell && nc_loc == n && zcols == ld && alias_ok(dZ, ldz);
   double *wB = aliasB ? dB : a.get<double>((size_t)ld * ld);
   double *wV = a.get<double>((size_t)ld * ld);
-  double *wZ = aliasZ ? dZ : a.get<double>((size_t)ld * zcols);
+  double *wZ = (aliasZ || values_only) ? dZ : a.get<double>((size_t)ld * zcols);
   double *x0 = a.get<double>((size_t)ld * ld);
   char *x1 = a.get<char>(pl.x1);
   double *dInv = a.get<double>((size_t)nblk * kDiagNB * kDiagNB);
@@ -479,7 +495,7 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   double *dt1 = a.get<double>(ld);
   char *work_sy2sb = two_stage ? a.get<char>(pl.wb_sy2sb) : nullptr;
   char *work_sb2st = two_stage ? a.get<char>(pl.wb_sb2st) : nullptr;
-  char *q1prep = two_stage ? a.get<char>(pl.wb_q1prep) : nullptr;
+  char *q1prep = (two_stage && !values_only) ? a.get<char>(pl.wb_q1prep) : nullptr;
   double *inv256 = pl.inv256 ? (double *)a.get<char>(pl.inv256) : nullptr;
   struct Inv256Guard { ~Inv256Guard() { trsm_register_inv256(nullptr, nullptr, 0); } } inv256_guard;   // (whichever way the call ends)
   double *wA = aliasA ? dA : x0;         // X0, first life: the matrix (unless the caller's array serves)
@@ -642,6 +658,35 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
     a_out();
   }
   mark();                                                              // 4
+  if (values_only) {
+    // the bisection takes the D&C's slot; nothing of the back-transformation or of the recovery runs
+    stebz(s, n, dd, de, vals->il, vals->iu, dwv, x1);
+    mark(); mark(); mark();                                            // 5, 6, 7
+    const int m = vals->iu - vals->il + 1;
+    if (sigma != 1.0) scale_vector(s, m, 1.0 / sigma, dwv);
+    EK_HIP_CHECK(hipMemcpyAsync(dw, dwv, (size_t)m * 8, hipMemcpyDeviceToDevice, s));
+    if (problem == 1 && !aliasB) copy_matrix(s, n, n, wB, ld, dB, ldb);
+    mark();                                                            // 8
+    EK_HIP_CHECK(hipGetLastError());
+    int info[4] = {0, 0, 0, 0};
+    EK_HIP_CHECK(hipMemcpyAsync(info, g_ctx.d_info, sizeof(info), hipMemcpyDeviceToHost, s));
+    EK_HIP_CHECK(hipStreamSynchronize(s));
+    g_ctx.stats[0] = 0.0;
+    g_ctx.stats[1] = two_stage_done ? 1.0 : 0.0;
+    g_ctx.stats[2] = rescued_panels;
+    g_ctx.stats[3] = (two_stage_done && band_input) ? 1.0 : 0.0;
+    if (timing) {
+      float ms[8];
+      for (int i = 0; i < 8; ++i) (void)hipEventElapsedTime(&ms[i], tm.ev[i], tm.ev[i + 1]);
+      double st[EK_HIP_N_STAGES] = {0};
+      st[EK_STAGE_COPY] = (ms[0] + ms[7]) * 1e-3;
+      st[EK_STAGE_POTRF] = ms[1] * 1e-3; st[EK_STAGE_SYGST] = ms[2] * 1e-3;
+      st[EK_STAGE_SYTRD] = ms[3] * 1e-3; st[EK_STAGE_STEDC] = ms[4] * 1e-3;   // ORMTR, TRTRS, GATHER: 0
+      for (int i = 0; i < n_stages && i < EK_HIP_N_STAGES; ++i) stage_seconds[i] = st[i];
+      tm.destroy();
+    }
+    return info[0];                          // Cholesky: leading minor not positive definite
+  }
   // eigenvector columns wanted: the first n_vec, or this grid cell's share of them; the D&C
   // forms only those (columns 0..nc_loc-1 of wZ) and the two remaining stages treat the
   // columns of Z independently
@@ -853,6 +898,79 @@ int ek_hip_solve_device(int problem, int n, int n_vec, double *dA, int lda, doub
   std::lock_guard<std::mutex> lk(g_mu);
   return solve_device_locked(problem, n, n_vec, dA, lda, dB, ldb, dw, dZ, ldz, stage_seconds, n_stages);
 }
+
+int ek_hip_eigenvalues_device(int problem, int n, int il, int iu, double *dA, int lda, double *dB, int ldb,
+                              double *dw, double *stage_seconds, int n_stages) {
+  if (problem != 0 && problem != 1) return -1;
+  if (n < 0) return -2;
+  if (n > 0 && (il < 1 || il > n)) return -3;
+  if (n > 0 && (iu < il || iu > n)) return -4;
+  if (n > 0 && !dA) return -5;
+  if (lda < (n > 1 ? n : 1)) return -6;
+  if (problem == 1 && n > 0 && !dB) return -7;
+  if (problem == 1 && ldb < (n > 1 ? n : 1)) return -8;
+  if (n > 0 && !dw) return -9;
+  int rc = ensure_init(); if (rc) return rc;
+  if (n == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  const ValuesRange r{il, iu};
+  rc = solve_device_locked(problem, n, n, dA, lda, dB, ldb, dw, nullptr, n, stage_seconds, n_stages, nullptr, nullptr, &r);
+  return rc == -4 ? -5 : rc;                // NaN / Inf in A: A is argument 5 here
+}
+
+int ek_hip_eigenvalues(int problem, int n, int il, int iu, const double *A, int lda, const double *B, int ldb,
+                       double *w, double *stage_seconds, int n_stages) {
+  if (problem != 0 && problem != 1) return -1;
+  if (n < 0) return -2;
+  if (n > 0 && (il < 1 || il > n)) return -3;
+  if (n > 0 && (iu < il || iu > n)) return -4;
+  if (n > 0 && !A) return -5;
+  if (lda < (n > 1 ? n : 1)) return -6;
+  if (problem == 1 && n > 0 && !B) return -7;
+  if (problem == 1 && ldb < (n > 1 ? n : 1)) return -8;
+  if (n > 0 && !w) return -9;
+  int rc = ensure_init(); if (rc) return rc;
+  if (n == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int m = iu - il + 1;
+  const size_t nn = (size_t)n * n * 8;
+  // the caller's arrays are left as they are: the path works on device copies of them
+  auto t0 = std::chrono::steady_clock::now();
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr;
+  rc = mem.alloc(&uA, nn);
+  if (!rc) rc = mem.alloc(&uw, (size_t)m * 8);
+  if (!rc && problem == 1) rc = mem.alloc(&uB, nn);
+  if (rc) return rc;
+  rc = h2d_matrix(n, n, A, lda, uA, n, s);
+  if (!rc && problem == 1) rc = h2d_matrix(n, n, B, ldb, uB, n, s);
+  if (!rc) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) rc = -1000 - (int)e; }
+  if (rc) return rc;
+  auto t1 = std::chrono::steady_clock::now();
+  const ValuesRange r{il, iu};
+  int info = solve_device_locked(problem, n, n, uA, n, uB, n, uw, nullptr, n, stage_seconds, n_stages, nullptr, nullptr, &r);
+  if (info == -4) info = -5;
+  auto t2 = std::chrono::steady_clock::now();
+  if (info > -1000) {
+    hipError_t e = hipMemcpyAsync(w, uw, (size_t)m * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess && info == 0) info = -1000 - (int)e;
+  }
+  auto t3 = std::chrono::steady_clock::now();
+  if (stage_seconds && n_stages > EK_STAGE_COPY)
+    stage_seconds[EK_STAGE_COPY] += std::chrono::duration<double>(t1 - t0).count() +
+                                    std::chrono::duration<double>(t3 - t2).count();
+  return info;
+}
+
+// Pure host arithmetic: the workspace of an eigenvalues-only call (ek_hip_eigenvalues*)
+unsigned long long ek_hip_debug_values_workspace_bytes(int problem, int n) {
+  if (n < 1 || (problem != 0 && problem != 1)) return 0;
+  return plan_path(problem, n, n, n, 0, 0, /*values_only=*/true).total;
+}
+
+int ek_hip_debug_set_stebz(int lanes) { return stebz_set_lanes(lanes); }
 
 // Pure host arithmetic (no GPU needed): bytes of workspace one whole-path call asks for -- on one GPU (nranks <= 1: all
 // n_vec eigenvector columns) or as rank 0 of a 1 x nranks team with a communicator attached (its share of the columns,

@@ -125,6 +125,11 @@ def load_library(path=None):
         "ek_hip_debug_stedc_team_get": (c_int, [_dp]),
         "ek_hip_debug_last_pipe_stats": (c_int, [_dp, c_int]),
         "ek_hip_debug_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
+        "ek_hip_eigenvalues_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, vp, _dp, c_int]),
+        "ek_hip_eigenvalues": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, _dp, c_int, _dp, _dp, c_int]),
+        "ek_hip_stebz": (c_int, [c_int, _dp, _dp, c_int, c_int, _dp]),
+        "ek_hip_debug_values_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int]),
+        "ek_hip_debug_set_stebz": (c_int, [c_int]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -157,6 +162,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_sy2sb_team", "ek_hip_debug_sy2sb_team_timing", "ek_hip_debug_sy2sb_team_profile", "ek_hip_debug_workspace_bytes", "ek_hip_debug_fail_next_chase", "ek_hip_debug_last_pipe_stats",
     "ek_hip_debug_stedc_team", "ek_hip_debug_stedc_team_get",
     "ek_hip_debug_potrf_team_profile", "ek_hip_debug_potrf_team_profile_get",
+    "ek_hip_eigenvalues_device", "ek_hip_eigenvalues", "ek_hip_stebz",
+    "ek_hip_debug_values_workspace_bytes", "ek_hip_debug_set_stebz",
 )
 
 
@@ -429,6 +436,21 @@ def stedc(d, e):
     return d, Z, info
 
 
+def stebz(d, e, il=1, iu=None):
+    """DSTEBZ('I', 'E') on the GPU (ek_hip_stebz): eigenvalues il..iu (1-based, ascending) of the symmetric tridiagonal
+    (d, e).  Returns w (iu - il + 1 values); raises SolverError on a nonzero info."""
+    lib = load_library()
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    n = d.shape[0]
+    iu = n if iu is None else int(iu)
+    ee = np.zeros(max(n, 1)); ee[:max(n - 1, 0)] = np.asarray(e, dtype=np.float64)[:max(n - 1, 0)]
+    w = np.zeros(max(iu - int(il) + 1, 1))
+    info = lib.ek_hip_stebz(n, _P(d) if n else None, _P(ee), int(il), iu, _P(w))
+    if info != 0:
+        raise SolverError("ek_hip_stebz failed", info)
+    return w[:max(iu - int(il) + 1, 0)] if n else w[:0]
+
+
 def ormtr(Ar, tau, Z):
     """PDORMTR('L','L','N') (solver_scalapack_all.f90:115). Returns (QZ, info)."""
     lib = load_library()
@@ -488,6 +510,36 @@ def workspace_bytes(problem, n, n_vec=None, nranks=1):
     parts = (ctypes.c_ulonglong * 6)()
     tot = load_library().ek_hip_debug_workspace_bytes(int(problem), int(n), int(n if n_vec is None else n_vec), int(nranks), parts)
     return int(tot), [int(x) for x in parts]
+
+
+def values_workspace_bytes(problem, n):
+    """Bytes of device workspace one eigenvalues-only call asks for (host arithmetic: works without a GPU)."""
+    return int(load_library().ek_hip_debug_values_workspace_bytes(int(problem), int(n)))
+
+
+def set_stebz_lanes(lanes=0):
+    """Lanes per eigenvalue index of the bisection (1, 2, 4, 8, 16; 0: the default)."""
+    rc = load_library().ek_hip_debug_set_stebz(int(lanes))
+    assert rc == 0, rc
+
+
+def eigenvalues(A, B=None, il=1, iu=None, stage_seconds=None):
+    """Eigenvalues il..iu (1-based, ascending) of A x = l x, or of A x = l B x with B SPD (ek_hip_eigenvalues: no
+    eigenvectors are formed).  A and B are not modified.  stage_seconds: None or a float64 array of EK_HIP_N_STAGES
+    entries that receives the stage times.  Returns w; raises SolverError on a nonzero info."""
+    lib = load_library()
+    A = _farr(A)
+    n = A.shape[0]
+    problem = 0 if B is None else 1
+    Bf = _farr(B) if B is not None else None
+    iu = n if iu is None else int(iu)
+    w = np.zeros(max(iu - int(il) + 1, 1))
+    st = None if stage_seconds is None else stage_seconds
+    info = lib.ek_hip_eigenvalues(problem, n, int(il), iu, _P(A), max(n, 1), _P(Bf) if Bf is not None else None,
+                                  max(n, 1), _P(w), _P(st) if st is not None else None, 0 if st is None else len(st))
+    if info != 0:
+        raise SolverError("ek_hip_eigenvalues failed", info)
+    return w[:max(iu - int(il) + 1, 0)] if n else w[:0]
 
 
 def sy2sb(A):

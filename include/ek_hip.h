@@ -62,7 +62,8 @@ extern "C" {
 /* Library / device management ---------------------------------------------------------- */
 int ek_hip_version(void);                       /* 100*major + minor.  2: round 5 (version 1's
                                                  * ek_hip_comm_peer_enable / _disable are gone since
-                                                 * round 4: INTEGRATION.md 5) */
+                                                 * round 4: INTEGRATION.md 5); 3: the eigenvalues-only
+                                                 * entries ek_hip_eigenvalues* and ek_hip_stebz */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
 const char *ek_hip_stage_name(int stage);       /* reference event name of a stage index    */
@@ -113,6 +114,33 @@ int ek_hip_solve_device(int problem, int n, int n_vec,
                         double *dA, int lda, double *dB, int ldb,
                         double *dw, double *dZ, int ldz,
                         double *stage_seconds, int n_stages);
+
+/* Eigenvalues only -- LAPACK DSYGVD / DSYEVD with JOBZ = 'N', DSYEVX with RANGE = 'I': the same reduction and
+ * tridiagonalisation as ek_hip_solve, then bisection with Sturm counts on the GPU (ek_hip_stebz) in place of the
+ * divide & conquer; no eigenvectors are formed, nothing is back-transformed or recovered, and the call reserves no
+ * eigenvector or back-transformation workspace.  NOT COLLECTIVE: it computes on the bound GPU alone and uses no grid
+ * and no communicator, even when one is attached.
+ *   problem, A, B : as in ek_hip_solve (0 standard, 1 generalized with B SPD; lower triangles referenced)
+ *   il, iu        : 1-based indices of the wanted eigenvalues in ascending order, 1 <= il <= iu <= n (n = 0: nothing)
+ *   w             : out: iu - il + 1 doubles, ascending.  The value of an index is bit-identical whatever [il, iu]
+ *                   is asked for; absolute accuracy about 2 eps max|lambda| of the tridiagonal stage (normwise, as
+ *                   the divide & conquer's)
+ *   stage_seconds : NULL or up to EK_HIP_N_STAGES doubles: the bisection in EK_STAGE_STEDC, EK_STAGE_ORMTR and
+ *                   EK_STAGE_TRTRS are 0
+ * info: -k for argument k; -5 also when A contains NaN/Inf; a B that is not SPD gives the positive info of
+ * ek_hip_solve_device for that B; <= -1000 HIP runtime error; -992 as in ek_hip_solve. */
+/* problem 0/1 as ek_hip_solve; w receives iu-il+1 doubles, ascending; 1 <= il <= iu <= n (n = 0: nothing)
+ * in place, as ek_hip_solve_device: dA and dB (device, lda / ldb) come back as that call leaves them after the
+ * tridiagonalisation (dA) and the Cholesky factorisation (dB); dw is device memory */
+int ek_hip_eigenvalues_device(int problem, int n, int il, int iu, double *dA, int lda, double *dB, int ldb,
+                              double *dw, double *stage_seconds, int n_stages);
+/* host arrays A (lda), B (ldb), w; A and B are left untouched (the call works on device copies) */
+int ek_hip_eigenvalues(int problem, int n, int il, int iu, const double *A, int lda, const double *B, int ldb,
+                       double *w, double *stage_seconds, int n_stages);
+/* The stage alone, host arrays: DSTEBZ('I', 'E') -- eigenvalues il..iu (1-based, ascending) of the symmetric
+ * tridiagonal d(n), e(n-1) into w(iu-il+1), bit-identical per index whatever the range.  info -k for argument k
+ * (-2 / -3 also for NaN / Inf in d / e). */
+int ek_hip_stebz(int n, const double *d, const double *e, int il, int iu, double *w);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs

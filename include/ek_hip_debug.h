@@ -78,6 +78,13 @@ int ek_hip_debug_last_solve_stats(double *out, int count);
    scratch), the rest.  ek_solve.hip plan_path. */
 unsigned long long ek_hip_debug_workspace_bytes(int problem, int n, int n_vec, int nranks, unsigned long long *parts);
 
+/* workspace one eigenvalues-only call (ek_hip_eigenvalues*) asks for (host arithmetic, no GPU): the same plan without
+   the eigenvector array, the records of Q2, the scratch of Q1, of the D&C and of the back-transformation. */
+unsigned long long ek_hip_debug_values_workspace_bytes(int problem, int n);
+/* lanes per eigenvalue index of the bisection (ek_stebz.hip): 1, 2, 4, 8 or 16, each lane evaluating 2 points per pass
+   (<= 0: the default, 4).  A tuning hook: the grid of the bisection, hence the last bits of the values, depends on it. */
+int ek_hip_debug_set_stebz(int lanes);
+
 /* test aid: the next `times` bulge chasings of whole-path calls count as abandoned (exercises the repetition from the
    saved band and the -992 exit of ek_solve.hip) */
 int ek_hip_debug_fail_next_chase(int times);
