@@ -532,6 +532,53 @@ int ek_hip_stebz(int n, const double *d, const double *e, int il, int iu, double
   return 0;
 }
 
+int ek_hip_stebz_range(int n, const double *d, const double *e, double vl, double vu, int *il, int *m, double *w) {
+  if (n < 0) return -1;
+  if (n > 0 && !d) return -2;
+  if (n > 1 && !e) return -3;
+  if (vl != vl) return -4;
+  if (!(vl < vu)) return -5;                // (vu NaN, or an empty interval)
+  if (!il) return -6;
+  if (!m) return -7;
+  if (n > 0 && !w) return -8;
+  double tnorm = 0.0;                       // (NaN / Inf: illegal value of d or e, as ek_hip_stebz)
+  for (int i = 0; i < n; ++i) { const double v = fabs(d[i]); if (!(v <= DBL_MAX)) return -2; if (v > tnorm) tnorm = v; }
+  for (int i = 0; i + 1 < n; ++i) { const double v = fabs(e[i]); if (!(v <= DBL_MAX)) return -3; if (v > tnorm) tnorm = v; }
+  *il = 1; *m = 0;
+  int rc = ensure_init(); if (rc) return rc;
+  if (n == 0) return 0;
+  // the power-of-two scaling of ek_hip_stebz (exact), applied to the bounds as well
+  int ex = 0;
+  if (tnorm > 0.0) { (void)frexp(tnorm, &ex); ex = (ex > 400 || ex < -400) ? -ex : 0; }
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n);
+  void *ws;
+  rc = workspace(al(stebz_work_bytes(n)) + 3 * al((size_t)ld * 8), &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  char *work = a.get<char>(stebz_work_bytes(n));
+  double *dd = a.get<double>(ld), *de = a.get<double>(ld), *dw = a.get<double>(ld);
+  EK_HIP_CHECK(hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemsetAsync(de, 0, (size_t)ld * 8, s));
+  if (n > 1) EK_HIP_CHECK(hipMemcpyAsync(de, e, (size_t)(n - 1) * 8, hipMemcpyHostToDevice, s));
+  if (ex != 0) { scale_vector(s, n, ldexp(1.0, ex), dd); scale_vector(s, n, ldexp(1.0, ex), de); }
+  const int *d_ilu = stebz_window(s, n, dd, de, ldexp(vl, ex), ldexp(vu, ex), work);
+  int ilu[2] = {1, 0};
+  EK_HIP_CHECK(hipMemcpyAsync(ilu, d_ilu, sizeof(ilu), hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  const int cnt = ilu[1] >= ilu[0] ? ilu[1] - ilu[0] + 1 : 0;
+  if (cnt > 0) {
+    stebz(s, n, dd, de, ilu[0], ilu[1], dw, work);
+    if (ex != 0) scale_vector(s, cnt, ldexp(1.0, -ex), dw);
+    EK_HIP_CHECK(hipGetLastError());
+    EK_HIP_CHECK(hipMemcpyAsync(w, dw, (size_t)cnt * 8, hipMemcpyDeviceToHost, s));
+    EK_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  *il = ilu[0]; *m = cnt;
+  return 0;
+}
+
 int ek_hip_ormtr(int n, int ncols, const double *A_loc, const int desc_A[9], const double *tau,
                  double *Z_loc, const int desc_Z[9]) {
   if (n < 0) return -1;

@@ -254,7 +254,8 @@ bool stedc_compact(int n, int nsel);               // whether stedc keeps its ba
 // l = 0..nsel-1, are formed (the block-cyclic share of a process column; nb >= n, npcol = 1 gives
 // the lowest nsel) and returned in columns 0..nsel-1 of Z: the top-level merge, two thirds of the
 // D&C flops, then multiplies only those columns.  All n eigenvalues are always returned.
-struct StedcSelect { int nsel, nb, npcol, mycol; };
+// first (1 x 1 only, npcol = 1, nb >= n; grids and teams keep 0): a window -- ranks first..first+nsel-1 (0-based).
+struct StedcSelect { int nsel, nb, npcol, mycol; int first = 0; };
 // d_flops (optional, device): receives the flops of the merge products this solve executed (after deflation)
 // wscratch (optional): an n x n array with leading dimension ldz for the permuted bases of the merges; without it Z
 // itself serves (and must then be n x n even where only sel->nsel columns are wanted)
@@ -287,6 +288,10 @@ void stedc(hipStream_t s, int n, const double *d, const double *e, double *w, do
 size_t stebz_work_bytes(int n);
 void stebz(hipStream_t s, int n, const double *d, const double *e, int il, int iu, double *w, void *work);
 int stebz_set_lanes(int lanes);                    // lanes per index: 1, 2, 4, 8 or 16 (<= 0: the default, 4)
+// RANGE = 'V': the indices of the eigenvalues in (vl, vu] -- il = count(vl) + 1, iu = count(vu) -- with the recurrence,
+// pivmin and Gershgorin interval of stebz (bounds outside it clamp to 0 and n: +-Inf are legal).  Returns the device
+// int[2] {il, iu} inside work (valid once the stream reaches it; iu < il: no eigenvalue in the interval).
+int *stebz_window(hipStream_t s, int n, const double *d, const double *e, double vl, double vu, void *work);
 
 // ---------------------------------------------------------------- back-transformation (ek_ormtr.hip)
 size_t ormtr_work_bytes(int n, int ncols, int ncols_global = -1);   // ncols_global: columns of the whole Z (a grid cell holds ncols of them)

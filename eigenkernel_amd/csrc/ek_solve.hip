@@ -377,9 +377,13 @@ struct PathPlan {
 // values_only: the plan of an eigenvalues-only call (ek_hip_eigenvalues*): the stages up to the tridiagonalisation, then
 // the bisection -- no eigenvector array, no records of Q2, no scratch of Q1, of the D&C or of the back-transformation;
 // X1 is then [phase A | the bisection's scratch] (never distributed).
+// value_window: a RANGE = 'V' call with eigenvectors (ek_hip_eigenpairs*), whose m is known only after the
+// tridiagonalisation: the full plan (n_vec = nc_loc = n), with X1 grown where the window's own D&C (compact for
+// m <= n - n/2) or back-transformation scratch could need more for some m -- a few n doubles on odd orders, nothing on
+// the even orders the tests check (256 ... 32768).
 PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /* 0: not distributed */,
                    size_t exch_bytes = 0 /* X1's last life: the eigenvector pieces on their way between the cells of a process column */,
-                   bool values_only = false) {
+                   bool values_only = false, bool value_window = false) {
   PathPlan p{};
   const bool dist = nranks_dist > 0;
   p.ld = pad_ld(n); p.nblk = ceil_div(n, kDiagNB);
@@ -421,6 +425,15 @@ PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /*
   if (p.wb_rec > p.x1) p.x1 = p.wb_rec;
   if (al(p.wb_ormtr) > p.x1) p.x1 = al(p.wb_ormtr);
   if (al(exch_bytes) > p.x1) p.x1 = al(exch_bytes);
+  if (value_window) {
+    const size_t dc = al(stedc_work_bytes(n, n - n / 2));          // the compact D&C's largest selection
+    if (dc > p.x1) p.x1 = dc;
+    for (int c = 128; ; c += 128) {                                 // Q1 on m columns (its K split is a step function of m)
+      const int mc = c < n ? c : n;
+      if (al(ormtr_work_bytes(n, mc, mc)) > p.x1) p.x1 = al(ormtr_work_bytes(n, mc, mc));
+      if (mc == n) break;
+    }
+  }
   p.total = 2 * p.mat + p.zmat + p.x0 + p.x1 + al((size_t)p.nblk * kDiagNB * kDiagNB * 8) + p.trsm_work +
             5 * al((size_t)p.ld * 8) + p.wb_sy2sb + p.wb_sb2st + p.wb_q1prep + p.inv256 + 4096;
   return p;
@@ -434,13 +447,25 @@ PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /*
 // eigenvector columns this grid cell owns are back-transformed; dZ receives the local
 // block-cyclic piece numroc(n, nb, myrow, nprow) x numroc(n_vec, nb, mycol, npcol).
 //
-// vals != nullptr: an eigenvalues-only call (1 x 1, no pipeline): the same stages up to the tridiagonalisation, then the
-// bisection for eigenvalues vals->il..vals->iu into dw (iu - il + 1 doubles); n_vec, dZ and ldz are not referenced, and
-// dA / dB come back as after the full path's tridiagonalisation (A) and Cholesky factorisation (B).
-struct ValuesRange { int il, iu; };
+// win != nullptr: a window of the spectrum (1 x 1, no pipeline; ek_hip_eigenvalues*, ek_hip_eigenpairs*).
+//   range 0: indices win->il..iu; range 1: the eigenvalues in (vl, vu], counted on the tridiagonal after stage 4 (the
+//   bounds scaled as A was), which sets il and iu.  win->first = il - 1 and win->m = iu - il + 1 come back.
+//   jobz 0: the bisection for il..iu in the D&C's slot, dw receives m doubles; n_vec, dZ and ldz are not referenced.
+//   jobz 1: the D&C forms eigenvectors il..iu only (its rank offset), Q2, Q1 and the recovery treat those m columns, dw
+//   receives their m eigenvalues and dZ (ldz) the m columns.  The caller passes n_vec = m for range 0 (the *_select
+//   arm's plan) and n_vec = n for range 1 (the full plan); range 1 with m > win->zcap returns kWindowTooSmall before dw
+//   or dZ is written.
+//   dA / dB come back as after the full path's tridiagonalisation (A) and Cholesky factorisation (B).
+struct Window {
+  int jobz, range, il, iu;
+  double vl, vu;
+  int zcap;
+  int m, first;            // out
+};
+constexpr int kWindowTooSmall = -990;
 int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, double *dB, int ldb,
                         double *dw, double *dZ, int ldz, double *stage_seconds, int n_stages,
-                        const GridCell *cell = nullptr, HostPipe *pipe = nullptr, const ValuesRange *vals = nullptr) {
+                        const GridCell *cell = nullptr, HostPipe *pipe = nullptr, Window *win = nullptr) {
   hipStream_t s = g_ctx.stream;
   const int nc_out = cell ? numroc0(n_vec, cell->nb, cell->mycol, cell->npcol) : n_vec;    // columns of the piece of Z this call returns
   const int nr_loc = cell ? numroc0(n, cell->nb, cell->myrow, cell->nprow) : n;
@@ -457,12 +482,14 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   // on every rank whatever the grid's shape, as PDORMTR / PDTRTRS have it on the reference's 2 x 4 grid
   // (solver_scalapack_all.f90:115, generalized_to_standard.f90:103, processes.f90:56-65).
   const bool split_rows = dist && cell->nprow > 1;
-  const int nc_loc = split_rows ? numroc0(n_vec, cell->nb, g_comm.rank, g_comm.nranks) : nc_out;   // columns this call FORMS
+  int nc_loc = split_rows ? numroc0(n_vec, cell->nb, g_comm.rank, g_comm.nranks) : nc_out;   // columns this call FORMS
+                                                                       // (a value window: set to its m at stage 4)
   size_t exch_bytes = 0;
   if (split_rows) exch_bytes = ((size_t)n * (nc_loc > 0 ? nc_loc : 1) + (size_t)(nr_loc > 0 ? nr_loc : 1) * (nc_out > 0 ? nc_out : 1)) * 8 + 4096;
-  const bool values_only = vals != nullptr;
-  if (values_only && (cell || pipe)) return -1;
-  const PathPlan pl = plan_path(problem, n, n_vec, nc_loc, dist ? g_comm.nranks : 0, exch_bytes, values_only);
+  const bool values_only = win && win->jobz == 0;
+  const bool value_window = win && win->jobz == 1 && win->range == 1;
+  if (win && (cell || pipe)) return -1;
+  const PathPlan pl = plan_path(problem, n, n_vec, nc_loc, dist ? g_comm.nranks : 0, exch_bytes, values_only, value_window);
   const int ld = pl.ld, nblk = pl.nblk, zcols = pl.zcols;
   const bool two_stage = pl.two_stage, potrf_rl = pl.potrf_rl;
   const size_t wb_sytrd = pl.wb_sytrd;
@@ -483,7 +510,7 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
     return alias_env && p && n % 128 == 0 && ldu == ld && (((size_t)p) & 255) == 0;
   };
   const bool aliasA = alias_ok(dA, lda), aliasB = problem == 1 && alias_ok(dB, ldb);
-  const bool aliasZ = !values_only && !cell && nc_loc == n && zcols == ld && alias_ok(dZ, ldz);
+  const bool aliasZ = !values_only && !value_window && !cell && nc_loc == n && zcols == ld && alias_ok(dZ, ldz);
   double *wB = aliasB ? dB : a.get<double>((size_t)ld * ld);
   double *wV = a.get<double>((size_t)ld * ld);
   double *wZ = (aliasZ || values_only) ? dZ : a.get<double>((size_t)ld * zcols);
@@ -658,13 +685,28 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
     a_out();
   }
   mark();                                                              // 4
-  if (values_only) {
-    // the bisection takes the D&C's slot; nothing of the back-transformation or of the recovery runs
-    stebz(s, n, dd, de, vals->il, vals->iu, dwv, x1);
+  bool window_too_small = false;
+  if (win) {
+    if (win->range == 1) {
+      // the value window's indices: one count at each bound on the tridiagonal (X1 is free until the D&C), read back here
+      const int *d_ilu = stebz_window(s, n, dd, de, win->vl * sigma, win->vu * sigma, x1);
+      int ilu[2] = {1, 0};
+      EK_HIP_CHECK(hipMemcpyAsync(ilu, d_ilu, sizeof(ilu), hipMemcpyDeviceToHost, s));
+      EK_HIP_CHECK(hipStreamSynchronize(s));
+      win->il = ilu[0]; win->iu = ilu[1] >= ilu[0] ? ilu[1] : ilu[0] - 1;
+    }
+    win->first = win->il - 1;
+    win->m = win->iu - win->il + 1;
+    window_too_small = win->jobz == 1 && win->m > win->zcap;
+  }
+  if (values_only || (win && (win->m == 0 || window_too_small))) {
+    // the bisection takes the D&C's slot; nothing of the back-transformation or of the recovery runs (nor anything
+    // after the count for an empty window or one that dZ cannot hold)
+    const int m = win->m;
+    if (values_only && m > 0) stebz(s, n, dd, de, win->il, win->iu, dwv, x1);
     mark(); mark(); mark();                                            // 5, 6, 7
-    const int m = vals->iu - vals->il + 1;
-    if (sigma != 1.0) scale_vector(s, m, 1.0 / sigma, dwv);
-    EK_HIP_CHECK(hipMemcpyAsync(dw, dwv, (size_t)m * 8, hipMemcpyDeviceToDevice, s));
+    if (values_only && m > 0 && sigma != 1.0) scale_vector(s, m, 1.0 / sigma, dwv);
+    if (values_only && m > 0) EK_HIP_CHECK(hipMemcpyAsync(dw, dwv, (size_t)m * 8, hipMemcpyDeviceToDevice, s));
     if (problem == 1 && !aliasB) copy_matrix(s, n, n, wB, ld, dB, ldb);
     mark();                                                            // 8
     EK_HIP_CHECK(hipGetLastError());
@@ -685,13 +727,15 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
       for (int i = 0; i < n_stages && i < EK_HIP_N_STAGES; ++i) stage_seconds[i] = st[i];
       tm.destroy();
     }
-    return info[0];                          // Cholesky: leading minor not positive definite
+    if (info[0] != 0) return info[0];        // Cholesky: leading minor not positive definite
+    return window_too_small ? kWindowTooSmall : 0;
   }
+  if (value_window) { nc_loc = win->m; n_vec = win->m; }   // (the plan above holds any m; the columns formed are m)
   // eigenvector columns wanted: the first n_vec, or this grid cell's share of them; the D&C
   // forms only those (columns 0..nc_loc-1 of wZ) and the two remaining stages treat the
   // columns of Z independently
   const StedcSelect pick{nc_loc, cell ? cell->nb : (n > 0 ? n : 1), split_rows ? g_comm.nranks : (cell ? cell->npcol : 1),
-                         split_rows ? g_comm.rank : (cell ? cell->mycol : 0)};
+                         split_rows ? g_comm.rank : (cell ? cell->mycol : 0), win ? win->first : 0};
   // On a team the heights right below the top merge are sharded as well (strips of the compact bases, one all-gather
   // round per P strips: ek_stedc.hip); the top merge forms this cell's columns only, as in the replicated-input mode.
   SytrdExchange dcx{};
@@ -761,8 +805,10 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   mark();                                                              // 7
   // stage-out: eigenvalues, eigenvectors, and the in-place results the reference leaves
   // behind (L in B, reflectors in A)
-  if (sigma != 1.0) scale_vector(s, n, 1.0 / sigma, dwv);
-  EK_HIP_CHECK(hipMemcpyAsync(dw, dwv, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+  const int nw = win ? win->m : n;                      // (a window: its own eigenvalues, from rank first on)
+  double *wsrc = win ? dwv + win->first : dwv;
+  if (sigma != 1.0) scale_vector(s, nw, 1.0 / sigma, wsrc);
+  EK_HIP_CHECK(hipMemcpyAsync(dw, wsrc, (size_t)nw * 8, hipMemcpyDeviceToDevice, s));
   if (!pipe) {
     if (split_rows) {
       // every cell of this process column receives its rows of the columns the others formed: per peer one packed piece
@@ -913,7 +959,7 @@ int ek_hip_eigenvalues_device(int problem, int n, int il, int iu, double *dA, in
   int rc = ensure_init(); if (rc) return rc;
   if (n == 0) return 0;
   std::lock_guard<std::mutex> lk(g_mu);
-  const ValuesRange r{il, iu};
+  Window r{0, 0, il, iu, 0.0, 0.0, 0, 0, 0};
   rc = solve_device_locked(problem, n, n, dA, lda, dB, ldb, dw, nullptr, n, stage_seconds, n_stages, nullptr, nullptr, &r);
   return rc == -4 ? -5 : rc;                // NaN / Inf in A: A is argument 5 here
 }
@@ -948,7 +994,7 @@ int ek_hip_eigenvalues(int problem, int n, int il, int iu, const double *A, int 
   if (!rc) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) rc = -1000 - (int)e; }
   if (rc) return rc;
   auto t1 = std::chrono::steady_clock::now();
-  const ValuesRange r{il, iu};
+  Window r{0, 0, il, iu, 0.0, 0.0, 0, 0, 0};
   int info = solve_device_locked(problem, n, n, uA, n, uB, n, uw, nullptr, n, stage_seconds, n_stages, nullptr, nullptr, &r);
   if (info == -4) info = -5;
   auto t2 = std::chrono::steady_clock::now();
@@ -962,6 +1008,122 @@ int ek_hip_eigenvalues(int problem, int n, int il, int iu, const double *A, int 
     stage_seconds[EK_STAGE_COPY] += std::chrono::duration<double>(t1 - t0).count() +
                                     std::chrono::duration<double>(t3 - t2).count();
   return info;
+}
+
+}  // extern "C"
+
+namespace {
+// The argument checks of ek_hip_eigenpairs*, in argument order (LAPACK -k); zcap is checked against an index window's m
+// here, against a value window's after the count.
+int eigenpairs_args(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, const void *A, int lda,
+                    const void *B, int ldb, const int *m, const int *ifirst, const void *w, const void *Z, int ldz,
+                    int zcap) {
+  if (problem != 0 && problem != 1) return -1;
+  if (jobz != 0 && jobz != 1) return -2;
+  if (range != 0 && range != 1) return -3;
+  if (n < 0) return -4;
+  if (range == 1 && vl != vl) return -5;
+  if (range == 1 && !(vl < vu)) return -6;                    // (vu NaN, or an empty interval)
+  if (range == 0 && n > 0 && (il < 1 || il > n)) return -7;
+  if (range == 0 && n > 0 && (iu < il || iu > n)) return -8;
+  if (n > 0 && !A) return -9;
+  if (lda < (n > 1 ? n : 1)) return -10;
+  if (problem == 1 && n > 0 && !B) return -11;
+  if (problem == 1 && ldb < (n > 1 ? n : 1)) return -12;
+  if (!m) return -13;
+  if (!ifirst) return -14;
+  if (n > 0 && !w) return -15;
+  if (jobz == 1 && n > 0 && !Z) return -16;
+  if (jobz == 1 && ldz < (n > 1 ? n : 1)) return -17;
+  if (jobz == 1 && zcap < 0) return -18;
+  return 0;
+}
+
+// both entries, under the lock: m, ifirst are set on success and on a value window too wide for zcap (-18)
+int eigenpairs_locked(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, double *dA, int lda,
+                      double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ, int ldz, int zcap,
+                      double *stage_seconds, int n_stages) {
+  Window win{jobz, range, il, iu, vl, vu, zcap, 0, 0};
+  // plans: values only -> the eigenvalues-only plan; an index window -> the *_select arm's for n_vec = m; a value window
+  // -> the full plan (its m is not known yet)
+  const int n_vec = (jobz == 1 && range == 0) ? iu - il + 1 : n;
+  int info = solve_device_locked(problem, n, n_vec, dA, lda, dB, ldb, dw, dZ, ldz, stage_seconds, n_stages, nullptr,
+                                 nullptr, &win);
+  if (info == -4) info = -9;                 // NaN / Inf in A: A is argument 9 here
+  if (info == kWindowTooSmall) info = -18;
+  if (info == 0 || info == -18) { *m = win.m; *ifirst = win.first + 1; }
+  return info;
+}
+}  // namespace
+
+extern "C" {
+
+int ek_hip_eigenpairs_device(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                             double *dA, int lda, double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ,
+                             int ldz, int zcap, double *stage_seconds, int n_stages) {
+  int rc = eigenpairs_args(problem, jobz, range, n, vl, vu, il, iu, dA, lda, dB, ldb, m, ifirst, dw, dZ, ldz, zcap);
+  if (rc) return rc;
+  *m = 0; *ifirst = range == 0 ? il : 1;
+  if (jobz == 1 && range == 0 && n > 0 && iu - il + 1 > zcap) { *m = iu - il + 1; return -18; }
+  rc = ensure_init(); if (rc) return rc;
+  if (n == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return eigenpairs_locked(problem, jobz, range, n, vl, vu, il, iu, dA, lda, dB, ldb, m, ifirst, dw, dZ, ldz, zcap,
+                           stage_seconds, n_stages);
+}
+
+int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, const double *A,
+                      int lda, const double *B, int ldb, int *m, int *ifirst, double *w, double *Z, int ldz, int zcap,
+                      double *stage_seconds, int n_stages) {
+  int rc = eigenpairs_args(problem, jobz, range, n, vl, vu, il, iu, A, lda, B, ldb, m, ifirst, w, Z, ldz, zcap);
+  if (rc) return rc;
+  *m = 0; *ifirst = range == 0 ? il : 1;
+  if (jobz == 1 && range == 0 && n > 0 && iu - il + 1 > zcap) { *m = iu - il + 1; return -18; }
+  rc = ensure_init(); if (rc) return rc;
+  if (n == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int mw = range == 0 ? iu - il + 1 : n;                          // eigenvalues w can receive
+  const int zc = jobz == 0 ? 0 : (range == 0 ? iu - il + 1 : (zcap < n ? zcap : n));   // columns Z can receive
+  const size_t nn = (size_t)n * n * 8;
+  // the caller's arrays are left as they are: the path works on device copies of them
+  auto t0 = std::chrono::steady_clock::now();
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, nn);
+  if (!rc) rc = mem.alloc(&uw, (size_t)mw * 8);
+  if (!rc && problem == 1) rc = mem.alloc(&uB, nn);
+  if (!rc && jobz == 1) rc = mem.alloc(&uZ, (size_t)n * (zc > 0 ? zc : 1) * 8);
+  if (rc) return rc;
+  rc = h2d_matrix(n, n, A, lda, uA, n, s);
+  if (!rc && problem == 1) rc = h2d_matrix(n, n, B, ldb, uB, n, s);
+  if (!rc) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) rc = -1000 - (int)e; }
+  if (rc) return rc;
+  auto t1 = std::chrono::steady_clock::now();
+  int info = eigenpairs_locked(problem, jobz, range, n, vl, vu, il, iu, uA, n, uB, n, m, ifirst, uw, uZ, n, zc,
+                               stage_seconds, n_stages);
+  auto t2 = std::chrono::steady_clock::now();
+  if (info == 0 && *m > 0) {
+    hipError_t e = hipMemcpyAsync(w, uw, (size_t)*m * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) info = -1000 - (int)e;
+    if (!info && jobz == 1) info = d2h_matrix(n, *m, uZ, n, Z, ldz, s);
+    if (!info) { e = hipStreamSynchronize(s); if (e != hipSuccess) info = -1000 - (int)e; }
+  }
+  auto t3 = std::chrono::steady_clock::now();
+  if (stage_seconds && n_stages > EK_STAGE_COPY)
+    stage_seconds[EK_STAGE_COPY] += std::chrono::duration<double>(t1 - t0).count() +
+                                    std::chrono::duration<double>(t3 - t2).count();
+  return info;
+}
+
+// Pure host arithmetic: the workspace of a window call (ek_hip_eigenpairs*) with m pairs (range 1: any m)
+unsigned long long ek_hip_debug_window_workspace_bytes(int problem, int n, int jobz, int range, int m) {
+  if (n < 1 || (problem != 0 && problem != 1) || (jobz != 0 && jobz != 1) || (range != 0 && range != 1)) return 0;
+  if (m < 0 || m > n) return 0;
+  if (jobz == 0) return plan_path(problem, n, n, n, 0, 0, /*values_only=*/true).total;
+  if (range == 0) return plan_path(problem, n, m, m, 0).total;
+  return plan_path(problem, n, n, n, 0, 0, false, /*value_window=*/true).total;
 }
 
 // Pure host arithmetic: the workspace of an eigenvalues-only call (ek_hip_eigenvalues*)

@@ -9,6 +9,8 @@
 //                so a bracket is always a cell of one fixed grid: the value returned for index k depends on (d, e, k)
 //                alone -- not on il, iu or on the other indices (no atomics) -- and the returned values are
 //                non-decreasing in k (cells of one level do not overlap, the result is the cell's midpoint).
+//   stebz_window_count  one wave: the counts at vl and vu (RANGE = 'V', the half-open interval (vl, vu]) with the same
+//                recurrence, pivmin and [gl, gu] as the bisection -> il = count(vl) + 1, iu = count(vu).
 // The count of T - x I is the number of negative pivots of q_i = (d_i - x) - e_{i-1}^2 / q_{i-1}, |q| < pivmin clamped
 // to -pivmin (DLAEBZ).  It is monotone in x under IEEE arithmetic with every operation rounded on its own (Demmel,
 // Dhillon and Ren 1995): hence fp contract(off) in the recurrence and in the grid points.
@@ -133,6 +135,25 @@ __global__ void __launch_bounds__(256) stebz_bisect(int n, const double *__restr
   if (g == 0) w[grp] = lo + (hi - lo) * 0.5;
 }
 
+// out[0] = count(vl) + 1, out[1] = count(vu): the indices il..iu of the eigenvalues in (vl, vu] (iu < il: none).  A bound
+// below gl counts 0 and one at or above gu counts n (so -Inf / +Inf are legal); in between the clamped zero pivot counts an
+// eigenvalue equal to x as <= x, as DSTEBZ.  The two counts are the two interleaved chains of one lane (K = 2).
+__global__ void __launch_bounds__(64) stebz_window_count(int n, const double *__restrict__ d,
+                                                         const double *__restrict__ e2,
+                                                         const double *__restrict__ params, double vl, double vu,
+                                                         int *__restrict__ out) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0) return;
+  const double gl = params[0], gu = params[1], pivmin = params[2];
+  const double x[2] = {vl < gl ? gl : (vl > gu ? gu : vl), vu < gl ? gl : (vu > gu ? gu : vu)};
+  int cnt[2];
+  sturm_counts<2>(n, d, e2, pivmin, x, cnt);
+  if (vl < gl) cnt[0] = 0; else if (vl >= gu) cnt[0] = n;
+  if (vu < gl) cnt[1] = 0; else if (vu >= gu) cnt[1] = n;
+  out[0] = cnt[0] + 1;
+  out[1] = cnt[1];
+}
+
 template <int G>
 void launch_bisect(hipStream_t s, int n, const double *d, const double *e2, const double *params, int il, int m,
                    double *w) {
@@ -167,6 +188,17 @@ void stebz(hipStream_t s, int n, const double *d, const double *e, int il, int i
     case 16: launch_bisect<16>(s, n, d, e2, params, il, m, w); break;
     default: launch_bisect<4>(s, n, d, e2, params, il, m, w); break;
   }
+}
+
+int *stebz_window(hipStream_t s, int n, const double *d, const double *e, double vl, double vu, void *work) {
+  double *e2 = (double *)work;
+  double *params = (double *)((char *)work + stebz_work_bytes(n) - 256);
+  int *out = (int *)(params + 8);            // (the last 256 bytes: params[0..4], then the two indices)
+  if (n <= 0) return out;
+  const int G = g_stebz_lanes;
+  hipLaunchKernelGGL(stebz_prep, dim3(1), dim3(kPrepThreads), 0, s, n, d, e, e2, params, log2i(G * kStebzK));
+  hipLaunchKernelGGL(stebz_window_count, dim3(1), dim3(64), 0, s, n, d, e2, params, vl, vu, out);
+  return out;
 }
 
 }  // namespace ek

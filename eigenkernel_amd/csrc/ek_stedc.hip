@@ -622,7 +622,7 @@ __global__ void dc_final_rank_kernel(int n, DcBufs b, double *__restrict__ w, in
 
 // ------------------------------------------------------------------ selected eigenvectors only
 __device__ __forceinline__ int sel_rank(const StedcSelect &q, int l) {
-  return ((l / q.nb) * q.npcol + q.mycol) * q.nb + l % q.nb;
+  return q.first + ((l / q.nb) * q.npcol + q.mycol) * q.nb + l % q.nb;
 }
 
 // selcol[l] = basis column (root / deflated column of the top merge) that carries rank r(l);

@@ -130,6 +130,12 @@ def load_library(path=None):
         "ek_hip_stebz": (c_int, [c_int, _dp, _dp, c_int, c_int, _dp]),
         "ek_hip_debug_values_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int]),
         "ek_hip_debug_set_stebz": (c_int, [c_int]),
+        "ek_hip_eigenpairs_device": (c_int, [c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, vp, c_int, vp, c_int,
+                                             _ip, _ip, vp, vp, c_int, c_int, _dp, c_int]),
+        "ek_hip_eigenpairs": (c_int, [c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, _dp, c_int, _dp, c_int,
+                                      _ip, _ip, _dp, _dp, c_int, c_int, _dp, c_int]),
+        "ek_hip_stebz_range": (c_int, [c_int, _dp, _dp, c_dbl, c_dbl, _ip, _ip, _dp]),
+        "ek_hip_debug_window_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, c_int]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -164,6 +170,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_potrf_team_profile", "ek_hip_debug_potrf_team_profile_get",
     "ek_hip_eigenvalues_device", "ek_hip_eigenvalues", "ek_hip_stebz",
     "ek_hip_debug_values_workspace_bytes", "ek_hip_debug_set_stebz",
+    "ek_hip_eigenpairs_device", "ek_hip_eigenpairs", "ek_hip_stebz_range", "ek_hip_debug_window_workspace_bytes",
 )
 
 
@@ -451,6 +458,23 @@ def stebz(d, e, il=1, iu=None):
     return w[:max(iu - int(il) + 1, 0)] if n else w[:0]
 
 
+def stebz_range(d, e, vl, vu):
+    """DSTEBZ('V', 'E') on the GPU (ek_hip_stebz_range): the eigenvalues of the symmetric tridiagonal (d, e) in
+    (vl, vu].  Returns (w, il): w ascending (bit-identical to stebz(d, e, il, il + len(w) - 1)), il the 1-based index of
+    the first.  Raises SolverError on a nonzero info."""
+    lib = load_library()
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    n = d.shape[0]
+    ee = np.zeros(max(n, 1)); ee[:max(n - 1, 0)] = np.asarray(e, dtype=np.float64)[:max(n - 1, 0)]
+    w = np.zeros(max(n, 1))
+    il, m = ctypes.c_int(0), ctypes.c_int(0)
+    info = lib.ek_hip_stebz_range(n, _P(d) if n else None, _P(ee), float(vl), float(vu), ctypes.byref(il),
+                                  ctypes.byref(m), _P(w))
+    if info != 0:
+        raise SolverError("ek_hip_stebz_range failed", info)
+    return w[:m.value].copy(), il.value
+
+
 def ormtr(Ar, tau, Z):
     """PDORMTR('L','L','N') (solver_scalapack_all.f90:115). Returns (QZ, info)."""
     lib = load_library()
@@ -540,6 +564,48 @@ def eigenvalues(A, B=None, il=1, iu=None, stage_seconds=None):
     if info != 0:
         raise SolverError("ek_hip_eigenvalues failed", info)
     return w[:max(iu - int(il) + 1, 0)] if n else w[:0]
+
+
+def window_workspace_bytes(problem, n, vectors=True, by_value=False, m=None):
+    """Bytes of device workspace one window call (ek_hip_eigenpairs*) with m pairs asks for (host arithmetic)."""
+    m = n if m is None else m
+    return int(load_library().ek_hip_debug_window_workspace_bytes(int(problem), int(n), 1 if vectors else 0,
+                                                                  1 if by_value else 0, int(m)))
+
+
+def eigenpairs(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, stage_seconds=None):
+    """A window of eigenpairs of A x = l x, or of A x = l B x with B SPD (ek_hip_eigenpairs; PDSYEVX's RANGE).
+    By index: il..iu (1-based; defaults 1 and n).  By value: vl and / or vu given -> the eigenvalues in (vl, vu] (a missing
+    bound is -inf / +inf).  vectors=False: eigenvalues only.  A and B are not modified.  Returns (w, Z or None, ifirst):
+    w the m eigenvalues ascending, Z (n x m) their eigenvectors, ifirst the 1-based index of the first.  Raises
+    SolverError on a nonzero info."""
+    lib = load_library()
+    A = _farr(A)
+    n = A.shape[0]
+    problem = 0 if B is None else 1
+    Bf = _farr(B) if B is not None else None
+    by_value = vl is not None or vu is not None
+    if by_value and (il is not None or iu is not None):
+        raise ValueError("give either il / iu or vl / vu")
+    rng = 1 if by_value else 0
+    vl = -np.inf if vl is None else float(vl)
+    vu = np.inf if vu is None else float(vu)
+    il = 1 if il is None else int(il)
+    iu = n if iu is None else int(iu)
+    cap = n if by_value else max(iu - il + 1, 0)
+    w = np.zeros(max(cap, 1))
+    Z = np.zeros((max(n, 1), max(cap, 1)), order="F") if vectors else None
+    m, ifirst = ctypes.c_int(0), ctypes.c_int(0)
+    st = stage_seconds
+    info = lib.ek_hip_eigenpairs(problem, 1 if vectors else 0, rng, n, vl, vu, il, iu, _P(A),
+                                 max(n, 1), _P(Bf) if Bf is not None else None, max(n, 1), ctypes.byref(m),
+                                 ctypes.byref(ifirst), _P(w), _P(Z) if vectors else None, max(n, 1),
+                                 max(cap, 1) if vectors else 0, _P(st) if st is not None else None,
+                                 0 if st is None else len(st))
+    if info != 0:
+        raise SolverError("ek_hip_eigenpairs failed", info)
+    k = m.value
+    return w[:k].copy(), (Z[:n, :k].copy(order="F") if vectors else None), ifirst.value
 
 
 def sy2sb(A):

@@ -406,14 +406,20 @@ contains
     character(len=*), intent(in) :: msg
     integer, intent(in) :: code
     integer(c_int) :: rc
+    integer :: status
     if (my_rank == 0) then
       write (0, '("[Error] ", A)') msg
       flush (0)
     end if
     flush (6)
+    ! Every rank is here (each call site decides on values all ranks share), so the job ends with a clean finalize
+    ! and a non-zero exit status: the launcher then forwards what rank 0 wrote before it exits.  An MPI_Abort can end
+    ! the job before the launcher has read that message.
     rc = ekm_barrier()
-    call ekm_abort(int(max(1, abs(code)), c_int))
-    stop 1
+    rc = ekm_finalize()
+    status = max(1, abs(code))
+    if (mod(status, 256) == 0) status = 1           ! (an exit status keeps the low 8 bits only)
+    error stop status
   end subroutine die
 
   ! One rank alone has failed: it says so itself and takes the job down.

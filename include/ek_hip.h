@@ -63,7 +63,9 @@ extern "C" {
 int ek_hip_version(void);                       /* 100*major + minor.  2: round 5 (version 1's
                                                  * ek_hip_comm_peer_enable / _disable are gone since
                                                  * round 4: INTEGRATION.md 5); 3: the eigenvalues-only
-                                                 * entries ek_hip_eigenvalues* and ek_hip_stebz */
+                                                 * entries ek_hip_eigenvalues* and ek_hip_stebz.  Still 3
+                                                 * with the window entries ek_hip_eigenpairs* and
+                                                 * ek_hip_stebz_range: their symbols are the signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
 const char *ek_hip_stage_name(int stage);       /* reference event name of a stage index    */
@@ -141,6 +143,43 @@ int ek_hip_eigenvalues(int problem, int n, int il, int iu, const double *A, int 
  * tridiagonal d(n), e(n-1) into w(iu-il+1), bit-identical per index whatever the range.  info -k for argument k
  * (-2 / -3 also for NaN / Inf in d / e). */
 int ek_hip_stebz(int n, const double *d, const double *e, int il, int iu, double *w);
+
+/* A window of eigenpairs -- LAPACK DSYEVX / DSYGVX, ScaLAPACK PDSYEVX with RANGE = 'I' or 'V': the same reduction and
+ * tridiagonalisation as ek_hip_solve; then, for values only, the bisection of ek_hip_eigenvalues, and for values and
+ * vectors the divide & conquer restricted to the window's eigenvectors (its top merge forms those columns alone), with
+ * the back-transformation and the recovery on those m columns.  NOT COLLECTIVE, as ek_hip_eigenvalues.
+ *   problem, A, B : as in ek_hip_solve (0 standard, 1 generalized with B SPD; lower triangles referenced)
+ *   jobz          : 0 values only, 1 values and eigenvectors
+ *   range         : 0 = 'I': indices il..iu (1-based, 1 <= il <= iu <= n; vl, vu not referenced)
+ *                   1 = 'V': the eigenvalues in the half-open interval (vl, vu], vl < vu, -Inf / +Inf allowed (il, iu
+ *                   not referenced); the bounds are counted on the tridiagonal (Sturm counts, as DSTEBZ), so a bound
+ *                   within rounding of an eigenvalue may count it on either side
+ *   m, ifirst     : out: the number of pairs and the global 1-based index of the first (m = 0 is success)
+ *   w             : out: m eigenvalues, ascending; room for iu-il+1 ('I') or n ('V') doubles.  A value is
+ *                   bit-identical to the one ek_hip_eigenvalues returns for its index when jobz = 0, and to the one
+ *                   ek_hip_solve_device returns when jobz = 1.  The two may differ in the last bits.
+ *   Z, ldz, zcap  : jobz = 1: n x zcap, ldz >= n; columns 0..m-1 receive the eigenvectors of indices ifirst..ifirst+m-1
+ *                   (B-orthonormal for problem 1).  Not referenced when jobz = 0.  m > zcap: info -18 with *m set and
+ *                   nothing written to w or Z ('I': before any device work; 'V': after the count)
+ *   stage_seconds : NULL or up to EK_HIP_N_STAGES doubles: the count and the divide & conquer or the bisection in
+ *                   EK_STAGE_STEDC
+ * Workspace: values only, the eigenvalues-only plan; 'I' with vectors, the plan of ek_hip_solve_device with n_vec = m;
+ * 'V' with vectors, the full plan (m is known only after the tridiagonalisation).
+ * info: -k for argument k (checked before any device work; -9 also when A contains NaN/Inf); a B that is not SPD gives
+ * the positive info of ek_hip_solve_device for that B; <= -1000 HIP runtime error; -992 as in ek_hip_solve.
+ * The device form works in place as ek_hip_eigenvalues_device: dA and dB come back as after the tridiagonalisation
+ * (dA) and the Cholesky factorisation (dB); dw and dZ are device memory. */
+int ek_hip_eigenpairs_device(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                             double *dA, int lda, double *dB, int ldb, int *m, int *ifirst,
+                             double *dw, double *dZ, int ldz, int zcap, double *stage_seconds, int n_stages);
+/* host arrays A (lda), B (ldb), w, Z (ldz); A and B are left untouched (the call works on device copies) */
+int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                      const double *A, int lda, const double *B, int ldb, int *m, int *ifirst,
+                      double *w, double *Z, int ldz, int zcap, double *stage_seconds, int n_stages);
+/* The stage alone, host arrays: DSTEBZ('V', 'E') -- the eigenvalues of the symmetric tridiagonal d(n), e(n-1) in
+ * (vl, vu]: *il = the 1-based index of the first, *m = their number, w (n doubles) the values, bit-identical to what
+ * ek_hip_stebz returns for il..il+m-1.  info -k for argument k (-2 / -3 also for NaN / Inf in d / e). */
+int ek_hip_stebz_range(int n, const double *d, const double *e, double vl, double vu, int *il, int *m, double *w);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs

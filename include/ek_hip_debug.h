@@ -84,6 +84,10 @@ unsigned long long ek_hip_debug_values_workspace_bytes(int problem, int n);
 /* lanes per eigenvalue index of the bisection (ek_stebz.hip): 1, 2, 4, 8 or 16, each lane evaluating 2 points per pass
    (<= 0: the default, 4).  A tuning hook: the grid of the bisection, hence the last bits of the values, depends on it. */
 int ek_hip_debug_set_stebz(int lanes);
+/* workspace one window call (ek_hip_eigenpairs*) with m pairs asks for (host arithmetic, no GPU): jobz 0 the
+   eigenvalues-only plan; range 0 with vectors the plan of n_vec = m; range 1 with vectors the full plan, grown where the
+   window's compact D&C or back-transformation scratch could need more (m is then not referenced).  0: bad arguments. */
+unsigned long long ek_hip_debug_window_workspace_bytes(int problem, int n, int jobz, int range, int m);
 
 /* test aid: the next `times` bulge chasings of whole-path calls count as abandoned (exercises the repetition from the
    saved band and the -992 exit of ek_solve.hip) */
