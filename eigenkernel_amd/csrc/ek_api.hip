@@ -428,6 +428,74 @@ int ek_hip_trtrs(int n, int nrhs, const double *L_loc, const int desc_B[9], doub
   return 0;
 }
 
+int ek_hip_sygst_ibtype(int ibtype, int n, double *A_loc, const int desc_A[9], const double *L_loc,
+                        const int desc_B[9], double *scale) {
+  if (ibtype < 1 || ibtype > 3) return -1;
+  if (n < 0) return -2;
+  if (!A_loc && n > 0) return -3;
+  int rc = check_desc(desc_A, 4, n, n); if (rc) return rc;
+  if (!L_loc && n > 0) return -5;
+  rc = check_desc(desc_B, 6, n, n); if (rc) return rc;
+  if (ibtype == 1) return ek_hip_sygst(n, A_loc, desc_A, L_loc, desc_B, scale);
+  rc = ensure_init(); if (rc) return rc;
+  if (scale) *scale = 1.0;
+  if (n == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n);
+  void *ws;
+  rc = workspace(2 * al((size_t)ld * n * 8) + al(trmm_diag_doubles(n) * 8) + al((size_t)256 * ld * 8) +
+                 al(sygst_scratch_doubles(n) * 8), &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  double *dA = a.get<double>((size_t)ld * n);
+  double *dL = a.get<double>((size_t)ld * n);
+  double *diag = a.get<double>(trmm_diag_doubles(n));
+  double *work = a.get<double>((size_t)256 * ld);
+  double *scr = a.get<double>(sygst_scratch_doubles(n));
+  rc = h2d_matrix(n, n, A_loc, desc_A[8], dA, ld, s); if (rc) return rc;
+  rc = h2d_matrix(n, n, L_loc, desc_B[8], dL, ld, s); if (rc) return rc;
+  trmm_diag_blocks(s, n, dL, ld, diag);
+  sygst2_lower(s, n, dA, ld, dL, ld, diag, work, scr);
+  EK_HIP_CHECK(hipGetLastError());
+  rc = d2h_matrix(n, n, dA, ld, A_loc, desc_A[8], s); if (rc) return rc;
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ek_hip_trmm(int n, int nrhs, const double *L_loc, const int desc_B[9], double *Z_loc, const int desc_Z[9]) {
+  if (n < 0) return -1;
+  if (nrhs < 0) return -2;
+  if (!L_loc && n > 0) return -3;
+  int rc = check_desc(desc_B, 4, n, n); if (rc) return rc;
+  if (!Z_loc && n > 0 && nrhs > 0) return -5;
+  if (!desc_Z) return -6;
+  rc = check_desc(desc_Z, 6, n, desc_Z[3]); if (rc) return rc;
+  if (desc_Z[3] < nrhs) return -604;
+  rc = ensure_init(); if (rc) return rc;
+  if (n == 0 || nrhs == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n);
+  void *ws;
+  rc = workspace(al((size_t)ld * n * 8) + al((size_t)ld * nrhs * 8) + al(trmm_diag_doubles(n) * 8) +
+                 al((size_t)256 * nrhs * 8), &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  double *dL = a.get<double>((size_t)ld * n);
+  double *dZ = a.get<double>((size_t)ld * nrhs);
+  double *diag = a.get<double>(trmm_diag_doubles(n));
+  double *work = a.get<double>((size_t)256 * nrhs);
+  rc = h2d_matrix(n, n, L_loc, desc_B[8], dL, ld, s); if (rc) return rc;
+  rc = h2d_matrix(n, nrhs, Z_loc, desc_Z[8], dZ, ld, s); if (rc) return rc;
+  trmm_diag_blocks(s, n, dL, ld, diag);
+  trmm_lln(s, n, nrhs, dL, ld, diag, trmm_block_ld(n), dZ, ld, work);
+  EK_HIP_CHECK(hipGetLastError());
+  rc = d2h_matrix(n, nrhs, dZ, ld, Z_loc, desc_Z[8], s); if (rc) return rc;
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
 
 int ek_hip_sytrd(int n, double *A_loc, const int desc_A[9], double *d, double *e, double *tau) {
   if (n < 0) return -1;

@@ -499,6 +499,146 @@ void sygst_lower(hipStream_t s, int n, double *A, int lda, const double *L, int 
   sygst_rec(s, n, A, lda, L, ldl, invdiag, work, scratch);
 }
 
+// ---------------------------------------------------------------- triangular multiplies, C = L^T A L (ITYPE 2 / 3)
+// The multiplies recurse like the solves above (split_t, off-diagonal work in the GEMM) down to leaves of order <= 256
+// that sit on 256-aligned diagonal positions.  A leaf is one GEMM against a zero-masked lower copy of its diagonal block
+// (trmm_diag_blocks) and one copy back: after the Cholesky factorisation only B's lower triangle holds L, its strict
+// upper part is the caller's and is never read.
+
+// diag (ceil(n / ldd) blocks of ldd x ldd, ld ldd): block b <- the lower triangle of L(b ldd.., b ldd..), zeros elsewhere
+__global__ __launch_bounds__(256) void trmm_diag_kernel(int n, int ldd, const double *__restrict__ L, int ldl,
+                                                        double *__restrict__ diag) {
+  const int b = blockIdx.x, off = b * ldd;
+  const int nb = n - off < ldd ? n - off : ldd;
+  double *D = diag + (size_t)b * ldd * ldd;
+  const int per = ldd * ldd / gridDim.y;
+  for (int idx = blockIdx.y * per + threadIdx.x; idx < (blockIdx.y + 1) * per; idx += 256) {
+    const int i = idx % ldd, j = idx / ldd;
+    D[idx] = (i >= j && i < nb) ? L[(size_t)(off + i) + (size_t)(off + j) * ldl] : 0.0;
+  }
+}
+int trmm_block_ld(int n) { return n > kDiagNB ? 2 * NB : NB; }
+size_t trmm_diag_doubles(int n) {
+  const int ldd = trmm_block_ld(n);
+  return (size_t)ceil_div(n > 0 ? n : 1, ldd) * ldd * ldd;
+}
+void trmm_diag_blocks(hipStream_t s, int n, const double *L, int ldl, double *diag) {
+  if (n <= 0) return;
+  const int ldd = trmm_block_ld(n);
+  hipLaunchKernelGGL(trmm_diag_kernel, dim3(ceil_div(n, ldd), 16), dim3(256), 0, s, n, ldd, L, ldl, diag);
+}
+
+// X <- X L  (X: m x n, L: n x n lower)
+void trmm_rln(hipStream_t s, int m, int n, const double *L, int ldl, const double *diag, int ldd,
+              double *X, int ldx, double *work) {
+  if (m <= 0 || n <= 0) return;
+  if (n <= 2 * NB) {
+    gemm(s, false, false, m, n, n, 1.0, X, ldx, diag, ldd, 0.0, work, m);
+    copy_matrix(s, m, n, work, m, X, ldx);
+    return;
+  }
+  const int n1 = split_t(n), n2 = n - n1;
+  double *X2 = X + (size_t)n1 * ldx;
+  const double *L21 = L + n1, *L22 = L + (size_t)n1 + (size_t)n1 * ldl;
+  trmm_rln(s, m, n1, L, ldl, diag, ldd, X, ldx, work);
+  gemm(s, false, false, m, n1, n2, 1.0, X2, ldx, L21, ldl, 1.0, X, ldx);
+  trmm_rln(s, m, n2, L22, ldl, diag + (size_t)(n1 / ldd) * ldd * ldd, ldd, X2, ldx, work);
+}
+
+// X <- L^T X  (X: n x m)
+void trmm_llt(hipStream_t s, int n, int m, const double *L, int ldl, const double *diag, int ldd,
+              double *X, int ldx, double *work) {
+  if (m <= 0 || n <= 0) return;
+  if (n <= 2 * NB) {
+    gemm(s, true, false, n, m, n, 1.0, diag, ldd, X, ldx, 0.0, work, n);
+    copy_matrix(s, n, m, work, n, X, ldx);
+    return;
+  }
+  const int n1 = split_t(n), n2 = n - n1;
+  double *X2 = X + n1;
+  const double *L21 = L + n1, *L22 = L + (size_t)n1 + (size_t)n1 * ldl;
+  trmm_llt(s, n1, m, L, ldl, diag, ldd, X, ldx, work);
+  gemm(s, true, false, n1, m, n2, 1.0, L21, ldl, X2, ldx, 1.0, X, ldx);
+  trmm_llt(s, n2, m, L22, ldl, diag + (size_t)(n1 / ldd) * ldd * ldd, ldd, X2, ldx, work);
+}
+
+// X <- L X  (X: n x m)
+void trmm_lln(hipStream_t s, int n, int m, const double *L, int ldl, const double *diag, int ldd,
+              double *X, int ldx, double *work) {
+  if (m <= 0 || n <= 0) return;
+  if (n <= 2 * NB) {
+    gemm(s, false, false, n, m, n, 1.0, diag, ldd, X, ldx, 0.0, work, n);
+    copy_matrix(s, n, m, work, n, X, ldx);
+    return;
+  }
+  const int n1 = split_t(n), n2 = n - n1;
+  double *X2 = X + n1;
+  const double *L21 = L + n1, *L22 = L + (size_t)n1 + (size_t)n1 * ldl;
+  trmm_lln(s, n2, m, L22, ldl, diag + (size_t)(n1 / ldd) * ldd * ldd, ldd, X2, ldx, work);
+  gemm(s, false, false, n2, m, n1, 1.0, L21, ldl, X, ldx, 1.0, X2, ldx);
+  trmm_lln(s, n1, m, L, ldl, diag, ldd, X, ldx, work);
+}
+
+// X <- L^T X where only the lower triangle of the (square) result is wanted; reads only the lower triangle of X.
+// With C = L^T X: C11 = L11^T X11 + L21^T X21 (lower), C21 = L22^T X21, C22 = L22^T X22 (lower).
+static void trmm_llt_lower(hipStream_t s, int n, const double *L, int ldl, const double *diag, int ldd,
+                           double *X, int ldx, double *work) {
+  if (n <= 0) return;
+  if (n <= 2 * NB) { trmm_llt(s, n, n, L, ldl, diag, ldd, X, ldx, work); return; }
+  const int n1 = split_t(n), n2 = n - n1;
+  const double *L21 = L + n1, *L22 = L + (size_t)n1 + (size_t)n1 * ldl;
+  const double *diag2 = diag + (size_t)(n1 / ldd) * ldd * ldd;
+  double *X21 = X + n1, *X22 = X + (size_t)n1 + (size_t)n1 * ldx;
+  trmm_llt_lower(s, n1, L, ldl, diag, ldd, X, ldx, work);
+  gemm(s, true, false, n1, n1, n2, 1.0, L21, ldl, X21, ldx, 1.0, X, ldx, /*lower_only=*/true);   // (X21 still X's)
+  trmm_llt(s, n2, n1, L22, ldl, diag2, ldd, X21, ldx, work);
+  trmm_llt_lower(s, n2, L22, ldl, diag2, ldd, X22, ldx, work);
+}
+
+// Recursive blocked DSYGST(itype = 2 / 3, 'L'), C = L^T A L:  with A = [A11 .; A21 A22], L = [L11 0; L21 L22]
+//   C11 = sygst2(A11, L11)
+//   A21 <- A21 L11;  T = A22 L21;  A21 <- A21 + 1/2 T
+//   A11 <- A11 + A21^T L21 + L21^T A21            (SYR2K, lower: one full product and a fold)
+//   A21 <- A21 + 1/2 T;  A21 <- L22^T A21
+//   C22 = sygst2(A22, L22)
+// ~n^3 flops, the count of type 1.  Scratch per level: T (n2 x n1), then A22 in full (n2 x n2) whose place the product
+// of the SYR2K (n1 x n1) takes once T is formed: n2 n1 + max(n1, n2)^2 = max(n1, n2) n doubles.  Above the direct order
+// split_t gives max(n1, n2) <= n / 2 + 255, which sygst_scratch_doubles(n) = n^2 / 2 + 256 n + 32768 covers.
+static void sygst2_rec(hipStream_t s, int n, double *A, int lda, const double *L, int ldl, const double *diag, int ldd,
+                       double *work, double *scratch) {
+  if (n <= 0) return;
+  if (n <= sygst_direct()) {
+    // as type 1: the full right multiply, then the left multiply restricted to the lower triangle
+    symmetrize_lower(s, n, A, lda);
+    trmm_rln(s, n, n, L, ldl, diag, ldd, A, lda, work);
+    trmm_llt_lower(s, n, L, ldl, diag, ldd, A, lda, work);
+    return;
+  }
+  const int n1 = split_t(n), n2 = n - n1;
+  double *A21 = A + n1, *A22 = A + (size_t)n1 + (size_t)n1 * lda;
+  const double *L21 = L + n1, *L22 = L + (size_t)n1 + (size_t)n1 * ldl;
+  const double *diag2 = diag + (size_t)(n1 / ldd) * ldd * ldd;
+  sygst2_rec(s, n1, A, lda, L, ldl, diag, ldd, work, scratch);
+  trmm_rln(s, n2, n1, L, ldl, diag, ldd, A21, lda, work);
+  double *T = scratch, *F = scratch + (size_t)n2 * n1;            // n2 x n1; A22 in full (n2 x n2), then P (n1 x n1)
+  hipLaunchKernelGGL(full_from_lower_kernel, grid_mn(n2, n2), dim3(256), 0, s, n2, A22, lda, F, n2);
+  gemm(s, false, false, n2, n1, n2, 1.0, F, n2, L21, ldl, 0.0, T, n2);
+  hipLaunchKernelGGL(axpy_matrix_kernel, grid_mn(n2, n1), dim3(256), 0, s, n2, n1, 0.5, T, n2, A21, lda);
+  gemm(s, true, false, n1, n1, n2, -1.0, A21, lda, L21, ldl, 0.0, F, n1);                          // P = -A21^T L21
+  hipLaunchKernelGGL(syr2k_fold_kernel, dim3(ceil_div(n1, 32), ceil_div(n1, 32)), dim3(256), 0, s, n1, F, n1, A, lda);
+  hipLaunchKernelGGL(axpy_matrix_kernel, grid_mn(n2, n1), dim3(256), 0, s, n2, n1, 0.5, T, n2, A21, lda);
+  trmm_llt(s, n2, n1, L22, ldl, diag2, ldd, A21, lda, work);
+  sygst2_rec(s, n2, A22, lda, L22, ldl, diag2, ldd, work, scratch);
+}
+
+// A <- L^T A L, lower triangles in and out (PDSYGST(2 or 3, 'L')).  diag: trmm_diag_blocks of L.
+// work: >= 256 * n doubles; scratch: >= sygst_scratch_doubles(n) doubles.
+void sygst2_lower(hipStream_t s, int n, double *A, int lda, const double *L, int ldl, const double *diag,
+                  double *work, double *scratch) {
+  if (n <= 0) return;
+  sygst2_rec(s, n, A, lda, L, ldl, diag, trmm_block_ld(n), work, scratch);
+}
+
 namespace {
 inline size_t al256c(size_t b) { return (b + 255) & ~(size_t)255; }
 struct PotrfDistLayout {

@@ -115,6 +115,24 @@ void trtri256_blocks(hipStream_t s, int n, const double *L, int ldl, const doubl
 void trsm_register_inv256(const double *invdiag, const double *inv256, int n);
 void sygst_lower(hipStream_t s, int n, double *A, int lda, const double *L, int ldl,
                  const double *invdiag, double *work, double *scratch);
+// Triangular multiplies (PDTRMM 'L', 'N'-unit) and the reduction of ITYPE 2 / 3.  Their leaves (order <= 256) are GEMMs
+// against zero-masked lower copies of L's diagonal blocks, so the strict upper triangle of L's array is never read:
+// diag receives trmm_diag_doubles(n) doubles (ceil(n / ldd) blocks of ldd x ldd, ldd = trmm_block_ld(n): 256, or 128
+// for n <= 128).  A multiply takes the blocks of the L it is given (diag at its first block, 256-aligned in the whole L)
+// and work >= 256 * (rows or columns of X) doubles.
+int trmm_block_ld(int n);
+size_t trmm_diag_doubles(int n);
+void trmm_diag_blocks(hipStream_t s, int n, const double *L, int ldl, double *diag);
+void trmm_rln(hipStream_t s, int m, int n, const double *L, int ldl, const double *diag, int ldd,
+              double *X, int ldx, double *work);   // X <- X L     (X m x n, L n x n)
+void trmm_llt(hipStream_t s, int n, int m, const double *L, int ldl, const double *diag, int ldd,
+              double *X, int ldx, double *work);   // X <- L^T X   (X n x m)
+void trmm_lln(hipStream_t s, int n, int m, const double *L, int ldl, const double *diag, int ldd,
+              double *X, int ldx, double *work);   // X <- L X     (X n x m)
+// A <- L^T A L, lower triangles (PDSYGST(2 / 3, 'L')); diag from trmm_diag_blocks(n, L); work >= 256 * n doubles;
+// scratch >= sygst_scratch_doubles(n) doubles
+void sygst2_lower(hipStream_t s, int n, double *A, int lda, const double *L, int ldl, const double *diag,
+                  double *work, double *scratch);
 // Distributed form (PDSYGST on a 1 x P grid): both triangular solves are sharded by columns,
 //   Y(:, C_r) = L^-1 A(:, C_r)   on the rank's contiguous column block C_r, one all-gather of Y,
 //   A'(:, S)  = L^-1 (Y(S, :))^T on every strip S the rank owns (r, r+P, ...: the strips the

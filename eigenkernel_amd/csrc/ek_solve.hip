@@ -456,6 +456,12 @@ PathPlan plan_path(int problem, int n, int n_vec, int nc_loc, int nranks_dist /*
 //   arm's plan) and n_vec = n for range 1 (the full plan); range 1 with m > win->zcap returns kWindowTooSmall before dw
 //   or dZ is written.
 //   dA / dB come back as after the full path's tridiagonalisation (A) and Cholesky factorisation (B).
+//
+// itype (problem 1, 1 x 1, no grid cell; ek_hip_sygvx*): the generalized problem of DSYGVX -- 1: A x = l B x, the
+// reduction C = L^-1 A L^-T and the recovery x = L^-T y; 2: A B x = l x, C = L^T A L and x = L^-T y; 3: B A x = l x,
+// C = L^T A L and x = L y.  Everything between the reduction and the recovery is the same for all three, and so is the
+// plan: the multiplies' masked diagonal blocks of L live in the array of Q1's reflectors (wV), which is free during the
+// reduction (zeroed again behind it) and after Q1.
 struct Window {
   int jobz, range, il, iu;
   double vl, vu;
@@ -465,7 +471,8 @@ struct Window {
 constexpr int kWindowTooSmall = -990;
 int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, double *dB, int ldb,
                         double *dw, double *dZ, int ldz, double *stage_seconds, int n_stages,
-                        const GridCell *cell = nullptr, HostPipe *pipe = nullptr, Window *win = nullptr) {
+                        const GridCell *cell = nullptr, HostPipe *pipe = nullptr, Window *win = nullptr,
+                        int itype = 1) {
   hipStream_t s = g_ctx.stream;
   const int nc_out = cell ? numroc0(n_vec, cell->nb, cell->mycol, cell->npcol) : n_vec;    // columns of the piece of Z this call returns
   const int nr_loc = cell ? numroc0(n, cell->nb, cell->myrow, cell->nprow) : n;
@@ -489,6 +496,7 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   const bool values_only = win && win->jobz == 0;
   const bool value_window = win && win->jobz == 1 && win->range == 1;
   if (win && (cell || pipe)) return -1;
+  if (itype != 1 && (problem != 1 || cell)) return -1;
   const PathPlan pl = plan_path(problem, n, n_vec, nc_loc, dist ? g_comm.nranks : 0, exch_bytes, values_only, value_window);
   const int ld = pl.ld, nblk = pl.nblk, zcols = pl.zcols;
   const bool two_stage = pl.two_stage, potrf_rl = pl.potrf_rl;
@@ -599,7 +607,9 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
       potrf_lower(s, n, wB, ld, dInv, g_ctx.d_info, twork);
     }
   }
-  if (problem == 1 && n >= 256) {      // leaves of 256 for the solves of the reduction and of the recovery (ek_chol.hip)
+  // leaves of 256 for the solves of the reduction and of the recovery (ek_chol.hip); types 2 and 3 reduce by multiplies,
+  // and only type 2 solves (in the recovery)
+  if (problem == 1 && n >= 256 && (itype == 1 || (itype == 2 && !values_only))) {
     trtri256_blocks(s, n, wB, ld, dInv, inv256, twork);
     trsm_register_inv256(dInv, inv256, n);
   }
@@ -618,8 +628,12 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
     if (dist && g_comm.nranks >= dist_min_ranks()) {
       const SygstMember me{wA, ld, wB, ld, dInv, twork, sscr, g_comm.rank};
       sygst_lower_dist(s, n, 1, &me, team_exchange(0));
-    } else {
+    } else if (itype == 1) {
       sygst_lower(s, n, wA, ld, wB, ld, dInv, twork, sscr);
+    } else {
+      trmm_diag_blocks(s, n, wB, ld, wV);
+      sygst2_lower(s, n, wA, ld, wB, ld, wV, twork, sscr);
+      EK_HIP_CHECK(hipMemsetAsync(wV, 0, trmm_diag_doubles(n) * 8, s));   // (as the stage-in left it)
     }
   }
   mark();                                                              // 3
@@ -790,14 +804,20 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   }
   mark();                                                              // 6
   if (problem == 1) {
+    // x = L^-T y (types 1, 2) or x = L y (type 3, against the masked blocks of L in wV: Q1 is done with it)
+    if (itype == 3) trmm_diag_blocks(s, n, wB, ld, wV);
+    auto recover = [&](int nc, double *zp) {
+      if (itype == 3) trmm_lln(s, n, nc, wB, ld, wV, trmm_block_ld(n), zp, ld, twork);
+      else trsm_llt(s, n, nc, wB, ld, dInv, zp, ld, twork);
+    };
     if (pipe) {
       for (int c0 = 0, nc = 0; c0 < nc_loc; c0 += nc) {
         nc = slab_width(c0);
-        trsm_llt(s, n, nc, wB, ld, dInv, zc + (size_t)c0 * ld, ld, twork);
+        recover(nc, zc + (size_t)c0 * ld);
         z_out(c0, nc);
       }
     } else {
-      trsm_llt(s, n, nc_loc, wB, ld, dInv, zc, ld, twork);
+      recover(nc_loc, zc);
     }
   } else if (pipe && !(two_stage_done && zslab < nc_loc)) {
     z_out(0, nc_loc);
@@ -1042,25 +1062,23 @@ int eigenpairs_args(int problem, int jobz, int range, int n, double vl, double v
 // both entries, under the lock: m, ifirst are set on success and on a value window too wide for zcap (-18)
 int eigenpairs_locked(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, double *dA, int lda,
                       double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ, int ldz, int zcap,
-                      double *stage_seconds, int n_stages) {
+                      double *stage_seconds, int n_stages, int itype) {
   Window win{jobz, range, il, iu, vl, vu, zcap, 0, 0};
   // plans: values only -> the eigenvalues-only plan; an index window -> the *_select arm's for n_vec = m; a value window
   // -> the full plan (its m is not known yet)
   const int n_vec = (jobz == 1 && range == 0) ? iu - il + 1 : n;
   int info = solve_device_locked(problem, n, n_vec, dA, lda, dB, ldb, dw, dZ, ldz, stage_seconds, n_stages, nullptr,
-                                 nullptr, &win);
+                                 nullptr, &win, itype);
   if (info == -4) info = -9;                 // NaN / Inf in A: A is argument 9 here
   if (info == kWindowTooSmall) info = -18;
   if (info == 0 || info == -18) { *m = win.m; *ifirst = win.first + 1; }
   return info;
 }
-}  // namespace
 
-extern "C" {
-
-int ek_hip_eigenpairs_device(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu,
-                             double *dA, int lda, double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ,
-                             int ldz, int zcap, double *stage_seconds, int n_stages) {
+// the device and host entries of ek_hip_eigenpairs* (itype 1) and ek_hip_sygvx* (problem 1), after their own checks
+int eigenpairs_device(int problem, int itype, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                      double *dA, int lda, double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ,
+                      int ldz, int zcap, double *stage_seconds, int n_stages) {
   int rc = eigenpairs_args(problem, jobz, range, n, vl, vu, il, iu, dA, lda, dB, ldb, m, ifirst, dw, dZ, ldz, zcap);
   if (rc) return rc;
   *m = 0; *ifirst = range == 0 ? il : 1;
@@ -1069,12 +1087,12 @@ int ek_hip_eigenpairs_device(int problem, int jobz, int range, int n, double vl,
   if (n == 0) return 0;
   std::lock_guard<std::mutex> lk(g_mu);
   return eigenpairs_locked(problem, jobz, range, n, vl, vu, il, iu, dA, lda, dB, ldb, m, ifirst, dw, dZ, ldz, zcap,
-                           stage_seconds, n_stages);
+                           stage_seconds, n_stages, itype);
 }
 
-int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, const double *A,
-                      int lda, const double *B, int ldb, int *m, int *ifirst, double *w, double *Z, int ldz, int zcap,
-                      double *stage_seconds, int n_stages) {
+int eigenpairs_host(int problem, int itype, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                    const double *A, int lda, const double *B, int ldb, int *m, int *ifirst, double *w, double *Z,
+                    int ldz, int zcap, double *stage_seconds, int n_stages) {
   int rc = eigenpairs_args(problem, jobz, range, n, vl, vu, il, iu, A, lda, B, ldb, m, ifirst, w, Z, ldz, zcap);
   if (rc) return rc;
   *m = 0; *ifirst = range == 0 ? il : 1;
@@ -1101,7 +1119,7 @@ int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double
   if (rc) return rc;
   auto t1 = std::chrono::steady_clock::now();
   int info = eigenpairs_locked(problem, jobz, range, n, vl, vu, il, iu, uA, n, uB, n, m, ifirst, uw, uZ, n, zc,
-                               stage_seconds, n_stages);
+                               stage_seconds, n_stages, itype);
   auto t2 = std::chrono::steady_clock::now();
   if (info == 0 && *m > 0) {
     hipError_t e = hipMemcpyAsync(w, uw, (size_t)*m * 8, hipMemcpyDeviceToHost, s);
@@ -1115,6 +1133,46 @@ int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double
     stage_seconds[EK_STAGE_COPY] += std::chrono::duration<double>(t1 - t0).count() +
                                     std::chrono::duration<double>(t3 - t2).count();
   return info;
+}
+}  // namespace
+
+extern "C" {
+
+int ek_hip_eigenpairs_device(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                             double *dA, int lda, double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ,
+                             int ldz, int zcap, double *stage_seconds, int n_stages) {
+  return eigenpairs_device(problem, 1, jobz, range, n, vl, vu, il, iu, dA, lda, dB, ldb, m, ifirst, dw, dZ, ldz, zcap,
+                           stage_seconds, n_stages);
+}
+
+int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, const double *A,
+                      int lda, const double *B, int ldb, int *m, int *ifirst, double *w, double *Z, int ldz, int zcap,
+                      double *stage_seconds, int n_stages) {
+  return eigenpairs_host(problem, 1, jobz, range, n, vl, vu, il, iu, A, lda, B, ldb, m, ifirst, w, Z, ldz, zcap,
+                         stage_seconds, n_stages);
+}
+
+// DSYGVX's three problem types on the window path: argument 1 is itype, the rest are ek_hip_eigenpairs*'s with B
+int ek_hip_sygvx_device(int itype, int jobz, int range, int n, double vl, double vu, int il, int iu, double *dA, int lda,
+                        double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ, int ldz, int zcap,
+                        double *stage_seconds, int n_stages) {
+  if (itype < 1 || itype > 3) return -1;
+  return eigenpairs_device(1, itype, jobz, range, n, vl, vu, il, iu, dA, lda, dB, ldb, m, ifirst, dw, dZ, ldz, zcap,
+                           stage_seconds, n_stages);
+}
+
+int ek_hip_sygvx(int itype, int jobz, int range, int n, double vl, double vu, int il, int iu, const double *A, int lda,
+                 const double *B, int ldb, int *m, int *ifirst, double *w, double *Z, int ldz, int zcap,
+                 double *stage_seconds, int n_stages) {
+  if (itype < 1 || itype > 3) return -1;
+  return eigenpairs_host(1, itype, jobz, range, n, vl, vu, il, iu, A, lda, B, ldb, m, ifirst, w, Z, ldz, zcap,
+                         stage_seconds, n_stages);
+}
+
+// Pure host arithmetic: the workspace of ek_hip_sygvx* -- type 1's window plan, whatever the type
+unsigned long long ek_hip_debug_sygvx_workspace_bytes(int itype, int n, int jobz, int range, int m) {
+  if (itype < 1 || itype > 3) return 0;
+  return ek_hip_debug_window_workspace_bytes(1, n, jobz, range, m);
 }
 
 // Pure host arithmetic: the workspace of a window call (ek_hip_eigenpairs*) with m pairs (range 1: any m)

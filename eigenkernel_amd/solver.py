@@ -136,6 +136,13 @@ def load_library(path=None):
                                       _ip, _ip, _dp, _dp, c_int, c_int, _dp, c_int]),
         "ek_hip_stebz_range": (c_int, [c_int, _dp, _dp, c_dbl, c_dbl, _ip, _ip, _dp]),
         "ek_hip_debug_window_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, c_int]),
+        "ek_hip_sygvx_device": (c_int, [c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, vp, c_int, vp, c_int,
+                                        _ip, _ip, vp, vp, c_int, c_int, _dp, c_int]),
+        "ek_hip_sygvx": (c_int, [c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, _dp, c_int, _dp, c_int,
+                                 _ip, _ip, _dp, _dp, c_int, c_int, _dp, c_int]),
+        "ek_hip_sygst_ibtype": (c_int, [c_int, c_int, _dp, _ip, _dp, _ip, _dp]),
+        "ek_hip_trmm": (c_int, [c_int, c_int, _dp, _ip, _dp, _ip]),
+        "ek_hip_debug_sygvx_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, c_int]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -171,6 +178,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_eigenvalues_device", "ek_hip_eigenvalues", "ek_hip_stebz",
     "ek_hip_debug_values_workspace_bytes", "ek_hip_debug_set_stebz",
     "ek_hip_eigenpairs_device", "ek_hip_eigenpairs", "ek_hip_stebz_range", "ek_hip_debug_window_workspace_bytes",
+    "ek_hip_sygvx_device", "ek_hip_sygvx", "ek_hip_sygst_ibtype", "ek_hip_trmm", "ek_hip_debug_sygvx_workspace_bytes",
 )
 
 
@@ -495,6 +503,27 @@ def trtrs(L, Z):
     return Z, info
 
 
+def sygst_ibtype(A, L, ibtype):
+    """PDSYGST(ibtype,'L') (ek_hip_sygst_ibtype): ibtype 1 A <- L^-1 A L^-T, 2 and 3 A <- L^T A L (lower triangles).
+    Returns (A_out, info)."""
+    lib = load_library()
+    A = np.array(_farr(A), order="F", copy=True)
+    L = _farr(L)
+    scale = ctypes.c_double(0.0)
+    info = lib.ek_hip_sygst_ibtype(int(ibtype), A.shape[0], _P(A), _I(_desc_for(A)), _P(L), _I(_desc_for(L)),
+                                   ctypes.byref(scale))
+    return A, info
+
+
+def trmm(L, Z):
+    """PDTRMM('L','L','N','N') (ek_hip_trmm): Z <- L Z, the recovery of itype 3. Returns (X, info)."""
+    lib = load_library()
+    L = _farr(L)
+    Z = np.array(_farr(Z), order="F", copy=True)
+    info = lib.ek_hip_trmm(L.shape[0], Z.shape[1], _P(L), _I(_desc_for(L)), _P(Z), _I(_desc_for(Z)))
+    return Z, info
+
+
 BAND_W = 64   # half bandwidth of the two-stage tridiagonalisation (kBandW in csrc/ek_common.h)
 
 
@@ -571,6 +600,44 @@ def window_workspace_bytes(problem, n, vectors=True, by_value=False, m=None):
     m = n if m is None else m
     return int(load_library().ek_hip_debug_window_workspace_bytes(int(problem), int(n), 1 if vectors else 0,
                                                                   1 if by_value else 0, int(m)))
+
+
+def sygvx_workspace_bytes(itype, n, vectors=True, by_value=False, m=None):
+    """Bytes of device workspace one ek_hip_sygvx* call with m pairs asks for (host arithmetic; type 1's for all types)."""
+    m = n if m is None else m
+    return int(load_library().ek_hip_debug_sygvx_workspace_bytes(int(itype), int(n), 1 if vectors else 0,
+                                                                 1 if by_value else 0, int(m)))
+
+
+def sygvx(A, B, itype=1, il=None, iu=None, vl=None, vu=None, vectors=True, stage_seconds=None):
+    """DSYGVX on the GPU (ek_hip_sygvx): itype 1 A x = l B x, 2 A B x = l x, 3 B A x = l x, B SPD.  The window and
+    the return value are those of eigenpairs: (w, Z or None, ifirst).  Z is B-orthonormal for types 1 and 2,
+    B^-1-orthonormal for type 3.  A and B are not modified.  Raises SolverError on a nonzero info."""
+    lib = load_library()
+    A = _farr(A)
+    Bf = _farr(B)
+    n = A.shape[0]
+    by_value = vl is not None or vu is not None
+    if by_value and (il is not None or iu is not None):
+        raise ValueError("give either il / iu or vl / vu")
+    rng = 1 if by_value else 0
+    vl = -np.inf if vl is None else float(vl)
+    vu = np.inf if vu is None else float(vu)
+    il = 1 if il is None else int(il)
+    iu = n if iu is None else int(iu)
+    cap = n if by_value else max(iu - il + 1, 0)
+    w = np.zeros(max(cap, 1))
+    Z = np.zeros((max(n, 1), max(cap, 1)), order="F") if vectors else None
+    m, ifirst = ctypes.c_int(0), ctypes.c_int(0)
+    st = stage_seconds
+    info = lib.ek_hip_sygvx(int(itype), 1 if vectors else 0, rng, n, vl, vu, il, iu, _P(A), max(n, 1), _P(Bf),
+                            max(n, 1), ctypes.byref(m), ctypes.byref(ifirst), _P(w), _P(Z) if vectors else None,
+                            max(n, 1), max(cap, 1) if vectors else 0, _P(st) if st is not None else None,
+                            0 if st is None else len(st))
+    if info != 0:
+        raise SolverError("ek_hip_sygvx failed", info)
+    k = m.value
+    return w[:k].copy(), (Z[:n, :k].copy(order="F") if vectors else None), ifirst.value
 
 
 def eigenpairs(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, stage_seconds=None):

@@ -65,7 +65,9 @@ int ek_hip_version(void);                       /* 100*major + minor.  2: round 
                                                  * round 4: INTEGRATION.md 5); 3: the eigenvalues-only
                                                  * entries ek_hip_eigenvalues* and ek_hip_stebz.  Still 3
                                                  * with the window entries ek_hip_eigenpairs* and
-                                                 * ek_hip_stebz_range: their symbols are the signal */
+                                                 * ek_hip_stebz_range, and with ek_hip_sygvx*,
+                                                 * ek_hip_sygst_ibtype and ek_hip_trmm: their symbols
+                                                 * are the signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
 const char *ek_hip_stage_name(int stage);       /* reference event name of a stage index    */
@@ -180,6 +182,24 @@ int ek_hip_eigenpairs(int problem, int jobz, int range, int n, double vl, double
  * (vl, vu]: *il = the 1-based index of the first, *m = their number, w (n doubles) the values, bit-identical to what
  * ek_hip_stebz returns for il..il+m-1.  info -k for argument k (-2 / -3 also for NaN / Inf in d / e). */
 int ek_hip_stebz_range(int n, const double *d, const double *e, double vl, double vu, int *il, int *m, double *w);
+
+/* DSYGVX / PDSYGVX: the three generalized problems, B SPD, lower triangles of A and B referenced --
+ *   itype 1: A x = l B x   (C = L^-1 A L^-T, x = L^-T y; X^T B X = I)
+ *   itype 2: A B x = l x   (C = L^T A L,     x = L^-T y; X^T B X = I)
+ *   itype 3: B A x = l x   (C = L^T A L,     x = L y;    X^T B^-1 X = I)
+ * with B = L L^T.  jobz, range, vl, vu, il, iu, m, ifirst, w, Z, ldz, zcap, stage_seconds: exactly as
+ * ek_hip_eigenpairs* (argument k here is argument k there, with itype in the place of problem); types 2 and 3 report
+ * their reduction in EK_STAGE_SYGST and their recovery in EK_STAGE_TRTRS.  NOT COLLECTIVE, one GPU.
+ * info: -1 for itype outside 1..3, then as ek_hip_eigenpairs*: -9 also for NaN / Inf in A, the positive info of
+ * ek_hip_solve_device for a B that is not SPD.  itype 1 returns w and Z bit-identical to ek_hip_eigenpairs*(problem 1);
+ * types 2 and 3 return bit-identical eigenvalues for the same A and B.  The workspace is type 1's for every type. */
+int ek_hip_sygvx_device(int itype, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                        double *dA, int lda, double *dB, int ldb, int *m, int *ifirst,
+                        double *dw, double *dZ, int ldz, int zcap, double *stage_seconds, int n_stages);
+/* host arrays A (lda), B (ldb), w, Z (ldz); A and B are left untouched (the call works on device copies) */
+int ek_hip_sygvx(int itype, int jobz, int range, int n, double vl, double vu, int il, int iu,
+                 const double *A, int lda, const double *B, int ldb, int *m, int *ifirst,
+                 double *w, double *Z, int ldz, int zcap, double *stage_seconds, int n_stages);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs
@@ -309,6 +329,13 @@ int ek_hip_ormtr(int n, int ncols, const double *A_loc, const int desc_A[9], con
 /* PDTRTRS('L','T','N', n, nrhs, B, 1,1, desc_B, Z, 1,1, desc_Z, info)  generalized_to_standard.f90:103 */
 int ek_hip_trtrs(int n, int nrhs, const double *L_loc, const int desc_B[9],
                  double *Z_loc, const int desc_Z[9]);
+/* PDSYGST(ibtype, 'L', n, A, 1,1, desc_A, B, 1,1, desc_B, scale, info) (B holds L): ibtype 1 is ek_hip_sygst,
+ * 2 and 3 give A <- L^T A L (lower triangle; the strict upper triangle of L is not read).  info -k for argument k. */
+int ek_hip_sygst_ibtype(int ibtype, int n, double *A_loc, const int desc_A[9],
+                        const double *L_loc, const int desc_B[9], double *scale);
+/* PDTRMM('L','L','N','N', n, nrhs, 1, B, 1,1, desc_B, Z, 1,1, desc_Z): Z <- L Z, the recovery of itype 3 (the strict
+ * upper triangle of L is not read).  Argument codes as ek_hip_trtrs. */
+int ek_hip_trmm(int n, int nrhs, const double *L_loc, const int desc_B[9], double *Z_loc, const int desc_Z[9]);
 
 /* Building block exposed for the parity tests: C = alpha op(A) op(B) + beta C on the
  * fp64 matrix cores (host arrays; transa/transb: 0 = 'N', 1 = 'T'; lower_only: only

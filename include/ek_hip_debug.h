@@ -88,6 +88,9 @@ int ek_hip_debug_set_stebz(int lanes);
    eigenvalues-only plan; range 0 with vectors the plan of n_vec = m; range 1 with vectors the full plan, grown where the
    window's compact D&C or back-transformation scratch could need more (m is then not referenced).  0: bad arguments. */
 unsigned long long ek_hip_debug_window_workspace_bytes(int problem, int n, int jobz, int range, int m);
+/* workspace one ek_hip_sygvx* call asks for (host arithmetic, no GPU): ek_hip_debug_window_workspace_bytes(1, n, jobz,
+   range, m) for every itype 1..3 (types 2 and 3 keep type 1's plan).  0: bad arguments. */
+unsigned long long ek_hip_debug_sygvx_workspace_bytes(int itype, int n, int jobz, int range, int m);
 
 /* test aid: the next `times` bulge chasings of whole-path calls count as abandoned (exercises the repetition from the
    saved band and the -992 exit of ek_solve.hip) */
