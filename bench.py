@@ -8,7 +8,7 @@ configs[2], the configuration the metric is quoted on), inputs resident in HBM w
 timed region starts (they are regenerated on the device before every step, outside the
 timed region, because the solve overwrites A and B as the reference does).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--order 16384] [--problem gep|sep] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--order 16384] [--problem gep|sep] [--dump-outputs DIR] [--full]
 
 For N > 1 there is one rank per GPU: either the driver launches them with torch.distributed.run, or --
 when no RANK is in the environment -- `python bench.py --gpus N` starts them itself as fresh child
@@ -27,7 +27,7 @@ headline ("scaling": "weak").  `--distribution replicas | columns | grid` force 
 the metric is quoted on; c4 and c5 name 8-GPU layouts: with fewer ranks the same problem is run on
 the ranks there are).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields plus what the timed steps themselves recorded:
   "roofline"        : the dominant kernel, timed live with HIP events on its launch stream in the
                       timed region: with the two-stage tridiagonalisation (orders >= 512) the
                       MFMA-bound application of the bulge-chasing reflectors (q2_apply_nb_kernel<4>),
@@ -35,7 +35,17 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                       record only while the kernel's source file is the one it was measured with;
   "roofline_stages" : per stage of the path, algorithmic flops / device seconds
                       against the fp64 matrix peak, and the flops the path executed where that differs
-                      (divide & conquer after deflation, counted on the device; both back-transformations);
+                      (divide & conquer after deflation, counted on the device; both back-transformations).
+After its timed steps a plain run only writes --dump-outputs and prints the line.  With N > 1 ranks under
+`--distribution auto` the grid probe described above runs as well, because it can become the headline (under
+`--distribution replicas` it is an extra of --full).
+
+`--full` adds everything else, each a run of its own after the timed steps:
+  "parity"          : the reference's acceptance quantities (residual, B-orthogonality) of the last timed step's
+                      output at full size, on the GPU against regenerated inputs; a missed bound fails the run
+                      (null in a plain run and with --no-parity-check);
+  "roofline"."measured_mfma_ceiling_tflops": what the library's own large GEMM sustains right now (null in a
+                      plain run);
   "value_incl_copies": the same solve through ek_hip_solve on HOST arrays (PCIe staging of A, B in
                       and Z, A, B, w out included -- SURVEY.md 8(d)'s t_solve; the copies overlap the stages),
                       the second of two calls, outside the timed region, in a child process that loads the library
@@ -46,7 +56,9 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   "cpu_baseline"    : the reference's ScaLAPACK call sequence on the host cores on a bounded sample
                       (smaller N) of the same generator, rank 0 at N=1 only, with the GPU path timed
                       at that SAME order beside it ("gpu_same_order").
-Every extra runs after the headline exists and is caught on its own: none of them can take the line down.
+The last three run after the headline exists and are caught one by one: none of them can take the line down.
+A plain run spends seconds outside its steps; --full, minutes (the CPU baseline at the headline order alone
+takes a few on 64 cores).
 
 `--dump-outputs DIR` writes what the last timed step returned (rank 0's, before any extra runs) as float64 .npy
 files: the eigenvalues, and a fixed, seeded sample of the eigenvector columns (all of them when they fit) with
@@ -692,20 +704,27 @@ def main():
                     help="with --distribution columns on ONE GPU: play rank --virtual-rank of a 1 x P grid "
                          "(the mode has no collective, so a rank's time does not depend on the others)")
     ap.add_argument("--virtual-rank", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run everything else the benchmark measures or checks: the full-size "
+                         "parity check, the live GEMM ceiling of the roofline, on one GPU the PCIe-inclusive step, the "
+                         "other BASELINE configurations and the CPU baselines, on N>1 GPUs with --distribution replicas "
+                         "the grid probe (minutes; the --no-* options below leave out single parts)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the ScaLAPACK baseline (mandatory under a profiler: 64 MPI ranks are not to be profiled)")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive step (value_incl_copies)")
+                    help="with --full: skip the ScaLAPACK baseline (mandatory under a profiler: 64 MPI ranks are not to be "
+                         "profiled)")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the PCIe-inclusive step (value_incl_copies)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the other BASELINE configurations (c2, c5, c4 at full size, a few steps each) that the "
-                         "default single-GPU run appends as \"other_configs\"")
+                    help="with --full: skip the other BASELINE configurations (c2, c5, c4 at full size, a few steps each) "
+                         "that a single-GPU run appends as \"other_configs\"")
     ap.add_argument("--no-symv-events", action="store_true")
     ap.add_argument("--symv-events-stride", type=int, default=8,
                     help="time the symv launch of every k-th column with HIP events (1 = all launches; "
                          "a pair of event records costs ~5 us of host time, 90 ms per solve at k = 1)")
-    ap.add_argument("--no-parity-check", action="store_true")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: skip the full-size parity check")
     ap.add_argument("--no-grid-probe", action="store_true",
-                    help="N>1 with --distribution replicas: skip the extra measurement of ONE problem on the "
-                         "1 x N grid with the tridiagonalisation distributed over RCCL (reported as \"grid_probe\")")
+                    help="N>1: skip the measurement of ONE problem on the 1 x N grid with the tridiagonalisation "
+                         "distributed over RCCL (reported as \"grid_probe\"; --distribution auto runs it to choose the "
+                         "headline, --distribution replicas with --full only)")
     ap.add_argument("--force-grid-probe", action="store_true",
                     help="run the grid probe at world size 1 too (rehearsal of the code path on a one-GPU box; "
                          "needs a torch.distributed launch)")
@@ -716,8 +735,8 @@ def main():
     ap.add_argument("--grid-probe-timeout", type=float, default=240.0,
                     help="seconds after which a stuck grid probe is abandoned (the main line is still printed)")
     ap.add_argument("--budget-seconds", type=int, default=480,
-                    help="wall-clock budget of the whole run: the CPU baseline at the headline order (minutes on 64 cores) is "
-                         "only started if its projection fits what is left")
+                    help="with --full: wall-clock budget of the whole run: the CPU baseline at the headline order (minutes on "
+                         "64 cores) is only started if its projection fits what is left")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0's eigenvalues and a seeded "
                          "sample of its eigenvector columns, float64 .npy, at most 64 MB) under DIR")
@@ -852,7 +871,7 @@ def main():
         lib.ek_hip_profile_kernels_get(kp_s, kp_l)
         lib.ek_hip_profile_kernels(0)
 
-    # Parity guard on the output of the LAST timed step, at the full benchmark size, through the
+    # --full: parity guard on the output of the LAST timed step, at the full benchmark size, through the
     # reference's own acceptance quantities (verifier.f90:75-204, 233-330) evaluated on the GPU
     # against freshly regenerated inputs (the solve destroyed its copies): outside the timed region.
     w = dw.cpu().numpy()
@@ -863,7 +882,7 @@ def main():
         sys.stderr.write("[bench] outputs of the last timed step: %s under %s\n" % (sizes, args.dump_outputs))
     assert (w[1:n_vec] >= w[:n_vec - 1]).all() and abs(w[:n_vec]).max() < 1e6
     parity = None
-    if not args.no_parity_check and nc_loc > 0:
+    if args.full and not args.no_parity_check and nc_loc > 0:
         regenerate(0)
         an, ave, mx, orth = (ctypes.c_double(0) for _ in range(4))
         dwc = dw
@@ -930,7 +949,8 @@ def main():
                 "bound": "mfma", "achieved": ach, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "frac": ach / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_source": tsrc,
                 "launches": int(kp_l[0]), "avg_launch_us": 1e6 * dur, "algorithmic_flops_per_launch": fl,
-                "measured_mfma_ceiling_tflops": gemm_ceiling(lib, torch, dev, dAs[0], n),   # live, see gemm_ceiling()
+                # live (see gemm_ceiling()): a run of its own, so --full only
+                "measured_mfma_ceiling_tflops": gemm_ceiling(lib, torch, dev, dAs[0], n) if args.full else None,
                 "other_kernels": {
                     "chase_pos_kernel (band -> tridiagonal: positions of the band in registers, sweeps pass through by mail)":
                         {"launches": int(kp_l[1]), "avg_launch_us": 1e6 * kp_s[1] / max(kp_l[1], 1)},
@@ -994,8 +1014,8 @@ def main():
         out["tflops_equiv_note"] = ("tflops_equiv prices the solve with SURVEY.md 8(d)'s nominal F(N) (BASELINE.json's metric); "
                                     "tflops_executed with what the path ran: D&C after deflation, both back-transformations of "
                                     "the two-stage form")
-        _pending = out      # the headline exists from here on: none of the extras below can take it down
-        if world == 1 and not columns and not args.no_host_path:
+        _pending = out      # the headline exists from here on: none of the extras below (--full) can take it down
+        if args.full and world == 1 and not columns and not args.no_host_path:
             try:
                 here = host_path_step(lib, solver, problem, n, n_vec)
                 child = host_path_child(problem, n, n_vec)
@@ -1011,7 +1031,8 @@ def main():
                     out["value_incl_copies"] = child
             except Exception as exc:
                 out["value_incl_copies"] = {"error": repr(exc)}
-        if world == 1 and not columns and not args.no_other_configs and (n, args.problem, n_vec) == (16384, "gep", 16384):
+        if (args.full and world == 1 and not columns and not args.no_other_configs
+                and (n, args.problem, n_vec) == (16384, "gep", 16384)):
             # every other BASELINE configuration at full size on this GPU, driver-timed in the same run
             del dAs[:]
             if dBs is not None:
@@ -1024,7 +1045,7 @@ def main():
                 except Exception as exc:
                     out["other_configs"][name] = {"error": repr(exc)}
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 base = cpu_baseline_scalapack(problem, args.scalapack_sample_n)
                 out["cpu_baseline"] = base if base is not None else cpu_baseline(problem, args.cpu_sample_n)
@@ -1108,8 +1129,9 @@ def main():
             except Exception as exc:
                 out["cpu_baseline"] = {"error": repr(exc)}
         _pending = out
-    if ((world > 1 or args.force_grid_probe) and dist is not None and args.distribution in ("auto", "replicas")
-            and not args.no_grid_probe):
+    # (under "auto" the probe can become the headline; under "replicas" it is an extra)
+    if ((world > 1 or args.force_grid_probe) and dist is not None and not args.no_grid_probe
+            and (args.distribution == "auto" or (args.full and args.distribution == "replicas"))):
         probe = grid_probe(args, lib, solver, dist, torch, dev, cdev, rank, world, n, problem, n_vec,
                            dAs, dBs, dZ, dw, regenerate)
         if out is not None:

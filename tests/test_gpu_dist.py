@@ -762,7 +762,7 @@ def test_bench_self_launch_rehearsed_on_one_gpu(hip):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
-                          "--rehearse-on-one-gpu", "--order", "1536", "--steps", "1", "--warmup", "1",
+                          "--rehearse-on-one-gpu", "--order", "1536", "--steps", "1", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--no-host-path", "--no-other-configs"],
                          capture_output=True, text=True, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -214,6 +214,35 @@ def test_bench_dumps_the_eigenpairs_of_its_last_timed_step(oracle, tmp_path):
     _check_pairs(A, B, w, Z)
 
 
+def test_bench_leaves_the_extras_to_full():
+    """A plain `bench.py` run times its steps and prints the line, nothing else: the parity check, the live GEMM ceiling
+    of the roofline, the step on host arrays and the CPU baseline run with --full only (the CPU baseline is left out
+    here: it takes minutes)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(*extra):
+        out = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+                              "--order", "1024", "--steps", "2", "--warmup", "1"] + list(extra),
+                             capture_output=True, text=True)
+        assert out.returncode == 0, out.stderr[-3000:]
+        return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+    plain = run()
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["roofline"]["launches"] > 0 and plain["roofline"]["measured_mfma_ceiling_tflops"] is None
+    assert plain["parity"] is None
+    assert not {"value_incl_copies", "other_configs", "cpu_baseline"} & set(plain), sorted(plain)
+    full = run("--full", "--no-cpu-baseline")
+    assert full["steps"] == 2 and "cpu_baseline" not in full
+    assert full["parity"]["residual_norm_max"] <= full["parity"]["bounds"]["residual_norm_max"]
+    assert full["parity"]["orthogonality"] <= full["parity"]["bounds"]["orthogonality"]
+    assert full["roofline"]["measured_mfma_ceiling_tflops"] > 0
+    assert "value_incl_copies" in full
+
+
 @pytest.mark.parametrize("name,n,gep", [("gep_n256_np4", 256, True), ("sep_n256_np4", 256, False),
                                          ("gep_n1000_np4", 1000, True)])
 def test_hip_vs_scalapack_goldens(hip, oracle, golden_dir, name, n, gep):
