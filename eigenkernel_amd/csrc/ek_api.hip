@@ -260,6 +260,7 @@ int ek_hip_finalize(void) {
   release_scratch_choice();
   release_user_images();
   release_pipe_streams();
+  release_batched();
   // a communicator does not outlive the library's device state
   comm_teardown();
   return 0;

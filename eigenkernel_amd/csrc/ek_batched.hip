@@ -1,0 +1,621 @@
+// ek_batched.hip -- ek_hip_eigenpairs_batched*: many small problems (order <= EK_HIP_BATCH_NMAX) in ONE launch.
+//
+// One workgroup owns a problem from its first load to its last store, and the matrix it works on lives in LDS the
+// whole time: there is no launch and no host synchronise between the stages.
+//
+//   0  the lower triangle of A is read once for NaN / Inf (info -5)
+//   1  B's lower triangle -> LDS, right-looking Cholesky in LDS, L -> dB (lower triangle); a pivot that is not
+//      positive (or outside 1e-290 .. 1e290, or NaN) ends the problem with info = its 1-based index
+//   2  A's lower triangle -> LDS as a full symmetric image; X = L^-1 A (a thread per column), C = X L^-T (a thread
+//      per row, lower half, then mirrored).  L is read back from dB, a column per step, staged through LDS one step
+//      ahead: at order 128 the image (129 KiB) leaves no room for a second one
+//   3  unblocked Householder tridiagonalisation of the image (DSYTD2, lower): d, e and the reflectors' tails go to
+//      dA's lower triangle as LAPACK lays them out; tau stays in LDS (tau_k = 2 / (1 + |tail_k|^2) restores it)
+//   4  implicit QL on (d, e), scaled by a power of two and taken upside down when d[0] outweighs d[n-1]: lane 0
+//      runs a sweep's rotation chain and leaves (c, s) in LDS, then every thread applies the sweep to the row of Z it
+//      owns -- dc_leaf_kernel's arithmetic with the barriers taken out of the chain; rank sort, w -> dw
+//   5  Z <- Q Z (reflector tails read back from dA, staged like L), Z <- L^-T Z, columns stored in ascending order
+//
+// Image layout: column-major with leading dimension NC + 1 (odd), NC the class size 32 / 64 / 128.  A wave that walks
+// down a column (consecutive rows) and a wave that walks along a row (stride NC + 1, odd) both hit 32 different
+// 64-bit banks per 32 lanes.  Threads: T = 2 NC; thread t is (row or column t % NC, half t / NC).
+//
+// Same bits wherever a problem sits: a problem's arithmetic depends on (n, A, B) alone -- fixed loop orders, sums
+// across a workgroup by a fixed butterfly and a fixed order over the waves, no atomics, one code path per class.
+#include "ek_api_internal.h"
+
+#include <cfloat>
+
+namespace ek {
+namespace batched {
+
+struct Args {
+  int problem, jobz, n;
+  double *A; int lda; long long sA;
+  double *B; int ldb; long long sB;
+  double *w;
+  double *Z; int ldz; long long sZ;
+  int *info;
+};
+
+// Sum (or maximum) over the workgroup, the same bits in every thread.  `red` holds 2 * NW doubles; the two halves
+// alternate so that a call needs one barrier: between two uses of a half lies the barrier of the call between them.
+template <int NW, bool MAX>
+__device__ __forceinline__ double block_reduce(double x, double *red, int &phase) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double y = __shfl_xor(x, o, 64);
+    x = MAX ? fmax(x, y) : x + y;
+  }
+  if (NW == 1) return x;
+  double *rr = red + phase * NW;
+  phase ^= 1;
+  if ((threadIdx.x & 63) == 0) rr[threadIdx.x >> 6] = x;
+  __syncthreads();
+  double s = rr[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s = MAX ? fmax(s, rr[w]) : s + rr[w];
+  return s;
+}
+
+// y[i * SY] -= a * x[i] for i0 <= i < i1, x and y in LDS: four elements' loads go out before the first store, so that
+// a thread pays the LDS latency once per four elements and not once per element.
+template <int SY>
+__device__ __forceinline__ void lds_axpy(double *y, const double *x, double a, int i0, int i1) {
+  int i = i0;
+  for (; i + 4 <= i1; i += 4) {
+    const double y0 = y[i * SY], y1 = y[(i + 1) * SY], y2 = y[(i + 2) * SY], y3 = y[(i + 3) * SY];
+    const double x0 = x[i], x1 = x[i + 1], x2 = x[i + 2], x3 = x[i + 3];
+    y[i * SY] = y0 - x0 * a;
+    y[(i + 1) * SY] = y1 - x1 * a;
+    y[(i + 2) * SY] = y2 - x2 * a;
+    y[(i + 3) * SY] = y3 - x3 * a;
+  }
+  for (; i < i1; ++i) y[i * SY] -= x[i] * a;
+}
+
+template <int NC, int T>
+__global__ __launch_bounds__(T) void batched_kernel(Args a) {
+  constexpr int LD = NC + 1, P = T / NC, NW = T / 64;
+  static_assert(P == 2 && T % 64 == 0, "two threads per row");
+  extern __shared__ double smem[];
+  double *S = smem;                       // NC x NC image, leading dimension LD
+  double *sd = S + NC * LD;               // d, e, tau: alive from stage 3 to the end
+  double *se = sd + NC, *st = se + NC;
+  double *sv = st + NC, *sw = sv + NC;    // stage 3: v, w;  stage 4: c, s of a sweep
+  double *sp = sw + NC;                   // stage 3: P x NC partial sums of the symv
+  double *sl = sp + P * NC;               // 2 x NC: a column of L or a reflector, and the next one
+  __shared__ double red[2 * (NW > 1 ? NW : 1)];
+  __shared__ int srank[NC];
+  __shared__ int s_state, s_m, s_lo;
+
+  const int t = threadIdx.x, n = a.n;
+  const int r = t % NC, sub = t / NC;
+  const bool row = r < n;
+  const long long pb = blockIdx.x;
+  double *A = a.A + pb * a.sA;
+  double *B = a.problem ? a.B + pb * a.sB : nullptr;
+  const int lda = a.lda, ldb = a.ldb;
+  int *info = a.info + pb;
+  int phase = 0;
+
+  // ---- 0: A finite?
+  {
+    int bad = 0;
+    if (row)
+      for (int j = sub; j <= r; j += P) bad |= !(fabs(A[r + (size_t)j * lda]) <= DBL_MAX);
+    if (__syncthreads_or(bad)) {
+      if (t == 0) *info = -5;
+      return;
+    }
+  }
+
+  if (a.problem) {
+    // ---- 1: B = L L^T in the image
+    if (row)
+      for (int j = sub; j <= r; j += P) S[r + j * LD] = B[r + (size_t)j * ldb];
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+      const double piv = S[j + j * LD];             // read by all after a barrier: the exit is uniform
+      if (!(piv > 1e-290) || !(piv < 1e290)) {      // chol64_upper_wg's rule: ek_hip_solve_device's info
+        if (t == 0) *info = j + 1;
+        return;
+      }
+      const double l = sqrt(piv);                   // the image keeps the pivot; the diagonal of L is formed on the way out
+      if (sub == 0 && row && r > j) S[r + j * LD] = S[r + j * LD] / l;
+      __syncthreads();
+      if (row && r > j) {
+        const double lr = S[r + j * LD];
+        for (int k = j + 1 + sub; k <= r; k += P) S[r + k * LD] -= lr * S[k + j * LD];
+      }
+      __syncthreads();
+    }
+    if (row)
+      for (int j = sub; j <= r; j += P) B[r + (size_t)j * ldb] = (r == j) ? sqrt(S[j + j * LD]) : S[r + j * LD];
+    __syncthreads();                                // L is in dB for the whole workgroup; the image is free
+  }
+
+  // ---- 2: A -> full symmetric image; C = L^-1 A L^-T
+  if (row)
+    for (int j = sub; j <= r; j += P) {
+      const double x = A[r + (size_t)j * lda];
+      S[r + j * LD] = x;
+      S[j + r * LD] = x;
+    }
+  if (a.problem) {
+    if (t < n) sl[t] = B[t];                        // column 0 of L
+    __syncthreads();
+    // X = L^-1 A: thread t owns column t of the image
+    for (int k = 0; k < n; ++k) {
+      const double *cur = sl + (k & 1) * NC;
+      double nx = 0.0;
+      if (k + 1 < n && t > k && t < n) nx = B[t + (size_t)(k + 1) * ldb];
+      if (t < n) {
+        double *col = S + t * LD;
+        const double xk = col[k] / cur[k];
+        col[k] = xk;
+        lds_axpy<1>(col, cur, xk, k + 1, n);
+      }
+      if (t < n) sl[((k + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+    if (t < n) sl[t] = B[t];
+    __syncthreads();
+    // C = X L^-T, lower half: thread t owns row t of the image, columns 0..t
+    for (int k = 0; k < n; ++k) {
+      const double *cur = sl + (k & 1) * NC;
+      double nx = 0.0;
+      if (k + 1 < n && t > k && t < n) nx = B[t + (size_t)(k + 1) * ldb];
+      if (t < n && k <= t) {
+        const double ck = S[t + k * LD] / cur[k];
+        S[t + k * LD] = ck;
+        lds_axpy<LD>(S + t, cur, ck, k + 1, t + 1);
+      }
+      if (t < n) sl[((k + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+    if (row)
+      for (int j = sub; j < r; j += P) S[j + r * LD] = S[r + j * LD];
+  }
+  __syncthreads();
+
+  // ---- 3: Householder tridiagonalisation of the image (both triangles kept, bitwise symmetric)
+  for (int k = 0; k + 1 < n; ++k) {
+    double x = 0.0;
+    if (sub == 0 && row && r >= k + 2) x = S[r + k * LD];
+    const double xn2 = block_reduce<NW, false>(x * x, red, phase);
+    const double alpha = S[k + 1 + k * LD], dk = S[k + k * LD];
+    double tau = 0.0, beta = alpha, scal = 0.0;
+    if (xn2 != 0.0) {
+      beta = -copysign(sqrt(alpha * alpha + xn2), alpha);
+      tau = (beta - alpha) / beta;
+      scal = 1.0 / (alpha - beta);
+    }
+    if (sub == 0 && row) {
+      if (r >= k + 2) {
+        const double vi = x * scal;
+        sv[r] = vi;
+        A[r + (size_t)k * lda] = vi;
+      } else if (r == k + 1) {
+        sv[r] = 1.0;
+        se[k] = beta;
+        st[k] = tau;
+        A[r + (size_t)k * lda] = beta;
+      } else if (r == k) {
+        sd[k] = dk;
+        A[k + (size_t)k * lda] = dk;
+      }
+    }
+    if (tau == 0.0) continue;                       // H = I (uniform: tau has the same bits in every thread)
+    __syncthreads();
+    if (row && r > k) {                             // p = C v, the columns split between the two halves
+      double acc = 0.0;
+      for (int j = k + 1 + sub; j < n; j += P) acc += S[r + j * LD] * sv[j];
+      sp[sub * NC + r] = acc;
+    }
+    __syncthreads();
+    double pr = 0.0, vr = 0.0;
+    if (sub == 0 && row && r > k) {
+      pr = tau * (sp[r] + sp[NC + r]);
+      vr = sv[r];
+    }
+    const double dot = block_reduce<NW, false>(pr * vr, red, phase);
+    const double al2 = -0.5 * tau * dot;
+    if (sub == 0 && row && r > k) sw[r] = pr + al2 * vr;
+    __syncthreads();
+    if (row && r > k) {                             // C -= v w^T + w v^T; (r, j) and (j, r) evaluate the same expression
+      const double vr2 = sv[r], wr2 = sw[r];
+      auto term = [&](int j, double vj, double wj) {
+        const bool up = j > r;
+        const double vh = up ? vj : vr2, wh = up ? wj : wr2, vl = up ? vr2 : vj, wl = up ? wr2 : wj;
+        return vh * wl + wh * vl;
+      };
+      int j = k + 1 + sub;
+      for (; j + 3 * P < n; j += 4 * P) {             // four elements' loads before the first store
+        double *c0 = S + r + j * LD;
+        const double a0 = c0[0], a1 = c0[P * LD], a2 = c0[2 * P * LD], a3 = c0[3 * P * LD];
+        const double v0 = sv[j], v1 = sv[j + P], v2 = sv[j + 2 * P], v3 = sv[j + 3 * P];
+        const double w0 = sw[j], w1 = sw[j + P], w2 = sw[j + 2 * P], w3 = sw[j + 3 * P];
+        c0[0] = a0 - term(j, v0, w0);
+        c0[P * LD] = a1 - term(j + P, v1, w1);
+        c0[2 * P * LD] = a2 - term(j + 2 * P, v2, w2);
+        c0[3 * P * LD] = a3 - term(j + 3 * P, v3, w3);
+      }
+      for (; j < n; j += P) S[r + j * LD] -= term(j, sv[j], sw[j]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double dl = S[(n - 1) * (LD + 1)];
+    sd[n - 1] = dl;
+    se[n - 1] = 0.0;
+    A[(size_t)(n - 1) * lda + (n - 1)] = dl;
+  }
+  __syncthreads();
+
+  // ---- 4: implicit QL with Z in the image
+  double unscale = 1.0;
+  {
+    double mx = 0.0;
+    int bad = 0;
+    if (sub == 0 && row) {
+      mx = fmax(fabs(sd[r]), fabs(se[r]));
+      bad = !(mx <= DBL_MAX);
+    }
+    if (__syncthreads_or(bad)) {                    // the reduction overflowed: a non-finite eigenvalue (k = n + 1)
+      if (t == 0) *info = 100000 + n + 1;
+      return;
+    }
+    const double anorm = block_reduce<NW, true>(mx, red, phase);
+    if (anorm > 0.0) {
+      int ex;
+      (void)frexp(anorm, &ex);
+      const double sc = ldexp(1.0, -ex);
+      unscale = ldexp(1.0, ex);
+      __syncthreads();
+      if (sub == 0 && row) { sd[r] *= sc; se[r] *= sc; }
+    }
+  }
+  __syncthreads();
+  // QL converges fast towards a small top; a matrix graded the other way (rank one: everything in d[0]) is taken
+  // upside down, T' = P T P, which QL sees as DSTEQR's QR sees T.  Z starts as P, so that Z' comes out as P Z'.
+  const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
+  {
+    double dr = 0.0, er = 0.0;
+    if (flip && sub == 0 && row) {
+      dr = sd[n - 1 - r];
+      er = (r < n - 1) ? se[n - 2 - r] : 0.0;
+    }
+    __syncthreads();
+    if (flip && sub == 0 && row) { sd[r] = dr; se[r] = er; }
+  }
+  if (a.jobz && row)
+    for (int j = sub; j < n; j += P) S[r + j * LD] = (r == (flip ? n - 1 - j : j)) ? 1.0 : 0.0;
+  __syncthreads();
+  {
+    const double eps = 1.1102230246251565e-16;
+    double *sc_ = sv, *ss_ = sw;
+    int failed = 0;
+    int iter = 0;                                   // lane 0's: sweeps so far, 30 n in all as in DSTEQR
+    for (int l = 0; l < n && !failed; ++l) {
+      while (true) {
+        if (t == 0) {
+          int m = l;                                // the first negligible e from l on, eight tests per round of loads
+          for (bool found = false; !found;) {
+            double dv[9], ev[8];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) dv[q] = sd[min(m + q, n - 1)];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) ev[q] = se[min(m + q, n - 1)];
+            int hit = -1;
+#pragma unroll
+            for (int q = 7; q >= 0; --q)
+              if (m + q >= n - 1 || fabs(ev[q]) <= eps * (fabs(dv[q]) + fabs(dv[q + 1]))) hit = q;
+            if (hit >= 0) { m = min(m + hit, n - 1); found = true; } else m += 8;
+          }
+          if (m == l) {
+            s_state = 0;
+          } else if (iter++ == 30 * n) {
+            s_state = 2;
+          } else {
+            const double dl = sd[l], el = se[l];
+            double g = (sd[l + 1] - dl) / (2.0 * el);
+            double rr = sqrt(g * g + 1.0);
+            g = sd[m] - dl + el / (g + copysign(rr, g));
+            double s = 1.0, c = 1.0, p = 0.0;
+            int i, lo = l;
+            bool under = false;
+            // d[i], e[i] are loaded one rotation ahead (no store of the chain touches them before their use), so
+            // that the chain waits for arithmetic only
+            double ei = se[m - 1], di = sd[m - 1], dup = sd[m];
+            for (i = m - 1; i >= l; --i) {
+              double en = 0.0, dn = 0.0;
+              if (i > l) { en = se[i - 1]; dn = sd[i - 1]; }
+              const double f = s * ei, bb = c * ei;
+              const double h = f * f + g * g;
+              if (!(h >= 1e-280)) {                 // recover from underflow (T has norm 1/2..1): split here
+                se[i + 1] = 0.0;
+                sd[i + 1] = dup - p;
+                se[m] = 0.0;
+                under = true;
+                lo = i + 1;
+                break;
+              }
+              // one lane works, but every instruction costs a whole wave's issue slot: 1 / sqrt(h) by the hardware's
+              // seed and two Newton steps serves r, s and c at a third of the instructions of a square root and two
+              // divisions (rounding: a few ulp in s and c, as DLARTG's own)
+              double y = __builtin_amdgcn_rsq(h);
+              y = y * (1.5 - 0.5 * h * y * y);
+              y = y * (1.5 - 0.5 * h * y * y);
+              rr = h * y;
+              se[i + 1] = rr;
+              s = f * y;
+              c = g * y;
+              g = dup - p;
+              rr = (di - g) * s + 2.0 * c * bb;
+              p = s * rr;
+              sd[i + 1] = g + p;
+              g = c * rr - bb;
+              sc_[i] = c;
+              ss_[i] = s;
+              dup = di; di = dn; ei = en;
+            }
+            if (!under) {
+              sd[l] = dup - p;
+              se[l] = g;
+              se[m] = 0.0;
+            }
+            s_state = 1; s_m = m; s_lo = lo;
+          }
+        }
+        __syncthreads();
+        const int state = s_state, m = s_m, lo = s_lo;
+        if (state == 1 && a.jobz && t < n) {        // the sweep's rotations on row t of Z
+          double *zr = S + t;
+          double f = zr[m * LD];
+          int i = m - 1;
+          for (; i - 3 >= lo; i -= 4) {             // four rotations' loads before the first store
+            const double z0 = zr[i * LD], z1 = zr[(i - 1) * LD], z2 = zr[(i - 2) * LD], z3 = zr[(i - 3) * LD];
+            const double c0 = sc_[i], c1 = sc_[i - 1], c2 = sc_[i - 2], c3 = sc_[i - 3];
+            const double s0 = ss_[i], s1 = ss_[i - 1], s2 = ss_[i - 2], s3 = ss_[i - 3];
+            zr[(i + 1) * LD] = s0 * z0 + c0 * f; f = c0 * z0 - s0 * f;
+            zr[i * LD] = s1 * z1 + c1 * f; f = c1 * z1 - s1 * f;
+            zr[(i - 1) * LD] = s2 * z2 + c2 * f; f = c2 * z2 - s2 * f;
+            zr[(i - 2) * LD] = s3 * z3 + c3 * f; f = c3 * z3 - s3 * f;
+          }
+          for (; i >= lo; --i) {
+            const double c = sc_[i], s = ss_[i], z0 = zr[i * LD];
+            zr[(i + 1) * LD] = s * z0 + c * f;
+            f = c * z0 - s * f;
+          }
+          zr[lo * LD] = f;
+        }
+        __syncthreads();
+        if (state == 2) failed = l + 1;
+        if (state != 1) break;
+      }
+    }
+    if (failed) {
+      if (t == 0) *info = 100000 + failed;
+      return;
+    }
+  }
+  // ascending order: rank sort (ties by index; a NaN sorts last so that the ranks stay a permutation)
+  if (sub == 0 && row) {
+    const double di = sd[r], ki = (di == di) ? di : INFINITY;
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const double dj = sd[j], kj = (dj == dj) ? dj : INFINITY;
+      rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
+    }
+    srank[r] = rank;
+    a.w[pb * n + rank] = di * unscale;
+  }
+  if (!a.jobz) {
+    if (t == 0) *info = 0;
+    return;
+  }
+  double *Z = a.Z + pb * a.sZ;
+  const int ldz = a.ldz;
+
+  // ---- 5: Z <- H_0 ... H_{n-3} Z (H_{n-2} = I), thread t owns column t of Z
+  if (n >= 3) {
+    if (t < n) sl[t] = (t >= n - 1) ? A[t + (size_t)(n - 3) * lda] : 0.0;
+    __syncthreads();
+    for (int k = n - 3, s = 0; k >= 0; --k, ++s) {
+      const double *cur = sl + (s & 1) * NC;
+      double nx = 0.0;
+      if (k >= 1 && t > k && t < n) nx = A[t + (size_t)(k - 1) * lda];
+      const double tau = st[k];
+      if (tau != 0.0 && t < n) {
+        double *col = S + t * LD;
+        double dot = col[k + 1];
+        for (int i = k + 2; i < n; ++i) dot += cur[i] * col[i];
+        dot *= tau;
+        col[k + 1] -= dot;
+        lds_axpy<1>(col, cur, dot, k + 2, n);
+      }
+      if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+  }
+  // Z <- L^-T Z
+  if (a.problem) {
+    __syncthreads();
+    if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
+    __syncthreads();
+    for (int i = n - 1, s = 0; i >= 0; --i, ++s) {
+      const double *cur = sl + (s & 1) * NC;
+      double nx = 0.0;
+      if (i >= 1 && t >= i - 1 && t < n) nx = B[t + (size_t)(i - 1) * ldb];
+      if (t < n) {
+        double *col = S + t * LD;
+        double acc = col[i];
+        for (int k = i + 1; k < n; ++k) acc -= cur[k] * col[k];
+        col[i] = acc / cur[i];
+      }
+      if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (row)
+    for (int j = sub; j < n; j += P) Z[r + (size_t)srank[j] * ldz] = S[r + j * LD];
+  if (t == 0) *info = 0;
+}
+
+template <int NC, int T>
+static int launch_class(hipStream_t s, int batch, const Args &a) {
+  constexpr size_t lds = (size_t)(NC * (NC + 1) + 9 * NC) * sizeof(double);
+  static bool raised = false;
+  if (lds > 64 * 1024 && !raised) {
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)batched_kernel<NC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds));
+    raised = true;
+  }
+  hipLaunchKernelGGL((batched_kernel<NC, T>), dim3(batch), dim3(T), lds, s, a);
+  EK_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// LDS bytes (dynamic part) and threads of the class that takes order n: host arithmetic for tools and DESIGN.md 12
+static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
+
+// per-problem status words: grown, never shrunk, released in ek_hip_finalize
+static int *g_dinfo = nullptr;
+static size_t g_dinfo_count = 0;
+
+}  // namespace batched
+
+namespace api {
+void release_batched() {
+  if (batched::g_dinfo) (void)hipFree(batched::g_dinfo);
+  batched::g_dinfo = nullptr;
+  batched::g_dinfo_count = 0;
+}
+}  // namespace api
+}  // namespace ek
+
+using namespace ek;
+using namespace ek::api;
+
+static int batched_check(int problem, int jobz, int n, int batch, const void *A, int lda, long long strideA,
+                         const void *B, int ldb, long long strideB, const void *w, const void *Z, int ldz,
+                         long long strideZ, const int *info, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (jobz != 0 && jobz != 1) return -2;
+  if (n < 0 || n > EK_HIP_BATCH_NMAX) return -3;
+  if (batch < 0) return -4;
+  if (n == 0 || batch == 0) { *nothing = true; return 0; }
+  if (!A) return -5;
+  if (lda < n) return -6;
+  if (strideA < (long long)lda * n) return -7;
+  if (problem == 1) {
+    if (!B) return -8;
+    if (ldb < n) return -9;
+    if (strideB < (long long)ldb * n) return -10;
+  }
+  if (!w) return -11;
+  if (jobz == 1) {
+    if (!Z) return -12;
+    if (ldz < n) return -13;
+    if (strideZ < (long long)ldz * n) return -14;
+  }
+  if (!info) return -15;
+  return 0;
+}
+
+// arguments checked, context up, g_mu held
+static int batched_device_locked(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                 double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                 long long strideZ, int *info, double *seconds) {
+  hipStream_t s = g_ctx.stream;
+  if ((size_t)batch > batched::g_dinfo_count) {
+    release_batched();
+    EK_HIP_CHECK(hipMalloc((void **)&batched::g_dinfo, (size_t)batch * sizeof(int)));
+    batched::g_dinfo_count = (size_t)batch;
+  }
+  batched::Args a{problem, jobz, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, batched::g_dinfo};
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (seconds) {
+    EK_HIP_CHECK(hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e != hipSuccess) { (void)hipEventDestroy(e0); return -1000 - (int)e; }
+    (void)hipEventRecord(e0, s);
+  }
+  int rc;
+  switch (batched::class_of(n)) {
+    case 32: rc = batched::launch_class<32, 64>(s, batch, a); break;
+    case 64: rc = batched::launch_class<64, 128>(s, batch, a); break;
+    default: rc = batched::launch_class<128, 256>(s, batch, a); break;
+  }
+  if (seconds) (void)hipEventRecord(e1, s);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(info, batched::g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
+  if (seconds) {
+    float ms = 0.f;
+    if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *seconds = (double)ms * 1e-3;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  return rc;
+}
+
+extern "C" {
+
+int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                     double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                     long long strideZ, int *info, double *seconds) {
+  bool nothing;
+  int rc = batched_check(problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                         &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return batched_device_locked(problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                               seconds);
+}
+
+int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                              const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                              long long strideZ, int *info, double *seconds) {
+  bool nothing;
+  int rc = batched_check(problem, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
+                         &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  // the caller's arrays are left as they are: the kernel works on device copies with the caller's own layout (what
+  // lies between the columns and between the problems travels with them, and comes back as it was)
+  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
+  const size_t cA = span(lda, strideA), cB = problem ? span(ldb, strideB) : 0, cZ = jobz ? span(ldz, strideZ) : 0;
+  const size_t cw = (size_t)batch * n;
+  const bool zpad = jobz && (ldz != n || strideZ != (long long)n * n);
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cA * 8);
+  if (!rc) rc = mem.alloc(&uw, cw * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
+  if (!rc && jobz) rc = mem.alloc(&uZ, cZ * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
+  if (zpad) EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
+  rc = batched_device_locked(problem, jobz, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info,
+                             seconds);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
+  if (jobz) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+}  // extern "C"

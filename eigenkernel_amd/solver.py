@@ -54,6 +54,7 @@ def load_library(path=None):
     lib = ctypes.CDLL(p)
     c_int, c_dbl, c_ull = ctypes.c_int, ctypes.c_double, ctypes.c_ulonglong
     vp = ctypes.c_void_p
+    c_ll = ctypes.c_longlong
     sigs = {
         "ek_hip_version": (c_int, []),
         "ek_hip_init": (c_int, [c_int]),
@@ -143,6 +144,10 @@ def load_library(path=None):
         "ek_hip_sygst_ibtype": (c_int, [c_int, c_int, _dp, _ip, _dp, _ip, _dp]),
         "ek_hip_trmm": (c_int, [c_int, c_int, _dp, _ip, _dp, _ip]),
         "ek_hip_debug_sygvx_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, c_int]),
+        "ek_hip_eigenpairs_batched_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp,
+                                                     vp, c_int, c_ll, _ip, _dp]),
+        "ek_hip_eigenpairs_batched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp,
+                                              _dp, c_int, c_ll, _ip, _dp]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -179,6 +184,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_values_workspace_bytes", "ek_hip_debug_set_stebz",
     "ek_hip_eigenpairs_device", "ek_hip_eigenpairs", "ek_hip_stebz_range", "ek_hip_debug_window_workspace_bytes",
     "ek_hip_sygvx_device", "ek_hip_sygvx", "ek_hip_sygst_ibtype", "ek_hip_trmm", "ek_hip_debug_sygvx_workspace_bytes",
+    "ek_hip_eigenpairs_batched_device", "ek_hip_eigenpairs_batched",
 )
 
 
@@ -673,6 +679,42 @@ def eigenpairs(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, stag
         raise SolverError("ek_hip_eigenpairs failed", info)
     k = m.value
     return w[:k].copy(), (Z[:n, :k].copy(order="F") if vectors else None), ifirst.value
+
+
+BATCH_NMAX = 128   # EK_HIP_BATCH_NMAX
+
+
+def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
+    """Many small problems in one launch (ek_hip_eigenpairs_batched): A (and B, SPD) of shape (batch, n, n) with
+    n <= BATCH_NMAX, lower triangles referenced.  Returns (w, Z or None, info): w[b] problem b's eigenvalues ascending,
+    Z[b][:, k] the eigenvector of w[b, k] (B-orthonormal with B), info[b] its status (0; k > 0: B[b] not SPD at pivot
+    k; -5: NaN / Inf in A[b]) -- the w and Z of a failed problem are unspecified, the others are unaffected.  A and B
+    are not modified.  seconds: None or a float64 array of one entry that receives the device time.  Raises SolverError
+    only when the call itself fails (illegal argument, HIP error), never for a problem's info."""
+    lib = load_library()
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("A must have shape (batch, n, n)")
+    batch, n = A.shape[0], A.shape[1]
+    problem = 0 if B is None else 1
+    # column-major per problem: the transpose of each C-ordered slice
+    At = np.ascontiguousarray(A.transpose(0, 2, 1))
+    Bt = None
+    if B is not None:
+        B = np.asarray(B, dtype=np.float64)
+        if B.shape != A.shape:
+            raise ValueError("B must have the shape of A")
+        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
+    w = np.zeros((batch, n))
+    Zt = np.zeros((batch, n, n)) if vectors else None
+    info = np.zeros(max(batch, 1), dtype=np.int32)
+    rc = lib.ek_hip_eigenpairs_batched(problem, 1 if vectors else 0, n, batch, _P(At), n, n * n,
+                                       _P(Bt) if Bt is not None else None, n, n * n, _P(w),
+                                       _P(Zt) if vectors else None, n, n * n, _I(info),
+                                       _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError("ek_hip_eigenpairs_batched failed", rc)
+    return w, (Zt.transpose(0, 2, 1) if vectors else None), info[:batch]
 
 
 def sy2sb(A):

@@ -66,8 +66,9 @@ int ek_hip_version(void);                       /* 100*major + minor.  2: round 
                                                  * entries ek_hip_eigenvalues* and ek_hip_stebz.  Still 3
                                                  * with the window entries ek_hip_eigenpairs* and
                                                  * ek_hip_stebz_range, and with ek_hip_sygvx*,
-                                                 * ek_hip_sygst_ibtype and ek_hip_trmm: their symbols
-                                                 * are the signal */
+                                                 * ek_hip_sygst_ibtype and ek_hip_trmm, and with
+                                                 * ek_hip_eigenpairs_batched*: their symbols are the
+                                                 * signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
 const char *ek_hip_stage_name(int stage);       /* reference event name of a stage index    */
@@ -200,6 +201,46 @@ int ek_hip_sygvx_device(int itype, int jobz, int range, int n, double vl, double
 int ek_hip_sygvx(int itype, int jobz, int range, int n, double vl, double vu, int il, int iu,
                  const double *A, int lda, const double *B, int ldb, int *m, int *ifirst,
                  double *w, double *Z, int ldz, int zcap, double *stage_seconds, int n_stages);
+
+/* Many small problems in one call -- what syevjBatched / sygvdBatched are to cuSOLVER / rocSOLVER users: `batch`
+ * independent problems of one order n <= EK_HIP_BATCH_NMAX, strided in memory, solved by ONE kernel launch in which a
+ * workgroup owns a problem from its first load to its last store and keeps the matrix in LDS (Cholesky, reduction to
+ * standard form, Householder tridiagonalisation, implicit QL, back-transformation, recovery: no launch between them).
+ * NOT COLLECTIVE: one GPU, no grid, no communicator; the call synchronises.
+ *   problem, jobz : as in ek_hip_eigenpairs* (0 standard / 1 generalized with B SPD; 0 values / 1 values and vectors)
+ *   n, batch      : 0 <= n <= EK_HIP_BATCH_NMAX, batch >= 0 (n = 0 or batch = 0: success, nothing referenced)
+ *   A, lda, strideA : problem b's A is the column-major n x n array at A + b * strideA, lda >= n, strideA >= lda * n
+ *                   (a stride of 0 is an argument error, not a broadcast); lower triangle referenced
+ *   B, ldb, strideB : the same for B; not referenced (may be NULL) when problem = 0
+ *   w             : out: batch x n doubles, problem b's eigenvalues ascending at w + b * n
+ *   Z, ldz, strideZ : out (jobz = 1): problem b's eigenvectors at Z + b * strideZ, ldz >= n, strideZ >= ldz * n, column k
+ *                   belonging to w[b * n + k]; orthonormal, B-orthonormal for problem 1.  Not referenced when jobz = 0
+ *   info          : out: HOST array of batch ints, one per problem: 0 success; k > 0: B is not SPD (a NaN in B
+ *                   included), k the 1-based failing pivot -- the value ek_hip_solve_device returns for that B;
+ *                   -5: the lower triangle of that A holds NaN / Inf; 100000 + k: the QL iteration failed as in
+ *                   ek_hip_solve (k = n + 1: the reduction left a non-finite tridiagonal).  The w and Z slots of a
+ *                   failed problem hold unspecified values; nothing outside its own slots is written and the other
+ *                   problems of the batch are unaffected
+ *   seconds       : NULL or one double: device time of the launch (events around it)
+ * Return value: 0 when the arguments were legal and the launch ran (whatever info[] says); -k for argument k, decided
+ * before any device work; <= -1000 HIP runtime error.
+ * A problem's result does not depend on the batch around it: the same (A, B) gives bit-identical w and Z alone, at
+ * any position of any batch, and in the host and the device form.  Eigenvalues agree with ek_hip_solve_device's to
+ * rounding, not to the bit (QL here, divide & conquer there).
+ * Device form, IN PLACE like ek_hip_solve_device: on return the lower triangle of each A holds what DSYTD2 leaves (d on
+ * the diagonal, e below it, the tails of the Householder vectors below that; tau_k = 2 / (1 + |tail_k|^2)), the lower
+ * triangle of each B holds L.  The strictly upper triangles of A and B are never read and never written (a NaN there
+ * survives bit for bit), nor is anything between the columns (rows n..ld-1) or between the problems.
+ * Workspace: batch ints of device memory, kept until ek_hip_finalize. */
+#define EK_HIP_BATCH_NMAX 128
+int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                     double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                     long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout; A and B are left untouched (the call works on device copies), and so is
+ * what lies between the columns and the problems of Z */
+int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                              const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                              long long strideZ, int *info, double *seconds);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs
