@@ -22,8 +22,13 @@
 //
 // Same bits wherever a problem sits: a problem's arithmetic depends on (n, A, B) alone -- fixed loop orders, sums
 // across a workgroup by a fixed butterfly and a fixed order over the waves, no atomics, one code path per class.
+//
+// ek_hip_eigenpairs_vbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in
+// a table instead of at blockIdx.x * stride; every problem runs in the class its own order picks (the uniform call's
+// bits), the classes as one launch each, the problems of a class in descending order.
 #include "ek_api_internal.h"
 
+#include <algorithm>
 #include <cfloat>
 
 namespace ek {
@@ -37,6 +42,41 @@ struct Args {
   double *Z; int ldz; long long sZ;
   int *info;
 };
+
+// ek_hip_eigenpairs_vbatched*: problems of different orders in one call.  A workgroup finds its problem in a table
+// (one entry per problem of order > 0, a class after the other, descending order inside a class); `index` is the
+// problem's place in the caller's batch, where its status word goes.
+struct Desc {
+  double *A, *B, *w, *Z;
+  int n, lda, ldb, ldz, index, pad;
+};
+struct VArgs {
+  int problem, jobz;
+  const Desc *table;
+  int *info;
+};
+
+// What a workgroup works on, whichever way it found it.  The pointers are typed as global: one that arrives as a kernel
+// argument is known to be, but one loaded from the table is generic to the compiler, which would emit flat loads and
+// stores for it (64-bit addresses in VGPRs, waits shared with LDS).
+typedef __attribute__((address_space(1))) double gdouble;
+struct Problem {
+  int n;
+  gdouble *A; int lda;
+  gdouble *B; int ldb;
+  gdouble *w;
+  gdouble *Z; int ldz;
+  int *info;
+};
+__device__ __forceinline__ Problem locate(const Args &a) {
+  const long long pb = blockIdx.x;
+  return {a.n, (gdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (gdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (gdouble *)(a.w + pb * a.n), a.jobz ? (gdouble *)(a.Z + pb * a.sZ) : nullptr, a.ldz, a.info + pb};
+}
+__device__ __forceinline__ Problem locate(const VArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz, a.info + d.index};
+}
 
 // Sum (or maximum) over the workgroup, the same bits in every thread.  `red` holds 2 * NW doubles; the two halves
 // alternate so that a call needs one barrier: between two uses of a half lies the barrier of the call between them.
@@ -74,8 +114,9 @@ __device__ __forceinline__ void lds_axpy(double *y, const double *x, double a, i
   for (; i < i1; ++i) y[i * SY] -= x[i] * a;
 }
 
-template <int NC, int T>
-__global__ __launch_bounds__(T) void batched_kernel(Args a) {
+// ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or VArgs (a table entry)
+template <int NC, int T, typename ARGS = Args>
+__global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   constexpr int LD = NC + 1, P = T / NC, NW = T / 64;
   static_assert(P == 2 && T % 64 == 0, "two threads per row");
   extern __shared__ double smem[];
@@ -89,14 +130,14 @@ __global__ __launch_bounds__(T) void batched_kernel(Args a) {
   __shared__ int srank[NC];
   __shared__ int s_state, s_m, s_lo;
 
-  const int t = threadIdx.x, n = a.n;
+  const Problem p = locate(a);
+  const int t = threadIdx.x, n = p.n;
   const int r = t % NC, sub = t / NC;
   const bool row = r < n;
-  const long long pb = blockIdx.x;
-  double *A = a.A + pb * a.sA;
-  double *B = a.problem ? a.B + pb * a.sB : nullptr;
-  const int lda = a.lda, ldb = a.ldb;
-  int *info = a.info + pb;
+  gdouble *A = p.A;
+  gdouble *B = p.B;
+  const int lda = p.lda, ldb = p.ldb;
+  int *info = p.info;
   int phase = 0;
 
   // ---- 0: A finite?
@@ -409,14 +450,14 @@ __global__ __launch_bounds__(T) void batched_kernel(Args a) {
       rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
     }
     srank[r] = rank;
-    a.w[pb * n + rank] = di * unscale;
+    p.w[rank] = di * unscale;
   }
   if (!a.jobz) {
     if (t == 0) *info = 0;
     return;
   }
-  double *Z = a.Z + pb * a.sZ;
-  const int ldz = a.ldz;
+  gdouble *Z = p.Z;
+  const int ldz = p.ldz;
 
   // ---- 5: Z <- H_0 ... H_{n-3} Z (H_{n-2} = I), thread t owns column t of Z
   if (n >= 3) {
@@ -464,16 +505,16 @@ __global__ __launch_bounds__(T) void batched_kernel(Args a) {
   if (t == 0) *info = 0;
 }
 
-template <int NC, int T>
-static int launch_class(hipStream_t s, int batch, const Args &a) {
+template <int NC, int T, typename ARGS>
+static int launch_class(hipStream_t s, int batch, const ARGS &a) {
   constexpr size_t lds = (size_t)(NC * (NC + 1) + 9 * NC) * sizeof(double);
-  static bool raised = false;
+  static bool raised = false;                       // one per instantiation, the variable ones included
   if (lds > 64 * 1024 && !raised) {
-    EK_HIP_CHECK(hipFuncSetAttribute((const void *)batched_kernel<NC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)batched_kernel<NC, T, ARGS>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     raised = true;
   }
-  hipLaunchKernelGGL((batched_kernel<NC, T>), dim3(batch), dim3(T), lds, s, a);
+  hipLaunchKernelGGL((batched_kernel<NC, T, ARGS>), dim3(batch), dim3(T), lds, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -485,13 +526,63 @@ static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
 static int *g_dinfo = nullptr;
 static size_t g_dinfo_count = 0;
 
+// the variable form's problem table, the streams of the classes of 64 and 32 (the class of 128 runs on the context's
+// stream) and the events that tie them to it: kept like the status words
+static Desc *g_dtable = nullptr;
+static size_t g_dtable_count = 0;
+static std::vector<Desc> g_htable;                 // its host image
+static hipStream_t g_side[2] = {nullptr, nullptr};
+constexpr int kEvents = 10;                         // fork, two joins, start / end of each class, end of the call
+static hipEvent_t g_ev[kEvents] = {};
+static int g_streams = 3;                           // 3: a stream per class; 1: one stream (ek_hip_debug_vbatched_streams)
+static double g_class_seconds[3] = {0.0, 0.0, 0.0}; // the last timed variable call's kernels: classes of 128, 64, 32
+static int g_class_count[3] = {0, 0, 0};
+
+static int ensure_info(size_t batch) {
+  if (batch <= g_dinfo_count) return 0;
+  if (g_dinfo) (void)hipFree(g_dinfo);
+  g_dinfo = nullptr;
+  g_dinfo_count = 0;
+  EK_HIP_CHECK(hipMalloc((void **)&g_dinfo, batch * sizeof(int)));
+  g_dinfo_count = batch;
+  return 0;
+}
+
+static int ensure_variable(size_t entries) {
+  if (entries > g_dtable_count) {
+    if (g_dtable) (void)hipFree(g_dtable);
+    g_dtable = nullptr;
+    g_dtable_count = 0;
+    EK_HIP_CHECK(hipMalloc((void **)&g_dtable, entries * sizeof(Desc)));
+    g_dtable_count = entries;
+  }
+  for (int k = 0; k < 2; ++k)
+    if (!g_side[k]) EK_HIP_CHECK(hipStreamCreateWithFlags(&g_side[k], hipStreamNonBlocking));
+  for (int k = 0; k < kEvents; ++k)
+    if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
+  return 0;
+}
+
 }  // namespace batched
 
 namespace api {
 void release_batched() {
-  if (batched::g_dinfo) (void)hipFree(batched::g_dinfo);
-  batched::g_dinfo = nullptr;
-  batched::g_dinfo_count = 0;
+  using namespace batched;
+  if (g_dinfo) (void)hipFree(g_dinfo);
+  g_dinfo = nullptr;
+  g_dinfo_count = 0;
+  if (g_dtable) (void)hipFree(g_dtable);
+  g_dtable = nullptr;
+  g_dtable_count = 0;
+  std::vector<Desc>().swap(g_htable);
+  for (int k = 0; k < 2; ++k) {
+    if (g_side[k]) (void)hipStreamDestroy(g_side[k]);
+    g_side[k] = nullptr;
+  }
+  for (int k = 0; k < kEvents; ++k) {
+    if (g_ev[k]) (void)hipEventDestroy(g_ev[k]);
+    g_ev[k] = nullptr;
+  }
 }
 }  // namespace api
 }  // namespace ek
@@ -531,11 +622,7 @@ static int batched_device_locked(int problem, int jobz, int n, int batch, double
                                  double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                  long long strideZ, int *info, double *seconds) {
   hipStream_t s = g_ctx.stream;
-  if ((size_t)batch > batched::g_dinfo_count) {
-    release_batched();
-    EK_HIP_CHECK(hipMalloc((void **)&batched::g_dinfo, (size_t)batch * sizeof(int)));
-    batched::g_dinfo_count = (size_t)batch;
-  }
+  { int rc0 = batched::ensure_info((size_t)batch); if (rc0) return rc0; }
   batched::Args a{problem, jobz, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, batched::g_dinfo};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (seconds) {
@@ -561,6 +648,124 @@ static int batched_device_locked(int problem, int jobz, int n, int batch, double
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
   }
+  return rc;
+}
+
+// ---- problems of different orders (ek_hip_eigenpairs_vbatched*)
+
+// All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.
+static int vbatched_check(int problem, int jobz, int batch, const int *n, const void *const *A, const int *lda,
+                          const void *const *B, const int *ldb, const void *const *w, const void *const *Z,
+                          const int *ldz, const int *info, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (jobz != 0 && jobz != 1) return -2;
+  if (batch < 0) return -3;
+  if (batch == 0) { *nothing = true; return 0; }
+  if (!n) return -4;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] < 0 || n[b] > EK_HIP_BATCH_NMAX) return -4;
+  auto entries = [&](const void *const *P) {
+    if (!P) return false;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && !P[b]) return false;
+    return true;
+  };
+  auto leading = [&](const int *ld) {
+    if (!ld) return false;
+    for (int b = 0; b < batch; ++b)
+      if (ld[b] < (n[b] > 1 ? n[b] : 1)) return false;
+    return true;
+  };
+  if (!entries(A)) return -5;
+  if (!leading(lda)) return -6;
+  if (problem == 1) {
+    if (!entries(B)) return -7;
+    if (!leading(ldb)) return -8;
+  }
+  if (!entries(w)) return -9;
+  if (jobz == 1) {
+    if (!entries(Z)) return -10;
+    if (!leading(ldz)) return -11;
+  }
+  if (!info) return -12;
+  return 0;
+}
+
+// arguments checked, context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses
+static int vbatched_device_locked(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                  double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                  const int *ldz, int *info, double *seconds) {
+  using namespace batched;
+  // a class after the other, the largest first; inside a class descending order: the dispatcher hands out workgroups
+  // in index order and a workgroup's time grows like n^2 .. n^3, so this is longest-first list scheduling
+  std::vector<int> order;
+  order.reserve((size_t)batch);
+  for (int b = 0; b < batch; ++b)
+    if (n[b] > 0) order.push_back(b);
+  if (order.empty()) {
+    for (int b = 0; b < batch; ++b) info[b] = 0;
+    return 0;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
+  g_htable.resize(order.size());                    // static: the upload below may still read it when an error returns
+  int count[3] = {0, 0, 0};                         // classes of 128, 64, 32
+  for (size_t i = 0; i < order.size(); ++i) {
+    const int b = order[i], c = class_of(n[b]);
+    ++count[c == 128 ? 0 : c == 64 ? 1 : 2];
+    g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], jobz ? dZ[b] : nullptr, n[b], lda[b],
+                       problem ? ldb[b] : 1, jobz ? ldz[b] : 1, b, 0};
+  }
+  { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
+  { int rc0 = ensure_variable(order.size()); if (rc0) return rc0; }
+  hipStream_t s = g_ctx.stream;
+  EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+  // the largest class present runs on the context's stream, the others on a stream of their own behind the fork event
+  hipStream_t cs[3] = {s, s, s};
+  for (int k = 0, used = 0; k < 3; ++k)
+    if (count[k]) {
+      if (g_streams == 3 && used > 0) cs[k] = g_side[used - 1];
+      ++used;
+    }
+  EK_HIP_CHECK(hipEventRecord(g_ev[0], s));         // before the first launch
+  int rc = 0, off = 0;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && !rc && e == hipSuccess; ++k) {
+    if (!count[k]) continue;
+    if (cs[k] != s) e = hipStreamWaitEvent(cs[k], g_ev[0], 0);
+    if (e != hipSuccess) break;
+    VArgs a{problem, jobz, g_dtable + off, g_dinfo};
+    if (seconds) (void)hipEventRecord(g_ev[3 + 2 * k], cs[k]);
+    rc = k == 0 ? launch_class<128, 256>(cs[k], count[k], a)
+       : k == 1 ? launch_class<64, 128>(cs[k], count[k], a) : launch_class<32, 64>(cs[k], count[k], a);
+    if (seconds) (void)hipEventRecord(g_ev[4 + 2 * k], cs[k]);
+    if (cs[k] != s) {                               // join
+      e = hipEventRecord(g_ev[k], cs[k]);
+      if (e == hipSuccess) e = hipStreamWaitEvent(s, g_ev[k], 0);
+    }
+    off += count[k];
+  }
+  if (seconds) (void)hipEventRecord(g_ev[9], s);    // after the last launch has ended
+  if (!rc && e == hipSuccess)
+    e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  hipError_t es = hipStreamSynchronize(s);
+  if (e != hipSuccess || rc)                        // an error may have left a class outside the join
+    for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(g_side[k]);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
+  if (seconds && !rc) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[9]) == hipSuccess) *seconds = (double)ms * 1e-3;
+    for (int k = 0; k < 3; ++k) {
+      g_class_count[k] = count[k];
+      g_class_seconds[k] = 0.0;
+      if (count[k] && hipEventElapsedTime(&ms, g_ev[3 + 2 * k], g_ev[4 + 2 * k]) == hipSuccess)
+        g_class_seconds[k] = (double)ms * 1e-3;
+    }
+  }
+  if (!rc)
+    for (int b = 0; b < batch; ++b)
+      if (n[b] == 0) info[b] = 0;
   return rc;
 }
 
@@ -615,6 +820,113 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
   EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
   if (jobz) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
   EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                      double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                      const int *ldz, int *info, double *seconds) {
+  bool nothing;
+  int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)dA, lda, (const void *const *)dB, ldb,
+                          (const void *const *)dw, (const void *const *)dZ, ldz, info, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  bool work = false;
+  for (int b = 0; b < batch && !work; ++b) work = n[b] > 0;
+  if (!work) {
+    for (int b = 0; b < batch; ++b) info[b] = 0;
+    return 0;
+  }
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return vbatched_device_locked(problem, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
+}
+
+int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                               const double *const *B, const int *ldb, double *const *w, double *const *Z,
+                               const int *ldz, int *info, double *seconds) {
+  bool nothing;
+  int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
+                          (const void *const *)w, (const void *const *)Z, ldz, info, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  // compact device layout (ld = n[b]), a problem behind the other: the caller's padding never travels
+  std::vector<size_t> offm((size_t)batch + 1, 0), offv((size_t)batch + 1, 0);
+  for (int b = 0; b < batch; ++b) {
+    offm[b + 1] = offm[b] + (size_t)n[b] * n[b];
+    offv[b + 1] = offv[b] + (size_t)n[b];
+  }
+  const size_t cm = offm[batch], cv = offv[batch];
+  if (cm == 0) {
+    for (int b = 0; b < batch; ++b) info[b] = 0;
+    return 0;
+  }
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  // one staging buffer per matrix kind: the lower triangles, column by column (what lies above them is never read)
+  auto pack = [&](const double *const *M, const int *ld, std::vector<double> &h) {
+    h.assign(cm, 0.0);
+    for (int b = 0; b < batch; ++b)
+      for (int j = 0; j < n[b]; ++j)
+        std::memcpy(&h[offm[b] + (size_t)j * n[b] + j], M[b] + (size_t)j * ld[b] + j, (size_t)(n[b] - j) * 8);
+  };
+  std::vector<double> hA, hB, hw, hZ;
+  pack(A, lda, hA);
+  if (problem) pack(B, ldb, hB);
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cm * 8);
+  if (!rc) rc = mem.alloc(&uw, cv * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cm * 8);
+  if (!rc && jobz) rc = mem.alloc(&uZ, cm * 8);
+  if (rc) return rc;
+  std::vector<double *> pA((size_t)batch), pB((size_t)batch), pw((size_t)batch), pZ((size_t)batch);
+  std::vector<int> ldc((size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    pA[b] = uA + offm[b];
+    pB[b] = problem ? uB + offm[b] : nullptr;
+    pw[b] = uw + offv[b];
+    pZ[b] = jobz ? uZ + offm[b] : nullptr;
+    ldc[b] = n[b] > 1 ? n[b] : 1;
+  }
+  EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
+  rc = vbatched_device_locked(problem, jobz, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(),
+                              pZ.data(), ldc.data(), info, seconds);
+  if (rc) return rc;
+  hw.resize(cv);
+  EK_HIP_CHECK(hipMemcpyAsync(hw.data(), uw, cv * 8, hipMemcpyDeviceToHost, s));
+  if (jobz) {
+    hZ.resize(cm);
+    EK_HIP_CHECK(hipMemcpyAsync(hZ.data(), uZ, cm * 8, hipMemcpyDeviceToHost, s));
+  }
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  for (int b = 0; b < batch; ++b) {                 // like the device form, a failed problem leaves its slots alone
+    if (info[b] != 0 || n[b] == 0) continue;
+    std::memcpy(w[b], &hw[offv[b]], (size_t)n[b] * 8);
+    if (jobz)
+      for (int j = 0; j < n[b]; ++j)
+        std::memcpy(Z[b] + (size_t)j * ldz[b], &hZ[offm[b] + (size_t)j * n[b]], (size_t)n[b] * 8);
+  }
+  return 0;
+}
+
+int ek_hip_debug_vbatched_streams(int streams) {
+  if (streams != 1 && streams != 3) streams = 3;
+  std::lock_guard<std::mutex> lk(g_mu);
+  batched::g_streams = streams;
+  return 0;
+}
+
+int ek_hip_debug_vbatched_last(double *class_seconds, int *class_count) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (int k = 0; k < 3; ++k) {
+    if (class_seconds) class_seconds[k] = batched::g_class_seconds[k];
+    if (class_count) class_count[k] = batched::g_class_count[k];
+  }
   return 0;
 }
 

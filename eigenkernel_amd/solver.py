@@ -148,6 +148,12 @@ def load_library(path=None):
                                                      vp, c_int, c_ll, _ip, _dp]),
         "ek_hip_eigenpairs_batched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp,
                                               _dp, c_int, c_ll, _ip, _dp]),
+        # the pointer arrays (double *const *) are passed as ctypes arrays of c_void_p
+        "ek_hip_eigenpairs_vbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip,
+                                                      _dp]),
+        "ek_hip_eigenpairs_vbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
+        "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -185,6 +191,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_eigenpairs_device", "ek_hip_eigenpairs", "ek_hip_stebz_range", "ek_hip_debug_window_workspace_bytes",
     "ek_hip_sygvx_device", "ek_hip_sygvx", "ek_hip_sygst_ibtype", "ek_hip_trmm", "ek_hip_debug_sygvx_workspace_bytes",
     "ek_hip_eigenpairs_batched_device", "ek_hip_eigenpairs_batched",
+    "ek_hip_eigenpairs_vbatched_device", "ek_hip_eigenpairs_vbatched",
+    "ek_hip_debug_vbatched_streams", "ek_hip_debug_vbatched_last",
 )
 
 
@@ -715,6 +723,45 @@ def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
     if rc != 0:
         raise SolverError("ek_hip_eigenpairs_batched failed", rc)
     return w, (Zt.transpose(0, 2, 1) if vectors else None), info[:batch]
+
+
+def eigenpairs_vbatched(As, Bs=None, vectors=True, seconds=None):
+    """Many small problems of DIFFERENT orders in one call (ek_hip_eigenpairs_vbatched): As (and Bs, SPD) sequences of
+    square 2-D arrays, problem b of order As[b].shape[0] <= BATCH_NMAX (0 allowed), lower triangles referenced.
+    Returns (list of w, list of Z or None, info) with the meaning of eigenpairs_batched per problem; each problem's
+    bits are those of eigenpairs_batched on that pair alone.  As and Bs are not modified.  Raises ValueError for bad
+    shapes before the library is called, SolverError only when the call itself fails."""
+    lib = load_library()
+    Af = []
+    for M in As:
+        M = np.asarray(M, dtype=np.float64)
+        if M.ndim != 2 or M.shape[0] != M.shape[1]:
+            raise ValueError("every A must be a square 2-D array")
+        Af.append(np.asfortranarray(M))
+    batch = len(Af)
+    Bf = None
+    if Bs is not None:
+        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
+        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
+            raise ValueError("Bs must hold one array of A's shape per problem")
+    if batch == 0:
+        return [], ([] if vectors else None), np.zeros(0, dtype=np.int32)
+    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
+    ld = np.maximum(n, 1).astype(np.int32)
+    w = [np.zeros(k) for k in n]
+    Z = [np.zeros((k, k), order="F") for k in n] if vectors else None
+    info = np.zeros(batch, dtype=np.int32)
+
+    def table(arrays):
+        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
+
+    rc = lib.ek_hip_eigenpairs_vbatched(0 if Bf is None else 1, 1 if vectors else 0, batch, _I(n), table(Af), _I(ld),
+                                        table(Bf) if Bf is not None else None, _I(ld), table(w),
+                                        table(Z) if vectors else None, _I(ld), _I(info),
+                                        _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError("ek_hip_eigenpairs_vbatched failed", rc)
+    return w, Z, info
 
 
 def sy2sb(A):

@@ -67,7 +67,8 @@ int ek_hip_version(void);                       /* 100*major + minor.  2: round 
                                                  * with the window entries ek_hip_eigenpairs* and
                                                  * ek_hip_stebz_range, and with ek_hip_sygvx*,
                                                  * ek_hip_sygst_ibtype and ek_hip_trmm, and with
-                                                 * ek_hip_eigenpairs_batched*: their symbols are the
+                                                 * ek_hip_eigenpairs_batched* and
+                                                 * ek_hip_eigenpairs_vbatched*: their symbols are the
                                                  * signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
@@ -241,6 +242,44 @@ int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, do
 int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                               long long strideZ, int *info, double *seconds);
+
+/* The same for problems of DIFFERENT orders in one call ("vbatched"): problem b has order n[b], 0 <= n[b] <=
+ * EK_HIP_BATCH_NMAX, and its own arrays, named by pointer arrays instead of a base and a stride.
+ *   n, lda, ldb, ldz, info and the four pointer arrays dA, dB, dw, dZ are HOST arrays of `batch` entries in both forms;
+ *   the pointers IN the pointer arrays are device addresses (device form) or host addresses (host form).
+ *   problem, jobz : as above, one value for the whole batch
+ *   batch         : >= 0 (0: success, nothing referenced)
+ *   n             : n[b] = 0: problem b references nothing (its pointers may be NULL) and gets info[b] = 0
+ *   dA, lda       : dA[b]: problem b's column-major n[b] x n[b] A, lda[b] >= max(1, n[b]); lower triangle referenced
+ *   dB, ldb       : the same for B; not looked at (may be NULL) when problem = 0
+ *   dw            : out: dw[b]: n[b] eigenvalues, ascending
+ *   dZ, ldz       : out (jobz = 1): dZ[b]: n[b] x n[b] eigenvectors, ldz[b] >= max(1, n[b]), column k belonging to
+ *                   dw[b][k]; not looked at when jobz = 0
+ *   info          : out: one int per problem, the codes of ek_hip_eigenpairs_batched* (0; k > 0 failing pivot of B;
+ *                   -5 NaN / Inf in A's lower triangle; 100000 + k QL).  A failed problem writes nothing outside its own
+ *                   slots; the other problems are unaffected
+ *   seconds       : NULL or one double: device time from before the first launch to after the last
+ * Return value: 0 when the arguments were legal and the launches ran (whatever info[] says); -k for argument k of this
+ * prototype, decided before any device work and without dereferencing any pointer of the pointer arrays, the first
+ * offending argument deciding: -4 n NULL or an order outside 0 .. EK_HIP_BATCH_NMAX; -5 / -7 / -9 / -10 array NULL or
+ * a NULL entry for a problem of order > 0; -6 / -8 / -11 array NULL or a leading dimension too small; -12 info NULL;
+ * <= -1000 HIP runtime error.  The problems must not overlap in memory (not checked).
+ * THE SAME BITS AS THE UNIFORM CALL: problem b's w, Z, info and in-place images are bit-identical to what
+ * ek_hip_eigenpairs_batched_device returns for the same (n, A, B) alone, wherever the problem sits in the batch and
+ * whatever surrounds it.  Every problem runs in the kernel class its own order picks (n <= 32 / 64 / 128); the
+ * classes are launched largest first (at most three launches, no host synchronise between them), a class's
+ * problems in descending order.
+ * NOT COLLECTIVE; the call synchronises.  Device form IN PLACE as above (dA[b] <- DSYTD2's layout, dB[b] <- L; strictly
+ * upper triangles and rows n[b] .. ld-1 neither read nor written).  Workspace: batch ints and one 56-byte table entry
+ * per problem of device memory, two streams and ten events, kept until ek_hip_finalize. */
+int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                      double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                      const int *ldz, int *info, double *seconds);
+/* host addresses in A, B, w, Z; A and B are left untouched: the lower triangles travel packed (ld = n[b]) in one copy
+ * per matrix kind, and w and Z come back in one copy each.  w[b] and Z[b] of a failed problem are left as they were */
+int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                               const double *const *B, const int *ldb, double *const *w, double *const *Z,
+                               const int *ldz, int *info, double *seconds);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs

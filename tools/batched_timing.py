@@ -5,6 +5,11 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
   python tools/batched_timing.py [--sizes 30,64,128] [--batches 1,256,4096] [--loop-max 64]
   python tools/batched_timing.py --once 64g      one batched call (256 generalized pairs of order 64 with vectors)
                                                  after a warm-up: what a kernel trace should look at
+  python tools/batched_timing.py --mixed [--mixed-batch 2048] [--mixed-orders 8,128]
+                                                 problems of different orders: one variable call
+                                                 (ek_hip_eigenpairs_vbatched_device, a stream per class and one stream)
+                                                 against a uniform call per distinct order and against one uniform call
+                                                 with every problem padded to order 128
 
 Per (problem, jobz, n, batch): one warm-up of each kind, then three rounds that alternate the kinds, best by wall clock
 (both calls synchronise; both work in place, so the inputs are restored outside the clock).  The loop is timed over
@@ -94,15 +99,121 @@ class Case:
             self.lib.ek_hip_free(p)
 
 
+def mixed(lib, batch, lo, hi):
+    """Generalized with vectors, orders drawn i.i.d. uniformly from lo..hi (seeded).  Best of 3 after a warm-up, the kinds
+    alternated, inputs restored outside the clock.  Wall times; for the variable call also the device time and the time of
+    every class's launch (events on its stream)."""
+    ip = ctypes.POINTER(ctypes.c_int)
+    orders = np.random.default_rng(2048).integers(lo, hi + 1, batch)
+    mats = {}
+    for n in np.unique(orders):                     # eight distinct pairs per order, reused round robin
+        mats[int(n)] = pairs(int(n), 8, int(n))
+    seen = {}
+    A, B = [], []
+    for n in orders:
+        k = seen.get(int(n), 0)
+        seen[int(n)] = k + 1
+        A.append(mats[int(n)][0][k % 8].T.ravel())  # column-major (symmetric: the same either way)
+        B.append(mats[int(n)][1][k % 8].T.ravel())
+    off = np.concatenate(([0], np.cumsum(orders.astype(np.int64) ** 2)))
+    woff = np.concatenate(([0], np.cumsum(orders.astype(np.int64))))
+    hA, hB = np.concatenate(A), np.concatenate(B)
+    by_order = np.argsort(orders, kind="stable")
+    gA, gB = np.concatenate([A[b] for b in by_order]), np.concatenate([B[b] for b in by_order])
+    goff = np.concatenate(([0], np.cumsum(orders[by_order].astype(np.int64) ** 2)))
+    gwoff = np.concatenate(([0], np.cumsum(orders[by_order].astype(np.int64))))
+    distinct, first, counts = np.unique(orders[by_order], return_index=True, return_counts=True)
+    pad = Case(lib, 128, batch)
+
+    keep = []
+
+    def up(a):
+        p = ctypes.c_void_p()
+        assert lib.ek_hip_malloc(ctypes.byref(p), int(a.nbytes)) == 0
+        keep.append(p)
+        return p
+
+    def put(p, a):
+        assert lib.ek_hip_memcpy_h2d(p, a.ctypes.data, a.nbytes) == 0
+
+    dA, dB, dgA, dgB = up(hA), up(hB), up(gA), up(gB)
+    dw, dZ = pad.dw, pad.dZ                         # large enough for every kind
+    n32 = orders.astype(np.int32)
+    info = np.zeros(batch, dtype=np.int32)
+
+    def table(base, offs):
+        return (ctypes.c_void_p * batch)(*[base.value + int(offs[b]) * 8 for b in range(batch)])
+
+    tA, tB, tw, tZ = table(dA, off), table(dB, off), table(dw, woff), table(dZ, off)
+
+    def var():
+        put(dA, hA); put(dB, hB)
+        sec = ctypes.c_double(0.0)
+        t0 = time.perf_counter()
+        rc = lib.ek_hip_eigenpairs_vbatched_device(1, 1, batch, n32.ctypes.data_as(ip), tA, n32.ctypes.data_as(ip), tB,
+                                                   n32.ctypes.data_as(ip), tw, tZ, n32.ctypes.data_as(ip),
+                                                   info.ctypes.data_as(ip), ctypes.byref(sec))
+        t = time.perf_counter() - t0
+        assert rc == 0 and not info.any(), (rc, info[info != 0][:4])
+        cls, cnt = np.zeros(3), np.zeros(3, dtype=np.int32)
+        assert lib.ek_hip_debug_vbatched_last(cls.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              cnt.ctypes.data_as(ip)) == 0
+        return t, sec.value, cls, cnt
+
+    def grouped():
+        put(dgA, gA); put(dgB, gB)
+        t = 0.0
+        at = lambda p, o: ctypes.c_void_p(p.value + int(o) * 8)  # noqa: E731
+        for n, f, c in zip(distinct, first, counts):
+            n, c = int(n), int(c)
+            t0 = time.perf_counter()
+            rc = lib.ek_hip_eigenpairs_batched_device(1, 1, n, c, at(dgA, goff[f]), n, n * n, at(dgB, goff[f]), n, n * n,
+                                                      at(dw, gwoff[f]), at(dZ, goff[f]), n, n * n,
+                                                      info.ctypes.data_as(ip), None)
+            t += time.perf_counter() - t0
+            assert rc == 0 and not info[:c].any()
+        return t
+
+    print("# mixed: %d generalized problems with vectors, orders %d..%d (%d distinct; classes of 128 / 64 / 32: %d / %d / %d)"
+          % (batch, lo, hi, len(distinct), (orders > 64).sum(), ((orders > 32) & (orders <= 64)).sum(),
+             (orders <= 32).sum()))
+    res = {}
+    for streams in (3, 1):
+        assert lib.ek_hip_debug_vbatched_streams(streams) == 0
+        tv, tg, tp = [], [], []
+        var(); grouped(); pad.batched(1, 1)             # warm-up
+        for _ in range(3):
+            tv.append(var()); tg.append(grouped()); tp.append(pad.batched(1, 1)[0])
+        best = min(tv, key=lambda x: x[0])
+        res[streams] = best[0]
+        print("  streams=%d | t_var wall %.3f ms device %.3f ms | class launches 128: %.3f ms  64: %.3f ms  32: %.3f ms | "
+              "t_grouped %.3f ms (ratio %.1f) | t_pad %.3f ms (ratio %.2f)"
+              % (streams, best[0] * 1e3, best[1] * 1e3, best[2][0] * 1e3, best[2][1] * 1e3, best[2][2] * 1e3,
+                 min(tg) * 1e3, min(tg) / best[0], min(tp) * 1e3, min(tp) / best[0]), flush=True)
+        print("            all t_var wall ms: %s" % " ".join("%.3f" % (x[0] * 1e3) for x in tv))
+    assert lib.ek_hip_debug_vbatched_streams(3) == 0
+    for p in keep:
+        lib.ek_hip_free(p)
+    pad.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="30,64,128")
     ap.add_argument("--batches", default="1,256,4096")
     ap.add_argument("--loop-max", type=int, default=64)
     ap.add_argument("--once", default=None, help="<n>g or <n>s: one generalized / standard batch of 256 with vectors")
+    ap.add_argument("--mixed", action="store_true", help="problems of different orders: the variable call")
+    ap.add_argument("--mixed-batch", type=int, default=2048)
+    ap.add_argument("--mixed-orders", default="8,128", help="lo,hi of the uniformly drawn orders")
     args = ap.parse_args()
     lib = solver.load_library()
     assert lib.ek_hip_init(0) == 0
+    if args.mixed:
+        lo, hi = (int(x) for x in args.mixed_orders.split(","))
+        mixed(lib, args.mixed_batch, lo, hi)
+        lib.ek_hip_finalize()
+        return
     if args.once:
         n, problem = int(args.once[:-1]), 1 if args.once.endswith("g") else 0
         c = Case(lib, n, 256)
