@@ -3,7 +3,8 @@
 // One workgroup owns a problem from its first load to its last store, and the matrix it works on lives in LDS the
 // whole time: there is no launch and no host synchronise between the stages.
 //
-//   0  the lower triangle of A is read once for NaN / Inf (info -5)
+//   0  the lower triangle of A is read once for NaN / Inf (info -5) and for max|a|: outside 2^-256 .. 2^256 the image
+//      of stage 2 is A times an exact power of two, and d, e, w go out multiplied back
 //   1  B's lower triangle -> LDS, right-looking Cholesky in LDS, L -> dB (lower triangle); a pivot that is not
 //      positive (or outside 1e-290 .. 1e290, or NaN) ends the problem with info = its 1-based index
 //   2  A's lower triangle -> LDS as a full symmetric image; X = L^-1 A (a thread per column), C = X L^-T (a thread
@@ -140,15 +141,27 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   int *info = p.info;
   int phase = 0;
 
-  // ---- 0: A finite?
+  // ---- 0: A finite?  max|a| comes off the same pass: an A whose squares would leave the normal range is scaled
+  int aex = 0;                                      // the image holds 2^-aex A; d, e and w go out times 2^aex
   {
-    int bad = 0;
+    double mx = 0.0;
     if (row)
-      for (int j = sub; j <= r; j += P) bad |= !(fabs(A[r + (size_t)j * lda]) <= DBL_MAX);
-    if (__syncthreads_or(bad)) {
+      for (int j = sub; j <= r; j += P) {
+        const double ax = fabs(A[r + (size_t)j * lda]);
+        mx = (ax <= DBL_MAX) ? fmax(mx, ax) : INFINITY;   // a NaN counts as Inf: fmax would drop it
+      }
+    const double amax = block_reduce<NW, true>(mx, red, phase);
+    if (!(amax <= DBL_MAX)) {                       // uniform: amax has the same bits in every thread
       if (t == 0) *info = -5;
       return;
     }
+    // Stage 3 forms plain sums of squares (DSYEV scales for the same reason, and so does ek_solve.hip's stage_in_A).
+    // Inside 2^-256 .. 2^256 nothing is done and the arithmetic is the unscaled kernel's to the bit: there the square
+    // of every entry down to eps / n of max|a| is a normal number (>= 2^-632) and n^1.5 max|a|^2 is finite (<= 2^523),
+    // and the other half of the exponent range is left to what L^-1 . L^-T amplifies (1 / lambda_min(B) up to 2^250).
+    // Outside, max|a| goes to [1/2, 1) by an exact power of two (not by rmin / anrm as DSYEV does), so that the
+    // result is that of the scaled matrix to the bit.
+    if (amax > 0.0 && (amax < 0x1p-256 || amax > 0x1p256)) (void)frexp(amax, &aex);
   }
 
   if (a.problem) {
@@ -179,7 +192,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   // ---- 2: A -> full symmetric image; C = L^-1 A L^-T
   if (row)
     for (int j = sub; j <= r; j += P) {
-      const double x = A[r + (size_t)j * lda];
+      const double x = ldexp(A[r + (size_t)j * lda], -aex);   // exact; aex = 0 leaves the bits alone
       S[r + j * LD] = x;
       S[j + r * LD] = x;
     }
@@ -241,10 +254,10 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
         sv[r] = 1.0;
         se[k] = beta;
         st[k] = tau;
-        A[r + (size_t)k * lda] = beta;
+        A[r + (size_t)k * lda] = ldexp(beta, aex);   // d and e of the caller's A
       } else if (r == k) {
         sd[k] = dk;
-        A[k + (size_t)k * lda] = dk;
+        A[k + (size_t)k * lda] = ldexp(dk, aex);
       }
     }
     if (tau == 0.0) continue;                       // H = I (uniform: tau has the same bits in every thread)
@@ -290,12 +303,12 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
     const double dl = S[(n - 1) * (LD + 1)];
     sd[n - 1] = dl;
     se[n - 1] = 0.0;
-    A[(size_t)(n - 1) * lda + (n - 1)] = dl;
+    A[(size_t)(n - 1) * lda + (n - 1)] = ldexp(dl, aex);
   }
   __syncthreads();
 
   // ---- 4: implicit QL with Z in the image
-  double unscale = 1.0;
+  int wex = aex;                                    // w = 2^wex d: stage 0's scaling and the one below
   {
     double mx = 0.0;
     int bad = 0;
@@ -312,7 +325,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
       int ex;
       (void)frexp(anorm, &ex);
       const double sc = ldexp(1.0, -ex);
-      unscale = ldexp(1.0, ex);
+      wex += ex;
       __syncthreads();
       if (sub == 0 && row) { sd[r] *= sc; se[r] *= sc; }
     }
@@ -442,15 +455,24 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
     }
   }
   // ascending order: rank sort (ties by index; a NaN sorts last so that the ranks stay a permutation)
-  if (sub == 0 && row) {
-    const double di = sd[r], ki = (di == di) ? di : INFINITY;
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double dj = sd[j], kj = (dj == dj) ? dj : INFINITY;
-      rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
+  {
+    int rank = 0, bad = 0;
+    double wr = 0.0;
+    if (sub == 0 && row) {
+      const double di = sd[r], ki = (di == di) ? di : INFINITY;
+      for (int j = 0; j < n; ++j) {
+        const double dj = sd[j], kj = (dj == dj) ? dj : INFINITY;
+        rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
+      }
+      srank[r] = rank;
+      wr = ldexp(di, wex);                          // one rounding at most (a denormal result), as di * 2^ex had
+      bad = !(fabs(wr) <= DBL_MAX);
     }
-    srank[r] = rank;
-    p.w[rank] = di * unscale;
+    if (__syncthreads_or(bad)) {                    // an eigenvalue beyond the range of a double (or a NaN that QL made):
+      if (t == 0) *info = 100000 + n + 1;           // reported like a reduction that overflowed, and nothing is written
+      return;
+    }
+    if (sub == 0 && row) p.w[rank] = wr;
   }
   if (!a.jobz) {
     if (t == 0) *info = 0;

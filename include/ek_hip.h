@@ -219,7 +219,8 @@ int ek_hip_sygvx(int itype, int jobz, int range, int n, double vl, double vu, in
  *   info          : out: HOST array of batch ints, one per problem: 0 success; k > 0: B is not SPD (a NaN in B
  *                   included), k the 1-based failing pivot -- the value ek_hip_solve_device returns for that B;
  *                   -5: the lower triangle of that A holds NaN / Inf; 100000 + k: the QL iteration failed as in
- *                   ek_hip_solve (k = n + 1: the reduction left a non-finite tridiagonal).  The w and Z slots of a
+ *                   ek_hip_solve (k = n + 1: the reduction left a non-finite tridiagonal, or an eigenvalue lies beyond
+ *                   the range of a double: info = 0 always comes with finite w).  The w and Z slots of a
  *                   failed problem hold unspecified values; nothing outside its own slots is written and the other
  *                   problems of the batch are unaffected
  *   seconds       : NULL or one double: device time of the launch (events around it)
@@ -228,6 +229,9 @@ int ek_hip_sygvx(int itype, int jobz, int range, int n, double vl, double vu, in
  * A problem's result does not depend on the batch around it: the same (A, B) gives bit-identical w and Z alone, at
  * any position of any batch, and in the host and the device form.  Eigenvalues agree with ek_hip_solve_device's to
  * rounding, not to the bit (QL here, divide & conquer there).
+ * An A of any finite magnitude is scaled internally, as in ek_hip_solve_device (by an exact power of two when max|a|
+ * lies outside 2^-256 .. 2^256); the d and e left in dA are those of the caller's A.  The scale is taken from A alone:
+ * for problem 1, max|a| / lambda_min(B) beyond about 2^500 can still overflow and is reported as 100000 + n + 1.
  * Device form, IN PLACE like ek_hip_solve_device: on return the lower triangle of each A holds what DSYTD2 leaves (d on
  * the diagonal, e below it, the tails of the Householder vectors below that; tau_k = 2 / (1 + |tail_k|^2)), the lower
  * triangle of each B holds L.  The strictly upper triangles of A and B are never read and never written (a NaN there
