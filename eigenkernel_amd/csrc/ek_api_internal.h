@@ -58,6 +58,7 @@ int user_images(size_t bytes, void **p);   // device images of host arrays, kept
 void release_user_images();
 void release_pipe_streams();       // the staging pipeline's copy streams (ek_solve.hip)
 void release_batched();            // the batched entries' per-problem status words (ek_batched.hip)
+void release_batched_check();      // the batched checks' scratch, output words, table and events (ek_batched_check.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);
 
 // device buffers of one host-array call: released on every exit path

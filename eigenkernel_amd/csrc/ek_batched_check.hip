@@ -1,0 +1,652 @@
+// ek_batched_check.hip -- ek_hip_check_batched* / ek_hip_check_vbatched*: the reference's acceptance checks and the
+// inverse participation ratios of EVERY problem of a batch, with the normalisations of ek_verify.hip (and of
+// eigenkernel_amd/verifier.py), in one launch per kernel class.
+//
+// One workgroup owns a problem from its first load to its last store; the classes are the solver's (order <= 32, 64,
+// 128, T = 2 NC threads).  Z lives in LDS the whole time, as an image with the odd leading dimension NC + 1 of
+// ek_batched.hip; thread (r, h) = (t % NC, t / NC) owns column r of Z and half h of the work on it.
+//
+//   1  the rows of the symmetric A and B stream from global memory through staged LDS vectors, two rows a step (row
+//      2m + h for half h), loaded one step ahead: entry (i, k) with k > i is read as (k, i), so that only the lower
+//      triangles are referenced.  Thread (r, h) forms (A Z)_ir and s_ir = (B Z)_ir over k in ascending order and adds
+//      r_ir^2 = ((A Z)_ir - w_r s_ir)^2, z_ir s_ir and z_ir^4 to its own sums in row order; the square of the entry of
+//      A it staged goes to its own sum for ||A||_F.  Generalized problems leave S = B Z in a device scratch of n^2
+//      doubles (standard problems need none: S = Z)
+//   2  the halves' sums meet in a fixed order: ||r_j||, G_jj = sum_i z_ij s_ij (the IPR's denominator and the scaling
+//      of the orthogonality check), sum_i z_ij^4
+//   3  column of S by column of S (two a step, staged like the rows; for a standard problem read from the image
+//      itself), thread (l, h) forms G_lj = sum_i z_il s_ij and adds (G_lj / sqrt(G_ll) / sqrt(G_jj))^2, j != l, to
+//      its own sum
+//
+// Same bits wherever a problem sits: a problem's outputs depend on (n, A, B, w, Z) alone -- fixed loop orders, sums
+// across the workgroup by a fixed butterfly and a fixed order over the waves, no atomics, one code path per class, the
+// same kernel body for the strided and the table form.  A, B, w and Z are read only.
+#include "ek_api_internal.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace ek {
+namespace bcheck {
+
+struct Args {
+  int problem, n;
+  const double *A; int lda; long long sA;
+  const double *B; int ldb; long long sB;
+  const double *w;
+  const double *Z; int ldz; long long sZ;
+  const int *map;       // the problems to check, one per workgroup; nullptr: workgroup b takes problem b
+  double *S;            // problem 1: n^2 doubles per problem
+  double *out;          // EK_HIP_CHECK_NOUT doubles per problem
+  double *ipr;          // n doubles per problem, or nullptr
+};
+
+// the variable form's table: one entry per problem to check, a class after the other, descending order inside a class
+struct Desc {
+  const double *A, *B, *w, *Z;
+  double *S, *ipr;
+  int n, lda, ldb, ldz, index, pad;
+};
+struct VArgs {
+  int problem;
+  const Desc *table;
+  double *out;
+};
+
+// global address space, as in ek_batched.hip: a pointer loaded from the table would otherwise cost flat accesses
+typedef __attribute__((address_space(1))) double gdouble;
+typedef const __attribute__((address_space(1))) double cgdouble;
+struct Problem {
+  int n;
+  cgdouble *A; int lda;
+  cgdouble *B; int ldb;
+  cgdouble *w;
+  cgdouble *Z; int ldz;
+  gdouble *S, *out, *ipr;
+};
+__device__ __forceinline__ Problem locate(const Args &a) {
+  const long long pb = a.map ? a.map[blockIdx.x] : (int)blockIdx.x;
+  return {a.n, (cgdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (cgdouble *)(a.w + pb * a.n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
+          a.problem ? (gdouble *)(a.S + pb * a.n * a.n) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
+          a.ipr ? (gdouble *)(a.ipr + pb * a.n) : nullptr};
+}
+__device__ __forceinline__ Problem locate(const VArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
+          (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};
+}
+
+// Sum (or maximum) over the workgroup, the same bits in every thread: a butterfly inside the wave, then the waves in
+// ascending order.  The maximum keeps a NaN (fmax would drop it): a problem with a NaN residual reports NaN.
+template <int NW, bool MAX>
+__device__ __forceinline__ double wg_reduce(double x, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double y = __shfl_xor(x, o, 64);
+    x = MAX ? ((y > x || y != y) ? y : x) : x + y;
+  }
+  if (NW == 1) return x;
+  __syncthreads();                                  // the previous call's readers are through
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+    const double y = red[w];
+    s = MAX ? ((y > s || y != y) ? y : s) : s + y;
+  }
+  return s;
+}
+
+// sum_{k < n} x[k] y[k] in ascending order, x and y in LDS: four elements' loads go out before the first use.  Every
+// multiply-add of this file is written as fma(): the instantiations must round alike, whatever the compiler contracts
+__device__ __forceinline__ double lds_dot(const double *x, const double *y, int n) {
+  double acc = 0.0;
+  int k = 0;
+  for (; k + 4 <= n; k += 4) {
+    const double x0 = x[k], x1 = x[k + 1], x2 = x[k + 2], x3 = x[k + 3];
+    const double y0 = y[k], y1 = y[k + 1], y2 = y[k + 2], y3 = y[k + 3];
+    acc = fma(x0, y0, acc); acc = fma(x1, y1, acc); acc = fma(x2, y2, acc); acc = fma(x3, y3, acc);
+  }
+  for (; k < n; ++k) acc = fma(x[k], y[k], acc);
+  return acc;
+}
+// the same for two vectors against one y (a row of A and a row of B against a column of Z)
+__device__ __forceinline__ void lds_dot2(const double *xa, const double *xb, const double *y, int n, double &da,
+                                         double &db) {
+  double a = 0.0, b = 0.0;
+  int k = 0;
+  for (; k + 4 <= n; k += 4) {
+    const double y0 = y[k], y1 = y[k + 1], y2 = y[k + 2], y3 = y[k + 3];
+    const double a0 = xa[k], a1 = xa[k + 1], a2 = xa[k + 2], a3 = xa[k + 3];
+    const double b0 = xb[k], b1 = xb[k + 1], b2 = xb[k + 2], b3 = xb[k + 3];
+    a = fma(a0, y0, a); b = fma(b0, y0, b); a = fma(a1, y1, a); b = fma(b1, y1, b);
+    a = fma(a2, y2, a); b = fma(b2, y2, b); a = fma(a3, y3, a); b = fma(b3, y3, b);
+  }
+  for (; k < n; ++k) { a = fma(xa[k], y[k], a); b = fma(xb[k], y[k], b); }
+  da = a; db = b;
+}
+
+// LDS doubles of a class: the image, 2 buffers x 2 rows of A and of B, 1 / sqrt(G_jj), a word per wave for the sums
+// over the workgroup.  At 64 that is 37 920 B: four workgroups share a CU's 160 KiB
+constexpr int lds_doubles(int NC) { return NC * (NC + 1) + 8 * NC + NC + 4; }
+
+// ARGS: how the workgroup finds its problem -- Args (one order, strided) or VArgs (a table entry)
+template <int NC, int T, typename ARGS>
+__global__ __launch_bounds__(T) void check_kernel(ARGS a) {
+  constexpr int LD = NC + 1, NW = T / 64;
+  static_assert(T == 2 * NC && T % 64 == 0, "two threads per column");
+  extern __shared__ double smem[];
+  double *Zs = smem;                      // NC x NC image of Z, leading dimension LD
+  double *sa = Zs + NC * LD;              // [buffer][half][NC]: rows of A; step 3: columns of S
+  double *sb = sa + 4 * NC;               // the same for B
+  double *sg = sb + 4 * NC;               // 1 / sqrt(G_jj)
+  double *red = sg + NC;                  // a word per wave
+  double *sx = sa;                        // step 2: [3][half][NC], the halves' sums of r^2, z s and z^4
+
+  const Problem p = locate(a);
+  const int t = threadIdx.x, n = p.n;
+  const int r = t % NC, h = t / NC;
+  const bool col = r < n;
+  const bool gen = a.problem != 0;
+  cgdouble *A = p.A;
+  cgdouble *B = p.B;
+  const int lda = p.lda, ldb = p.ldb;
+  gdouble *S = p.S;
+
+  if (col)
+    for (int j = h; j < n; j += 2) Zs[r + j * LD] = p.Z[r + (size_t)j * p.ldz];
+  const double wr = col ? p.w[r] : 0.0;
+
+  // ---- 1: R = A Z - B Z diag(w), S = B Z, the diagonal of G = Z^T S, sum z^4, ||A||_F^2
+  // entry (i, r) of the symmetric matrix whose lower triangle is M
+  auto entry = [&](cgdouble *M, int ld, int i) { return (r <= i) ? M[i + (size_t)r * ld] : M[r + (size_t)i * ld]; };
+  double asq = 0.0, rs = 0.0, gd = 0.0, p4 = 0.0;
+  {
+    double xa = 0.0, xb = 0.0;
+    if (col && h < n) {
+      xa = entry(A, lda, h);
+      if (gen) xb = entry(B, ldb, h);
+    }
+    sa[h * NC + r] = xa;
+    sb[h * NC + r] = xb;
+    asq = fma(xa, xa, asq);
+  }
+  __syncthreads();
+  const double *zc = Zs + r * LD;
+  const int steps = (n + 1) >> 1;
+  for (int m = 0; m < steps; ++m) {
+    const int i = 2 * m + h, in = i + 2;
+    double xa = 0.0, xb = 0.0;                      // the row after this one: in flight while this one is used
+    if (col && in < n) {
+      xa = entry(A, lda, in);
+      if (gen) xb = entry(B, ldb, in);
+    }
+    if (col && i < n) {
+      const int off = ((m & 1) * 2 + h) * NC;
+      const double zi = zc[i];
+      double az, bz;
+      if (gen) {
+        lds_dot2(sa + off, sb + off, zc, n, az, bz);
+        S[i + (size_t)r * n] = bz;
+      } else {
+        az = lds_dot(sa + off, zc, n);
+        bz = zi;
+      }
+      const double rr = fma(-wr, bz, az);
+      const double z2 = zi * zi;
+      rs = fma(rr, rr, rs);
+      gd = fma(zi, bz, gd);
+      p4 = fma(z2, z2, p4);
+    }
+    const int offn = (((m + 1) & 1) * 2 + h) * NC;
+    sa[offn + r] = xa;
+    sb[offn + r] = xb;
+    asq = fma(xa, xa, asq);
+    __syncthreads();
+  }
+
+  // ---- 2: the halves meet
+  sx[h * NC + r] = rs;
+  sx[(2 + h) * NC + r] = gd;
+  sx[(4 + h) * NC + r] = p4;
+  __syncthreads();
+  double rn = 0.0;
+  if (h == 0 && col) {
+    rn = sqrt(sx[r] + sx[NC + r]);
+    const double g = sx[2 * NC + r] + sx[3 * NC + r];
+    const double q = sx[4 * NC + r] + sx[5 * NC + r];
+    sg[r] = 1.0 / sqrt(g);
+    if (p.ipr) p.ipr[r] = q / (g * g);
+  }
+  const double rsum = wg_reduce<NW, false>(rn, red);
+  const double rmax = wg_reduce<NW, true>(rn, red);
+  const double anorm = sqrt(wg_reduce<NW, false>(asq, red));
+  __syncthreads();                                  // sg is written, S is in the scratch for the whole workgroup
+
+  // ---- 3: || D^-1/2 G D^-1/2 - its diagonal ||_F
+  double os = 0.0;
+  if (gen) {
+    sa[h * NC + r] = (col && h < n) ? S[r + (size_t)h * n] : 0.0;
+    __syncthreads();
+    for (int m = 0; m < steps; ++m) {
+      const int j = 2 * m + h, jn = j + 2;
+      double xs = 0.0;
+      if (col && jn < n) xs = S[r + (size_t)jn * n];
+      if (col && j < n && j != r) {
+        const double g = lds_dot(zc, sa + ((m & 1) * 2 + h) * NC, n) * sg[r] * sg[j];
+        os = fma(g, g, os);
+      }
+      sa[(((m + 1) & 1) * 2 + h) * NC + r] = xs;
+      __syncthreads();
+    }
+  } else if (col) {
+    for (int j = h; j < n; j += 2) {
+      if (j == r) continue;
+      const double g = lds_dot(zc, Zs + j * LD, n) * sg[r] * sg[j];
+      os = fma(g, g, os);
+    }
+  }
+  const double osum = wg_reduce<NW, false>(os, red);
+  if (t == 0) {
+    p.out[0] = anorm;
+    p.out[1] = rsum / anorm / (double)n;
+    p.out[2] = rmax / anorm;
+    p.out[3] = sqrt(osum);
+  }
+}
+
+template <int NC, int T, typename ARGS>
+static int launch_class(hipStream_t s, int count, const ARGS &a) {
+  constexpr size_t lds = (size_t)lds_doubles(NC) * sizeof(double);
+  static bool raised = false;                       // one per instantiation
+  if (lds > 64 * 1024 && !raised) {
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)check_kernel<NC, T, ARGS>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised = true;
+  }
+  hipLaunchKernelGGL((check_kernel<NC, T, ARGS>), dim3(count), dim3(T), lds, s, a);
+  EK_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
+
+// Device memory the entries keep (grown, never shrunk, released in ek_hip_finalize): the scratch S, the output words
+// (out, then the IPRs), the table or the map of the problems to check; two events for `seconds`
+static double *g_scratch = nullptr, *g_dout = nullptr;
+static void *g_dtable = nullptr;
+static size_t g_scratch_count = 0, g_dout_count = 0, g_dtable_bytes = 0;
+static hipEvent_t g_ev[2] = {nullptr, nullptr};
+static std::vector<Desc> g_htable;                  // host images: an upload may still read them when an error returns
+static std::vector<int> g_hmap;
+static std::vector<double> g_hout;
+
+template <typename P>
+static int grow(P **p, size_t *have, size_t want, size_t unit) {
+  if (want <= *have) return 0;
+  if (*p) (void)hipFree((void *)*p);
+  *p = nullptr;
+  *have = 0;
+  EK_HIP_CHECK(hipMalloc((void **)p, want * unit));
+  *have = want;
+  return 0;
+}
+
+static int ensure(size_t scratch, size_t dout, size_t table_bytes) {
+  { int rc = grow(&g_scratch, &g_scratch_count, scratch, sizeof(double)); if (rc) return rc; }
+  { int rc = grow(&g_dout, &g_dout_count, dout, sizeof(double)); if (rc) return rc; }
+  { int rc = grow((char **)&g_dtable, &g_dtable_bytes, table_bytes, 1); if (rc) return rc; }
+  for (int k = 0; k < 2; ++k)
+    if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
+  return 0;
+}
+
+}  // namespace bcheck
+
+namespace api {
+void release_batched_check() {
+  using namespace bcheck;
+  if (g_scratch) (void)hipFree(g_scratch);
+  if (g_dout) (void)hipFree(g_dout);
+  if (g_dtable) (void)hipFree(g_dtable);
+  g_scratch = g_dout = nullptr;
+  g_dtable = nullptr;
+  g_scratch_count = g_dout_count = g_dtable_bytes = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (g_ev[k]) (void)hipEventDestroy(g_ev[k]);
+    g_ev[k] = nullptr;
+  }
+  std::vector<Desc>().swap(g_htable);
+  std::vector<int>().swap(g_hmap);
+  std::vector<double>().swap(g_hout);
+}
+}  // namespace api
+}  // namespace ek
+
+using namespace ek;
+using namespace ek::api;
+
+static const double kNaN = std::nan("");
+
+static int uniform_check(int problem, int n, int batch, const void *A, int lda, long long strideA, const void *B,
+                         int ldb, long long strideB, const void *w, const void *Z, int ldz, long long strideZ,
+                         const double *out, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (n < 0 || n > EK_HIP_BATCH_NMAX) return -2;
+  if (batch < 0) return -3;
+  if (n == 0 || batch == 0) { *nothing = true; return 0; }
+  if (!A) return -4;
+  if (lda < n) return -5;
+  if (strideA < (long long)lda * n) return -6;
+  if (problem == 1) {
+    if (!B) return -7;
+    if (ldb < n) return -8;
+    if (strideB < (long long)ldb * n) return -9;
+  }
+  if (!w) return -10;
+  if (!Z) return -11;
+  if (ldz < n) return -12;
+  if (strideZ < (long long)ldz * n) return -13;
+  if (!out) return -15;                             // 14 is info: NULL means every problem
+  return 0;
+}
+
+// The launches' end: the output words come to the host, and problem b's go to the caller's out and ipr unless it was
+// skipped.  ipr_of(b): where the caller wants problem b's IPRs (or nullptr); off[b]: where they are behind the out words.
+template <typename NOF, typename IPR>
+static void scatter(int batch, NOF n_of, const int *info, const std::vector<size_t> &off, double *out, IPR ipr_of) {
+  const double *h = bcheck::g_hout.data();
+  for (int b = 0; b < batch; ++b) {
+    double *o = out + (size_t)b * EK_HIP_CHECK_NOUT;
+    const int n = n_of(b);
+    if (info && info[b] != 0) {
+      o[0] = o[1] = o[2] = o[3] = kNaN;
+    } else if (n == 0) {
+      o[0] = 0.0;
+      o[1] = o[2] = o[3] = kNaN;
+    } else {
+      std::memcpy(o, h + (size_t)b * EK_HIP_CHECK_NOUT, EK_HIP_CHECK_NOUT * sizeof(double));
+      double *q = ipr_of(b);
+      if (q) std::memcpy(q, h + off[b], (size_t)n * sizeof(double));
+    }
+  }
+}
+
+// launches on the context's stream between the two events, the output words to the host, one synchronise
+template <typename LAUNCH>
+static int run_and_fetch(size_t words, double *seconds, LAUNCH launch) {
+  using namespace bcheck;
+  hipStream_t s = g_ctx.stream;
+  if (seconds) (void)hipEventRecord(g_ev[0], s);
+  int rc = launch(s);
+  if (seconds) (void)hipEventRecord(g_ev[1], s);
+  g_hout.resize(words);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(g_hout.data(), g_dout, words * sizeof(double), hipMemcpyDeviceToHost, s);
+  hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
+  if (seconds && !rc) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess) *seconds = (double)ms * 1e-3;
+  }
+  return rc;
+}
+
+// arguments checked (n > 0, batch > 0), context up, g_mu held; dA, dB, dw, dZ device, info / out / ipr host
+static int uniform_device_locked(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                 const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                 int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                 double *seconds) {
+  using namespace bcheck;
+  g_hmap.clear();
+  bool skip = false;
+  if (info)
+    for (int b = 0; b < batch; ++b) {
+      if (info[b] == 0) g_hmap.push_back(b); else skip = true;
+    }
+  const int count = skip ? (int)g_hmap.size() : batch;
+  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (ipr ? (size_t)batch * n : 0);
+  std::vector<size_t> off((size_t)batch);
+  for (int b = 0; b < batch; ++b) off[b] = nout + (size_t)b * n;
+  int rc = 0;
+  if (count > 0) {
+    rc = ensure(problem ? (size_t)batch * n * n : 0, words, skip ? g_hmap.size() * sizeof(int) : 0);
+    if (rc) return rc;
+    rc = run_and_fetch(words, seconds, [&](hipStream_t s) -> int {
+      if (skip) EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_hmap.data(), g_hmap.size() * sizeof(int), hipMemcpyHostToDevice, s));
+      Args a{problem, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, skip ? (const int *)g_dtable : nullptr,
+             g_scratch, g_dout, ipr ? g_dout + nout : nullptr};
+      switch (class_of(n)) {
+        case 32: return launch_class<32, 64>(s, count, a);
+        case 64: return launch_class<64, 128>(s, count, a);
+        default: return launch_class<128, 256>(s, count, a);
+      }
+    });
+    if (rc) return rc;
+  }
+  scatter(batch, [&](int) { return n; }, info, off, out, [&](int b) { return ipr ? ipr + (size_t)b * n : nullptr; });
+  return 0;
+}
+
+// All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.
+static int variable_check(int problem, int batch, const int *n, const void *const *A, const int *lda,
+                          const void *const *B, const int *ldb, const void *const *w, const void *const *Z,
+                          const int *ldz, const double *out, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (batch < 0) return -2;
+  if (batch == 0) { *nothing = true; return 0; }
+  if (!n) return -3;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] < 0 || n[b] > EK_HIP_BATCH_NMAX) return -3;
+  auto entries = [&](const void *const *P) {
+    if (!P) return false;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && !P[b]) return false;
+    return true;
+  };
+  auto leading = [&](const int *ld) {
+    if (!ld) return false;
+    for (int b = 0; b < batch; ++b)
+      if (ld[b] < (n[b] > 1 ? n[b] : 1)) return false;
+    return true;
+  };
+  if (!entries(A)) return -4;
+  if (!leading(lda)) return -5;
+  if (problem == 1) {
+    if (!entries(B)) return -6;
+    if (!leading(ldb)) return -7;
+  }
+  if (!entries(w)) return -8;
+  if (!entries(Z)) return -9;
+  if (!leading(ldz)) return -10;
+  if (!out) return -12;                             // 11 is info: NULL means every problem
+  return 0;
+}
+
+// arguments checked (batch > 0), context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses
+static int variable_device_locked(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                  const double *const *dB, const int *ldb, const double *const *dw,
+                                  const double *const *dZ, const int *ldz, const int *info, double *out,
+                                  double *const *ipr, double *seconds) {
+  using namespace bcheck;
+  // the solver's order: a class after the other, the largest first, descending order inside a class
+  std::vector<int> order;
+  order.reserve((size_t)batch);
+  for (int b = 0; b < batch; ++b)
+    if (n[b] > 0 && !(info && info[b] != 0)) order.push_back(b);
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
+  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT;
+  std::vector<size_t> off((size_t)batch, 0), offs((size_t)batch, 0);
+  size_t words = nout, scratch = 0;
+  for (int b : order) {
+    if (ipr && ipr[b]) { off[b] = words; words += (size_t)n[b]; }
+    if (problem) { offs[b] = scratch; scratch += (size_t)n[b] * n[b]; }
+  }
+  if (!order.empty()) {
+    int rc = ensure(scratch, words, order.size() * sizeof(Desc));
+    if (rc) return rc;
+    g_htable.resize(order.size());
+    int count[3] = {0, 0, 0};                       // classes of 128, 64, 32
+    for (size_t i = 0; i < order.size(); ++i) {
+      const int b = order[i], c = class_of(n[b]);
+      ++count[c == 128 ? 0 : c == 64 ? 1 : 2];
+      g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], dZ[b], problem ? g_scratch + offs[b] : nullptr,
+                         (ipr && ipr[b]) ? g_dout + off[b] : nullptr, n[b], lda[b], problem ? ldb[b] : 1, ldz[b], b, 0};
+    }
+    rc = run_and_fetch(words, seconds, [&](hipStream_t s) -> int {
+      EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+      int rcl = 0, at = 0;
+      for (int k = 0; k < 3 && !rcl; ++k) {
+        if (!count[k]) continue;
+        VArgs a{problem, (const Desc *)g_dtable + at, g_dout};
+        rcl = k == 0 ? launch_class<128, 256>(s, count[k], a)
+            : k == 1 ? launch_class<64, 128>(s, count[k], a) : launch_class<32, 64>(s, count[k], a);
+        at += count[k];
+      }
+      return rcl;
+    });
+    if (rc) return rc;
+  }
+  scatter(batch, [&](int b) { return n[b]; }, info, off, out,
+          [&](int b) { return (ipr && ipr[b]) ? ipr[b] : nullptr; });
+  return 0;
+}
+
+extern "C" {
+
+int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                double *seconds) {
+  bool nothing;
+  int rc = uniform_check(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, out, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return uniform_device_locked(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out,
+                               ipr, seconds);
+}
+
+int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                         int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                         const int *info, double *out, double *ipr, double *seconds) {
+  bool nothing;
+  int rc = uniform_check(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, out, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  // device copies with the caller's own layout, as in ek_hip_eigenpairs_batched
+  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
+  const size_t cA = span(lda, strideA), cB = problem ? span(ldb, strideB) : 0, cZ = span(ldz, strideZ);
+  const size_t cw = (size_t)batch * n;
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cA * 8);
+  if (!rc) rc = mem.alloc(&uw, cw * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
+  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
+  return uniform_device_locked(problem, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info, out,
+                               ipr, seconds);
+}
+
+int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                 const double *const *dB, const int *ldb, const double *const *dw,
+                                 const double *const *dZ, const int *ldz, const int *info, double *out,
+                                 double *const *ipr, double *seconds) {
+  bool nothing;
+  int rc = variable_check(problem, batch, n, (const void *const *)dA, lda, (const void *const *)dB, ldb,
+                          (const void *const *)dw, (const void *const *)dZ, ldz, out, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  bool work = false;
+  for (int b = 0; b < batch && !work; ++b) work = n[b] > 0 && !(info && info[b] != 0);
+  if (work) {
+    rc = ensure_init(); if (rc) return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_mu);
+  return variable_device_locked(problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds);
+}
+
+int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                          const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                          const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
+  bool nothing;
+  int rc = variable_check(problem, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
+                          (const void *const *)w, (const void *const *)Z, ldz, out, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  // compact device layout (ld = n[b]), a problem behind the other; a skipped problem takes no room and is not read
+  std::vector<size_t> offm((size_t)batch + 1, 0), offv((size_t)batch + 1, 0);
+  for (int b = 0; b < batch; ++b) {
+    const size_t k = (info && info[b] != 0) ? 0 : (size_t)n[b];
+    offm[b + 1] = offm[b] + k * k;
+    offv[b + 1] = offv[b] + k;
+  }
+  const size_t cm = offm[batch], cv = offv[batch];
+  std::vector<const double *> pA((size_t)batch), pB((size_t)batch), pw((size_t)batch), pZ((size_t)batch);
+  std::vector<int> ldc((size_t)batch);
+  for (int b = 0; b < batch; ++b) ldc[b] = n[b] > 1 ? n[b] : 1;
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (cm == 0)                                      // nothing to launch: the slots are filled on the host
+    return variable_device_locked(problem, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(), pZ.data(),
+                                  ldc.data(), info, out, ipr, seconds);
+  rc = ensure_init(); if (rc) return rc;
+  hipStream_t s = g_ctx.stream;
+  // one staging buffer per matrix kind: the lower triangles of A and B column by column (what lies above them is
+  // never read), the columns of Z, w
+  auto live = [&](int b) { return offm[b + 1] > offm[b]; };
+  auto pack = [&](const double *const *M, const int *ld, bool lower, std::vector<double> &h) {
+    h.assign(cm, 0.0);
+    for (int b = 0; b < batch; ++b) {
+      if (!live(b)) continue;
+      for (int j = 0; j < n[b]; ++j) {
+        const int i0 = lower ? j : 0;
+        std::memcpy(&h[offm[b] + (size_t)j * n[b] + i0], M[b] + (size_t)j * ld[b] + i0, (size_t)(n[b] - i0) * 8);
+      }
+    }
+  };
+  std::vector<double> hA, hB, hZ, hw(cv);
+  pack(A, lda, true, hA);
+  if (problem) pack(B, ldb, true, hB);
+  pack(Z, ldz, false, hZ);
+  for (int b = 0; b < batch; ++b)
+    if (live(b)) std::memcpy(&hw[offv[b]], w[b], (size_t)n[b] * 8);
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cm * 8);
+  if (!rc) rc = mem.alloc(&uw, cv * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cm * 8);
+  if (!rc) rc = mem.alloc(&uZ, cm * 8);
+  if (rc) return rc;
+  for (int b = 0; b < batch; ++b) {
+    pA[b] = uA + offm[b];
+    pB[b] = problem ? uB + offm[b] : nullptr;
+    pw[b] = uw + offv[b];
+    pZ[b] = uZ + offm[b];
+  }
+  EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, hw.data(), cv * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uZ, hZ.data(), cm * 8, hipMemcpyHostToDevice, s));
+  return variable_device_locked(problem, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(), pZ.data(),
+                                ldc.data(), info, out, ipr, seconds);
+}
+
+}  // extern "C"

@@ -152,6 +152,12 @@ def load_library(path=None):
         "ek_hip_eigenpairs_vbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip,
                                                       _dp]),
         "ek_hip_eigenpairs_vbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_check_batched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int, c_ll,
+                                                _ip, _dp, _dp, _dp]),
+        "ek_hip_check_batched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
+                                         _ip, _dp, _dp, _dp]),
+        "ek_hip_check_vbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
+        "ek_hip_check_vbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
         "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
         "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
     }
@@ -193,6 +199,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_eigenpairs_batched_device", "ek_hip_eigenpairs_batched",
     "ek_hip_eigenpairs_vbatched_device", "ek_hip_eigenpairs_vbatched",
     "ek_hip_debug_vbatched_streams", "ek_hip_debug_vbatched_last",
+    "ek_hip_check_batched_device", "ek_hip_check_batched", "ek_hip_check_vbatched_device", "ek_hip_check_vbatched",
 )
 
 
@@ -762,6 +769,106 @@ def eigenpairs_vbatched(As, Bs=None, vectors=True, seconds=None):
     if rc != 0:
         raise SolverError("ek_hip_eigenpairs_vbatched failed", rc)
     return w, Z, info
+
+
+CHECK_NOUT = 4   # EK_HIP_CHECK_NOUT: a_norm, res_ave, res_max, orthogonality
+
+
+def _check_info(info, batch):
+    if info is None:
+        return None
+    info = np.ascontiguousarray(np.asarray(info), dtype=np.int32)
+    if info.shape != (batch,):
+        raise ValueError("info must hold one int per problem")
+    return info
+
+
+def check_batched(A, B, w, Z, info=None, ipr=True, seconds=None):
+    """The acceptance checks and the IPRs of every problem of a batch in one launch (ek_hip_check_batched), with the
+    normalisations of eigenkernel_amd.verifier: A (and B, or None) of shape (batch, n, n) -- the ORIGINAL matrices, lower
+    triangles referenced -- and w (batch, n), Z (batch, n, n) as eigenpairs_batched returns them.  Returns (out, ipr):
+    out[b] = (a_norm, res_ave, res_max, orthogonality) of problem b, ipr[b, j] the inverse participation ratio of column
+    j (ipr=False: None).  info: None (check every problem) or eigenpairs_batched's status words: a problem with
+    info[b] != 0 is skipped, its out row is NaN and its ipr row stays NaN.  seconds: None or a float64 array of one entry
+    that receives the device time.  Raises ValueError for bad shapes before the library is called, SolverError only
+    when the call itself fails."""
+    lib = load_library()
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("A must have shape (batch, n, n)")
+    batch, n = A.shape[0], A.shape[1]
+    Z = np.asarray(Z, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    if Z.shape != A.shape:
+        raise ValueError("Z must have the shape of A")
+    if w.shape != (batch, n):
+        raise ValueError("w must have shape (batch, n)")
+    Bt = None
+    if B is not None:
+        B = np.asarray(B, dtype=np.float64)
+        if B.shape != A.shape:
+            raise ValueError("B must have the shape of A")
+        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
+    info = _check_info(info, batch)
+    At = np.ascontiguousarray(A.transpose(0, 2, 1))
+    Zt = np.ascontiguousarray(Z.transpose(0, 2, 1))
+    wc = np.ascontiguousarray(w)
+    out = np.full((batch, CHECK_NOUT), np.nan)
+    q = np.full((batch, n), np.nan) if ipr else None
+    if n == 0:                                      # the library references nothing, `out` included
+        if batch:
+            out[:, 0] = np.where(info != 0, np.nan, 0.0) if info is not None else 0.0
+        return out, q
+    rc = lib.ek_hip_check_batched(0 if B is None else 1, n, batch, _P(At), n, n * n,
+                                  _P(Bt) if Bt is not None else None, n, n * n, _P(wc), _P(Zt), n, n * n,
+                                  _I(info) if info is not None else None, _P(out), _P(q) if ipr else None,
+                                  _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError("ek_hip_check_batched failed", rc)
+    return out, q
+
+
+def check_vbatched(As, Bs, ws, Zs, info=None, ipr=True, seconds=None):
+    """check_batched for problems of DIFFERENT orders (ek_hip_check_vbatched): As, Bs (or None), ws, Zs sequences as
+    eigenpairs_vbatched takes and returns them.  Returns (out, list of ipr arrays or None); a problem of order 0 gets
+    a_norm = 0 and NaN in its other three slots.  Each problem's bits are those of check_batched on it alone."""
+    lib = load_library()
+    Af = []
+    for M in As:
+        M = np.asarray(M, dtype=np.float64)
+        if M.ndim != 2 or M.shape[0] != M.shape[1]:
+            raise ValueError("every A must be a square 2-D array")
+        Af.append(np.asfortranarray(M))
+    batch = len(Af)
+    Bf = None
+    if Bs is not None:
+        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
+        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
+            raise ValueError("Bs must hold one array of A's shape per problem")
+    Zf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Zs]
+    if len(Zf) != batch or any(Zf[b].shape != Af[b].shape for b in range(batch)):
+        raise ValueError("Zs must hold one array of A's shape per problem")
+    wf = [np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for v in ws]
+    if len(wf) != batch or any(wf[b].shape != (Af[b].shape[0],) for b in range(batch)):
+        raise ValueError("ws must hold one vector of A's order per problem")
+    info = _check_info(info, batch)
+    out = np.full((batch, CHECK_NOUT), np.nan)
+    q = [np.full(M.shape[0], np.nan) for M in Af] if ipr else None
+    if batch == 0:
+        return out, q
+    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
+    ld = np.maximum(n, 1).astype(np.int32)
+
+    def table(arrays):
+        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
+
+    rc = lib.ek_hip_check_vbatched(0 if Bf is None else 1, batch, _I(n), table(Af), _I(ld),
+                                   table(Bf) if Bf is not None else None, _I(ld), table(wf), table(Zf), _I(ld),
+                                   _I(info) if info is not None else None, _P(out), table(q) if ipr else None,
+                                   _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError("ek_hip_check_vbatched failed", rc)
+    return out, q
 
 
 def sy2sb(A):

@@ -67,8 +67,9 @@ int ek_hip_version(void);                       /* 100*major + minor.  2: round 
                                                  * with the window entries ek_hip_eigenpairs* and
                                                  * ek_hip_stebz_range, and with ek_hip_sygvx*,
                                                  * ek_hip_sygst_ibtype and ek_hip_trmm, and with
-                                                 * ek_hip_eigenpairs_batched* and
-                                                 * ek_hip_eigenpairs_vbatched*: their symbols are the
+                                                 * ek_hip_eigenpairs_batched*,
+                                                 * ek_hip_eigenpairs_vbatched*, ek_hip_check_batched*
+                                                 * and ek_hip_check_vbatched*: their symbols are the
                                                  * signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
@@ -284,6 +285,72 @@ int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const in
 int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
                                const double *const *B, const int *ldb, double *const *w, double *const *Z,
                                const int *ldz, int *info, double *seconds);
+
+/* The acceptance checks and the inverse participation ratios of EVERY problem of a batch -- what ek_hip_residual_device,
+ * ek_hip_orthogonality_device and ek_hip_ipratios_device are to one problem, with the same normalisations (the
+ * reference's: verifier.f90:75-204, :233-330, distribute_matrix.f90:18-78), for the eigenpairs that
+ * ek_hip_eigenpairs_batched* / ek_hip_eigenpairs_vbatched* return.  One kernel launch per call (uniform form), at most
+ * three (variable form: one per kernel class present, largest class first, descending order inside a class); a
+ * workgroup owns a problem from its first load to its last store.  NOT COLLECTIVE; the calls synchronise.
+ * Per problem, all n columns checked, A and B symmetric by their lower triangles (as PDSYMM('L','L')):
+ *   out[4 b + 0]  a_norm         ||A||_F
+ *   out[4 b + 1]  res_ave        sum_j ||r_j||_2 / a_norm / n,  r_j = A z_j - w_j B z_j  (B = I for problem 0)
+ *   out[4 b + 2]  res_max        max_j ||r_j||_2 / a_norm
+ *   out[4 b + 3]  orthogonality  || D^-1/2 G D^-1/2 with zero diagonal ||_F, G = Z^T B Z, D = diag(G): scaled by the
+ *                                computed G_jj, the reference's quirk
+ *   ipr           ipr_j = sum_i z_ij^4 / G_jj^2
+ * Arguments: problem, n, batch, lda / ldb / ldz, strideA / strideB / strideZ and the layouts are those of
+ * ek_hip_eigenpairs_batched* (0 <= n <= EK_HIP_BATCH_NMAX; a stride of 0 is an argument error; dB, ldb, strideB not
+ * looked at for problem 0; n = 0 or batch = 0: success, nothing referenced and nothing written, `out` included).
+ *   dA, dB        : in: the ORIGINAL matrices.  ek_hip_eigenpairs_batched_device overwrites its dA and dB, so a caller of
+ *                   the device forms keeps copies for this call.  Only the lower triangles are referenced; strictly
+ *                   upper triangles and the rows n..ld-1 of a column are never read (a NaN there shows nowhere)
+ *   dw, dZ        : in: the eigenvalues (batch x n, problem b at dw + b * n) and eigenvectors of the solver entries
+ *   info          : HOST array of batch ints or NULL.  NULL: every problem is checked.  Otherwise a problem with
+ *                   info[b] != 0 is skipped: its four out slots receive NaN, its ipr slots are left as they were, its w
+ *                   and Z are not read by the kernel
+ *   out           : HOST array, batch * EK_HIP_CHECK_NOUT doubles
+ *   ipr           : HOST array of batch x n doubles (problem b at ipr + b * n), or NULL
+ *   seconds       : NULL or one double: device time from before the first launch to after the last
+ * Divisions are plain IEEE, as in the one-problem entries: a zero A gives NaN or Inf in the residual slots, a zero
+ * column of Z NaN in orthogonality and in its own ipr slot, NaN or Inf in a problem's w or Z shows in that problem's
+ * outputs only; none of it changes the return value.
+ * Return value: 0 when the arguments were legal and the launches ran; -k for argument k of the prototype, the first
+ * offending argument deciding, decided before any device work and without dereferencing any data pointer (info = NULL
+ * and ipr = NULL are legal, out = NULL is -15); <= -1000 HIP runtime error.
+ * THE SAME BITS WHEREVER A PROBLEM SITS: a problem's outputs depend on (n, A, B, w, Z) alone -- alone, at any position
+ * of any batch, in the uniform and the variable form, in the host and the device form.  The call writes only out and
+ * ipr: A, B, w and Z are const and come back bit for bit.
+ * Workspace (device memory, kept until ek_hip_finalize): n^2 doubles per checked problem of a generalized batch (S = B Z;
+ * none for problem 0), 4 + n doubles per problem for the outputs, 4 bytes (uniform form with skipped problems) or one
+ * 72-byte table entry (variable form) per checked problem, two events. */
+#define EK_HIP_CHECK_NOUT 4   /* out + 4*b: a_norm, res_ave, res_max, orthogonality of problem b */
+int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                double *seconds);
+/* host arrays A, B, w, Z with the same layout (the call works on device copies; the caller's arrays are untouched) */
+int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                         int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                         const int *info, double *out, double *ipr, double *seconds);
+/* The same for problems of DIFFERENT orders, with the conventions of ek_hip_eigenpairs_vbatched*: n, lda, ldb, ldz, info,
+ * out and the pointer arrays dA, dB, dw, dZ, ipr are HOST arrays of `batch` entries; the pointers IN dA, dB, dw, dZ are
+ * device addresses (device form) or host addresses (host form), those in ipr always host addresses.
+ *   n             : 0 <= n[b] <= EK_HIP_BATCH_NMAX; a problem of order 0 references nothing and gets a_norm = 0 and NaN in
+ *                   its other three slots (0 / 0, as the formulas give)
+ *   ipr           : NULL, or ipr[b] holds n[b] doubles; a NULL entry means "not wanted for this problem"
+ * Return value: -3 n NULL or an order out of range; -4 / -6 / -8 / -9 array NULL or a NULL entry for a problem of order
+ * > 0; -5 / -7 / -10 array NULL or a leading dimension below max(1, n[b]); -12 out NULL.  Problem b's outputs are
+ * bit-identical to the uniform call's for the same (n, A, B, w, Z). */
+int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                 const double *const *dB, const int *ldb, const double *const *dw,
+                                 const double *const *dZ, const int *ldz, const int *info, double *out,
+                                 double *const *ipr, double *seconds);
+/* host addresses in A, B, w, Z: the lower triangles of A and B travel packed (ld = n[b]), one copy per matrix kind; the
+ * caller's arrays are untouched, and a skipped problem's arrays are not read at all */
+int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                          const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                          const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs

@@ -10,6 +10,12 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  (ek_hip_eigenpairs_vbatched_device, a stream per class and one stream)
                                                  against a uniform call per distinct order and against one uniform call
                                                  with every problem padded to order 128
+  python tools/batched_timing.py --check [--sizes 64,128] [--batches 1024,4096]
+                                                 with vectors only: after each timed solve, the batched check
+                                                 (ek_hip_check_batched_device) on its w and Z -- the check's device time
+                                                 beside the solve's, the worst res_max and orthogonality of the batch
+  python tools/batched_timing.py --once 64g --once-batch 1024 --check
+                                                 one solve and one check after a warm-up of each
 
 Per (problem, jobz, n, batch): one warm-up of each kind, then three rounds that alternate the kinds, best by wall clock
 (both calls synchronise; both work in place, so the inputs are restored outside the clock).  The loop is timed over
@@ -52,6 +58,7 @@ class Case:
         self.dA, self.dB, self.dZ = (self.alloc(batch * n * n * 8) for _ in range(3))
         self.dw = self.alloc(batch * n * 8)
         self.info = np.zeros(batch, dtype=np.int32)
+        self.dA0 = self.dB0 = None                  # the original matrices, for the check (the solver works in place)
 
     def alloc(self, nbytes):
         p = ctypes.c_void_p()
@@ -76,6 +83,26 @@ class Case:
         t = time.perf_counter() - t0
         assert rc == 0 and not self.info.any(), (rc, self.info[self.info != 0][:4])
         return t, sec.value
+
+    def check(self, problem):
+        """The batched check on what the last batched(problem, 1) left in dw and dZ: wall time, device time, out."""
+        n, nn = self.n, self.n * self.n
+        if self.dA0 is None:
+            self.dA0, self.dB0 = self.alloc(self.hA.nbytes), self.alloc(self.hB.nbytes)
+            assert self.lib.ek_hip_memcpy_h2d(self.dA0, self.hA.ctypes.data, self.hA.nbytes) == 0
+            assert self.lib.ek_hip_memcpy_h2d(self.dB0, self.hB.ctypes.data, self.hB.nbytes) == 0
+        out = np.zeros((self.batch, 4))
+        ipr = np.zeros((self.batch, n))
+        dp = ctypes.POINTER(ctypes.c_double)
+        sec = ctypes.c_double(0.0)
+        t0 = time.perf_counter()
+        rc = self.lib.ek_hip_check_batched_device(problem, n, self.batch, self.dA0, n, nn,
+                                                  self.dB0 if problem else None, n, nn, self.dw, self.dZ, n, nn,
+                                                  self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                  out.ctypes.data_as(dp), ipr.ctypes.data_as(dp), ctypes.byref(sec))
+        t = time.perf_counter() - t0
+        assert rc == 0, rc
+        return t, sec.value, out
 
     def loop(self, problem, jobz, count):
         n, nn = self.n, self.n * self.n
@@ -203,6 +230,8 @@ def main():
     ap.add_argument("--batches", default="1,256,4096")
     ap.add_argument("--loop-max", type=int, default=64)
     ap.add_argument("--once", default=None, help="<n>g or <n>s: one generalized / standard batch of 256 with vectors")
+    ap.add_argument("--once-batch", type=int, default=256)
+    ap.add_argument("--check", action="store_true", help="time the batched check behind each solve (with vectors)")
     ap.add_argument("--mixed", action="store_true", help="problems of different orders: the variable call")
     ap.add_argument("--mixed-batch", type=int, default=2048)
     ap.add_argument("--mixed-orders", default="8,128", help="lo,hi of the uniformly drawn orders")
@@ -216,11 +245,39 @@ def main():
         return
     if args.once:
         n, problem = int(args.once[:-1]), 1 if args.once.endswith("g") else 0
-        c = Case(lib, n, 256)
+        c = Case(lib, n, args.once_batch)
         c.batched(problem, 1)
+        if args.check:
+            c.check(problem)
         t, dev = c.batched(problem, 1)
-        print("once: n=%d problem=%d batch=256 wall %.3f ms device %.3f ms" % (n, problem, t * 1e3, dev * 1e3))
+        print("once: n=%d problem=%d batch=%d wall %.3f ms device %.3f ms"
+              % (n, problem, args.once_batch, t * 1e3, dev * 1e3))
+        if args.check:
+            t, dev, out = c.check(problem)
+            print("once: the check on its w and Z: wall %.3f ms device %.3f ms, worst res_max %.2e orthogonality %.2e"
+                  % (t * 1e3, dev * 1e3, out[:, 2].max(), out[:, 3].max()))
         c.close()
+        lib.ek_hip_finalize()
+        return
+    if args.check:
+        print("# problem     n batch | solve device ms | check wall ms  device ms  us/problem | check / solve | "
+              "worst res_max  orthogonality")
+        for n in (int(x) for x in args.sizes.split(",")):
+            for batch in (int(x) for x in args.batches.split(",")):
+                c = Case(lib, n, batch)
+                for problem in (1, 0):
+                    ts, tc, worst = [], [], np.zeros(2)
+                    c.batched(problem, 1); c.check(problem)                         # warm-up
+                    for _ in range(3):
+                        ts.append(c.batched(problem, 1)[1])
+                        t, d, out = c.check(problem)
+                        tc.append((d, t))
+                        worst = np.maximum(worst, [out[:, 2].max(), out[:, 3].max()])
+                    d, t = min(tc)
+                    print("  %7d %5d %5d | %15.3f | %13.3f %10.3f %11.2f | %13.3f | %13.2e %14.2e"
+                          % (problem, n, batch, min(ts) * 1e3, t * 1e3, d * 1e3, d / batch * 1e6, d / min(ts), worst[0],
+                             worst[1]), flush=True)
+                c.close()
         lib.ek_hip_finalize()
         return
     print("# problem jobz     n batch | batched wall ms  device ms  us/problem  problems/s | loop ms (scaled)  "
