@@ -17,6 +17,17 @@
 //      owns -- dc_leaf_kernel's arithmetic with the barriers taken out of the chain; rank sort, w -> dw
 //   5  Z <- Q Z (reflector tails read back from dA, staged like L), Z <- L^-T Z, columns stored in ascending order
 //
+// ek_hip_sygv_batched*: DSYGV's problem types 2 and 3 (A B x = l x, B A x = l x) differ from type 1 in two stages only.
+//   2  C = L^T A L, in place in the image: X = A L (a thread pair per row: X[t, j] = sum_{k >= j} A[t, k] L[k, j] for
+//      ascending j reads columns >= j of its own row, which are still A), then C = L^T X, lower half (a thread pair per
+//      column: C[i, t] = sum_{k >= i} L[k, i] X[k, t] for ascending i reads rows >= i of its own column), then the
+//      mirror.  The two threads of a pair take every other term and the two partial sums are added in one order
+//   5  type 2 keeps Z <- L^-T Z; type 3 runs Z <- L Z (a thread per column, the columns of L in descending order)
+// Everything between works on C unchanged, so the two types return the same w and leave the same image in dA, and
+// itype 1 is problem 1.  The two types have an instantiation of their own (CONG), so that the kernel of the standard
+// problem and of type 1 holds nothing of them.  Scaling of A is stage 0's; what is amplified here is lambda_max(B),
+// not 1 / lambda_min(B).
+//
 // Image layout: column-major with leading dimension NC + 1 (odd), NC the class size 32 / 64 / 128.  A wave that walks
 // down a column (consecutive rows) and a wave that walks along a row (stride NC + 1, odd) both hit 32 different
 // 64-bit banks per 32 lanes.  Threads: T = 2 NC; thread t is (row or column t % NC, half t / NC).
@@ -42,7 +53,8 @@ struct Args {
   double *w;
   double *Z; int ldz; long long sZ;
   int *info;
-};
+  int itype;                                        // 1 / 2 / 3 as DSYGV's, looked at when problem == 1; last, so that
+};                                                  // what the kernel of type 1 loads lies where it always lay
 
 // ek_hip_eigenpairs_vbatched*: problems of different orders in one call.  A workgroup finds its problem in a table
 // (one entry per problem of order > 0, a class after the other, descending order inside a class); `index` is the
@@ -55,6 +67,7 @@ struct VArgs {
   int problem, jobz;
   const Desc *table;
   int *info;
+  int itype;
 };
 
 // What a workgroup works on, whichever way it found it.  The pointers are typed as global: one that arrives as a kernel
@@ -115,8 +128,90 @@ __device__ __forceinline__ void lds_axpy(double *y, const double *x, double a, i
   for (; i < i1; ++i) y[i * SY] -= x[i] * a;
 }
 
+// sum of x[k * SX] * l[k] over k = k0, k0 + 2, ... < n, in that order: four elements' loads go out before the first
+// multiply-add (lds_axpy's reason)
+template <int SX>
+__device__ __forceinline__ double lds_dot2(const double *x, const double *l, int k0, int n) {
+  double acc = 0.0;
+  int k = k0;
+  for (; k + 6 < n; k += 8) {
+    const double x0 = x[k * SX], x1 = x[(k + 2) * SX], x2 = x[(k + 4) * SX], x3 = x[(k + 6) * SX];
+    const double l0 = l[k], l1 = l[k + 2], l2 = l[k + 4], l3 = l[k + 6];
+    acc += x0 * l0;
+    acc += x1 * l1;
+    acc += x2 * l2;
+    acc += x3 * l3;
+  }
+  for (; k < n; k += 2) acc += x[k * SX] * l[k];
+  return acc;
+}
+
+// Types 2 and 3, stage 2: the image A (full, symmetric) becomes C = L^T A L (lower half), in place.  L comes back from
+// dB a column per step through the two sl vectors, as in type 1's solves.  Thread (r, sub) sums the terms k = j + sub,
+// j + sub + 2, ...; the partial sums meet in sq (2 x 2 NC doubles, the halves alternating between steps, so that a
+// step needs one barrier) and are added as sub 0's plus sub 1's: the order of every sum depends on n alone.
+template <int NC>
+__device__ __forceinline__ void congruence_in_image(double *S, double *sl, double *sq, const gdouble *B, int ldb,
+                                                    int n) {
+  constexpr int LD = NC + 1;
+  const int t = threadIdx.x, r = t % NC, sub = t / NC;
+  const bool row = r < n;
+  if (t < n) sl[t] = B[t];                          // column 0 of L
+  __syncthreads();
+  // X = A L: the pair r owns row r.  Step j reads columns >= j of the row, which are still A, and leaves X[r, j]
+  for (int j = 0; j < n; ++j) {
+    const double *cur = sl + (j & 1) * NC;
+    double *q = sq + (j & 1) * 2 * NC;
+    double nx = 0.0;
+    if (j + 1 < n && t > j && t < n) nx = B[t + (size_t)(j + 1) * ldb];
+    if (row) q[sub * NC + r] = lds_dot2<LD>(S + r, cur, j + sub, n);
+    if (t < n) sl[((j + 1) & 1) * NC + t] = nx;
+    __syncthreads();
+    if (sub == 0 && row) S[r + j * LD] = q[r] + q[NC + r];
+  }
+  if (t < n) sl[t] = B[t];
+  __syncthreads();
+  // C = L^T X, lower half: the pair r owns column r.  Step i reads rows >= i of the column and leaves C[i, r]
+  for (int i = 0; i < n; ++i) {
+    const double *cur = sl + (i & 1) * NC;
+    double *q = sq + (i & 1) * 2 * NC;
+    double nx = 0.0;
+    if (i + 1 < n && t > i && t < n) nx = B[t + (size_t)(i + 1) * ldb];
+    if (row && r <= i) q[sub * NC + r] = lds_dot2<1>(S + r * LD, cur, i + sub, n);
+    if (t < n) sl[((i + 1) & 1) * NC + t] = nx;
+    __syncthreads();
+    if (sub == 0 && row && r <= i) S[i + r * LD] = q[r] + q[NC + r];
+  }
+  __syncthreads();                                  // the mirror reads rows that other threads wrote
+}
+
+// Type 3, stage 5: Z <- L Z, thread t owns column t of Z.  For k = n-1 .. 0: z[i] += L[i, k] z[k] for i > k, then
+// z[k] *= L[k, k]; column k of L is staged like the reflectors.
+template <int NC>
+__device__ __forceinline__ void multiply_by_l(double *S, double *sl, const gdouble *B, int ldb, int n) {
+  constexpr int LD = NC + 1;
+  const int t = threadIdx.x;
+  if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
+  __syncthreads();
+  for (int k = n - 1, s = 0; k >= 0; --k, ++s) {
+    const double *cur = sl + (s & 1) * NC;
+    double nx = 0.0;
+    if (k >= 1 && t >= k - 1 && t < n) nx = B[t + (size_t)(k - 1) * ldb];
+    if (t < n) {
+      double *col = S + t * LD;
+      const double zk = col[k];
+      lds_axpy<1>(col, cur, -zk, k + 1, n);         // y - x (-zk): the sign change is exact
+      col[k] = zk * cur[k];
+    }
+    if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+    __syncthreads();
+  }
+}
+
 // ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or VArgs (a table entry)
-template <int NC, int T, typename ARGS = Args>
+// CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
+// CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
+template <int NC, int T, typename ARGS = Args, bool CONG = false>
 __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   constexpr int LD = NC + 1, P = T / NC, NW = T / 64;
   static_assert(P == 2 && T % 64 == 0, "two threads per row");
@@ -189,14 +284,18 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
     __syncthreads();                                // L is in dB for the whole workgroup; the image is free
   }
 
-  // ---- 2: A -> full symmetric image; C = L^-1 A L^-T
+  // ---- 2: A -> full symmetric image; C = L^-1 A L^-T (type 1), C = L^T A L (types 2 and 3)
   if (row)
     for (int j = sub; j <= r; j += P) {
       const double x = ldexp(A[r + (size_t)j * lda], -aex);   // exact; aex = 0 leaves the bits alone
       S[r + j * LD] = x;
       S[j + r * LD] = x;
     }
-  if (a.problem) {
+  if (CONG) {
+    congruence_in_image<NC>(S, sl, sv, B, ldb, n);  // sv, sw, sp: 4 NC doubles, free until stage 3
+    if (row)
+      for (int j = sub; j < r; j += P) S[j + r * LD] = S[r + j * LD];
+  } else if (a.problem) {
     if (t < n) sl[t] = B[t];                        // column 0 of L
     __syncthreads();
     // X = L^-1 A: thread t owns column t of the image
@@ -502,8 +601,11 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
       __syncthreads();
     }
   }
-  // Z <- L^-T Z
-  if (a.problem) {
+  // Z <- L^-T Z (types 1 and 2), Z <- L Z (type 3)
+  if (CONG && a.itype == 3) {
+    __syncthreads();
+    multiply_by_l<NC>(S, sl, B, ldb, n);
+  } else if (a.problem) {
     __syncthreads();
     if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
     __syncthreads();
@@ -527,18 +629,24 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   if (t == 0) *info = 0;
 }
 
-template <int NC, int T, typename ARGS>
-static int launch_class(hipStream_t s, int batch, const ARGS &a) {
+template <int NC, int T, typename ARGS, bool CONG>
+static int launch_instance(hipStream_t s, int batch, const ARGS &a) {
   constexpr size_t lds = (size_t)(NC * (NC + 1) + 9 * NC) * sizeof(double);
-  static bool raised = false;                       // one per instantiation, the variable ones included
+  static bool raised = false;                       // one per instantiation, the variable ones and CONG's included
   if (lds > 64 * 1024 && !raised) {
-    EK_HIP_CHECK(hipFuncSetAttribute((const void *)batched_kernel<NC, T, ARGS>,
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)batched_kernel<NC, T, ARGS, CONG>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     raised = true;
   }
-  hipLaunchKernelGGL((batched_kernel<NC, T, ARGS>), dim3(batch), dim3(T), lds, s, a);
+  hipLaunchKernelGGL((batched_kernel<NC, T, ARGS, CONG>), dim3(batch), dim3(T), lds, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
+}
+
+template <int NC, int T, typename ARGS>
+static int launch_class(hipStream_t s, int batch, const ARGS &a) {
+  return (a.problem && a.itype != 1) ? launch_instance<NC, T, ARGS, true>(s, batch, a)
+                                     : launch_instance<NC, T, ARGS, false>(s, batch, a);
 }
 
 // LDS bytes (dynamic part) and threads of the class that takes order n: host arithmetic for tools and DESIGN.md 12
@@ -640,12 +748,12 @@ static int batched_check(int problem, int jobz, int n, int batch, const void *A,
 }
 
 // arguments checked, context up, g_mu held
-static int batched_device_locked(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
-                                 double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
-                                 long long strideZ, int *info, double *seconds) {
+static int batched_device_locked(int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
+                                 long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ,
+                                 int ldz, long long strideZ, int *info, double *seconds) {
   hipStream_t s = g_ctx.stream;
   { int rc0 = batched::ensure_info((size_t)batch); if (rc0) return rc0; }
-  batched::Args a{problem, jobz, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, batched::g_dinfo};
+  batched::Args a{problem, jobz, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, batched::g_dinfo, itype};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (seconds) {
     EK_HIP_CHECK(hipEventCreate(&e0));
@@ -715,9 +823,9 @@ static int vbatched_check(int problem, int jobz, int batch, const int *n, const 
 }
 
 // arguments checked, context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses
-static int vbatched_device_locked(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
-                                  double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
-                                  const int *ldz, int *info, double *seconds) {
+static int vbatched_device_locked(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
+                                  const int *lda, double *const *dB, const int *ldb, double *const *dw,
+                                  double *const *dZ, const int *ldz, int *info, double *seconds) {
   using namespace batched;
   // a class after the other, the largest first; inside a class descending order: the dispatcher hands out workgroups
   // in index order and a workgroup's time grows like n^2 .. n^3, so this is longest-first list scheduling
@@ -756,7 +864,7 @@ static int vbatched_device_locked(int problem, int jobz, int batch, const int *n
     if (!count[k]) continue;
     if (cs[k] != s) e = hipStreamWaitEvent(cs[k], g_ev[0], 0);
     if (e != hipSuccess) break;
-    VArgs a{problem, jobz, g_dtable + off, g_dinfo};
+    VArgs a{problem, jobz, g_dtable + off, g_dinfo, itype};
     if (seconds) (void)hipEventRecord(g_ev[3 + 2 * k], cs[k]);
     rc = k == 0 ? launch_class<128, 256>(cs[k], count[k], a)
        : k == 1 ? launch_class<64, 128>(cs[k], count[k], a) : launch_class<32, 64>(cs[k], count[k], a);
@@ -791,11 +899,11 @@ static int vbatched_device_locked(int problem, int jobz, int batch, const int *n
   return rc;
 }
 
-extern "C" {
-
-int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
-                                     double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
-                                     long long strideZ, int *info, double *seconds) {
+// The bodies of the entries: ek_hip_eigenpairs_* pass itype 1, ek_hip_sygv_* problem 1 (argument k of the one is
+// argument k of the other).
+static int batched_device_entry(int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
+                                long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ,
+                                int ldz, long long strideZ, int *info, double *seconds) {
   bool nothing;
   int rc = batched_check(problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
                          &nothing);
@@ -804,13 +912,13 @@ int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, do
   if (nothing) return 0;
   rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
-  return batched_device_locked(problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                               seconds);
+  return batched_device_locked(problem, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
+                               info, seconds);
 }
 
-int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
-                              const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
-                              long long strideZ, int *info, double *seconds) {
+static int batched_host_entry(int problem, int itype, int jobz, int n, int batch, const double *A, int lda,
+                              long long strideA, const double *B, int ldb, long long strideB, double *w, double *Z,
+                              int ldz, long long strideZ, int *info, double *seconds) {
   bool nothing;
   int rc = batched_check(problem, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
                          &nothing);
@@ -836,8 +944,8 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
   EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
   if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
   if (zpad) EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  rc = batched_device_locked(problem, jobz, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info,
-                             seconds);
+  rc = batched_device_locked(problem, itype, jobz, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ,
+                             info, seconds);
   if (rc) return rc;
   EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
   if (jobz) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
@@ -845,9 +953,9 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
   return 0;
 }
 
-int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
-                                      double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
-                                      const int *ldz, int *info, double *seconds) {
+static int vbatched_device_entry(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
+                                 const int *lda, double *const *dB, const int *ldb, double *const *dw,
+                                 double *const *dZ, const int *ldz, int *info, double *seconds) {
   bool nothing;
   int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)dA, lda, (const void *const *)dB, ldb,
                           (const void *const *)dw, (const void *const *)dZ, ldz, info, &nothing);
@@ -862,12 +970,12 @@ int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const in
   }
   rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
-  return vbatched_device_locked(problem, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
+  return vbatched_device_locked(problem, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
 }
 
-int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
-                               const double *const *B, const int *ldb, double *const *w, double *const *Z,
-                               const int *ldz, int *info, double *seconds) {
+static int vbatched_host_entry(int problem, int itype, int jobz, int batch, const int *n, const double *const *A,
+                               const int *lda, const double *const *B, const int *ldb, double *const *w,
+                               double *const *Z, const int *ldz, int *info, double *seconds) {
   bool nothing;
   int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
                           (const void *const *)w, (const void *const *)Z, ldz, info, &nothing);
@@ -916,7 +1024,7 @@ int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, c
   }
   EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
   if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
-  rc = vbatched_device_locked(problem, jobz, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(),
+  rc = vbatched_device_locked(problem, itype, jobz, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(),
                               pZ.data(), ldc.data(), info, seconds);
   if (rc) return rc;
   hw.resize(cv);
@@ -934,6 +1042,65 @@ int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, c
         std::memcpy(Z[b] + (size_t)j * ldz[b], &hZ[offm[b] + (size_t)j * n[b]], (size_t)n[b] * 8);
   }
   return 0;
+}
+
+extern "C" {
+
+int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                     double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                     long long strideZ, int *info, double *seconds) {
+  return batched_device_entry(problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                              seconds);
+}
+
+int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                              const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                              long long strideZ, int *info, double *seconds) {
+  return batched_host_entry(problem, 1, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
+                            seconds);
+}
+
+int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                      double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                      const int *ldz, int *info, double *seconds) {
+  return vbatched_device_entry(problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
+}
+
+int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                               const double *const *B, const int *ldb, double *const *w, double *const *Z,
+                               const int *ldz, int *info, double *seconds) {
+  return vbatched_host_entry(problem, 1, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds);
+}
+
+// DSYGV's three problem types: problem 1 with itype in its place, so that every other argument keeps its number
+int ek_hip_sygv_batched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                               double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                               long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return batched_device_entry(1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                              seconds);
+}
+
+int ek_hip_sygv_batched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                        const double *B, int ldb, long long strideB, double *w, double *Z, int ldz, long long strideZ,
+                        int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return batched_host_entry(1, itype, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
+                            seconds);
+}
+
+int ek_hip_sygv_vbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                const int *ldz, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return vbatched_device_entry(1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
+}
+
+int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                         const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
+                         int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds);
 }
 
 int ek_hip_debug_vbatched_streams(int streams) {

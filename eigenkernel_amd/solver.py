@@ -152,6 +152,12 @@ def load_library(path=None):
         "ek_hip_eigenpairs_vbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip,
                                                       _dp]),
         "ek_hip_eigenpairs_vbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_sygv_batched_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp,
+                                               c_int, c_ll, _ip, _dp]),
+        "ek_hip_sygv_batched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
+                                        c_ll, _ip, _dp]),
+        "ek_hip_sygv_vbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_sygv_vbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_check_batched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int, c_ll,
                                                 _ip, _dp, _dp, _dp]),
         "ek_hip_check_batched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
@@ -200,6 +206,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_eigenpairs_vbatched_device", "ek_hip_eigenpairs_vbatched",
     "ek_hip_debug_vbatched_streams", "ek_hip_debug_vbatched_last",
     "ek_hip_check_batched_device", "ek_hip_check_batched", "ek_hip_check_vbatched_device", "ek_hip_check_vbatched",
+    "ek_hip_sygv_batched_device", "ek_hip_sygv_batched", "ek_hip_sygv_vbatched_device", "ek_hip_sygv_vbatched",
 )
 
 
@@ -699,19 +706,14 @@ def eigenpairs(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, stag
 BATCH_NMAX = 128   # EK_HIP_BATCH_NMAX
 
 
-def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
-    """Many small problems in one launch (ek_hip_eigenpairs_batched): A (and B, SPD) of shape (batch, n, n) with
-    n <= BATCH_NMAX, lower triangles referenced.  Returns (w, Z or None, info): w[b] problem b's eigenvalues ascending,
-    Z[b][:, k] the eigenvector of w[b, k] (B-orthonormal with B), info[b] its status (0; k > 0: B[b] not SPD at pivot
-    k; -5: NaN / Inf in A[b]) -- the w and Z of a failed problem are unspecified, the others are unaffected.  A and B
-    are not modified.  seconds: None or a float64 array of one entry that receives the device time.  Raises SolverError
-    only when the call itself fails (illegal argument, HIP error), never for a problem's info."""
+def _batched_call(name, first, A, B, vectors, seconds):
+    """ek_hip_eigenpairs_batched / ek_hip_sygv_batched on (batch, n, n) arrays; `first` is the first argument (problem
+    or itype)."""
     lib = load_library()
     A = np.asarray(A, dtype=np.float64)
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
         raise ValueError("A must have shape (batch, n, n)")
     batch, n = A.shape[0], A.shape[1]
-    problem = 0 if B is None else 1
     # column-major per problem: the transpose of each C-ordered slice
     At = np.ascontiguousarray(A.transpose(0, 2, 1))
     Bt = None
@@ -723,21 +725,40 @@ def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
     w = np.zeros((batch, n))
     Zt = np.zeros((batch, n, n)) if vectors else None
     info = np.zeros(max(batch, 1), dtype=np.int32)
-    rc = lib.ek_hip_eigenpairs_batched(problem, 1 if vectors else 0, n, batch, _P(At), n, n * n,
-                                       _P(Bt) if Bt is not None else None, n, n * n, _P(w),
-                                       _P(Zt) if vectors else None, n, n * n, _I(info),
-                                       _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, name)(first, 1 if vectors else 0, n, batch, _P(At), n, n * n,
+                            _P(Bt) if Bt is not None else None, n, n * n, _P(w),
+                            _P(Zt) if vectors else None, n, n * n, _I(info),
+                            _P(seconds) if seconds is not None else None)
     if rc != 0:
-        raise SolverError("ek_hip_eigenpairs_batched failed", rc)
+        raise SolverError(name + " failed", rc)
     return w, (Zt.transpose(0, 2, 1) if vectors else None), info[:batch]
 
 
-def eigenpairs_vbatched(As, Bs=None, vectors=True, seconds=None):
-    """Many small problems of DIFFERENT orders in one call (ek_hip_eigenpairs_vbatched): As (and Bs, SPD) sequences of
-    square 2-D arrays, problem b of order As[b].shape[0] <= BATCH_NMAX (0 allowed), lower triangles referenced.
-    Returns (list of w, list of Z or None, info) with the meaning of eigenpairs_batched per problem; each problem's
-    bits are those of eigenpairs_batched on that pair alone.  As and Bs are not modified.  Raises ValueError for bad
-    shapes before the library is called, SolverError only when the call itself fails."""
+def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
+    """Many small problems in one launch (ek_hip_eigenpairs_batched): A (and B, SPD) of shape (batch, n, n) with
+    n <= BATCH_NMAX, lower triangles referenced.  Returns (w, Z or None, info): w[b] problem b's eigenvalues ascending,
+    Z[b][:, k] the eigenvector of w[b, k] (B-orthonormal with B), info[b] its status (0; k > 0: B[b] not SPD at pivot
+    k; -5: NaN / Inf in A[b]) -- the w and Z of a failed problem are unspecified, the others are unaffected.  A and B
+    are not modified.  seconds: None or a float64 array of one entry that receives the device time.  Raises SolverError
+    only when the call itself fails (illegal argument, HIP error), never for a problem's info."""
+    return _batched_call("ek_hip_eigenpairs_batched", 0 if B is None else 1, A, B, vectors, seconds)
+
+
+def sygv_batched(A, B, itype=1, vectors=True, seconds=None):
+    """eigenpairs_batched for DSYGV's three problem types (ek_hip_sygv_batched): itype 1 A x = l B x, 2 A B x = l x,
+    3 B A x = l x, B SPD and always required.  Returns and errors are those of eigenpairs_batched; Z[b] is B-orthonormal
+    for types 1 and 2 and B^-1-orthonormal for type 3; itype 1 is eigenpairs_batched(A, B) to the bit.  A missing B or an
+    itype outside 1 .. 3 raises ValueError before the library is called."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if B is None:
+        raise ValueError("B is required")
+    return _batched_call("ek_hip_sygv_batched", int(itype), A, B, vectors, seconds)
+
+
+def _vbatched_call(name, first, As, Bs, vectors, seconds):
+    """ek_hip_eigenpairs_vbatched / ek_hip_sygv_vbatched on sequences of square arrays; `first` is the first argument
+    (problem or itype)."""
     lib = load_library()
     Af = []
     for M in As:
@@ -762,13 +783,34 @@ def eigenpairs_vbatched(As, Bs=None, vectors=True, seconds=None):
     def table(arrays):
         return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
 
-    rc = lib.ek_hip_eigenpairs_vbatched(0 if Bf is None else 1, 1 if vectors else 0, batch, _I(n), table(Af), _I(ld),
-                                        table(Bf) if Bf is not None else None, _I(ld), table(w),
-                                        table(Z) if vectors else None, _I(ld), _I(info),
-                                        _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, name)(first, 1 if vectors else 0, batch, _I(n), table(Af), _I(ld),
+                            table(Bf) if Bf is not None else None, _I(ld), table(w),
+                            table(Z) if vectors else None, _I(ld), _I(info),
+                            _P(seconds) if seconds is not None else None)
     if rc != 0:
-        raise SolverError("ek_hip_eigenpairs_vbatched failed", rc)
+        raise SolverError(name + " failed", rc)
     return w, Z, info
+
+
+def eigenpairs_vbatched(As, Bs=None, vectors=True, seconds=None):
+    """Many small problems of DIFFERENT orders in one call (ek_hip_eigenpairs_vbatched): As (and Bs, SPD) sequences of
+    square 2-D arrays, problem b of order As[b].shape[0] <= BATCH_NMAX (0 allowed), lower triangles referenced.
+    Returns (list of w, list of Z or None, info) with the meaning of eigenpairs_batched per problem; each problem's
+    bits are those of eigenpairs_batched on that pair alone.  As and Bs are not modified.  Raises ValueError for bad
+    shapes before the library is called, SolverError only when the call itself fails."""
+    return _vbatched_call("ek_hip_eigenpairs_vbatched", 0 if Bs is None else 1, As, Bs, vectors, seconds)
+
+
+def sygv_vbatched(As, Bs, itype=1, vectors=True, seconds=None):
+    """eigenpairs_vbatched for DSYGV's three problem types (ek_hip_sygv_vbatched), itype as in sygv_batched, one value
+    for the whole call.  Returns and errors are those of eigenpairs_vbatched; each problem's bits are those of
+    sygv_batched on that pair alone.  A missing Bs or an itype outside 1 .. 3 raises ValueError before the library is
+    called."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if Bs is None:
+        raise ValueError("Bs is required")
+    return _vbatched_call("ek_hip_sygv_vbatched", int(itype), As, Bs, vectors, seconds)
 
 
 CHECK_NOUT = 4   # EK_HIP_CHECK_NOUT: a_norm, res_ave, res_max, orthogonality

@@ -69,8 +69,10 @@ int ek_hip_version(void);                       /* 100*major + minor.  2: round 
                                                  * ek_hip_sygst_ibtype and ek_hip_trmm, and with
                                                  * ek_hip_eigenpairs_batched*,
                                                  * ek_hip_eigenpairs_vbatched*, ek_hip_check_batched*
-                                                 * and ek_hip_check_vbatched*: their symbols are the
-                                                 * signal */
+                                                 * and ek_hip_check_vbatched*, and with
+                                                 * ek_hip_sygv_batched_device, ek_hip_sygv_batched,
+                                                 * ek_hip_sygv_vbatched_device and
+                                                 * ek_hip_sygv_vbatched: their symbols are the signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
 const char *ek_hip_stage_name(int stage);       /* reference event name of a stage index    */
@@ -285,6 +287,44 @@ int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const in
 int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
                                const double *const *B, const int *ldb, double *const *w, double *const *Z,
                                const int *ldz, int *info, double *seconds);
+
+/* DSYGV's three problem types for the batched forms -- what itype is to rocSOLVER's / cuSOLVER's sygvd batched calls and
+ * what ek_hip_sygvx* is to ek_hip_eigenpairs*:
+ *   itype 1: A x = l B x   (C = L^-1 A L^-T, x = L^-T y; X^T B X = I)
+ *   itype 2: A B x = l x   (C = L^T A L,     x = L^-T y; X^T B X = I)
+ *   itype 3: B A x = l x   (C = L^T A L,     x = L y;    X^T B^-1 X = I)
+ * with B = L L^T, one itype for the whole call.  Every other argument is exactly that of ek_hip_eigenpairs_batched* /
+ * ek_hip_eigenpairs_vbatched* with problem = 1 (argument k here is argument k there, itype in the place of problem), B is
+ * always required, and the same kernel runs: only the reduction to standard form and the recovery depend on the type.
+ * Return value: -1 for itype outside 1 .. 3, then the codes of the eigenpairs forms (uniform: -8 / -9 / -10 for B, ldb,
+ * strideB; variable: -7 / -8 for dB, ldb), decided before any device work and without dereferencing a data pointer.
+ * info[b]: 0; k > 0 the failing pivot of B (the value type 1 reports for that B); -5 NaN / Inf in A's lower triangle;
+ * 100000 + k as above; info = 0 always comes with finite w.
+ * itype 1 IS ek_hip_eigenpairs_*batched*(problem = 1): the same bits in w, Z, info and the in-place images of dA and dB.
+ * Types 2 and 3 return bit-identical w for the same (A, B) and leave the same images: dA[b] <- DSYTD2's layout of
+ * C = L^T A L (d and e those of the caller's scaling), dB[b] <- L, the L of type 1.  Their Z are related by Z3 = B Z2 to
+ * rounding.  What holds for the eigenpairs forms holds here: the same bits wherever a problem sits and in the host, the
+ * device, the uniform and the variable form; strictly upper triangles, rows n .. ld-1 and the gaps between problems are
+ * neither read nor written; a failed problem touches its own slots only.
+ * A of any finite magnitude is scaled as above, from A alone.  For types 2 and 3 the reduction amplifies by lambda_max(B)
+ * where type 1's amplifies by 1 / lambda_min(B): max|a| lambda_max(B) beyond about 2^500 can overflow and is reported as
+ * 100000 + n + 1, never as info = 0.
+ * ek_hip_check_batched* / ek_hip_check_vbatched* below remain checks of type 1 (and of the standard problem): their
+ * normalisations are the reference verifier's, which has none for types 2 and 3. */
+int ek_hip_sygv_batched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                               double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                               long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout; A and B are left untouched (the call works on device copies) */
+int ek_hip_sygv_batched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                        const double *B, int ldb, long long strideB, double *w, double *Z, int ldz, long long strideZ,
+                        int *info, double *seconds);
+int ek_hip_sygv_vbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                const int *ldz, int *info, double *seconds);
+/* host addresses in A, B, w, Z; A and B are left untouched; w[b] and Z[b] of a failed problem are left as they were */
+int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                         const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
+                         int *info, double *seconds);
 
 /* The acceptance checks and the inverse participation ratios of EVERY problem of a batch -- what ek_hip_residual_device,
  * ek_hip_orthogonality_device and ek_hip_ipratios_device are to one problem, with the same normalisations (the

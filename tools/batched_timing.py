@@ -2,7 +2,9 @@
 """The batched call (ek_hip_eigenpairs_batched_device) against the only other way to solve many small problems: a host
 loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (tools, not product).
 
-  python tools/batched_timing.py [--sizes 30,64,128] [--batches 1,256,4096] [--loop-max 64]
+  python tools/batched_timing.py [--sizes 30,64,128] [--batches 1,256,4096] [--loop-max 64] [--itype 1]
+                                                 --itype 2 / 3: the generalized rows solve A B x = l x / B A x = l x
+                                                 through ek_hip_sygv_batched_device (the loop stays type 1's: a yardstick)
   python tools/batched_timing.py --once 64g      one batched call (256 generalized pairs of order 64 with vectors)
                                                  after a warm-up: what a kernel trace should look at
   python tools/batched_timing.py --mixed [--mixed-batch 2048] [--mixed-orders 8,128]
@@ -48,8 +50,8 @@ def pairs(seed, count, n):
 
 
 class Case:
-    def __init__(self, lib, n, batch, distinct=64):
-        self.lib, self.n, self.batch = lib, n, batch
+    def __init__(self, lib, n, batch, distinct=64, itype=1):
+        self.lib, self.n, self.batch, self.itype = lib, n, batch, itype
         A, B = pairs(n, min(batch, distinct), n)
         reps = -(-batch // A.shape[0])
         self.hA = np.ascontiguousarray(np.tile(A, (reps, 1, 1))[:batch]).ravel()
@@ -75,11 +77,12 @@ class Case:
         self.restore()
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
-        rc = self.lib.ek_hip_eigenpairs_batched_device(problem, jobz, n, self.batch, self.dA, n, nn,
-                                                       self.dB if problem else None, n, nn, self.dw,
-                                                       self.dZ if jobz else None, n, nn,
-                                                       self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                       ctypes.byref(sec))
+        fn, first = self.lib.ek_hip_eigenpairs_batched_device, problem
+        if problem and self.itype != 1:
+            fn, first = self.lib.ek_hip_sygv_batched_device, self.itype
+        rc = fn(first, jobz, n, self.batch, self.dA, n, nn, self.dB if problem else None, n, nn, self.dw,
+                self.dZ if jobz else None, n, nn, self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                ctypes.byref(sec))
         t = time.perf_counter() - t0
         assert rc == 0 and not self.info.any(), (rc, self.info[self.info != 0][:4])
         return t, sec.value
@@ -229,6 +232,8 @@ def main():
     ap.add_argument("--sizes", default="30,64,128")
     ap.add_argument("--batches", default="1,256,4096")
     ap.add_argument("--loop-max", type=int, default=64)
+    ap.add_argument("--itype", type=int, choices=(1, 2, 3), default=1,
+                    help="problem type of the generalized batched rows (2, 3: ek_hip_sygv_batched_device)")
     ap.add_argument("--once", default=None, help="<n>g or <n>s: one generalized / standard batch of 256 with vectors")
     ap.add_argument("--once-batch", type=int, default=256)
     ap.add_argument("--check", action="store_true", help="time the batched check behind each solve (with vectors)")
@@ -245,7 +250,7 @@ def main():
         return
     if args.once:
         n, problem = int(args.once[:-1]), 1 if args.once.endswith("g") else 0
-        c = Case(lib, n, args.once_batch)
+        c = Case(lib, n, args.once_batch, itype=args.itype)
         c.batched(problem, 1)
         if args.check:
             c.check(problem)
@@ -280,11 +285,13 @@ def main():
                 c.close()
         lib.ek_hip_finalize()
         return
+    if args.itype != 1:
+        print("# generalized rows: itype %d (ek_hip_sygv_batched_device)" % args.itype)
     print("# problem jobz     n batch | batched wall ms  device ms  us/problem  problems/s | loop ms (scaled)  "
           "us/problem | ratio")
     for n in (int(x) for x in args.sizes.split(",")):
         for batch in (int(x) for x in args.batches.split(",")):
-            c = Case(lib, n, batch)
+            c = Case(lib, n, batch, itype=args.itype)
             count = min(batch, args.loop_max)
             for problem in (1, 0):
                 for jobz in (1, 0):
