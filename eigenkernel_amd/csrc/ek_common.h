@@ -48,6 +48,23 @@ struct GemmDesc {
 };
 void gemm(hipStream_t s, const GemmDesc &g);
 
+// What gemm() launches for a descriptor: a pure host function of it (and of EK_GEMM_VEC / EK_GEMM_W8 / EK_GEMM_RANKK, read
+// once), no GPU.  gemm() itself launches by it; the test hooks of ek_debug.hip report it.
+enum { kGemmNone = -1, kGemmSmall = 0, kGemmW4 = 1, kGemmW8 = 2, kGemmRankK = 3 };
+struct GemmPlan {
+  int kernel;            // kGemm*: gemm_small_kernel, gemm_kernel, gemm_kernel_w8, gemm_rankk_kernel; None: nothing to do
+  bool vec;              // the VEC instantiation (16-byte operand fetch); rank-k: what its own run-time test finds for
+                         // one product without tables
+  int lower_only;        // as launched: 0, 1 (full grid, tiles above the diagonal leave), 2 (compact grid, tile_of)
+  int tile;              // 64 or 128
+  int tiles_m, tiles_n;
+  unsigned grid_x;       // workgroups per batch entry
+};
+GemmPlan gemm_plan(const GemmDesc &g);
+// the compact grid's map (lower_only == 2): workgroup `tile` of a tiles_m x tiles_n tiling (tiles_n <= tiles_m) -> (tm, tn);
+// false: the workgroup has no tile.  The kernels' own function, compiled for the host.
+bool gemm_compact_tile(int tiles_m, int tiles_n, int tile, int &tm, int &tn);
+
 inline void gemm(hipStream_t s, bool ta, bool tb, int M, int N, int K, double alpha,
                  const double *A, int lda, const double *B, int ldb, double beta, double *C,
                  int ldc, bool lower_only = false, bool staged_rank_k = false, bool small_tiles = false) {

@@ -706,6 +706,111 @@ int ek_hip_debug_gemm_at(int transa, int transb, int m, int n, int k, const doub
   return 0;
 }
 
+}  // extern "C"
+
+// The descriptor of ek_hip_debug_gemm_desc / _plan from their arguments; 0 or -k for the k-th argument (decided on the
+// host: no pointer is dereferenced but the host tables).
+static int gemm_desc_of(int transa, int transb, int m, int n, int k, double alpha, double beta, const double *dA, int lda,
+                        long long strideA, const double *dB, int ldb, long long strideB, double *dC, int ldc,
+                        long long strideC, int batch, int lower_only, int staged_rank_k, int small_tiles, int even_offs,
+                        const long long *offs, const int *dims, const int *variant, GemmDesc *g) {
+  if (transa != 0 && transa != 1) return -1;
+  if (transb != 0 && transb != 1) return -2;
+  if (m < 0) return -3;
+  if (n < 0) return -4;
+  if (k < 0) return -5;
+  const bool work = m > 0 && n > 0 && batch > 0;
+  if (work && k > 0 && !dA) return -8;
+  if (lda < 1 || lda < (transa ? k : m)) return -9;
+  if (work && k > 0 && !dB) return -11;
+  if (ldb < 1 || ldb < (transb ? n : k)) return -12;
+  if (work && !dC) return -14;
+  if (ldc < 1 || ldc < m) return -15;
+  if (batch < 0) return -17;
+  if (lower_only != 0 && lower_only != 1) return -18;
+  if (staged_rank_k != 0 && staged_rank_k != 1) return -19;
+  if (small_tiles != 0 && small_tiles != 1) return -20;
+  if (even_offs != 0 && even_offs != 1) return -21;
+  if (offs)
+    for (int i = 0; i < 3 * batch; ++i) {
+      if (offs[i] < 0) return -22;
+      if (even_offs && i % 3 != 2 && (offs[i] & 1)) return -21;   // the promise is checked here, not in gemm()
+    }
+  if (dims)
+    for (int i = 0; i < 3 * batch; ++i)
+      if (dims[i] < 0 || dims[i] > (i % 3 == 0 ? m : i % 3 == 1 ? n : k)) return -23;
+  if (!variant) return -24;
+  *g = GemmDesc{m, n, k, transa != 0, transb != 0, alpha, beta, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch,
+                lower_only != 0, staged_rank_k != 0};
+  g->even_offs = even_offs != 0; g->small_tiles = small_tiles != 0;
+  // the plan looks at whether there are tables, not at them
+  g->d_offs = offs; g->d_dims = dims;
+  return 0;
+}
+static void gemm_variant_out(const GemmPlan &pl, int batch, int *variant) {
+  variant[0] = pl.kernel; variant[1] = pl.vec ? 1 : 0; variant[2] = pl.lower_only; variant[3] = pl.tile;
+  variant[4] = pl.tiles_m; variant[5] = pl.tiles_n; variant[6] = (int)pl.grid_x; variant[7] = pl.kernel == kGemmNone ? 0 : batch;
+}
+
+extern "C" {
+
+// Test hooks of the GEMM (ek_gemm.hip), see include/ek_hip_debug.h.
+int ek_hip_debug_gemm_plan(int transa, int transb, int m, int n, int k, double alpha, double beta, const double *dA, int lda,
+                           long long strideA, const double *dB, int ldb, long long strideB, double *dC, int ldc,
+                           long long strideC, int batch, int lower_only, int staged_rank_k, int small_tiles, int even_offs,
+                           const long long *offs, const int *dims, int *variant) {
+  GemmDesc g;
+  int rc = gemm_desc_of(transa, transb, m, n, k, alpha, beta, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch,
+                        lower_only, staged_rank_k, small_tiles, even_offs, offs, dims, variant, &g);
+  if (rc) return rc;
+  gemm_variant_out(gemm_plan(g), batch, variant);
+  return 0;
+}
+
+int ek_hip_debug_gemm_desc(int transa, int transb, int m, int n, int k, double alpha, double beta, const double *dA, int lda,
+                           long long strideA, const double *dB, int ldb, long long strideB, double *dC, int ldc,
+                           long long strideC, int batch, int lower_only, int staged_rank_k, int small_tiles, int even_offs,
+                           const long long *offs, const int *dims, int *variant) {
+  GemmDesc g;
+  int rc = gemm_desc_of(transa, transb, m, n, k, alpha, beta, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch,
+                        lower_only, staged_rank_k, small_tiles, even_offs, offs, dims, variant, &g);
+  if (rc) return rc;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  DevMem mem;
+  if (offs && batch > 0) {
+    double *p; rc = mem.alloc(&p, (size_t)3 * batch * sizeof(long long)); if (rc) return rc;
+    EK_HIP_CHECK(hipMemcpy(p, offs, (size_t)3 * batch * sizeof(long long), hipMemcpyHostToDevice));
+    g.d_offs = reinterpret_cast<const long long *>(p);
+  }
+  if (dims && batch > 0) {
+    double *p; rc = mem.alloc(&p, (size_t)3 * batch * sizeof(int)); if (rc) return rc;
+    EK_HIP_CHECK(hipMemcpy(p, dims, (size_t)3 * batch * sizeof(int), hipMemcpyHostToDevice));
+    g.d_dims = reinterpret_cast<const int *>(p);
+  }
+  gemm_variant_out(gemm_plan(g), batch, variant);
+  gemm(s, g);
+  EK_HIP_CHECK(hipGetLastError());
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ek_hip_debug_gemm_compact_map(int tiles_m, int tiles_n, long long first, int count, int *tm, int *tn, int *valid) {
+  if (tiles_m < 1) return -1;
+  if (tiles_n < 1 || tiles_n > tiles_m) return -2;
+  if (first < 0) return -3;
+  if (count < 0 || first + count > 0x7fffffffLL) return -4;
+  if (count > 0 && (!tm || !tn)) return -5;
+  int ok = 0;
+  for (int i = 0; i < count; ++i) {
+    const bool v = gemm_compact_tile(tiles_m, tiles_n, (int)(first + i), tm[i], tn[i]);
+    if (valid) valid[i] = v ? 1 : 0;
+    ok += v ? 1 : 0;
+  }
+  return ok;
+}
+
 int ek_hip_debug_sytrd_split(void *alt, int mask) {
   std::lock_guard<std::mutex> lk(g_mu);
   sytrd_debug_split(alt, mask);

@@ -22,6 +22,7 @@
 //       17-double row stride keeps both the writes and the fragment reads conflict-free.
 #include "ek_common.h"
 
+#include <cmath>
 #include <cstdlib>
 
 namespace ek {
@@ -127,7 +128,7 @@ __device__ __forceinline__ double frag(const double *s, int x, int k) {
 // same grid, workgroups of tiles above the diagonal leave at once; lower_only == 2 (square tilings, one product, set by
 // gemm()): the grid holds the tiles on and below the diagonal only, column by column -- a trailing update of 120 x 120
 // tiles no longer dispatches 7140 workgroups that have nothing to do.
-__device__ __forceinline__ bool tile_of(const GemmArgs &p, int tile, int &tm, int &tn) {
+__host__ __device__ __forceinline__ bool tile_of(const GemmArgs &p, int tile, int &tm, int &tn) {
   if (p.lower_only == 2) {
     const long long T = p.tiles_m, c = tile;
     int j = (int)(((double)(2 * T + 1) - sqrt((double)((2 * T + 1) * (2 * T + 1) - 8 * c))) * 0.5);
@@ -660,16 +661,11 @@ __global__ __launch_bounds__(512) void gemm_rankk_kernel(GemmArgs p) {
 
 }  // namespace
 
-void gemm(hipStream_t s, const GemmDesc &g) {
-  if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return;
-  GemmArgs p;
-  p.M = g.M; p.N = g.N; p.K = g.K > 0 ? g.K : 0;
-  p.alpha = g.alpha; p.beta = g.beta;
-  p.A = g.A; p.lda = g.lda; p.sA = g.strideA;
-  p.B = g.B; p.ldb = g.ldb; p.sB = g.strideB;
-  p.C = g.C; p.ldc = g.ldc; p.sC = g.strideC;
-  p.lower_only = g.lower_only ? 1 : 0;
-  p.offs = g.d_offs; p.dims = g.d_dims;
+GemmPlan gemm_plan(const GemmDesc &g) {
+  GemmPlan pl;
+  pl.kernel = kGemmNone; pl.vec = false; pl.lower_only = 0; pl.tile = 0; pl.tiles_m = pl.tiles_n = 0; pl.grid_x = 0;
+  if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return pl;
+  pl.lower_only = g.lower_only ? 1 : 0;
   // lower_only is defined on the 128x128 tiling (callers rely on whole diagonal tiles being
   // written), so the small-grid variant is used for plain products only
   const long long big_tiles = (long long)ceil_div(g.M, BM) * ceil_div(g.N, BN) * g.batch;
@@ -679,15 +675,53 @@ void gemm(hipStream_t s, const GemmDesc &g) {
   // even batch strides, no per-batch offsets from device memory (EK_GEMM_VEC=0 turns the variants off)
   static int vec_env = -1;
   if (vec_env < 0) { const char *e = getenv("EK_GEMM_VEC"); vec_env = e ? atoi(e) : 1; }
-  const bool vec = vec_env && (!g.d_offs || g.even_offs) && ((g.lda | g.ldb) & 1) == 0 &&
-                   ((((size_t)g.A | (size_t)g.B) & 15) == 0) && (g.batch == 1 || ((g.strideA | g.strideB) & 1) == 0);
-  if ((big_tiles < 256 && !g.lower_only) || (g.lower_only && g.small_tiles)) {
-    p.tiles_m = ceil_div(g.M, SM); p.tiles_n = ceil_div(g.N, SN);
-    dim3 sgrid(p.tiles_m * p.tiles_n, g.batch), sblock(256);
-    if (compact && p.tiles_n <= p.tiles_m) {
-      p.lower_only = 2;
-      sgrid.x = (unsigned)((long long)p.tiles_n * p.tiles_m - (long long)p.tiles_n * (p.tiles_n - 1) / 2);
-    }
+  pl.vec = vec_env && (!g.d_offs || g.even_offs) && ((g.lda | g.ldb) & 1) == 0 &&
+           ((((size_t)g.A | (size_t)g.B) & 15) == 0) && (g.batch == 1 || ((g.strideA | g.strideB) & 1) == 0);
+  const bool small = (big_tiles < 256 && !g.lower_only) || (g.lower_only && g.small_tiles);
+  pl.tile = small ? SM : BM;
+  pl.tiles_m = ceil_div(g.M, pl.tile); pl.tiles_n = ceil_div(g.N, pl.tile);
+  pl.grid_x = (unsigned)(pl.tiles_m * pl.tiles_n);
+  if (compact && pl.tiles_n <= pl.tiles_m) {
+    pl.lower_only = 2;
+    pl.grid_x = (unsigned)((long long)pl.tiles_n * pl.tiles_m - (long long)pl.tiles_n * (pl.tiles_n - 1) / 2);
+  }
+  if (small) { pl.kernel = kGemmSmall; return pl; }
+  // Rank-k updates (short K, C read-modify-write) run on the 8-wave variant: twice the resident
+  // waves hide the operand and C latency that the 4-wave kernel exposes when there are only a few
+  // k-steps per tile (measured: SYR2K of the tridiagonalisation -25 %); long-K products stay on
+  // the 4-wave kernel (measured 3 % faster there).  EK_GEMM_W8=0/1 forces one of them.
+  static int w8 = -2;
+  if (w8 == -2) { const char *e = getenv("EK_GEMM_W8"); w8 = e ? atoi(e) : -1; }
+  // rank-k updates with short K: the staged 8-wave kernel (EK_GEMM_RANKK=0 turns it off)
+  static int rankk = -1;
+  if (rankk < 0) { const char *e = getenv("EK_GEMM_RANKK"); rankk = e ? atoi(e) : 1; }
+  if (rankk && g.staged_rank_k && !g.transA && g.transB && g.K <= 256 && g.K >= 32 && w8 < 0) { pl.kernel = kGemmRankK; return pl; }
+  const bool use_w8 = (w8 >= 0) ? (w8 != 0) : (g.K <= 512 && g.beta != 0.0);
+  pl.kernel = use_w8 ? kGemmW8 : kGemmW4;
+  return pl;
+}
+
+bool gemm_compact_tile(int tiles_m, int tiles_n, int tile, int &tm, int &tn) {
+  GemmArgs p;
+  p.lower_only = 2; p.tiles_m = tiles_m; p.tiles_n = tiles_n;
+  return tile_of(p, tile, tm, tn);
+}
+
+void gemm(hipStream_t s, const GemmDesc &g) {
+  const GemmPlan pl = gemm_plan(g);
+  if (pl.kernel == kGemmNone) return;
+  GemmArgs p;
+  p.M = g.M; p.N = g.N; p.K = g.K > 0 ? g.K : 0;
+  p.alpha = g.alpha; p.beta = g.beta;
+  p.A = g.A; p.lda = g.lda; p.sA = g.strideA;
+  p.B = g.B; p.ldb = g.ldb; p.sB = g.strideB;
+  p.C = g.C; p.ldc = g.ldc; p.sC = g.strideC;
+  p.lower_only = pl.lower_only;
+  p.offs = g.d_offs; p.dims = g.d_dims;
+  p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
+  const bool vec = pl.vec;
+  if (pl.kernel == kGemmSmall) {
+    dim3 sgrid(pl.grid_x, g.batch), sblock(256);
     if (vec) {
       if (!g.transA && !g.transB) hipLaunchKernelGGL((gemm_small_kernel<false, false, true>), sgrid, sblock, 0, s, p);
       else if (!g.transA && g.transB) hipLaunchKernelGGL((gemm_small_kernel<false, true, true>), sgrid, sblock, 0, s, p);
@@ -701,31 +735,19 @@ void gemm(hipStream_t s, const GemmDesc &g) {
     else hipLaunchKernelGGL((gemm_small_kernel<true, true, false>), sgrid, sblock, 0, s, p);
     return;
   }
-  p.tiles_m = ceil_div(g.M, BM); p.tiles_n = ceil_div(g.N, BN);
-  dim3 grid(p.tiles_m * p.tiles_n, g.batch), block(256);
-  if (compact && p.tiles_n <= p.tiles_m) {
-    p.lower_only = 2;
-    grid.x = (unsigned)((long long)p.tiles_n * p.tiles_m - (long long)p.tiles_n * (p.tiles_n - 1) / 2);
-  }
-  // Rank-k updates (short K, C read-modify-write) run on the 8-wave variant: twice the resident
-  // waves hide the operand and C latency that the 4-wave kernel exposes when there are only a few
-  // k-steps per tile (measured: SYR2K of the tridiagonalisation -25 %); long-K products stay on
-  // the 4-wave kernel (measured 3 % faster there).  EK_GEMM_W8=0/1 forces one of them.
-  static int w8 = -2;
-  if (w8 == -2) { const char *e = getenv("EK_GEMM_W8"); w8 = e ? atoi(e) : -1; }
-  // rank-k updates with short K: the staged 8-wave kernel (EK_GEMM_RANKK=0 turns it off)
-  static int rankk = -1;
-  if (rankk < 0) {
-    const char *e = getenv("EK_GEMM_RANKK"); rankk = e ? atoi(e) : 1;
+  dim3 grid(pl.grid_x, g.batch), block(256);
+  // the staged rank-k kernel's LDS (set when the first product reaches the 128-tiling, as it always was)
+  static bool rk_attr = false;
+  if (!rk_attr) {
+    rk_attr = true;
     (void)hipFuncSetAttribute((const void *)gemm_rankk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               2 * RK * RK_LD * (int)sizeof(double));
   }
-  if (rankk && g.staged_rank_k && !g.transA && g.transB && g.K <= 256 && g.K >= 32 && w8 < 0) {
+  if (pl.kernel == kGemmRankK) {
     hipLaunchKernelGGL(gemm_rankk_kernel, grid, dim3(512), 2 * RK * RK_LD * sizeof(double), s, p);
     return;
   }
-  const bool use_w8 = (w8 >= 0) ? (w8 != 0) : (g.K <= 512 && g.beta != 0.0);
-  if (use_w8) {
+  if (pl.kernel == kGemmW8) {
     dim3 b8(512);
     if (vec) {
       if (!g.transA && !g.transB) hipLaunchKernelGGL((gemm_kernel_w8<false, false, true>), grid, b8, 0, s, p);

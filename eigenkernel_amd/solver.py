@@ -107,6 +107,12 @@ def load_library(path=None):
         "ek_hip_debug_gemm_at": (c_int, [c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, c_dbl, vp, c_int,
                                          c_int, c_int, _dp]),
         "ek_hip_debug_sytrd_at": (c_int, [c_int, c_int, c_int, vp, vp, vp, _dp]),
+        # offs / dims: host tables (or None); the last argument: int variant[8]
+        "ek_hip_debug_gemm_desc": (c_int, [c_int] * 5 + [c_dbl, c_dbl, vp, c_int, c_ll, vp, c_int, c_ll, vp, c_int, c_ll]
+                                   + [c_int] * 5 + [_llp, _ip, _ip]),
+        "ek_hip_debug_gemm_plan": (c_int, [c_int] * 5 + [c_dbl, c_dbl, vp, c_int, c_ll, vp, c_int, c_ll, vp, c_int, c_ll]
+                                   + [c_int] * 5 + [_llp, _ip, _ip]),
+        "ek_hip_debug_gemm_compact_map": (c_int, [c_int, c_int, c_ll, c_int, _ip, _ip, _ip]),
         "ek_hip_debug_reduce_team": (c_int, [c_int, c_int, c_int, _dp]),
         "ek_hip_profile_symv_get": (c_int, [_dp, ctypes.POINTER(ctypes.c_longlong), _dp]),
         "ek_hip_debug_sy2sb": (c_int, [c_int, _dp, c_int, _dp, c_int, _dp, _ip]),
@@ -193,6 +199,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_comm_destroy", "ek_hip_comm_allreduce_device", "ek_hip_debug_sytrd_team", "ek_hip_sygst_team",
     "ek_hip_potrf_team", "ek_hip_debug_reduce_team", "ek_hip_comm_attach_host",
     "ek_hip_debug_set_sytrd_maxcols", "ek_hip_debug_sytrd_work_bytes", "ek_hip_debug_sytrd_at", "ek_hip_debug_sytrd_split", "ek_hip_debug_gemm_at",
+    "ek_hip_debug_gemm_desc", "ek_hip_debug_gemm_plan", "ek_hip_debug_gemm_compact_map",
     "ek_hip_debug_sy2sb", "ek_hip_debug_sb2st", "ek_hip_debug_two_stage_timing", "ek_hip_debug_set_two_stage",
     "ek_hip_profile_kernels", "ek_hip_profile_kernels_get", "ek_hip_debug_last_solve_stats",
     "ek_hip_debug_sy2sb_team", "ek_hip_debug_sy2sb_team_timing", "ek_hip_debug_sy2sb_team_profile", "ek_hip_debug_workspace_bytes", "ek_hip_debug_fail_next_chase", "ek_hip_debug_last_pipe_stats",

@@ -32,6 +32,34 @@ unsigned long long ek_hip_debug_sytrd_work_bytes(int n);
 int ek_hip_debug_sytrd_at(int n, int max_cols, int reps, double *dA, void *work, double *vecs, double *seconds);
 int ek_hip_debug_gemm_at(int transa, int transb, int m, int n, int k, const double *dA, int lda, const double *dB,
                          int ldb, double beta, double *dC, int ldc, int lower_only, int reps, double *seconds);
+/* Test hooks of the GEMM under every O(n^3) stage (ek_gemm.hip), at the level of its descriptor.
+ *   _gemm_desc : ONE product C <- alpha op(A) op(B) + beta C, batched over `batch` entries, on the caller's DEVICE arrays at
+ *            the caller's addresses, with every field of the descriptor: element strides between the entries, lower_only
+ *            (tiles strictly above the diagonal are not referenced), staged_rank_k, small_tiles (lower_only on the 64-tiling)
+ *            and even_offs.  offs (3 * batch: element offsets {A, B, C} of every entry, added to the strides) and dims
+ *            (3 * batch: {M, N, K} of every entry, at most the m, n, k given) are optional HOST arrays the hook puts into
+ *            device memory for the call.  Synchronises.  Returns 0, -k for an illegal k-th argument (also: an offset below
+ *            zero -22, even_offs with an odd offset of A or B -21, an entry of dims outside 0 .. m, n, k -23) -- decided
+ *            before any device work -- or <= -1000.
+ *            variant[0..7] = what was launched: [0] the kernel (0 gemm_small_kernel, 1 gemm_kernel: 4 waves, 2 gemm_kernel_w8:
+ *            8 waves, 3 gemm_rankk_kernel, -1 none: an empty product), [1] 1 the VEC instantiation / 0 the scalar one (rank-k:
+ *            what the kernel's own test finds for one product without tables), [2] lower_only as launched (0; 1 the whole grid,
+ *            tiles above the diagonal leave; 2 the compact grid), [3] the tile (64 or 128), [4] [5] tiles along M and N,
+ *            [6] [7] the grid.
+ *   _gemm_plan : the same decision alone, with the same arguments and the same -k (host arithmetic, no GPU: nothing is
+ *            dereferenced but offs and dims).
+ *   _gemm_compact_map : the compact grid's map workgroup -> tile for the workgroups first .. first + count - 1 of a
+ *            tiles_m x tiles_n tiling (tiles_n <= tiles_m): tm[i], tn[i] and valid[i] (may be NULL; 0: the workgroup has no
+ *            tile).  The kernels' own function compiled for the host, no GPU.  Returns the number of valid ones or -k. */
+int ek_hip_debug_gemm_desc(int transa, int transb, int m, int n, int k, double alpha, double beta, const double *dA, int lda,
+                           long long strideA, const double *dB, int ldb, long long strideB, double *dC, int ldc,
+                           long long strideC, int batch, int lower_only, int staged_rank_k, int small_tiles, int even_offs,
+                           const long long *offs, const int *dims, int *variant /* 8 */);
+int ek_hip_debug_gemm_plan(int transa, int transb, int m, int n, int k, double alpha, double beta, const double *dA, int lda,
+                           long long strideA, const double *dB, int ldb, long long strideB, double *dC, int ldc,
+                           long long strideC, int batch, int lower_only, int staged_rank_k, int small_tiles, int even_offs,
+                           const long long *offs, const int *dims, int *variant /* 8 */);
+int ek_hip_debug_gemm_compact_map(int tiles_m, int tiles_n, long long first, int count, int *tm, int *tn, int *valid);
 int ek_hip_debug_sytrd_split(void *alt, int mask);  /* placement experiments: sub-buffers of the scratch from alt */
 int ek_hip_debug_set_sytrd_maxcols(int max_cols);   /* the hooks stop after max_cols columns (-1: all) */
 int ek_hip_debug_sytrd_team(int n, int nteam, int reps, double *seconds);
