@@ -815,4 +815,73 @@ int ek_hip_check(int what, int problem, int n, int n_cols, int index1, int index
   return rc;
 }
 
+// ---- the same checks for DSYGV's three types, the first n_cols columns (what a window of ek_hip_sygvx* returns)
+static int sygvx_check_args(int itype, int n, int n_cols, const void *A, int lda, const void *B, int ldb, const void *w,
+                            const void *Z, int ldz, const double *out) {
+  if (itype < 1 || itype > 3) return -1;
+  if (n < 0) return -2;
+  if (n_cols < 0 || n_cols > n) return -3;
+  const int ldmin = n > 1 ? n : 1;
+  if (n > 0 && !A) return -4;
+  if (lda < ldmin) return -5;
+  if (n > 0 && !B) return -6;
+  if (ldb < ldmin) return -7;
+  if (n_cols > 0 && !w) return -8;
+  if (n_cols > 0 && !Z) return -9;
+  if (ldz < ldmin) return -10;
+  if (!out) return -11;
+  return 0;
+}
+
+int ek_hip_check_sygvx_device(int itype, int n, int n_cols, const double *dA, int lda, const double *dB, int ldb,
+                              const double *dw, const double *dZ, int ldz, double out[4], double *ipr_host) {
+  int rc = sygvx_check_args(itype, n, n_cols, dA, lda, dB, ldb, dw, dZ, ldz, out);
+  if (rc) return rc;
+  if (n == 0 || n_cols == 0) return 0;
+  if (itype == 1) {                                 // the three one-problem entries themselves: their bits
+    rc = ek_hip_residual_device(1, n, n_cols, dA, lda, dB, ldb, dw, dZ, ldz, &out[0], &out[1], &out[2]);
+    if (!rc) rc = ek_hip_orthogonality_device(1, n, 1, n_cols, dB, ldb, dZ, ldz, &out[3]);
+    if (!rc && ipr_host) rc = ek_hip_ipratios_device(1, n, n_cols, dB, ldb, dZ, ldz, ipr_host);
+    return rc;
+  }
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const size_t wb = al(sygv_check_work_bytes(itype, n, n_cols));
+  void *ws;
+  rc = workspace(wb + al((size_t)(n_cols + 4) * 8), &ws); if (rc) return rc;
+  double *d_out = (double *)((char *)ws + wb), *d_ipr = d_out + 4;
+  sygv_check(s, itype, n, n_cols, dA, lda, dB, ldb, dw, dZ, ldz, d_out, d_ipr, g_ctx.d_info, ws);
+  EK_HIP_CHECK(hipGetLastError());
+  EK_HIP_CHECK(hipMemcpyAsync(out, d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (ipr_host) EK_HIP_CHECK(hipMemcpyAsync(ipr_host, d_ipr, (size_t)n_cols * 8, hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ek_hip_check_sygvx(int itype, int n, int n_cols, const double *A, int lda, const double *B, int ldb, const double *w,
+                       const double *Z, int ldz, double out[4], double *ipr_host) {
+  int rc = sygvx_check_args(itype, n, n_cols, A, lda, B, ldb, w, Z, ldz, out);
+  if (rc) return rc;
+  if (n == 0 || n_cols == 0) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  double *uA = nullptr, *uB = nullptr, *uZ = nullptr, *uw = nullptr;
+  const size_t nn = (size_t)n * n * 8;
+  DevMem mem;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    hipStream_t s = g_ctx.stream;
+    rc = mem.alloc(&uA, nn); if (rc) return rc;
+    rc = mem.alloc(&uB, nn); if (rc) return rc;
+    rc = mem.alloc(&uZ, (size_t)n * n_cols * 8); if (rc) return rc;
+    rc = mem.alloc(&uw, (size_t)n_cols * 8); if (rc) return rc;
+    rc = h2d_matrix(n, n, A, lda, uA, n, s); if (rc) return rc;
+    rc = h2d_matrix(n, n, B, ldb, uB, n, s); if (rc) return rc;
+    rc = h2d_matrix(n, n_cols, Z, ldz, uZ, n, s); if (rc) return rc;
+    EK_HIP_CHECK(hipMemcpyAsync(uw, w, (size_t)n_cols * 8, hipMemcpyHostToDevice, s));
+    EK_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return ek_hip_check_sygvx_device(itype, n, n_cols, uA, n, uB, n, uw, uZ, n, out, ipr_host);
+}
+
 }  // extern "C"

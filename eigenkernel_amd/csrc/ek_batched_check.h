@@ -1,0 +1,121 @@
+// ek_batched_check.h -- what the two translation units of the batched acceptance checks share (not installed):
+//   ek_batched_check.hip       the entries, the host side, the kernel of the standard problem and of type 1
+//   ek_batched_check_sygv.hip  the kernel of DSYGV's types 2 and 3
+// The kernels live in two units so that adding the second leaves the code generated for the first as it was.
+#pragma once
+#include "ek_api_internal.h"
+
+#include <cmath>
+
+namespace ek {
+namespace bcheck {
+
+struct Args {
+  int problem, n;
+  const double *A; int lda; long long sA;
+  const double *B; int ldb; long long sB;
+  const double *w;
+  const double *Z; int ldz; long long sZ;
+  const int *map;       // the problems to check, one per workgroup; nullptr: workgroup b takes problem b
+  double *S;            // problem 1: n^2 doubles per problem
+  double *out;          // EK_HIP_CHECK_NOUT doubles per problem
+  double *ipr;          // n doubles per problem, or nullptr
+};
+
+// the variable form's table: one entry per problem to check, a class after the other, descending order inside a class
+struct Desc {
+  const double *A, *B, *w, *Z;
+  double *S, *ipr;
+  int n, lda, ldb, ldz, index, pad;
+};
+struct VArgs {
+  int problem;
+  const Desc *table;
+  double *out;
+};
+
+// global address space, as in ek_batched.hip: a pointer loaded from the table would otherwise cost flat accesses
+typedef __attribute__((address_space(1))) double gdouble;
+typedef const __attribute__((address_space(1))) double cgdouble;
+struct Problem {
+  int n;
+  cgdouble *A; int lda;
+  cgdouble *B; int ldb;
+  cgdouble *w;
+  cgdouble *Z; int ldz;
+  gdouble *S, *out, *ipr;
+};
+__device__ __forceinline__ Problem locate(const Args &a) {
+  const long long pb = a.map ? a.map[blockIdx.x] : (int)blockIdx.x;
+  return {a.n, (cgdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (cgdouble *)(a.w + pb * a.n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
+          a.problem ? (gdouble *)(a.S + pb * a.n * a.n) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
+          a.ipr ? (gdouble *)(a.ipr + pb * a.n) : nullptr};
+}
+__device__ __forceinline__ Problem locate(const VArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
+          (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};
+}
+
+// Sum (or maximum) over the workgroup, the same bits in every thread: a butterfly inside the wave, then the waves in
+// ascending order.  The maximum keeps a NaN (fmax would drop it): a problem with a NaN residual reports NaN.
+template <int NW, bool MAX>
+__device__ __forceinline__ double wg_reduce(double x, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double y = __shfl_xor(x, o, 64);
+    x = MAX ? ((y > x || y != y) ? y : x) : x + y;
+  }
+  if (NW == 1) return x;
+  __syncthreads();                                  // the previous call's readers are through
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+    const double y = red[w];
+    s = MAX ? ((y > s || y != y) ? y : s) : s + y;
+  }
+  return s;
+}
+
+// sum_{k < n} x[k] y[k] in ascending order, x and y in LDS: four elements' loads go out before the first use.  Every
+// multiply-add of this file is written as fma(): the instantiations must round alike, whatever the compiler contracts
+__device__ __forceinline__ double lds_dot(const double *x, const double *y, int n) {
+  double acc = 0.0;
+  int k = 0;
+  for (; k + 4 <= n; k += 4) {
+    const double x0 = x[k], x1 = x[k + 1], x2 = x[k + 2], x3 = x[k + 3];
+    const double y0 = y[k], y1 = y[k + 1], y2 = y[k + 2], y3 = y[k + 3];
+    acc = fma(x0, y0, acc); acc = fma(x1, y1, acc); acc = fma(x2, y2, acc); acc = fma(x3, y3, acc);
+  }
+  for (; k < n; ++k) acc = fma(x[k], y[k], acc);
+  return acc;
+}
+// the same for two vectors against one y (a row of A and a row of B against a column of Z)
+__device__ __forceinline__ void lds_dot2(const double *xa, const double *xb, const double *y, int n, double &da,
+                                         double &db) {
+  double a = 0.0, b = 0.0;
+  int k = 0;
+  for (; k + 4 <= n; k += 4) {
+    const double y0 = y[k], y1 = y[k + 1], y2 = y[k + 2], y3 = y[k + 3];
+    const double a0 = xa[k], a1 = xa[k + 1], a2 = xa[k + 2], a3 = xa[k + 3];
+    const double b0 = xb[k], b1 = xb[k + 1], b2 = xb[k + 2], b3 = xb[k + 3];
+    a = fma(a0, y0, a); b = fma(b0, y0, b); a = fma(a1, y1, a); b = fma(b1, y1, b);
+    a = fma(a2, y2, a); b = fma(b2, y2, b); a = fma(a3, y3, a); b = fma(b3, y3, b);
+  }
+  for (; k < n; ++k) { a = fma(xa[k], y[k], a); b = fma(xb[k], y[k], b); }
+  da = a; db = b;
+}
+
+// LDS doubles of a class: the image, 2 buffers x 2 rows of A and of B, 1 / sqrt(G_jj), a word per wave for the sums
+// over the workgroup.  At 64 that is 37 920 B: four workgroups share a CU's 160 KiB
+constexpr int lds_doubles(int NC) { return NC * (NC + 1) + 8 * NC + NC + 4; }
+
+// one launch of the kernel of types 2 and 3 (itype) for `count` problems of class nc (32, 64, 128)
+int launch_sygv(hipStream_t s, int itype, int nc, int count, const Args &a);
+int launch_sygv(hipStream_t s, int itype, int nc, int count, const VArgs &a);
+
+}  // namespace bcheck
+}  // namespace ek

@@ -21,116 +21,16 @@
 // Same bits wherever a problem sits: a problem's outputs depend on (n, A, B, w, Z) alone -- fixed loop orders, sums
 // across the workgroup by a fixed butterfly and a fixed order over the waves, no atomics, one code path per class, the
 // same kernel body for the strided and the table form.  A, B, w and Z are read only.
-#include "ek_api_internal.h"
+//
+// ek_hip_check_sygv_batched* / ek_hip_check_sygv_vbatched*  check DSYGV's types 2 (A B x = l x) and 3
+// (B A x = l x): the same entries, classes, table and scatter, with the kernel of ek_batched_check_sygv.hip in the place of
+// the one below (a translation unit of its own, so that the code generated for this one stays what it was).
+#include "ek_batched_check.h"
 
 #include <algorithm>
-#include <cmath>
 
 namespace ek {
 namespace bcheck {
-
-struct Args {
-  int problem, n;
-  const double *A; int lda; long long sA;
-  const double *B; int ldb; long long sB;
-  const double *w;
-  const double *Z; int ldz; long long sZ;
-  const int *map;       // the problems to check, one per workgroup; nullptr: workgroup b takes problem b
-  double *S;            // problem 1: n^2 doubles per problem
-  double *out;          // EK_HIP_CHECK_NOUT doubles per problem
-  double *ipr;          // n doubles per problem, or nullptr
-};
-
-// the variable form's table: one entry per problem to check, a class after the other, descending order inside a class
-struct Desc {
-  const double *A, *B, *w, *Z;
-  double *S, *ipr;
-  int n, lda, ldb, ldz, index, pad;
-};
-struct VArgs {
-  int problem;
-  const Desc *table;
-  double *out;
-};
-
-// global address space, as in ek_batched.hip: a pointer loaded from the table would otherwise cost flat accesses
-typedef __attribute__((address_space(1))) double gdouble;
-typedef const __attribute__((address_space(1))) double cgdouble;
-struct Problem {
-  int n;
-  cgdouble *A; int lda;
-  cgdouble *B; int ldb;
-  cgdouble *w;
-  cgdouble *Z; int ldz;
-  gdouble *S, *out, *ipr;
-};
-__device__ __forceinline__ Problem locate(const Args &a) {
-  const long long pb = a.map ? a.map[blockIdx.x] : (int)blockIdx.x;
-  return {a.n, (cgdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
-          (cgdouble *)(a.w + pb * a.n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
-          a.problem ? (gdouble *)(a.S + pb * a.n * a.n) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
-          a.ipr ? (gdouble *)(a.ipr + pb * a.n) : nullptr};
-}
-__device__ __forceinline__ Problem locate(const VArgs &a) {
-  const Desc &d = a.table[blockIdx.x];
-  return {d.n, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
-          (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};
-}
-
-// Sum (or maximum) over the workgroup, the same bits in every thread: a butterfly inside the wave, then the waves in
-// ascending order.  The maximum keeps a NaN (fmax would drop it): a problem with a NaN residual reports NaN.
-template <int NW, bool MAX>
-__device__ __forceinline__ double wg_reduce(double x, double *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double y = __shfl_xor(x, o, 64);
-    x = MAX ? ((y > x || y != y) ? y : x) : x + y;
-  }
-  if (NW == 1) return x;
-  __syncthreads();                                  // the previous call's readers are through
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double s = red[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) {
-    const double y = red[w];
-    s = MAX ? ((y > s || y != y) ? y : s) : s + y;
-  }
-  return s;
-}
-
-// sum_{k < n} x[k] y[k] in ascending order, x and y in LDS: four elements' loads go out before the first use.  Every
-// multiply-add of this file is written as fma(): the instantiations must round alike, whatever the compiler contracts
-__device__ __forceinline__ double lds_dot(const double *x, const double *y, int n) {
-  double acc = 0.0;
-  int k = 0;
-  for (; k + 4 <= n; k += 4) {
-    const double x0 = x[k], x1 = x[k + 1], x2 = x[k + 2], x3 = x[k + 3];
-    const double y0 = y[k], y1 = y[k + 1], y2 = y[k + 2], y3 = y[k + 3];
-    acc = fma(x0, y0, acc); acc = fma(x1, y1, acc); acc = fma(x2, y2, acc); acc = fma(x3, y3, acc);
-  }
-  for (; k < n; ++k) acc = fma(x[k], y[k], acc);
-  return acc;
-}
-// the same for two vectors against one y (a row of A and a row of B against a column of Z)
-__device__ __forceinline__ void lds_dot2(const double *xa, const double *xb, const double *y, int n, double &da,
-                                         double &db) {
-  double a = 0.0, b = 0.0;
-  int k = 0;
-  for (; k + 4 <= n; k += 4) {
-    const double y0 = y[k], y1 = y[k + 1], y2 = y[k + 2], y3 = y[k + 3];
-    const double a0 = xa[k], a1 = xa[k + 1], a2 = xa[k + 2], a3 = xa[k + 3];
-    const double b0 = xb[k], b1 = xb[k + 1], b2 = xb[k + 2], b3 = xb[k + 3];
-    a = fma(a0, y0, a); b = fma(b0, y0, b); a = fma(a1, y1, a); b = fma(b1, y1, b);
-    a = fma(a2, y2, a); b = fma(b2, y2, b); a = fma(a3, y3, a); b = fma(b3, y3, b);
-  }
-  for (; k < n; ++k) { a = fma(xa[k], y[k], a); b = fma(xb[k], y[k], b); }
-  da = a; db = b;
-}
-
-// LDS doubles of a class: the image, 2 buffers x 2 rows of A and of B, 1 / sqrt(G_jj), a word per wave for the sums
-// over the workgroup.  At 64 that is 37 920 B: four workgroups share a CU's 160 KiB
-constexpr int lds_doubles(int NC) { return NC * (NC + 1) + 8 * NC + NC + 4; }
 
 // ARGS: how the workgroup finds its problem -- Args (one order, strided) or VArgs (a table entry)
 template <int NC, int T, typename ARGS>
@@ -257,8 +157,10 @@ __global__ __launch_bounds__(T) void check_kernel(ARGS a) {
   }
 }
 
+// itype: 0 the standard problem and type 1 (this unit's kernel), 2 or 3 those types (launch_sygv)
 template <int NC, int T, typename ARGS>
-static int launch_class(hipStream_t s, int count, const ARGS &a) {
+static int launch_class(hipStream_t s, int count, const ARGS &a, int itype) {
+  if (itype) return launch_sygv(s, itype, NC, count, a);
   constexpr size_t lds = (size_t)lds_doubles(NC) * sizeof(double);
   static bool raised = false;                       // one per instantiation
   if (lds > 64 * 1024 && !raised) {
@@ -396,10 +298,11 @@ static int run_and_fetch(size_t words, double *seconds, LAUNCH launch) {
   return rc;
 }
 
-// arguments checked (n > 0, batch > 0), context up, g_mu held; dA, dB, dw, dZ device, info / out / ipr host
-static int uniform_device_locked(int problem, int n, int batch, const double *dA, int lda, long long strideA,
-                                 const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
-                                 int ldz, long long strideZ, const int *info, double *out, double *ipr,
+// arguments checked (n > 0, batch > 0), context up, g_mu held; dA, dB, dw, dZ device, info / out / ipr host.  itype: 0 the
+// standard problem and type 1 (`problem` says which), 2 or 3 those types (problem = 1)
+static int uniform_device_locked(int itype, int problem, int n, int batch, const double *dA, int lda,
+                                 long long strideA, const double *dB, int ldb, long long strideB, const double *dw,
+                                 const double *dZ, int ldz, long long strideZ, const int *info, double *out, double *ipr,
                                  double *seconds) {
   using namespace bcheck;
   g_hmap.clear();
@@ -421,9 +324,9 @@ static int uniform_device_locked(int problem, int n, int batch, const double *dA
       Args a{problem, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, skip ? (const int *)g_dtable : nullptr,
              g_scratch, g_dout, ipr ? g_dout + nout : nullptr};
       switch (class_of(n)) {
-        case 32: return launch_class<32, 64>(s, count, a);
-        case 64: return launch_class<64, 128>(s, count, a);
-        default: return launch_class<128, 256>(s, count, a);
+        case 32: return launch_class<32, 64>(s, count, a, itype);
+        case 64: return launch_class<64, 128>(s, count, a, itype);
+        default: return launch_class<128, 256>(s, count, a, itype);
       }
     });
     if (rc) return rc;
@@ -468,9 +371,9 @@ static int variable_check(int problem, int batch, const int *n, const void *cons
   return 0;
 }
 
-// arguments checked (batch > 0), context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses
-static int variable_device_locked(int problem, int batch, const int *n, const double *const *dA, const int *lda,
-                                  const double *const *dB, const int *ldb, const double *const *dw,
+// arguments checked (batch > 0), context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses; itype as above
+static int variable_device_locked(int itype, int problem, int batch, const int *n, const double *const *dA,
+                                  const int *lda, const double *const *dB, const int *ldb, const double *const *dw,
                                   const double *const *dZ, const int *ldz, const int *info, double *out,
                                   double *const *ipr, double *seconds) {
   using namespace bcheck;
@@ -504,8 +407,8 @@ static int variable_device_locked(int problem, int batch, const int *n, const do
       for (int k = 0; k < 3 && !rcl; ++k) {
         if (!count[k]) continue;
         VArgs a{problem, (const Desc *)g_dtable + at, g_dout};
-        rcl = k == 0 ? launch_class<128, 256>(s, count[k], a)
-            : k == 1 ? launch_class<64, 128>(s, count[k], a) : launch_class<32, 64>(s, count[k], a);
+        rcl = k == 0 ? launch_class<128, 256>(s, count[k], a, itype)
+            : k == 1 ? launch_class<64, 128>(s, count[k], a, itype) : launch_class<32, 64>(s, count[k], a, itype);
         at += count[k];
       }
       return rcl;
@@ -517,9 +420,9 @@ static int variable_device_locked(int problem, int batch, const int *n, const do
   return 0;
 }
 
-extern "C" {
-
-int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+// The four entries behind both families: ek_hip_check_*batched* (itype = 0) and ek_hip_check_sygv_*batched* (itype = 2, 3
+// with problem = 1; their itype 1 is problem 1 of the first family)
+static int uniform_device_entry(int itype, int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                 const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                 int ldz, long long strideZ, const int *info, double *out, double *ipr,
                                 double *seconds) {
@@ -530,13 +433,13 @@ int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA,
   if (nothing) return 0;
   rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
-  return uniform_device_locked(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out,
-                               ipr, seconds);
+  return uniform_device_locked(itype, problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                               out, ipr, seconds);
 }
 
-int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
-                         int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
-                         const int *info, double *out, double *ipr, double *seconds) {
+static int uniform_host_entry(int itype, int problem, int n, int batch, const double *A, int lda, long long strideA,
+                              const double *B, int ldb, long long strideB, const double *w, const double *Z, int ldz,
+                              long long strideZ, const int *info, double *out, double *ipr, double *seconds) {
   bool nothing;
   int rc = uniform_check(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, out, &nothing);
   if (rc) return rc;
@@ -560,12 +463,12 @@ int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda
   if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
   EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
   EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  return uniform_device_locked(problem, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info, out,
-                               ipr, seconds);
+  return uniform_device_locked(itype, problem, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info,
+                               out, ipr, seconds);
 }
 
-int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
-                                 const double *const *dB, const int *ldb, const double *const *dw,
+static int variable_device_entry(int itype, int problem, int batch, const int *n, const double *const *dA,
+                                 const int *lda, const double *const *dB, const int *ldb, const double *const *dw,
                                  const double *const *dZ, const int *ldz, const int *info, double *out,
                                  double *const *ipr, double *seconds) {
   bool nothing;
@@ -580,12 +483,13 @@ int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const dou
     rc = ensure_init(); if (rc) return rc;
   }
   std::lock_guard<std::mutex> lk(g_mu);
-  return variable_device_locked(problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds);
+  return variable_device_locked(itype, problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds);
 }
 
-int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
-                          const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
-                          const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
+static int variable_host_entry(int itype, int problem, int batch, const int *n, const double *const *A,
+                               const int *lda, const double *const *B, const int *ldb, const double *const *w,
+                               const double *const *Z, const int *ldz, const int *info, double *out,
+                               double *const *ipr, double *seconds) {
   bool nothing;
   int rc = variable_check(problem, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
                           (const void *const *)w, (const void *const *)Z, ldz, out, &nothing);
@@ -605,8 +509,8 @@ int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *co
   for (int b = 0; b < batch; ++b) ldc[b] = n[b] > 1 ? n[b] : 1;
   std::lock_guard<std::mutex> lk(g_mu);
   if (cm == 0)                                      // nothing to launch: the slots are filled on the host
-    return variable_device_locked(problem, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(), pZ.data(),
-                                  ldc.data(), info, out, ipr, seconds);
+    return variable_device_locked(itype, problem, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(),
+                                  pZ.data(), ldc.data(), info, out, ipr, seconds);
   rc = ensure_init(); if (rc) return rc;
   hipStream_t s = g_ctx.stream;
   // one staging buffer per matrix kind: the lower triangles of A and B column by column (what lies above them is
@@ -645,8 +549,72 @@ int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *co
   if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
   EK_HIP_CHECK(hipMemcpyAsync(uw, hw.data(), cv * 8, hipMemcpyHostToDevice, s));
   EK_HIP_CHECK(hipMemcpyAsync(uZ, hZ.data(), cm * 8, hipMemcpyHostToDevice, s));
-  return variable_device_locked(problem, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(), pZ.data(),
-                                ldc.data(), info, out, ipr, seconds);
+  return variable_device_locked(itype, problem, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(),
+                                pZ.data(), ldc.data(), info, out, ipr, seconds);
+}
+
+extern "C" {
+
+int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                double *seconds) {
+  return uniform_device_entry(0, problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out,
+                              ipr, seconds);
+}
+
+int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                         int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                         const int *info, double *out, double *ipr, double *seconds) {
+  return uniform_host_entry(0, problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
+                            seconds);
+}
+
+int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                 const double *const *dB, const int *ldb, const double *const *dw,
+                                 const double *const *dZ, const int *ldz, const int *info, double *out,
+                                 double *const *ipr, double *seconds) {
+  return variable_device_entry(0, problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds);
+}
+
+int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                          const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                          const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
+  return variable_host_entry(0, problem, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds);
+}
+
+// DSYGV's types: -1 for an itype outside 1 .. 3, then the family above with problem = 1 (type 1 is that problem itself)
+int ek_hip_check_sygv_batched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
+                                     const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                     int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                     double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return uniform_device_entry(itype == 1 ? 0 : itype, 1, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz,
+                              strideZ, info, out, ipr, seconds);
+}
+
+int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                              int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                              const int *info, double *out, double *ipr, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return uniform_host_entry(itype == 1 ? 0 : itype, 1, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ,
+                            info, out, ipr, seconds);
+}
+
+int ek_hip_check_sygv_vbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
+                                      const double *const *dB, const int *ldb, const double *const *dw,
+                                      const double *const *dZ, const int *ldz, const int *info, double *out,
+                                      double *const *ipr, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return variable_device_entry(itype == 1 ? 0 : itype, 1, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr,
+                               seconds);
+}
+
+int ek_hip_check_sygv_vbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
+                               const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                               const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return variable_host_entry(itype == 1 ? 0 : itype, 1, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds);
 }
 
 }  // extern "C"

@@ -352,5 +352,10 @@ void orthogonality(hipStream_t s, int n, int c0, int nc, const double *B, int ld
                    double *d_result, void *work);
 void ipratios(hipStream_t s, int n, int n_vec, const double *B, int ldb, const double *V, int ldv,
               double *d_ipr, void *work);
+// DSYGV's types 2 and 3 (itype), the first ncols columns of Z: d_out[4] = ||A||_F ||B||_F, res_ave, res_max, orthogonality,
+// d_ipr[ncols]; *d_info: type 3's factorisation of a copy of B (not 0: d_out[3] and d_ipr are NaN).  A, B, w, Z read only
+size_t sygv_check_work_bytes(int itype, int n, int ncols);
+void sygv_check(hipStream_t s, int itype, int n, int ncols, const double *A, int lda, const double *B, int ldb,
+                const double *w, const double *Z, int ldz, double *d_out, double *d_ipr, int *d_info, void *work);
 
 }  // namespace ek

@@ -88,6 +88,63 @@ __global__ __launch_bounds__(256) void ipr_kernel(int m, const double *__restric
   if (threadIdx.x == 0) ipr[blockIdx.x] = p4 / (p2 * p2);
 }
 
+// ipr[j] = sum_i v_ij^4 / (sum_i x_ij y_ij)^2: the metric of DSYGV's types 2 (X = Z, Y = B Z) and 3 (X = Y = L^-1 Z)
+__global__ __launch_bounds__(256) void ipr_metric_kernel(int m, const double *__restrict__ V, int ldv,
+                                                         const double *__restrict__ X, int ldx,
+                                                         const double *__restrict__ Y, int ldy,
+                                                         double *__restrict__ ipr) {
+  __shared__ double red[4];
+  const double *v = V + (size_t)blockIdx.x * ldv, *x = X + (size_t)blockIdx.x * ldx, *y = Y + (size_t)blockIdx.x * ldy;
+  double p4 = 0.0, p2 = 0.0;
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const double z = v[i], z2 = z * z;
+    p4 += z2 * z2; p2 += x[i] * y[i];
+  }
+  p4 = wg_sum(p4, red);
+  p2 = wg_sum(p2, red);
+  if (threadIdx.x == 0) ipr[blockIdx.x] = p4 / (p2 * p2);
+}
+
+// Types 2 and 3: rho_j = sqrt(rsq[j]) / (||A||_F ||B||_F sqrt(zsq[j])), j < nc, with ||A||_F^2 = sum asq[0..n), ||B||_F^2 =
+// sum bsq[0..n).  out[0] = ||A||_F ||B||_F, out[1] = sum_j rho_j / nc, out[2] = max_j rho_j (a NaN is kept)
+__global__ __launch_bounds__(256) void finish_sygv_kernel(int nc, const double *__restrict__ rsq,
+                                                          const double *__restrict__ zsq, int n,
+                                                          const double *__restrict__ asq,
+                                                          const double *__restrict__ bsq, double *out) {
+  __shared__ double red[4];
+  __shared__ double mx[256];
+  double a = 0.0, b = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) { a += asq[j]; b += bsq[j]; }
+  a = wg_sum(a, red);
+  b = wg_sum(b, red);
+  const double nrm = sqrt(a) * sqrt(b);
+  double s = 0.0, m = 0.0;
+  for (int j = threadIdx.x; j < nc; j += 256) {
+    const double rho = sqrt(rsq[j]) / (nrm * sqrt(zsq[j]));
+    s += rho;
+    m = (rho > m || rho != rho) ? rho : m;
+  }
+  s = wg_sum(s, red);
+  mx[threadIdx.x] = m;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double y = mx[threadIdx.x + o], x = mx[threadIdx.x];
+      mx[threadIdx.x] = (y > x || y != y) ? y : x;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = nrm; out[1] = s / (double)nc; out[2] = mx[0]; }
+}
+
+// out[3] and the IPRs of a B whose factorisation failed (*d_info != 0): NaN
+__global__ void sygv_not_spd_kernel(const int *__restrict__ d_info, int nc, double *out, double *ipr) {
+  if (*d_info == 0) return;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j == 0) out[3] = __builtin_nan("");
+  if (j < nc) ipr[j] = __builtin_nan("");
+}
+
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -170,6 +227,71 @@ void ipratios(hipStream_t s, int n, int n_vec, const double *B, int ldb, const d
   } else {
     hipLaunchKernelGGL(ipr_kernel, dim3(n_vec), dim3(256), 0, s, n, V, ldv, V, ldv, d_ipr);
   }
+}
+
+// ---- DSYGV's types 2 and 3 for one problem of any order (ek_hip_check_sygvx*), the first nc columns of Z
+struct SygvCheckLayout {
+  size_t As, Bs, T1, T2, G, L, inv, twork, vec, total;
+  int ld;
+  SygvCheckLayout(int itype, int n, int nc) {
+    const size_t nn = (size_t)n * n, nz = (size_t)n * nc;
+    ld = round_up(n, kDiagNB);                      // the factor's leading dimension, as the Cholesky entries pad it
+    size_t o = 0;
+    auto take = [&](size_t doubles) { const size_t at = o; o += al256(doubles * 8); return at; };
+    As = take(nn); Bs = take(nn); T1 = take(nz); T2 = take(nz); G = take((size_t)nc * nc);
+    vec = take(4 * (size_t)n + 2 * (size_t)nc + 8);
+    L = inv = twork = o;
+    if (itype == 3) {
+      L = take((size_t)ld * n);
+      inv = take((size_t)ceil_div(n, kDiagNB) * kDiagNB * kDiagNB);
+      twork = take((size_t)256 * (ld > nc ? ld : nc));
+    }
+    total = o;
+  }
+};
+
+size_t sygv_check_work_bytes(int itype, int n, int ncols) { return SygvCheckLayout(itype, n, ncols).total; }
+
+// d_out (device, 4 doubles): ||A||_F ||B||_F, res_ave, res_max, orthogonality; d_ipr (device, nc doubles); *d_info (device
+// int): type 3's factorisation of a copy of B, 0 or the failing pivot -- then d_out[3] and d_ipr are NaN
+void sygv_check(hipStream_t s, int itype, int n, int nc, const double *A, int lda, const double *B, int ldb,
+                const double *w, const double *Z, int ldz, double *d_out, double *d_ipr, int *d_info, void *work) {
+  const SygvCheckLayout lay(itype, n, nc);
+  char *p = (char *)work;
+  double *As = (double *)(p + lay.As), *Bs = (double *)(p + lay.Bs), *T1 = (double *)(p + lay.T1);
+  double *T2 = (double *)(p + lay.T2), *G = (double *)(p + lay.G), *vec = (double *)(p + lay.vec);
+  double *asq = vec, *bsq = vec + n, *rsq = vec + 2 * (size_t)n, *zsq = rsq + nc, *gsq = zsq + nc;
+  copy_matrix(s, n, n, A, lda, As, n);
+  symmetrize_lower(s, n, As, n);
+  copy_matrix(s, n, n, B, ldb, Bs, n);
+  symmetrize_lower(s, n, Bs, n);
+  // T1 = S = B Z (type 2), U = A Z (type 3); T2 = R = -Z diag(w) + A S (type 2), + B U (type 3)
+  gemm(s, false, false, n, nc, n, 1.0, itype == 2 ? Bs : As, n, Z, ldz, 0.0, T1, n);
+  copy_matrix(s, n, nc, Z, ldz, T2, n);
+  hipLaunchKernelGGL(scale_cols_kernel, dim3(ceil_div(n, 256), nc < 1024 ? nc : 1024), dim3(256), 0, s, n, nc, T2, n, w);
+  gemm(s, false, false, n, nc, n, 1.0, itype == 2 ? As : Bs, n, T1, n, 1.0, T2, n);
+  hipLaunchKernelGGL(col_sumsq_kernel, dim3(nc), dim3(256), 0, s, n, T2, n, rsq);
+  hipLaunchKernelGGL(col_sumsq_kernel, dim3(nc), dim3(256), 0, s, n, Z, ldz, zsq);
+  hipLaunchKernelGGL(col_sumsq_kernel, dim3(n), dim3(256), 0, s, n, As, n, asq);
+  hipLaunchKernelGGL(col_sumsq_kernel, dim3(n), dim3(256), 0, s, n, Bs, n, bsq);
+  hipLaunchKernelGGL(finish_sygv_kernel, dim3(1), dim3(256), 0, s, nc, rsq, zsq, n, asq, bsq, d_out);
+  (void)hipMemsetAsync(d_info, 0, sizeof(int), s);
+  if (itype == 2) {                                 // G = Z^T (B Z)
+    gemm(s, true, false, nc, nc, n, 1.0, Z, ldz, T1, n, 0.0, G, nc);
+    hipLaunchKernelGGL(ipr_metric_kernel, dim3(nc), dim3(256), 0, s, n, Z, ldz, Z, ldz, T1, n, d_ipr);
+  } else {                                          // W = L^-1 Z over U, G = W^T W
+    double *L = (double *)(p + lay.L), *inv = (double *)(p + lay.inv), *tw = (double *)(p + lay.twork);
+    copy_matrix(s, n, n, B, ldb, L, lay.ld);
+    potrf_lower(s, n, L, lay.ld, inv, d_info, tw);
+    copy_matrix(s, n, nc, Z, ldz, T1, n);
+    trsm_lln(s, n, nc, L, lay.ld, inv, T1, n, tw);
+    gemm(s, true, false, nc, nc, n, 1.0, T1, n, T1, n, 0.0, G, nc);
+    hipLaunchKernelGGL(ipr_metric_kernel, dim3(nc), dim3(256), 0, s, n, Z, ldz, T1, n, T1, n, d_ipr);
+  }
+  hipLaunchKernelGGL(ortho_scale_kernel, dim3(nc), dim3(256), 0, s, nc, G, nc, gsq);
+  hipLaunchKernelGGL(finish_residual_kernel, dim3(1), dim3(256), 0, s, 0, gsq, nc, gsq, T2);   // T2[2] = ||.||_F
+  (void)hipMemcpyAsync(d_out + 3, T2 + 2, 8, hipMemcpyDeviceToDevice, s);
+  hipLaunchKernelGGL(sygv_not_spd_kernel, dim3(ceil_div(nc, 256)), dim3(256), 0, s, d_info, nc, d_out, d_ipr);
 }
 
 }  // namespace ek

@@ -170,6 +170,15 @@ def load_library(path=None):
                                          _ip, _dp, _dp, _dp]),
         "ek_hip_check_vbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
         "ek_hip_check_vbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
+        "ek_hip_check_sygv_batched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
+                                                     c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_sygv_batched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
+                                              c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_sygv_vbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp,
+                                                      _dp]),
+        "ek_hip_check_sygv_vbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
+        "ek_hip_check_sygvx_device": (c_int, [c_int, c_int, c_int, vp, c_int, vp, c_int, vp, vp, c_int, _dp, _dp]),
+        "ek_hip_check_sygvx": (c_int, [c_int, c_int, c_int, _dp, c_int, _dp, c_int, _dp, _dp, c_int, _dp, _dp]),
         "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
         "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
     }
@@ -214,6 +223,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_vbatched_streams", "ek_hip_debug_vbatched_last",
     "ek_hip_check_batched_device", "ek_hip_check_batched", "ek_hip_check_vbatched_device", "ek_hip_check_vbatched",
     "ek_hip_sygv_batched_device", "ek_hip_sygv_batched", "ek_hip_sygv_vbatched_device", "ek_hip_sygv_vbatched",
+    "ek_hip_check_sygv_batched_device", "ek_hip_check_sygv_batched", "ek_hip_check_sygv_vbatched_device",
+    "ek_hip_check_sygv_vbatched", "ek_hip_check_sygvx_device", "ek_hip_check_sygvx",
 )
 
 
@@ -832,15 +843,9 @@ def _check_info(info, batch):
     return info
 
 
-def check_batched(A, B, w, Z, info=None, ipr=True, seconds=None):
-    """The acceptance checks and the IPRs of every problem of a batch in one launch (ek_hip_check_batched), with the
-    normalisations of eigenkernel_amd.verifier: A (and B, or None) of shape (batch, n, n) -- the ORIGINAL matrices, lower
-    triangles referenced -- and w (batch, n), Z (batch, n, n) as eigenpairs_batched returns them.  Returns (out, ipr):
-    out[b] = (a_norm, res_ave, res_max, orthogonality) of problem b, ipr[b, j] the inverse participation ratio of column
-    j (ipr=False: None).  info: None (check every problem) or eigenpairs_batched's status words: a problem with
-    info[b] != 0 is skipped, its out row is NaN and its ipr row stays NaN.  seconds: None or a float64 array of one entry
-    that receives the device time.  Raises ValueError for bad shapes before the library is called, SolverError only
-    when the call itself fails."""
+def _check_batched_call(name, first, A, B, w, Z, info, ipr, seconds):
+    """ek_hip_check_batched / ek_hip_check_sygv_batched on (batch, n, n) arrays; `first` is the first argument (problem or
+    itype)."""
     lib = load_library()
     A = np.asarray(A, dtype=np.float64)
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
@@ -868,19 +873,41 @@ def check_batched(A, B, w, Z, info=None, ipr=True, seconds=None):
         if batch:
             out[:, 0] = np.where(info != 0, np.nan, 0.0) if info is not None else 0.0
         return out, q
-    rc = lib.ek_hip_check_batched(0 if B is None else 1, n, batch, _P(At), n, n * n,
-                                  _P(Bt) if Bt is not None else None, n, n * n, _P(wc), _P(Zt), n, n * n,
-                                  _I(info) if info is not None else None, _P(out), _P(q) if ipr else None,
-                                  _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, name)(first, n, batch, _P(At), n, n * n, _P(Bt) if Bt is not None else None, n, n * n, _P(wc),
+                            _P(Zt), n, n * n, _I(info) if info is not None else None, _P(out), _P(q) if ipr else None,
+                            _P(seconds) if seconds is not None else None)
     if rc != 0:
-        raise SolverError("ek_hip_check_batched failed", rc)
+        raise SolverError(name + " failed", rc)
     return out, q
 
 
-def check_vbatched(As, Bs, ws, Zs, info=None, ipr=True, seconds=None):
-    """check_batched for problems of DIFFERENT orders (ek_hip_check_vbatched): As, Bs (or None), ws, Zs sequences as
-    eigenpairs_vbatched takes and returns them.  Returns (out, list of ipr arrays or None); a problem of order 0 gets
-    a_norm = 0 and NaN in its other three slots.  Each problem's bits are those of check_batched on it alone."""
+def check_batched(A, B, w, Z, info=None, ipr=True, seconds=None):
+    """The acceptance checks and the IPRs of every problem of a batch in one launch (ek_hip_check_batched), with the
+    normalisations of eigenkernel_amd.verifier: A (and B, or None) of shape (batch, n, n) -- the ORIGINAL matrices, lower
+    triangles referenced -- and w (batch, n), Z (batch, n, n) as eigenpairs_batched returns them.  Returns (out, ipr):
+    out[b] = (a_norm, res_ave, res_max, orthogonality) of problem b, ipr[b, j] the inverse participation ratio of column
+    j (ipr=False: None).  info: None (check every problem) or eigenpairs_batched's status words: a problem with
+    info[b] != 0 is skipped, its out row is NaN and its ipr row stays NaN.  seconds: None or a float64 array of one entry
+    that receives the device time.  Raises ValueError for bad shapes before the library is called, SolverError only
+    when the call itself fails."""
+    return _check_batched_call("ek_hip_check_batched", 0 if B is None else 1, A, B, w, Z, info, ipr, seconds)
+
+
+def check_sygv_batched(A, B, w, Z, itype=1, info=None, ipr=True, seconds=None):
+    """check_batched for DSYGV's three problem types (ek_hip_check_sygv_batched), behind sygv_batched: itype 1 is
+    check_batched(A, B, ...) to the bit; for types 2 and 3 out[b] = (||A||_F ||B||_F, res_ave, res_max, orthogonality) and
+    ipr with the quantities of eigenkernel_amd.verifier's *_sygv functions (a B[b] that is not SPD gives NaN in
+    orthogonality and ipr of type 3).  A missing B or an itype outside 1 .. 3 raises ValueError before the library is
+    called."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if B is None:
+        raise ValueError("B is required")
+    return _check_batched_call("ek_hip_check_sygv_batched", int(itype), A, B, w, Z, info, ipr, seconds)
+
+
+def _check_vbatched_call(name, first, As, Bs, ws, Zs, info, ipr, seconds):
+    """ek_hip_check_vbatched / ek_hip_check_sygv_vbatched on sequences of arrays; `first` is the first argument."""
     lib = load_library()
     Af = []
     for M in As:
@@ -911,12 +938,52 @@ def check_vbatched(As, Bs, ws, Zs, info=None, ipr=True, seconds=None):
     def table(arrays):
         return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
 
-    rc = lib.ek_hip_check_vbatched(0 if Bf is None else 1, batch, _I(n), table(Af), _I(ld),
-                                   table(Bf) if Bf is not None else None, _I(ld), table(wf), table(Zf), _I(ld),
-                                   _I(info) if info is not None else None, _P(out), table(q) if ipr else None,
-                                   _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, name)(first, batch, _I(n), table(Af), _I(ld), table(Bf) if Bf is not None else None, _I(ld),
+                            table(wf), table(Zf), _I(ld), _I(info) if info is not None else None, _P(out),
+                            table(q) if ipr else None, _P(seconds) if seconds is not None else None)
     if rc != 0:
-        raise SolverError("ek_hip_check_vbatched failed", rc)
+        raise SolverError(name + " failed", rc)
+    return out, q
+
+
+def check_vbatched(As, Bs, ws, Zs, info=None, ipr=True, seconds=None):
+    """check_batched for problems of DIFFERENT orders (ek_hip_check_vbatched): As, Bs (or None), ws, Zs sequences as
+    eigenpairs_vbatched takes and returns them.  Returns (out, list of ipr arrays or None); a problem of order 0 gets
+    a_norm = 0 and NaN in its other three slots.  Each problem's bits are those of check_batched on it alone."""
+    return _check_vbatched_call("ek_hip_check_vbatched", 0 if Bs is None else 1, As, Bs, ws, Zs, info, ipr, seconds)
+
+
+def check_sygv_vbatched(As, Bs, ws, Zs, itype=1, info=None, ipr=True, seconds=None):
+    """check_sygv_batched for problems of DIFFERENT orders (ek_hip_check_sygv_vbatched), behind sygv_vbatched; arguments
+    and returns as check_vbatched, each problem's bits those of check_sygv_batched on it alone."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if Bs is None:
+        raise ValueError("Bs is required")
+    return _check_vbatched_call("ek_hip_check_sygv_vbatched", int(itype), As, Bs, ws, Zs, info, ipr, seconds)
+
+
+def check_sygvx(A, B, w, Z, itype=1):
+    """The checks of one problem of any order for DSYGV's three types (ek_hip_check_sygvx), behind sygvx: A, B (n, n) the
+    ORIGINAL matrices, w (m,) and Z (n, m) the window's eigenpairs.  Returns the array _check returns for the residual
+    with the orthogonality behind it, (norm, res_ave, res_max, orthogonality), and the m IPRs."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    lib = load_library()
+    A_, B_, Z_ = _farr(A), _farr(B), _farr(Z)
+    n = A_.shape[0]
+    if A_.shape != (n, n) or B_.shape != (n, n) or Z_.ndim != 2 or Z_.shape[0] != n or Z_.shape[1] > n:
+        raise ValueError("A and B must be (n, n) and Z (n, m) with m <= n")
+    m = Z_.shape[1]
+    wv = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+    if wv.shape != (m,):
+        raise ValueError("w must hold one eigenvalue per column of Z")
+    out = np.full(CHECK_NOUT, np.nan)
+    q = np.full(m, np.nan)
+    ld = max(n, 1)
+    info = lib.ek_hip_check_sygvx(int(itype), n, m, _P(A_), ld, _P(B_), ld, _P(wv), _P(Z_), ld, _P(out), _P(q))
+    if info:
+        raise RuntimeError("ek_hip_check_sygvx info=%d" % info)
     return out, q
 
 

@@ -309,8 +309,9 @@ int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, c
  * A of any finite magnitude is scaled as above, from A alone.  For types 2 and 3 the reduction amplifies by lambda_max(B)
  * where type 1's amplifies by 1 / lambda_min(B): max|a| lambda_max(B) beyond about 2^500 can overflow and is reported as
  * 100000 + n + 1, never as info = 0.
- * ek_hip_check_batched* / ek_hip_check_vbatched* below remain checks of type 1 (and of the standard problem): their
- * normalisations are the reference verifier's, which has none for types 2 and 3. */
+ * ek_hip_check_batched* / ek_hip_check_vbatched* below remain checks of type 1 (and of the standard problem), with the
+ * reference verifier's normalisations; ek_hip_check_sygv_batched* / ek_hip_check_sygv_vbatched* behind them carry those
+ * normalisations over to types 2 and 3, and ek_hip_check_sygvx* does the same for one problem of any order. */
 int ek_hip_sygv_batched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                long long strideZ, int *info, double *seconds);
@@ -391,6 +392,65 @@ int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const dou
 int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
                           const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
                           const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
+
+/* The same checks for DSYGV's three problem types -- what ek_hip_check_batched* / ek_hip_check_vbatched* are to
+ * ek_hip_eigenpairs_*batched*, these are to ek_hip_sygv_batched* / ek_hip_sygv_vbatched*.  With B = L L^T (B SPD), A and B
+ * symmetric by their lower triangles, all n columns checked and plain IEEE divisions:
+ *                 type 1 (A x = l B x)          type 2 (A B x = l x)          type 3 (B A x = l x)
+ *   r_j           A z_j - w_j B z_j             A (B z_j) - w_j z_j           B (A z_j) - w_j z_j
+ *   rho_j         ||r_j||_2 / ||A||_F           ||r_j||_2 / (||A||_F ||B||_F ||z_j||_2)   (types 2 and 3)
+ *   G             Z^T B Z                       Z^T B Z                       (L^-1 Z)^T (L^-1 Z)  (= Z^T B^-1 Z)
+ *   out[4 b + 0]  the norm the residuals are divided by: ||A||_F (type 1), ||A||_F ||B||_F (types 2 and 3)
+ *   out[4 b + 1]  sum_j rho_j / n
+ *   out[4 b + 2]  max_j rho_j
+ *   out[4 b + 3]  || D^-1/2 G D^-1/2 with zero diagonal ||_F, D = diag(G): scaled by the computed G_jj, as above
+ *   ipr           ipr_j = sum_i z_ij^4 / G_jj^2, with the G of the type
+ * Type 3 needs a factor of B: the check makes its own from the caller's ORIGINAL B (right-looking Cholesky inside the
+ * workgroup).  A pivot that is not positive and finite gives NaN in out[4 b + 3] and in the problem's ipr slots; its
+ * residual slots stay valid, and the return value is unaffected.
+ * Argument k is argument k of the corresponding ek_hip_check_*batched* entry, itype (1, 2, 3) in the place of problem; B is
+ * always required.  Return value: -1 for itype outside 1 .. 3, then the codes of those entries with problem = 1 (uniform:
+ * -7 / -8 / -9 for B, ldb, strideB; variable: -6 / -7 for dB, ldb), decided before any device work and without
+ * dereferencing a data pointer.  info, out, ipr, seconds, skipped problems, n = 0 and batch = 0 behave as there (NaN in
+ * the four slots of a skipped problem, its ipr left alone).
+ * itype 1 IS ek_hip_check_*batched*(problem = 1): the same bits in out and ipr.  For the same (B, Z), out[4 b + 3] and ipr
+ * of type 2 are the bits of type 1.  THE SAME BITS WHEREVER A PROBLEM SITS: a problem's outputs depend on (itype, n, A, B,
+ * w, Z) alone, in the uniform and the variable form, in the host and the device form.  One launch per call (uniform), at
+ * most three (variable), one workgroup per problem, the classes n <= 32 / 64 / 128; A, B, w and Z are const and come back
+ * bit for bit; strictly upper triangles, rows n .. ld-1 and the gaps between problems are never read.
+ * NOT COLLECTIVE; the calls synchronise.  Workspace: that of ek_hip_check_*batched* for a generalized batch (n^2 doubles
+ * per checked problem: S = B Z, then A Z and L in turn). */
+int ek_hip_check_sygv_batched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
+                                     const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                     int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                     double *seconds);
+int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                              int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                              const int *info, double *out, double *ipr, double *seconds);
+int ek_hip_check_sygv_vbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
+                                      const double *const *dB, const int *ldb, const double *const *dw,
+                                      const double *const *dZ, const int *ldz, const int *info, double *out,
+                                      double *const *ipr, double *seconds);
+int ek_hip_check_sygv_vbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
+                               const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                               const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
+/* One problem of ANY order: the quantities above for the first n_cols columns of Z (what a window of ek_hip_sygvx*
+ * returns; sum_j rho_j / n_cols, G of order n_cols), out[0 .. 3] and ipr_host[0 .. n_cols-1] (host; ipr_host may be NULL).
+ * dA, dB: the ORIGINAL column-major matrices (lda, ldb >= max(1, n); lower triangles referenced), dw: n_cols eigenvalues,
+ * dZ: n x n_cols (ldz >= max(1, n)).  itype 1 returns what ek_hip_residual_device, ek_hip_orthogonality_device(1, n_cols)
+ * and ek_hip_ipratios_device return, bit for bit.  Types 2 and 3 are composed from the products behind those entries and,
+ * for type 3, the factorisation and forward solve of ek_hip_potrf / ek_hip_sygst on a copy of B; a B that is not SPD
+ * gives NaN in out[3] and ipr_host, valid residual slots and the return value 0.  A, B, w and Z are const and come back
+ * bit for bit.  Return value: -k for argument k (-1 itype outside 1 .. 3, -2 n < 0, -3 n_cols outside 0 .. n, -4 / -6 /
+ * -8 / -9 NULL, -5 / -7 / -10 leading dimension, -11 out NULL), the first offender deciding, before any device work;
+ * n = 0 or n_cols = 0: 0, nothing referenced or written.  NOT COLLECTIVE; the calls synchronise.
+ * Workspace (the library's cached device workspace): 2 n^2 + 2 n n_cols + n_cols^2 + 4 n + 3 n_cols doubles, and for
+ * type 3 n (n rounded up to 128) for the factor, 128^2 per 128 rows for its diagonal blocks' inverses and 256 max(n
+ * rounded up to 128, n_cols) for the triangular solve; the host form adds device copies of A, B, w and Z. */
+int ek_hip_check_sygvx_device(int itype, int n, int n_cols, const double *dA, int lda, const double *dB, int ldb,
+                              const double *dw, const double *dZ, int ldz, double out[4], double *ipr_host);
+int ek_hip_check_sygvx(int itype, int n, int n_cols, const double *A, int lda, const double *B, int ldb, const double *w,
+                       const double *Z, int ldz, double out[4], double *ipr_host);
 
 /* Process grids larger than 1x1 (one rank per GPU): replicated-input mode.
  * The reference broadcasts the global sparse matrices to every rank before the solver runs
