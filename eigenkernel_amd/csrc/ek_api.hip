@@ -261,6 +261,7 @@ int ek_hip_finalize(void) {
   release_user_images();
   release_pipe_streams();
   release_batched();
+  release_xbatched();
   release_batched_check();
   // a communicator does not outlive the library's device state
   comm_teardown();

@@ -722,11 +722,11 @@ using namespace ek::api;
 
 static int batched_check(int problem, int jobz, int n, int batch, const void *A, int lda, long long strideA,
                          const void *B, int ldb, long long strideB, const void *w, const void *Z, int ldz,
-                         long long strideZ, const int *info, bool *nothing) {
+                         long long strideZ, const int *info, bool *nothing, int nmax) {
   *nothing = false;
   if (problem != 0 && problem != 1) return -1;
   if (jobz != 0 && jobz != 1) return -2;
-  if (n < 0 || n > EK_HIP_BATCH_NMAX) return -3;
+  if (n < 0 || n > nmax) return -3;
   if (batch < 0) return -4;
   if (n == 0 || batch == 0) { *nothing = true; return 0; }
   if (!A) return -5;
@@ -762,7 +762,10 @@ static int batched_device_locked(int problem, int itype, int jobz, int n, int ba
     (void)hipEventRecord(e0, s);
   }
   int rc;
-  switch (batched::class_of(n)) {
+  if (n > EK_HIP_BATCH_NMAX) {                      // ek_hip_eigenpairs_xbatched*: the image in device memory
+    rc = xbatched_launch(s, problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
+                         batched::g_dinfo);
+  } else switch (batched::class_of(n)) {
     case 32: rc = batched::launch_class<32, 64>(s, batch, a); break;
     case 64: rc = batched::launch_class<64, 128>(s, batch, a); break;
     default: rc = batched::launch_class<128, 256>(s, batch, a); break;
@@ -900,13 +903,15 @@ static int vbatched_device_locked(int problem, int itype, int jobz, int batch, c
 }
 
 // The bodies of the entries: ek_hip_eigenpairs_* pass itype 1, ek_hip_sygv_* problem 1 (argument k of the one is
-// argument k of the other).
+// argument k of the other).  nmax is the largest order the entry takes: EK_HIP_XBATCH_NMAX for ek_hip_eigenpairs_xbatched*,
+// which are the batched entries up to EK_HIP_BATCH_NMAX and ek_batched_x.hip's kernel above it.
 static int batched_device_entry(int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
                                 long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ,
-                                int ldz, long long strideZ, int *info, double *seconds) {
+                                int ldz, long long strideZ, int *info, double *seconds,
+                                int nmax = EK_HIP_BATCH_NMAX) {
   bool nothing;
   int rc = batched_check(problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                         &nothing);
+                         &nothing, nmax);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -918,10 +923,11 @@ static int batched_device_entry(int problem, int itype, int jobz, int n, int bat
 
 static int batched_host_entry(int problem, int itype, int jobz, int n, int batch, const double *A, int lda,
                               long long strideA, const double *B, int ldb, long long strideB, double *w, double *Z,
-                              int ldz, long long strideZ, int *info, double *seconds) {
+                              int ldz, long long strideZ, int *info, double *seconds,
+                              int nmax = EK_HIP_BATCH_NMAX) {
   bool nothing;
   int rc = batched_check(problem, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
-                         &nothing);
+                         &nothing, nmax);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -1058,6 +1064,20 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
                               long long strideZ, int *info, double *seconds) {
   return batched_host_entry(problem, 1, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
                             seconds);
+}
+
+int ek_hip_eigenpairs_xbatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                      double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                      long long strideZ, int *info, double *seconds) {
+  return batched_device_entry(problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                              seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_eigenpairs_xbatched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                               long long strideZ, int *info, double *seconds) {
+  return batched_host_entry(problem, 1, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
+                            seconds, EK_HIP_XBATCH_NMAX);
 }
 
 int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,

@@ -1,0 +1,592 @@
+// ek_batched_x.hip -- ek_hip_eigenpairs_xbatched*: orders EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX of the batched solver.
+//
+// The six stages of ek_batched.hip with the same arithmetic rules, one workgroup per problem from its first load to its
+// last store and no launch between the stages -- but the n x n image lies in a device workspace (column-major, leading
+// dimension 257, one slot per workgroup of a launch) and not in LDS: 256 x 257 doubles are 514 KiB.  The vectors stay in
+// LDS (d, e, tau, v, w, the partial sums, the two staged columns: 9 x 256 doubles).  One class: NC = 256, 512 threads,
+// thread t is (row or column t % 256, half t / 256).  Problem 0 and problem 1 (A x = l B x) only.
+//
+// Every n^3 loop over the image runs with the lanes of a wave along consecutive rows (consecutive addresses):
+//   1  right-looking Cholesky: lane = row; the scaled column of a step is kept in LDS for the update
+//   2  X = L^-1 A is kept TRANSPOSED (A is symmetric, so the image of A is its own transpose): the pair t owns column t
+//      of X, which is row t of the image.  The upper triangle is then copied to the lower one (X's lower half the right
+//      way round) and C = X L^-T runs with the pair t on row t, as in ek_batched.hip.  Both solves are column-oriented
+//      (axpy form): every entry sees the same updates in the same order whichever thread applies them, so the two
+//      threads of a pair take every other entry; the entry that is the next step's pivot is carried in a register by
+//      both (the same instruction on the same operands), and only the half 0 stores it
+//   3  DSYTD2 as in ek_batched.hip: lane = row in the symv and in the rank-2 update
+//   4  QL: lane = row of Z
+//   5  Z is transposed in place, so that the pair t owns column t of Z as row t of the image; the dot of a reflector
+//      (and of a row of L^-T) is split between the two threads of a pair -- even and odd offsets, each in ascending
+//      order; a reflector's dot is half 0's sum plus half 1's, a row of L^-T gives (z - half 0's sum) - half 1's sum --
+//      and the last pass stores Z^T's rows as Z's columns
+// Five n^2 passes do have the lanes 257 doubles apart on one side (a cache line per lane): the mirror fill of A's image,
+// the copy of X's lower half, the mirror of C, the transpose of Z, and the reads of the last pass.
+// Loads from the image are issued eight at a time before the first use: a dependent round trip to L2 / Infinity Cache /
+// HBM is paid once per eight entries.  All traffic to the image between threads is ordered by __syncthreads(); plain
+// loads and stores, no atomics.  The order of every sum depends on n alone: same bits wherever a problem sits.
+//
+// A batch runs in chunks of at most K problems (K = 1024; ek_hip_debug_xbatched_chunk), launched one after the other on
+// the context's stream without a host synchronise; problem i of a chunk works in slot i of the workspace.
+#include "ek_api_internal.h"
+
+#include <algorithm>
+#include <cfloat>
+
+namespace ek {
+namespace batchedx {
+
+typedef __attribute__((address_space(1))) double gdouble;
+
+constexpr int NC = 256, T = 512, LD = NC + 1, P = T / NC, NW = T / 64;
+constexpr size_t kSlot = (size_t)NC * LD;           // doubles of one image
+constexpr int kChunk = 1024;                        // problems per launch: 1024 slots are 539 MB
+static_assert(P == 2 && NC == EK_HIP_XBATCH_NMAX, "two threads per row");
+
+struct Args {
+  int problem, jobz, n;
+  double *A; int lda; long long sA;
+  double *B; int ldb; long long sB;
+  double *w;
+  double *Z; int ldz; long long sZ;
+  int *info;
+  double *ws;
+};
+
+// ek_batched.hip's block_reduce: a sum (or maximum) over the workgroup, the same bits in every thread
+template <bool MAX>
+__device__ __forceinline__ double block_reduce(double x, double *red, int &phase) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double y = __shfl_xor(x, o, 64);
+    x = MAX ? fmax(x, y) : x + y;
+  }
+  double *rr = red + phase * NW;
+  phase ^= 1;
+  if ((threadIdx.x & 63) == 0) rr[threadIdx.x >> 6] = x;
+  __syncthreads();
+  double s = rr[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s = MAX ? fmax(s, rr[w]) : s + rr[w];
+  return s;
+}
+
+// y[i * SY] -= x[i] * a for i = i0, i0 + STEP, ... < i1; y in the image, x in LDS: eight loads before the first store
+template <int SY, int STEP>
+__device__ __forceinline__ void img_axpy(gdouble *y, const double *x, double a, int i0, int i1) {
+  int i = i0;
+  for (; i + 7 * STEP < i1; i += 8 * STEP) {
+    double yv[8], xv[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) yv[q] = y[(i + q * STEP) * SY];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xv[q] = x[i + q * STEP];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) y[(i + q * STEP) * SY] = yv[q] - xv[q] * a;
+  }
+  for (; i < i1; i += STEP) y[i * SY] -= x[i] * a;
+}
+
+// acc + sum of x[k * SX] * l[k] over k = k0, k0 + STEP, ... < k1, in that order; x in the image, l in LDS
+template <int SX, int STEP>
+__device__ __forceinline__ double img_dot(const gdouble *x, const double *l, int k0, int k1, double acc) {
+  int k = k0;
+  for (; k + 7 * STEP < k1; k += 8 * STEP) {
+    double xv[8], lv[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xv[q] = x[(k + q * STEP) * SX];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) lv[q] = l[k + q * STEP];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc += xv[q] * lv[q];
+  }
+  for (; k < k1; k += STEP) acc += x[k * SX] * l[k];
+  return acc;
+}
+
+__global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
+  __shared__ double sd[NC], se[NC], st[NC];         // d, e, tau: alive from stage 3 to the end
+  __shared__ double sv[NC], sw[NC];                 // stage 1: the scaled column; 3: v, w; 4: c, s of a sweep
+  __shared__ double sp[P * NC];                     // partial sums of a pair
+  __shared__ double sl[2 * NC];                     // a column of L or a reflector, and the next one
+  __shared__ double red[2 * NW];
+  __shared__ int srank[NC];
+  __shared__ int s_state, s_m, s_lo;
+
+  const long long pb = blockIdx.x;
+  const int t = threadIdx.x, n = a.n;
+  const int r = t % NC, sub = t / NC;
+  const bool row = r < n;
+  gdouble *A = (gdouble *)(a.A + pb * a.sA);
+  gdouble *B = a.problem ? (gdouble *)(a.B + pb * a.sB) : nullptr;
+  gdouble *S = (gdouble *)(a.ws + (size_t)pb * kSlot);
+  gdouble *W = (gdouble *)(a.w + pb * a.n);
+  const int lda = a.lda, ldb = a.ldb;
+  int *info = a.info + pb;
+  int phase = 0;
+
+  // ---- 0: A finite?  max|a| off the same pass (ek_batched.hip's rule: scaled outside 2^-256 .. 2^256)
+  int aex = 0;
+  {
+    double mx = 0.0;
+    if (row)
+      for (int j = sub; j <= r; j += P) {
+        const double ax = fabs(A[r + (size_t)j * lda]);
+        mx = (ax <= DBL_MAX) ? fmax(mx, ax) : INFINITY;
+      }
+    const double amax = block_reduce<true>(mx, red, phase);
+    if (!(amax <= DBL_MAX)) {
+      if (t == 0) *info = -5;
+      return;
+    }
+    if (amax > 0.0 && (amax < 0x1p-256 || amax > 0x1p256)) (void)frexp(amax, &aex);
+  }
+
+  if (a.problem) {
+    // ---- 1: B = L L^T in the image
+    if (row)
+      for (int j = sub; j <= r; j += P) S[r + j * LD] = B[r + (size_t)j * ldb];
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+      const double piv = S[j + j * LD];
+      if (!(piv > 1e-290) || !(piv < 1e290)) {
+        if (t == 0) *info = j + 1;
+        return;
+      }
+      const double l = sqrt(piv);
+      if (sub == 0 && row && r > j) {
+        const double lr = S[r + j * LD] / l;
+        S[r + j * LD] = lr;
+        sv[r] = lr;
+      }
+      __syncthreads();
+      if (row && r > j) img_axpy<LD, P>(S + r, sv, sv[r], j + 1 + sub, r + 1);
+      __syncthreads();
+    }
+    if (row)
+      for (int j = sub; j <= r; j += P) B[r + (size_t)j * ldb] = (r == j) ? sqrt(S[j + j * LD]) : S[r + j * LD];
+    __syncthreads();
+  }
+
+  // ---- 2: A -> full symmetric image; C = L^-1 A L^-T
+  if (row)
+    for (int j = sub; j <= r; j += P) {
+      const double x = ldexp(A[r + (size_t)j * lda], -aex);
+      S[r + j * LD] = x;
+      S[j + r * LD] = x;
+    }
+  if (a.problem) {
+    if (t < n) sl[t] = B[t];                        // column 0 of L
+    __syncthreads();
+    // X = L^-1 A, transposed: the pair r owns column r of X = row r of the image
+    {
+      double pv = row ? S[r] : 0.0;
+      __syncthreads();                              // both halves hold the first pivot before half 0 overwrites it
+      for (int k = 0; k < n; ++k) {
+        const double *cur = sl + (k & 1) * NC;
+        double nx = 0.0, nv = 0.0;
+        if (k + 1 < n && t > k && t < n) nx = B[t + (size_t)(k + 1) * ldb];
+        if (row) {
+          if (k + 1 < n) nv = S[r + (k + 1) * LD];  // step k - 1 wrote it; this step leaves it alone
+          const double xk = pv / cur[k];
+          if (sub == 0) S[r + k * LD] = xk;
+          pv = nv - cur[min(k + 1, n - 1)] * xk;
+          img_axpy<LD, P>(S + r, cur, xk, k + 2 + sub, n);
+        }
+        if (t < n) sl[((k + 1) & 1) * NC + t] = nx;
+        __syncthreads();
+      }
+    }
+    // the lower half of X the right way round: X[r, j] = image[j, r]
+    if (row)
+      for (int j = sub; j < r; j += P) S[r + j * LD] = S[j + r * LD];
+    if (t < n) sl[t] = B[t];
+    __syncthreads();
+    // C = X L^-T, lower half: the pair r owns row r, columns 0 .. r
+    {
+      double pv = row ? S[r] : 0.0;
+      __syncthreads();                              // both halves hold the first pivot before half 0 overwrites it
+      for (int k = 0; k < n; ++k) {
+        const double *cur = sl + (k & 1) * NC;
+        double nx = 0.0, nv = 0.0;
+        if (k + 1 < n && t > k && t < n) nx = B[t + (size_t)(k + 1) * ldb];
+        if (row && k <= r) {
+          if (k + 1 <= r) nv = S[r + (k + 1) * LD];
+          const double ck = pv / cur[k];
+          if (sub == 0) S[r + k * LD] = ck;
+          pv = nv - cur[min(k + 1, n - 1)] * ck;
+          img_axpy<LD, P>(S + r, cur, ck, k + 2 + sub, r + 1);
+        }
+        if (t < n) sl[((k + 1) & 1) * NC + t] = nx;
+        __syncthreads();
+      }
+    }
+    if (row)
+      for (int j = sub; j < r; j += P) S[j + r * LD] = S[r + j * LD];
+  }
+  __syncthreads();
+
+  // ---- 3: Householder tridiagonalisation of the image (both triangles kept, bitwise symmetric)
+  for (int k = 0; k + 1 < n; ++k) {
+    double x = 0.0;
+    if (sub == 0 && row && r >= k + 2) x = S[r + k * LD];
+    const double xn2 = block_reduce<false>(x * x, red, phase);
+    const double alpha = S[k + 1 + k * LD], dk = S[k + k * LD];
+    double tau = 0.0, beta = alpha, scal = 0.0;
+    if (xn2 != 0.0) {
+      beta = -copysign(sqrt(alpha * alpha + xn2), alpha);
+      tau = (beta - alpha) / beta;
+      scal = 1.0 / (alpha - beta);
+    }
+    if (sub == 0 && row) {
+      if (r >= k + 2) {
+        const double vi = x * scal;
+        sv[r] = vi;
+        A[r + (size_t)k * lda] = vi;
+      } else if (r == k + 1) {
+        sv[r] = 1.0;
+        se[k] = beta;
+        st[k] = tau;
+        A[r + (size_t)k * lda] = ldexp(beta, aex);
+      } else if (r == k) {
+        sd[k] = dk;
+        A[k + (size_t)k * lda] = ldexp(dk, aex);
+      }
+    }
+    if (tau == 0.0) continue;                       // H = I (uniform)
+    __syncthreads();
+    if (row && r > k) sp[sub * NC + r] = img_dot<LD, P>(S + r, sv, k + 1 + sub, n, 0.0);   // p = C v
+    __syncthreads();
+    double pr = 0.0, vr = 0.0;
+    if (sub == 0 && row && r > k) {
+      pr = tau * (sp[r] + sp[NC + r]);
+      vr = sv[r];
+    }
+    const double dot = block_reduce<false>(pr * vr, red, phase);
+    const double al2 = -0.5 * tau * dot;
+    if (sub == 0 && row && r > k) sw[r] = pr + al2 * vr;
+    __syncthreads();
+    if (row && r > k) {                             // C -= v w^T + w v^T; (r, j) and (j, r) evaluate the same expression
+      const double vr2 = sv[r], wr2 = sw[r];
+      auto term = [&](int j, double vj, double wj) {
+        const bool up = j > r;
+        const double vh = up ? vj : vr2, wh = up ? wj : wr2, vl = up ? vr2 : vj, wl = up ? wr2 : wj;
+        return vh * wl + wh * vl;
+      };
+      int j = k + 1 + sub;
+      for (; j + 7 * P < n; j += 8 * P) {
+        gdouble *c0 = S + r + j * LD;
+        double av[8], vv[8], wv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) av[q] = c0[q * P * LD];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { vv[q] = sv[j + q * P]; wv[q] = sw[j + q * P]; }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) c0[q * P * LD] = av[q] - term(j + q * P, vv[q], wv[q]);
+      }
+      for (; j < n; j += P) S[r + j * LD] -= term(j, sv[j], sw[j]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double dl = S[(n - 1) * (LD + 1)];
+    sd[n - 1] = dl;
+    se[n - 1] = 0.0;
+    A[(size_t)(n - 1) * lda + (n - 1)] = ldexp(dl, aex);
+  }
+  __syncthreads();
+
+  // ---- 4: implicit QL with Z in the image (ek_batched.hip's stage 4)
+  int wex = aex;
+  {
+    double mx = 0.0;
+    int bad = 0;
+    if (sub == 0 && row) {
+      mx = fmax(fabs(sd[r]), fabs(se[r]));
+      bad = !(mx <= DBL_MAX);
+    }
+    if (__syncthreads_or(bad)) {
+      if (t == 0) *info = 100000 + n + 1;
+      return;
+    }
+    const double anorm = block_reduce<true>(mx, red, phase);
+    if (anorm > 0.0) {
+      int ex;
+      (void)frexp(anorm, &ex);
+      const double sc = ldexp(1.0, -ex);
+      wex += ex;
+      __syncthreads();
+      if (sub == 0 && row) { sd[r] *= sc; se[r] *= sc; }
+    }
+  }
+  __syncthreads();
+  const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
+  {
+    double dr = 0.0, er = 0.0;
+    if (flip && sub == 0 && row) {
+      dr = sd[n - 1 - r];
+      er = (r < n - 1) ? se[n - 2 - r] : 0.0;
+    }
+    __syncthreads();
+    if (flip && sub == 0 && row) { sd[r] = dr; se[r] = er; }
+  }
+  if (a.jobz && row)
+    for (int j = sub; j < n; j += P) S[r + j * LD] = (r == (flip ? n - 1 - j : j)) ? 1.0 : 0.0;
+  __syncthreads();
+  {
+    const double eps = 1.1102230246251565e-16;
+    double *sc_ = sv, *ss_ = sw;
+    int failed = 0;
+    int iter = 0;
+    for (int l = 0; l < n && !failed; ++l) {
+      while (true) {
+        if (t == 0) {
+          int m = l;
+          for (bool found = false; !found;) {
+            double dv[9], ev[8];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) dv[q] = sd[min(m + q, n - 1)];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) ev[q] = se[min(m + q, n - 1)];
+            int hit = -1;
+#pragma unroll
+            for (int q = 7; q >= 0; --q)
+              if (m + q >= n - 1 || fabs(ev[q]) <= eps * (fabs(dv[q]) + fabs(dv[q + 1]))) hit = q;
+            if (hit >= 0) { m = min(m + hit, n - 1); found = true; } else m += 8;
+          }
+          if (m == l) {
+            s_state = 0;
+          } else if (iter++ == 30 * n) {
+            s_state = 2;
+          } else {
+            const double dl = sd[l], el = se[l];
+            double g = (sd[l + 1] - dl) / (2.0 * el);
+            double rr = sqrt(g * g + 1.0);
+            g = sd[m] - dl + el / (g + copysign(rr, g));
+            double s = 1.0, c = 1.0, p = 0.0;
+            int i, lo = l;
+            bool under = false;
+            double ei = se[m - 1], di = sd[m - 1], dup = sd[m];
+            for (i = m - 1; i >= l; --i) {
+              double en = 0.0, dn = 0.0;
+              if (i > l) { en = se[i - 1]; dn = sd[i - 1]; }
+              const double f = s * ei, bb = c * ei;
+              const double h = f * f + g * g;
+              if (!(h >= 1e-280)) {                 // recover from underflow: split here
+                se[i + 1] = 0.0;
+                sd[i + 1] = dup - p;
+                se[m] = 0.0;
+                under = true;
+                lo = i + 1;
+                break;
+              }
+              double y = __builtin_amdgcn_rsq(h);
+              y = y * (1.5 - 0.5 * h * y * y);
+              y = y * (1.5 - 0.5 * h * y * y);
+              rr = h * y;
+              se[i + 1] = rr;
+              s = f * y;
+              c = g * y;
+              g = dup - p;
+              rr = (di - g) * s + 2.0 * c * bb;
+              p = s * rr;
+              sd[i + 1] = g + p;
+              g = c * rr - bb;
+              sc_[i] = c;
+              ss_[i] = s;
+              dup = di; di = dn; ei = en;
+            }
+            if (!under) {
+              sd[l] = dup - p;
+              se[l] = g;
+              se[m] = 0.0;
+            }
+            s_state = 1; s_m = m; s_lo = lo;
+          }
+        }
+        __syncthreads();
+        const int state = s_state, m = s_m, lo = s_lo;
+        if (state == 1 && a.jobz && t < n) {        // the sweep's rotations on row t of Z
+          gdouble *zr = S + t;
+          double f = zr[m * LD];
+          int i = m - 1;
+          for (; i - 7 >= lo; i -= 8) {             // eight rotations' loads before the first store
+            double zv[8], cv[8], sv8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) zv[q] = zr[(i - q) * LD];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) { cv[q] = sc_[i - q]; sv8[q] = ss_[i - q]; }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              zr[(i + 1 - q) * LD] = sv8[q] * zv[q] + cv[q] * f;
+              f = cv[q] * zv[q] - sv8[q] * f;
+            }
+          }
+          for (; i >= lo; --i) {
+            const double c = sc_[i], s = ss_[i], z0 = zr[i * LD];
+            zr[(i + 1) * LD] = s * z0 + c * f;
+            f = c * z0 - s * f;
+          }
+          zr[lo * LD] = f;
+        }
+        __syncthreads();
+        if (state == 2) failed = l + 1;
+        if (state != 1) break;
+      }
+    }
+    if (failed) {
+      if (t == 0) *info = 100000 + failed;
+      return;
+    }
+  }
+  // ascending order: rank sort (ties by index; a NaN sorts last so that the ranks stay a permutation)
+  {
+    int rank = 0, bad = 0;
+    double wr = 0.0;
+    if (sub == 0 && row) {
+      const double di = sd[r], ki = (di == di) ? di : INFINITY;
+      for (int j = 0; j < n; ++j) {
+        const double dj = sd[j], kj = (dj == dj) ? dj : INFINITY;
+        rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
+      }
+      srank[r] = rank;
+      wr = ldexp(di, wex);
+      bad = !(fabs(wr) <= DBL_MAX);
+    }
+    if (__syncthreads_or(bad)) {
+      if (t == 0) *info = 100000 + n + 1;
+      return;
+    }
+    if (sub == 0 && row) W[rank] = wr;
+  }
+  if (!a.jobz) {
+    if (t == 0) *info = 0;
+    return;
+  }
+  gdouble *Z = (gdouble *)(a.Z + pb * a.sZ);
+  const int ldz = a.ldz;
+
+  // ---- 5: the image becomes Z^T: the pair r owns column r of Z = row r of the image
+  if (row)
+    for (int j = sub; j < r; j += P) {
+      const double lo = S[r + j * LD], up = S[j + r * LD];
+      S[r + j * LD] = up;
+      S[j + r * LD] = lo;
+    }
+  // Z <- H_0 ... H_{n-3} Z (H_{n-2} = I)
+  if (n >= 3) {
+    if (t < n) sl[t] = (t >= n - 1) ? A[t + (size_t)(n - 3) * lda] : 0.0;
+    __syncthreads();
+    for (int k = n - 3, s = 0; k >= 0; --k, ++s) {
+      const double *cur = sl + (s & 1) * NC;
+      double nx = 0.0;
+      if (k >= 1 && t > k && t < n) nx = A[t + (size_t)(k - 1) * lda];
+      const double tau = st[k];
+      if (tau != 0.0) {                             // uniform
+        double c1 = 0.0;
+        if (row) {
+          if (sub == 0) c1 = S[r + (k + 1) * LD];
+          sp[sub * NC + r] = img_dot<LD, P>(S + r, cur, k + 2 + sub, n, c1);
+        }
+        __syncthreads();
+        if (row) {
+          const double dot = (sp[r] + sp[NC + r]) * tau;
+          if (sub == 0) S[r + (k + 1) * LD] = c1 - dot;
+          img_axpy<LD, P>(S + r, cur, dot, k + 2 + sub, n);
+        }
+      }
+      if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+  }
+  // Z <- L^-T Z
+  if (a.problem) {
+    __syncthreads();
+    if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
+    __syncthreads();
+    for (int i = n - 1, s = 0; i >= 0; --i, ++s) {
+      const double *cur = sl + (s & 1) * NC;
+      double nx = 0.0;
+      if (i >= 1 && t >= i - 1 && t < n) nx = B[t + (size_t)(i - 1) * ldb];
+      double zi = 0.0;
+      if (row) {
+        if (sub == 0) zi = S[r + i * LD];
+        sp[sub * NC + r] = img_dot<LD, P>(S + r, cur, i + 1 + sub, n, 0.0);
+      }
+      __syncthreads();
+      if (sub == 0 && row) S[r + i * LD] = ((zi - sp[r]) - sp[NC + r]) / cur[i];
+      if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (row) {                                        // Z[r, j] = image[j, r]
+    int j = sub;
+    for (; j + 7 * P < n; j += 8 * P) {
+      double zv[8];
+      int rk[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) zv[q] = S[j + q * P + r * LD];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) rk[q] = srank[j + q * P];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) Z[r + (size_t)rk[q] * ldz] = zv[q];
+    }
+    for (; j < n; j += P) Z[r + (size_t)srank[j] * ldz] = S[j + r * LD];
+  }
+  if (t == 0) *info = 0;
+}
+
+// the images: grown, never shrunk, released in ek_hip_finalize
+static double *g_ws = nullptr;
+static size_t g_ws_slots = 0;
+static int g_chunk = kChunk;
+
+static int ensure_images(size_t slots) {
+  if (slots <= g_ws_slots) return 0;
+  if (g_ws) (void)hipFree(g_ws);
+  g_ws = nullptr;
+  g_ws_slots = 0;
+  EK_HIP_CHECK(hipMalloc((void **)&g_ws, slots * kSlot * sizeof(double)));
+  g_ws_slots = slots;
+  return 0;
+}
+
+}  // namespace batchedx
+
+namespace api {
+
+void release_xbatched() {
+  using namespace batchedx;
+  if (g_ws) (void)hipFree(g_ws);
+  g_ws = nullptr;
+  g_ws_slots = 0;
+}
+
+// arguments checked (EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX, batch > 0), g_mu held; dinfo holds `batch` words
+int xbatched_launch(hipStream_t s, int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                    double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
+                    int *dinfo) {
+  using namespace batchedx;
+  const int K = g_chunk;
+  { int rc0 = ensure_images((size_t)std::min(batch, K)); if (rc0) return rc0; }
+  for (int c0 = 0; c0 < batch; c0 += K) {
+    const int count = std::min(K, batch - c0);
+    Args a{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
+           problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
+           jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, dinfo + c0, g_ws};
+    hipLaunchKernelGGL(xbatched_kernel, dim3(count), dim3(T), 0, s, a);
+    EK_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+}  // namespace api
+}  // namespace ek
+
+extern "C" int ek_hip_debug_xbatched_chunk(int problems) {
+  std::lock_guard<std::mutex> lk(ek::api::g_mu);
+  const int before = ek::batchedx::g_chunk;
+  ek::batchedx::g_chunk = problems > 0 ? problems : ek::batchedx::kChunk;
+  return before;
+}

@@ -179,6 +179,11 @@ def load_library(path=None):
         "ek_hip_check_sygv_vbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
         "ek_hip_check_sygvx_device": (c_int, [c_int, c_int, c_int, vp, c_int, vp, c_int, vp, vp, c_int, _dp, _dp]),
         "ek_hip_check_sygvx": (c_int, [c_int, c_int, c_int, _dp, c_int, _dp, c_int, _dp, _dp, c_int, _dp, _dp]),
+        "ek_hip_eigenpairs_xbatched_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp,
+                                                      vp, c_int, c_ll, _ip, _dp]),
+        "ek_hip_eigenpairs_xbatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp,
+                                               _dp, c_int, c_ll, _ip, _dp]),
+        "ek_hip_debug_xbatched_chunk": (c_int, [c_int]),
         "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
         "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
     }
@@ -225,6 +230,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_sygv_batched_device", "ek_hip_sygv_batched", "ek_hip_sygv_vbatched_device", "ek_hip_sygv_vbatched",
     "ek_hip_check_sygv_batched_device", "ek_hip_check_sygv_batched", "ek_hip_check_sygv_vbatched_device",
     "ek_hip_check_sygv_vbatched", "ek_hip_check_sygvx_device", "ek_hip_check_sygvx",
+    "ek_hip_eigenpairs_xbatched_device", "ek_hip_eigenpairs_xbatched", "ek_hip_debug_xbatched_chunk",
 )
 
 
@@ -760,6 +766,22 @@ def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
     are not modified.  seconds: None or a float64 array of one entry that receives the device time.  Raises SolverError
     only when the call itself fails (illegal argument, HIP error), never for a problem's info."""
     return _batched_call("ek_hip_eigenpairs_batched", 0 if B is None else 1, A, B, vectors, seconds)
+
+
+XBATCH_NMAX = 256   # EK_HIP_XBATCH_NMAX
+
+
+def eigenpairs_xbatched(A, B=None, vectors=True, seconds=None):
+    """eigenpairs_batched for orders up to XBATCH_NMAX (ek_hip_eigenpairs_xbatched): the same arguments, returns and
+    errors.  Orders up to BATCH_NMAX give eigenpairs_batched's bits; above it a second kernel class keeps each problem's
+    matrix in a device workspace instead of LDS.  An order beyond XBATCH_NMAX raises SolverError with info -3."""
+    return _batched_call("ek_hip_eigenpairs_xbatched", 0 if B is None else 1, A, B, vectors, seconds)
+
+
+def xbatched_chunk(problems):
+    """Problems per launch of eigenpairs_xbatched above BATCH_NMAX (ek_hip_debug_xbatched_chunk): 0 restores the default.
+    Returns the previous value.  No result depends on it."""
+    return int(load_library().ek_hip_debug_xbatched_chunk(int(problems)))
 
 
 def sygv_batched(A, B, itype=1, vectors=True, seconds=None):

@@ -250,6 +250,42 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                               long long strideZ, int *info, double *seconds);
 
+/* The same call for orders up to EK_HIP_XBATCH_NMAX ("xbatched").  Argument for argument these are
+ * ek_hip_eigenpairs_batched_device / ek_hip_eigenpairs_batched -- 16 arguments, the same argument-error codes decided
+ * before any device work and without dereferencing a pointer, the first offending argument deciding -- with one
+ * difference: -3 is for n < 0 or n > EK_HIP_XBATCH_NMAX.
+ *   0 <= n <= EK_HIP_BATCH_NMAX : forwarded to the code behind ek_hip_eigenpairs_batched*: the same kernel, the same bits
+ *                   in w, Z, info and the in-place images
+ *   EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX : a second kernel class runs the same stages with the same arithmetic
+ *                   rules, again one workgroup per problem from first load to last store and no launch between the
+ *                   stages, but with the n x n working image in a device workspace instead of LDS
+ * The whole contract of ek_hip_eigenpairs_batched* holds at the new orders:
+ *   info[b]       : 0 success, always with finite w; k > 0: the 1-based failing pivot of B (a pivot must lie inside
+ *                   1e-290 < pivot < 1e290; a NaN in B included); -5: NaN / Inf in the lower triangle of A;
+ *                   100000 + k: the QL iteration failed (k = n + 1: the reduction overflowed, or an eigenvalue lies
+ *                   beyond the range of a double).  A failed problem writes nothing outside its own slots (whose w and Z
+ *                   hold unspecified values); the other problems of the batch are unaffected
+ *   scaling       : A is scaled by an exact power of two when max|a| lies outside 2^-256 .. 2^256; the d and e left in
+ *                   dA are those of the caller's A
+ *   device form   : IN PLACE: the lower triangle of each dA holds DSYTD2's lower layout (d, e, the tails of the
+ *                   Householder vectors; tau_k = 2 / (1 + |tail_k|^2)), the lower triangle of each dB holds L.  The
+ *                   strictly upper triangles, the rows n..ld-1 and the gaps between the problems are neither read nor
+ *                   written.  The host form leaves A and B untouched
+ *   same bits     : the same (A, B) gives bit-identical info, w, Z and images alone, at any position of any batch, and
+ *                   in the host and the device form
+ * A batch of an order above EK_HIP_BATCH_NMAX runs in chunks of at most 1024 problems, launched one after the other on
+ * one stream without a host synchronise in between.
+ * Workspace: batch ints, and for orders above EK_HIP_BATCH_NMAX min(batch, 1024) images of 256 x 257 doubles (526 336
+ * bytes each, 539 MB for 1024 problems or more) of device memory, grown on demand and kept until ek_hip_finalize.
+ * Not offered at the new orders: the variable-order form, problem types 2 and 3, the batched checks. */
+#define EK_HIP_XBATCH_NMAX 256
+int ek_hip_eigenpairs_xbatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                      double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                      long long strideZ, int *info, double *seconds);
+int ek_hip_eigenpairs_xbatched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                               long long strideZ, int *info, double *seconds);
+
 /* The same for problems of DIFFERENT orders in one call ("vbatched"): problem b has order n[b], 0 <= n[b] <=
  * EK_HIP_BATCH_NMAX, and its own arrays, named by pointer arrays instead of a base and a stride.
  *   n, lda, ldb, ldz, info and the four pointer arrays dA, dB, dw, dZ are HOST arrays of `batch` entries in both forms;

@@ -125,6 +125,10 @@ int ek_hip_debug_vbatched_streams(int streams);
 /* the last ek_hip_eigenpairs_vbatched* call that was given `seconds`: device time of the launch of the classes of 128,
    64 and 32 (events around each on its stream) and the problems each took; either pointer may be NULL */
 int ek_hip_debug_vbatched_last(double *class_seconds, int *class_count);
+/* ek_hip_eigenpairs_xbatched*, orders above EK_HIP_BATCH_NMAX: problems per launch (a batch runs in chunks of that many,
+   each chunk reusing the same image slots).  0 (or less) restores the default of 1024; returns the previous value.  A
+   tuning and test hook: no result depends on it. */
+int ek_hip_debug_xbatched_chunk(int problems);
 
 /* test aid: the next `times` bulge chasings of whole-path calls count as abandoned (exercises the repetition from the
    saved band and the -992 exit of ek_solve.hip) */

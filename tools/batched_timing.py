@@ -5,6 +5,8 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
   python tools/batched_timing.py [--sizes 30,64,128] [--batches 1,256,4096] [--loop-max 64] [--itype 1]
                                                  --itype 2 / 3: the generalized rows solve A B x = l x / B A x = l x
                                                  through ek_hip_sygv_batched_device (the loop stays type 1's: a yardstick)
+                                                 sizes above 128 (up to 256) time ek_hip_eigenpairs_xbatched_device
+                                                 against the same host loop
   python tools/batched_timing.py --once 64g      one batched call (256 generalized pairs of order 64 with vectors)
                                                  after a warm-up: what a kernel trace should look at
   python tools/batched_timing.py --mixed [--mixed-batch 2048] [--mixed-orders 8,128]
@@ -78,7 +80,10 @@ class Case:
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
         fn, first = self.lib.ek_hip_eigenpairs_batched_device, problem
-        if problem and self.itype != 1:
+        if n > solver.BATCH_NMAX:                   # orders 129 .. 256: the image in device memory (type 1 only)
+            assert self.itype == 1, "orders above %d: problem types 2 and 3 are not offered" % solver.BATCH_NMAX
+            fn = self.lib.ek_hip_eigenpairs_xbatched_device
+        elif problem and self.itype != 1:
             fn, first = self.lib.ek_hip_sygv_batched_device, self.itype
         rc = fn(first, jobz, n, self.batch, self.dA, n, nn, self.dB if problem else None, n, nn, self.dw,
                 self.dZ if jobz else None, n, nn, self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
