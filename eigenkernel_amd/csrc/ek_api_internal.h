@@ -64,6 +64,7 @@ int xbatched_launch(hipStream_t s, int problem, int jobz, int n, int batch, doub
                     double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
                     int *dinfo);
 void release_batched_check();      // the batched checks' scratch, output words, table and events (ek_batched_check.hip)
+void release_batched_check_x();    // the same of ek_hip_check_xbatched* above EK_HIP_BATCH_NMAX (ek_batched_check_x.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);
 
 // device buffers of one host-array call: released on every exit path

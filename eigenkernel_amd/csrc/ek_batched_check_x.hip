@@ -1,0 +1,504 @@
+// ek_batched_check_x.hip -- ek_hip_check_xbatched*: the batched acceptance checks for the orders
+// EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX that ek_hip_eigenpairs_xbatched* solves.  Orders up to
+// EK_HIP_BATCH_NMAX are forwarded to ek_hip_check_batched*, whose translation unit this one leaves as it was.
+//
+// One workgroup of 512 threads (8 waves) owns a problem from its first load to its last store.  At these orders neither Z
+// nor S = B Z nor A Z fits in LDS (512 KB each at n = 256), so the three products run on the fp64 matrix cores
+// (v_mfma_f64_16x16x4_f64) over LDS-staged tiles: an output tile has 128 rows x 64 columns, wave v owns its rows
+// 16 v .. 16 v + 15 as four 16 x 16 accumulator tiles per product, and the inner dimension advances 16 at a time through two
+// LDS buffers (the next step's operands travel global -> registers while this step's are multiplied, then go to the other
+// buffer: one barrier per step).
+//
+//   1  A Z and, for a generalized problem, S = B Z in the same sweep (one staged tile of Z feeds both).  The loader of the
+//      symmetric operands takes entry (i, k) with k > i from (k, i): a 16 x 16 block below the diagonal is read along i,
+//      one above it as the mirrored block along k and transposed on its way into LDS, the diagonal block entry by entry;
+//      nothing strictly above the diagonal and nothing at or beyond row n is read, and the tile is zero past n.  The
+//      squares of the staged entries of A give ||A||_F.  The epilogue works in the accumulators: r_ij = (A Z)_ij - w_j s_ij,
+//      and r^2, z s and z^4 are summed per column -- in the lane over its four rows, in the wave over the four lane >> 4
+//      groups, over the waves in ascending order through LDS, over the row tiles in ascending order.  S goes to a device
+//      scratch of n^2 doubles (a standard problem has S = Z and needs neither the scratch nor the second accumulators)
+//   2  G = Z^T S with the same machinery, both operands from global memory; entry (l, j), l != j, is scaled by
+//      G_ll^-1/2 G_jj^-1/2 from step 1, squared and added to its thread's sum in tile order
+//
+// Same bits wherever a problem sits: every loop bound and every summation order depends on n alone; no atomics; the same
+// kernel behind the host and the device form.  A, B, w and Z are read only.
+#include "ek_batched_check.h"
+
+#include <algorithm>
+
+namespace ek {
+namespace xcheck {
+
+using bcheck::cgdouble;
+using bcheck::gdouble;
+using bcheck::wg_reduce;
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+constexpr int T = 512, NW = T / 64;                 // threads, waves
+constexpr int TM = 128, TN = 64, KT = 16;           // output tile, step of the inner dimension
+constexpr int LDP = TM + 16, LDQ = TN + 16;         // leading dimensions of the staged tiles [k][row], [k][column]: 16 mod 32,
+                                                    // so that the four k of an operand read fall on different banks
+constexpr int kTileP = KT * LDP, kTileQ = KT * LDQ;
+constexpr int kBuf = 2 * kTileP + kTileQ;           // A, B, Z of one step (step 2: Z^T, unused, S)
+constexpr int kChunk = 1024;                        // problems per launch
+static_assert(TM == 16 * NW, "a wave per 16 rows of the tile");
+static_assert(EK_HIP_XBATCH_NMAX % TN == 0 && EK_HIP_XBATCH_NMAX <= T, "a thread per column in the reductions");
+
+// LDS doubles: two buffers, the waves' column sums of r^2, z s and z^4, 1 / sqrt(G_jj), a word per wave
+constexpr int kLdsDoubles = 2 * kBuf + 3 * NW * TN + EK_HIP_XBATCH_NMAX + NW;
+
+struct Args {
+  int problem, n;
+  const double *A; int lda; long long sA;
+  const double *B; int ldb; long long sB;
+  const double *w;
+  const double *Z; int ldz; long long sZ;
+  const int *map;       // the problems to check; nullptr: every problem
+  int first;            // this launch's first entry of the map (or first problem)
+  double *S;            // problem 1: n^2 doubles per workgroup of a launch
+  double *out;          // EK_HIP_CHECK_NOUT doubles per problem
+  double *ipr;          // n doubles per problem, or nullptr
+};
+
+// ---- loaders: global -> registers (tile), registers -> LDS (put).  Thread t of a symmetric tile: half = t / 256 takes the
+// 16 x 16 blocks 2 q + half, q = 0 .. 3, as (a, b) = (t % 16, t / 16 % 16)
+__device__ __forceinline__ void sym_tile(cgdouble *M, int ld, int n, int i0, int k0, double (&v)[4]) {
+  const int t = threadIdx.x, half = t >> 8, a = t & 15, b = (t >> 4) & 15;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int ib = i0 + 16 * (2 * q + half);
+    const bool low = ib >= k0;                      // on or below the diagonal: along i; above it: the mirrored block along k
+    const int i = ib + (low ? a : b), k = k0 + (low ? b : a);
+    // the load is unconditional: past n it takes the last row or column (inside the lower triangle) and is dropped
+    const int ic = min(i, n - 1), kc = min(k, n - 1), hi = max(ic, kc), lo = min(ic, kc);
+    const double x = M[hi + (size_t)lo * ld];
+    v[q] = (i < n && k < n) ? x : 0.0;
+  }
+}
+__device__ __forceinline__ void sym_put(double *s, int i0, int k0, const double (&v)[4]) {
+  const int t = threadIdx.x, half = t >> 8, a = t & 15, b = (t >> 4) & 15;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int blk = 16 * (2 * q + half);
+    s[(i0 + blk >= k0) ? b * LDP + blk + a : a * LDP + blk + b] = v[q];
+  }
+}
+// KT x W tile of a column-major matrix, rows k0 .. (the inner dimension), columns c0 ..: along k
+template <int W>
+__device__ __forceinline__ void col_tile(cgdouble *M, int ld, int n, int k0, int c0, double (&v)[W / 32]) {
+  const int t = threadIdx.x, k = k0 + (t & 15);
+#pragma unroll
+  for (int q = 0; q < W / 32; ++q) {
+    const int c = c0 + (t >> 4) + 32 * q;
+    const double x = M[min(k, n - 1) + (size_t)min(c, n - 1) * ld];   // unconditional, as above
+    v[q] = (k < n && c < n) ? x : 0.0;
+  }
+}
+template <int W, int LD>
+__device__ __forceinline__ void col_put(double *s, const double (&v)[W / 32]) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < W / 32; ++q) s[(t & 15) * LD + (t >> 4) + 32 * q] = v[q];
+}
+
+// one step of 16 of the inner dimension: acc += P^T-tile rows of this wave x Q-tile
+template <bool TWO>
+__device__ __forceinline__ void step_mfma(const double *sp, const double *sp2, const double *sq, double4_t (&acc)[4],
+                                          double4_t (&acc2)[4]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
+#pragma unroll
+  for (int kk = 0; kk < KT; kk += 4) {
+    const double x = sp[(kk + l4) * LDP + 16 * wave + l15];
+    const double x2 = TWO ? sp2[(kk + l4) * LDP + 16 * wave + l15] : 0.0;
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt) {
+      const double y = sq[(kk + l4) * LDQ + 16 * jt + l15];
+      acc[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, acc[jt], 0, 0, 0);
+      if (TWO) acc2[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y, acc2[jt], 0, 0, 0);
+    }
+  }
+}
+
+// x - w s with the product rounded on its own, whatever the compiler contracts elsewhere: (A Z)_ij and w_j s_ij that agree
+// as doubles give a residual of exactly zero
+__device__ __forceinline__ double minus_product(double x, double w, double s) {
+#pragma clang fp contract(off)
+  const double p = w * s;
+  return x - p;
+}
+
+template <bool GEN>
+__global__ __launch_bounds__(T) void xcheck_kernel(Args a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double *buf = smem;                               // [2][kBuf]
+  double *cs = buf + 2 * kBuf;                      // [3][NW][TN]: the waves' column sums
+  double *sg = cs + 3 * NW * TN;                    // 1 / sqrt(G_jj)
+  double *red = sg + EK_HIP_XBATCH_NMAX;            // a word per wave
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, l4 = lane >> 4;
+  const int n = a.n;
+  const long long pb = a.map ? a.map[a.first + (int)blockIdx.x] : a.first + (int)blockIdx.x;
+  cgdouble *A = (cgdouble *)(a.A + pb * a.sA);
+  cgdouble *B = GEN ? (cgdouble *)(a.B + pb * a.sB) : nullptr;
+  cgdouble *w = (cgdouble *)(a.w + pb * n);
+  cgdouble *Z = (cgdouble *)(a.Z + pb * a.sZ);
+  gdouble *S = GEN ? (gdouble *)(a.S + (long long)blockIdx.x * n * n) : nullptr;
+  gdouble *out = (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT);
+  gdouble *ipr = a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr;
+  const int lda = a.lda, ldb = a.ldb, ldz = a.ldz;
+  const int nk = (n + KT - 1) / KT;
+
+  // ---- 1: A Z, S = B Z, per column ||r_j||^2, G_jj, sum z^4; ||A||_F^2
+  double asq = 0.0, rsum = 0.0, rmax = 0.0;
+#pragma unroll 1
+  for (int j0 = 0; j0 < n; j0 += TN) {
+    double wj[4];
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt) {
+      const int j = j0 + 16 * jt + l15;
+      wj[jt] = (j < n) ? w[j] : 0.0;
+    }
+    double tr = 0.0, tg = 0.0, tp = 0.0;            // thread c < TN: column j0 + c, over the row tiles
+#pragma unroll 1
+    for (int i0 = 0; i0 < n; i0 += TM) {
+      double4_t accA[4], accB[4];
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) accA[jt] = accB[jt] = (double4_t){0.0, 0.0, 0.0, 0.0};
+      double va[4], vb[4], vz[2];
+      auto fetch = [&](int k0) {
+        sym_tile(A, lda, n, i0, k0, va);
+        if (GEN) sym_tile(B, ldb, n, i0, k0, vb);
+        col_tile<TN>(Z, ldz, n, k0, j0, vz);
+      };
+      auto put = [&](int k0, double *s) {
+        sym_put(s, i0, k0, va);
+        if (GEN) sym_put(s + kTileP, i0, k0, vb);
+        col_put<TN, LDQ>(s + 2 * kTileP, vz);
+        if (j0 == 0) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) asq = fma(va[q], va[q], asq);
+        }
+      };
+      fetch(0);
+      put(0, buf);
+      __syncthreads();
+#pragma unroll 1
+      for (int s = 0; s < nk; ++s) {
+        const double *cur = buf + (s & 1) * kBuf;
+        const bool more = s + 1 < nk;
+        if (more) fetch((s + 1) * KT);
+        step_mfma<GEN>(cur, cur + kTileP, cur + 2 * kTileP, accA, accB);
+        if (more) put((s + 1) * KT, buf + ((s + 1) & 1) * kBuf);
+        __syncthreads();
+      }
+      // the epilogue, in the accumulators: acc[jt][r] is entry (i0 + 16 wave + l4 + 4 r, j0 + 16 jt + l15)
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) {
+        const int j = j0 + 16 * jt + l15;
+        double cr = 0.0, cg = 0.0, cp = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = i0 + 16 * wave + l4 + 4 * r;
+          if (i < n && j < n) {
+            const double z = Z[i + (size_t)j * ldz];
+            const double sv = GEN ? accB[jt][r] : z;
+            const double rr = minus_product(accA[jt][r], wj[jt], sv);
+            const double z2 = z * z;
+            cr = fma(rr, rr, cr);
+            cg = fma(z, sv, cg);
+            cp = fma(z2, z2, cp);
+            if (GEN) S[i + (size_t)j * n] = sv;
+          }
+        }
+        cr += __shfl_xor(cr, 16, 64); cr += __shfl_xor(cr, 32, 64);
+        cg += __shfl_xor(cg, 16, 64); cg += __shfl_xor(cg, 32, 64);
+        cp += __shfl_xor(cp, 16, 64); cp += __shfl_xor(cp, 32, 64);
+        if (l4 == 0) {
+          cs[(0 * NW + wave) * TN + 16 * jt + l15] = cr;
+          cs[(1 * NW + wave) * TN + 16 * jt + l15] = cg;
+          cs[(2 * NW + wave) * TN + 16 * jt + l15] = cp;
+        }
+      }
+      __syncthreads();
+      if (t < TN) {                                 // the next write of cs lies behind the next tile's barriers
+        double xr = cs[t], xg = cs[NW * TN + t], xp = cs[2 * NW * TN + t];
+#pragma unroll
+        for (int v = 1; v < NW; ++v) {
+          xr += cs[(0 * NW + v) * TN + t];
+          xg += cs[(1 * NW + v) * TN + t];
+          xp += cs[(2 * NW + v) * TN + t];
+        }
+        tr += xr; tg += xg; tp += xp;
+      }
+    }
+    if (t < TN && j0 + t < n) {
+      const double rn = sqrt(tr);
+      sg[j0 + t] = 1.0 / sqrt(tg);
+      if (ipr) ipr[j0 + t] = tp / (tg * tg);
+      rsum += rn;
+      rmax = (rn > rmax || rn != rn) ? rn : rmax;
+    }
+  }
+  rsum = wg_reduce<NW, false>(rsum, red);
+  rmax = wg_reduce<NW, true>(rmax, red);
+  const double anorm = sqrt(wg_reduce<NW, false>(asq, red));
+  __syncthreads();                                  // sg is written, S is in the scratch for the whole workgroup
+
+  // ---- 2: || D^-1/2 G D^-1/2 - its diagonal ||_F, G = Z^T S
+  cgdouble *Q = GEN ? (cgdouble *)S : Z;
+  const int ldq = GEN ? n : ldz;
+  double os = 0.0;
+#pragma unroll 1
+  for (int j0 = 0; j0 < n; j0 += TN)
+#pragma unroll 1
+    for (int l0 = 0; l0 < n; l0 += TM) {
+      double4_t acc[4];
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) acc[jt] = (double4_t){0.0, 0.0, 0.0, 0.0};
+      double vp[4], vq[2];
+      col_tile<TM>(Z, ldz, n, 0, l0, vp);
+      col_tile<TN>(Q, ldq, n, 0, j0, vq);
+      col_put<TM, LDP>(buf, vp);
+      col_put<TN, LDQ>(buf + 2 * kTileP, vq);
+      __syncthreads();
+#pragma unroll 1
+      for (int s = 0; s < nk; ++s) {
+        const double *cur = buf + (s & 1) * kBuf;
+        double *nxt = buf + ((s + 1) & 1) * kBuf;
+        const bool more = s + 1 < nk;
+        if (more) {
+          col_tile<TM>(Z, ldz, n, (s + 1) * KT, l0, vp);
+          col_tile<TN>(Q, ldq, n, (s + 1) * KT, j0, vq);
+        }
+        step_mfma<false>(cur, cur, cur + 2 * kTileP, acc, acc);
+        if (more) {
+          col_put<TM, LDP>(nxt, vp);
+          col_put<TN, LDQ>(nxt + 2 * kTileP, vq);
+        }
+        __syncthreads();
+      }
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) {
+        const int j = j0 + 16 * jt + l15;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int l = l0 + 16 * wave + l4 + 4 * r;
+          if (l < n && j < n && l != j) {
+            const double g = acc[jt][r] * sg[l] * sg[j];
+            os = fma(g, g, os);
+          }
+        }
+      }
+    }
+  const double osum = wg_reduce<NW, false>(os, red);
+  if (t == 0) {
+    out[0] = anorm;
+    out[1] = rsum / anorm / (double)n;
+    out[2] = rmax / anorm;
+    out[3] = sqrt(osum);
+  }
+}
+
+// Device memory the entries keep (grown, never shrunk, released in ek_hip_finalize): the scratch S of a launch, the output
+// words (out, then the IPRs), the map of the problems to check; two events for `seconds`
+static double *g_scratch = nullptr, *g_dout = nullptr;
+static int *g_dmap = nullptr;
+static size_t g_scratch_count = 0, g_dout_count = 0, g_dmap_count = 0;
+static hipEvent_t g_ev[2] = {nullptr, nullptr};
+static std::vector<int> g_hmap;                     // host images: an upload may still read them when an error returns
+static std::vector<double> g_hout;
+static int g_chunk = kChunk;
+static bool g_raised[2] = {false, false};
+
+template <typename P>
+static int grow(P **p, size_t *have, size_t want) {
+  if (want <= *have) return 0;
+  if (*p) (void)hipFree((void *)*p);
+  *p = nullptr;
+  *have = 0;
+  EK_HIP_CHECK(hipMalloc((void **)p, want * sizeof(P)));
+  *have = want;
+  return 0;
+}
+
+template <bool GEN>
+static int launch(hipStream_t s, int count, const Args &a) {
+  constexpr size_t lds = (size_t)kLdsDoubles * sizeof(double);
+  if (!g_raised[GEN]) {
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)xcheck_kernel<GEN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds));
+    g_raised[GEN] = true;
+  }
+  hipLaunchKernelGGL((xcheck_kernel<GEN>), dim3(count), dim3(T), lds, s, a);
+  EK_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace xcheck
+
+namespace api {
+void release_batched_check_x() {
+  using namespace xcheck;
+  if (g_scratch) (void)hipFree(g_scratch);
+  if (g_dout) (void)hipFree(g_dout);
+  if (g_dmap) (void)hipFree(g_dmap);
+  g_scratch = g_dout = nullptr;
+  g_dmap = nullptr;
+  g_scratch_count = g_dout_count = g_dmap_count = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (g_ev[k]) (void)hipEventDestroy(g_ev[k]);
+    g_ev[k] = nullptr;
+  }
+  std::vector<int>().swap(g_hmap);
+  std::vector<double>().swap(g_hout);
+}
+}  // namespace api
+}  // namespace ek
+
+using namespace ek;
+using namespace ek::api;
+
+// the argument errors of ek_hip_check_batched* with EK_HIP_XBATCH_NMAX in the place of EK_HIP_BATCH_NMAX
+static int xcheck_arguments(int problem, int n, int batch, const void *A, int lda, long long strideA, const void *B,
+                            int ldb, long long strideB, const void *w, const void *Z, int ldz, long long strideZ,
+                            const double *out, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (n < 0 || n > EK_HIP_XBATCH_NMAX) return -2;
+  if (batch < 0) return -3;
+  if (n == 0 || batch == 0) { *nothing = true; return 0; }
+  if (!A) return -4;
+  if (lda < n) return -5;
+  if (strideA < (long long)lda * n) return -6;
+  if (problem == 1) {
+    if (!B) return -7;
+    if (ldb < n) return -8;
+    if (strideB < (long long)ldb * n) return -9;
+  }
+  if (!w) return -10;
+  if (!Z) return -11;
+  if (ldz < n) return -12;
+  if (strideZ < (long long)ldz * n) return -13;
+  if (!out) return -15;                             // 14 is info: NULL means every problem
+  return 0;
+}
+
+// arguments checked (EK_HIP_BATCH_NMAX < n, batch > 0), context up, g_mu held; dA, dB, dw, dZ device, info / out / ipr host
+static int xcheck_device_locked(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                const double *dB, int ldb, long long strideB, const double *dw, const double *dZ, int ldz,
+                                long long strideZ, const int *info, double *out, double *ipr, double *seconds) {
+  using namespace xcheck;
+  static const double kNaN = std::nan("");
+  g_hmap.clear();
+  bool skip = false;
+  if (info)
+    for (int b = 0; b < batch; ++b) {
+      if (info[b] == 0) g_hmap.push_back(b); else skip = true;
+    }
+  const int count = skip ? (int)g_hmap.size() : batch;
+  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (ipr ? (size_t)batch * n : 0);
+  if (count > 0) {
+    const int K = g_chunk;
+    { int rc = grow(&g_scratch, &g_scratch_count, problem ? (size_t)std::min(count, K) * n * n : 0); if (rc) return rc; }
+    { int rc = grow(&g_dout, &g_dout_count, words); if (rc) return rc; }
+    { int rc = grow(&g_dmap, &g_dmap_count, skip ? g_hmap.size() : 0); if (rc) return rc; }
+    for (int k = 0; k < 2; ++k)
+      if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
+    hipStream_t s = g_ctx.stream;
+    if (seconds) (void)hipEventRecord(g_ev[0], s);
+    int rc = [&]() -> int {
+      if (skip) EK_HIP_CHECK(hipMemcpyAsync(g_dmap, g_hmap.data(), g_hmap.size() * sizeof(int), hipMemcpyHostToDevice, s));
+      for (int c0 = 0; c0 < count; c0 += K) {       // one after the other on the stream: they share the scratch
+        Args a{problem, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, skip ? g_dmap : nullptr, c0,
+               g_scratch, g_dout, ipr ? g_dout + nout : nullptr};
+        const int rcl = problem ? launch<true>(s, std::min(K, count - c0), a) : launch<false>(s, std::min(K, count - c0), a);
+        if (rcl) return rcl;
+      }
+      return 0;
+    }();
+    if (seconds) (void)hipEventRecord(g_ev[1], s);
+    g_hout.resize(words);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(g_hout.data(), g_dout, words * sizeof(double), hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess && !rc) rc = -1000 - (int)e;
+    if (rc) return rc;
+    if (seconds) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess) *seconds = (double)ms * 1e-3;
+    }
+  }
+  for (int b = 0; b < batch; ++b) {                 // the scatter: a skipped problem gets NaN and keeps its ipr
+    double *o = out + (size_t)b * EK_HIP_CHECK_NOUT;
+    if (info && info[b] != 0) {
+      o[0] = o[1] = o[2] = o[3] = kNaN;
+    } else {
+      std::memcpy(o, g_hout.data() + (size_t)b * EK_HIP_CHECK_NOUT, EK_HIP_CHECK_NOUT * sizeof(double));
+      if (ipr) std::memcpy(ipr + (size_t)b * n, g_hout.data() + nout + (size_t)b * n, (size_t)n * sizeof(double));
+    }
+  }
+  return 0;
+}
+
+extern "C" {
+
+int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                 const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                 int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                 double *seconds) {
+  bool nothing;
+  int rc = xcheck_arguments(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, out, &nothing);
+  if (rc) return rc;
+  if (n <= EK_HIP_BATCH_NMAX)                       // n = 0 included: the same answers, the same kernel, the same bits
+    return ek_hip_check_batched_device(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                                       out, ipr, seconds);
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return xcheck_device_locked(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out, ipr,
+                              seconds);
+}
+
+int ek_hip_check_xbatched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                          int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                          const int *info, double *out, double *ipr, double *seconds) {
+  bool nothing;
+  int rc = xcheck_arguments(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, out, &nothing);
+  if (rc) return rc;
+  if (n <= EK_HIP_BATCH_NMAX)
+    return ek_hip_check_batched(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
+                                seconds);
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  // device copies with the caller's own layout, as in ek_hip_check_batched
+  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
+  const size_t cA = span(lda, strideA), cB = problem ? span(ldb, strideB) : 0, cZ = span(ldz, strideZ);
+  const size_t cw = (size_t)batch * n;
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cA * 8);
+  if (!rc) rc = mem.alloc(&uw, cw * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
+  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
+  return xcheck_device_locked(problem, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info, out, ipr,
+                              seconds);
+}
+
+int ek_hip_debug_check_xbatched_chunk(int problems) {
+  std::lock_guard<std::mutex> lk(ek::api::g_mu);
+  const int before = ek::xcheck::g_chunk;
+  ek::xcheck::g_chunk = problems > 0 ? problems : ek::xcheck::kChunk;
+  return before;
+}
+
+}  // extern "C"

@@ -184,6 +184,11 @@ def load_library(path=None):
         "ek_hip_eigenpairs_xbatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp,
                                                _dp, c_int, c_ll, _ip, _dp]),
         "ek_hip_debug_xbatched_chunk": (c_int, [c_int]),
+        "ek_hip_check_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
+                                                 c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
+                                          _ip, _dp, _dp, _dp]),
+        "ek_hip_debug_check_xbatched_chunk": (c_int, [c_int]),
         "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
         "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
     }
@@ -231,6 +236,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_sygv_batched_device", "ek_hip_check_sygv_batched", "ek_hip_check_sygv_vbatched_device",
     "ek_hip_check_sygv_vbatched", "ek_hip_check_sygvx_device", "ek_hip_check_sygvx",
     "ek_hip_eigenpairs_xbatched_device", "ek_hip_eigenpairs_xbatched", "ek_hip_debug_xbatched_chunk",
+    "ek_hip_check_xbatched_device", "ek_hip_check_xbatched", "ek_hip_debug_check_xbatched_chunk",
 )
 
 
@@ -913,6 +919,19 @@ def check_batched(A, B, w, Z, info=None, ipr=True, seconds=None):
     that receives the device time.  Raises ValueError for bad shapes before the library is called, SolverError only
     when the call itself fails."""
     return _check_batched_call("ek_hip_check_batched", 0 if B is None else 1, A, B, w, Z, info, ipr, seconds)
+
+
+def check_xbatched(A, B, w, Z, info=None, ipr=True, seconds=None):
+    """check_batched for orders up to XBATCH_NMAX (ek_hip_check_xbatched), behind eigenpairs_xbatched: the same arguments
+    and returns.  Orders up to BATCH_NMAX run the kernel of check_batched (the same bits); above it a kernel class of its
+    own forms A Z, B Z and Z^T B Z on the matrix cores.  An order beyond XBATCH_NMAX raises SolverError with info -2."""
+    return _check_batched_call("ek_hip_check_xbatched", 0 if B is None else 1, A, B, w, Z, info, ipr, seconds)
+
+
+def check_xbatched_chunk(problems):
+    """Checked problems per launch of check_xbatched above BATCH_NMAX (ek_hip_debug_check_xbatched_chunk): 0 restores the
+    default.  Returns the previous value.  No result depends on it."""
+    return int(load_library().ek_hip_debug_check_xbatched_chunk(int(problems)))
 
 
 def check_sygv_batched(A, B, w, Z, itype=1, info=None, ipr=True, seconds=None):

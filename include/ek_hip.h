@@ -277,7 +277,8 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
  * one stream without a host synchronise in between.
  * Workspace: batch ints, and for orders above EK_HIP_BATCH_NMAX min(batch, 1024) images of 256 x 257 doubles (526 336
  * bytes each, 539 MB for 1024 problems or more) of device memory, grown on demand and kept until ek_hip_finalize.
- * Not offered at the new orders: the variable-order form, problem types 2 and 3, the batched checks. */
+ * Not offered at the new orders: the variable-order form, problem types 2 and 3.  Their acceptance check is
+ * ek_hip_check_xbatched* below. */
 #define EK_HIP_XBATCH_NMAX 256
 int ek_hip_eigenpairs_xbatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                       double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
@@ -410,6 +411,36 @@ int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA,
 int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                          int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                          const int *info, double *out, double *ipr, double *seconds);
+/* The same checks for orders up to EK_HIP_XBATCH_NMAX, behind ek_hip_eigenpairs_xbatched*.  Argument for argument these are
+ * ek_hip_check_batched_device / ek_hip_check_batched -- 17 arguments, the same argument-error codes decided before any device
+ * work and without dereferencing a data pointer, the first offending argument deciding -- with one difference: -2 is for
+ * n < 0 or n > EK_HIP_XBATCH_NMAX.
+ *   0 <= n <= EK_HIP_BATCH_NMAX : forwarded to the code behind ek_hip_check_batched*: the same kernel, the same bits in out
+ *                   and ipr
+ *   EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX : a kernel class of its own, again one workgroup per problem from first load
+ *                   to last store: A Z, S = B Z and G = Z^T S on the fp64 matrix cores over LDS-staged tiles, Z and S in
+ *                   device memory instead of LDS
+ * The whole contract above holds at the new orders: the same quantities in the same slots, A and B symmetric by their
+ * lower triangles (strictly upper triangles, rows n..ld-1 and the gaps between problems are never read), info = NULL checks
+ * every problem and a problem with info[b] != 0 gets NaN in its four slots, keeps its ipr slots and has its w and Z left
+ * unread, ipr = NULL is legal, out = NULL is -15, n = 0 or batch = 0 returns 0 with nothing referenced or written, plain
+ * IEEE divisions, a maximum that keeps a NaN.  THE SAME BITS WHEREVER A PROBLEM SITS: a problem's outputs depend on
+ * (n, A, B, w, Z) alone -- alone, at any position of any batch, in any chunk, in the host and the device form.  A, B, w and
+ * Z are const and come back bit for bit.  NOT COLLECTIVE; the calls synchronise.
+ * A batch of an order above EK_HIP_BATCH_NMAX runs in chunks of at most 1024 checked problems, launched one after the other
+ * on one stream without a host synchronise in between.
+ * Workspace above EK_HIP_BATCH_NMAX (device memory, grown on demand, kept until ek_hip_finalize): n^2 doubles for each of the
+ * min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z; at most 512 MiB; none for problem 0),
+ * 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
+ * Not offered at these orders: the variable-order form and the checks of types 2 and 3. */
+int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                 const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                 int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                 double *seconds);
+/* host arrays A, B, w, Z with the same layout (the call works on device copies; the caller's arrays are untouched) */
+int ek_hip_check_xbatched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                          int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                          const int *info, double *out, double *ipr, double *seconds);
 /* The same for problems of DIFFERENT orders, with the conventions of ek_hip_eigenpairs_vbatched*: n, lda, ldb, ldz, info,
  * out and the pointer arrays dA, dB, dw, dZ, ipr are HOST arrays of `batch` entries; the pointers IN dA, dB, dw, dZ are
  * device addresses (device form) or host addresses (host form), those in ipr always host addresses.

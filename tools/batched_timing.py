@@ -16,7 +16,8 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  with every problem padded to order 128
   python tools/batched_timing.py --check [--sizes 64,128] [--batches 1024,4096]
                                                  with vectors only: after each timed solve, the batched check
-                                                 (ek_hip_check_batched_device) on its w and Z -- the check's device time
+                                                 (ek_hip_check_batched_device; ek_hip_check_xbatched_device for sizes
+                                                 above 128) on its w and Z -- the check's device time
                                                  beside the solve's, the worst res_max and orthogonality of the batch
   python tools/batched_timing.py --once 64g --once-batch 1024 --check
                                                  one solve and one check after a warm-up of each
@@ -104,10 +105,12 @@ class Case:
         dp = ctypes.POINTER(ctypes.c_double)
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
-        rc = self.lib.ek_hip_check_batched_device(problem, n, self.batch, self.dA0, n, nn,
-                                                  self.dB0 if problem else None, n, nn, self.dw, self.dZ, n, nn,
-                                                  self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                  out.ctypes.data_as(dp), ipr.ctypes.data_as(dp), ctypes.byref(sec))
+        fn = self.lib.ek_hip_check_batched_device
+        if n > solver.BATCH_NMAX:                   # orders 129 .. 256: the check of the xbatched solver
+            fn = self.lib.ek_hip_check_xbatched_device
+        rc = fn(problem, n, self.batch, self.dA0, n, nn, self.dB0 if problem else None, n, nn, self.dw, self.dZ, n, nn,
+                self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), out.ctypes.data_as(dp), ipr.ctypes.data_as(dp),
+                ctypes.byref(sec))
         t = time.perf_counter() - t0
         assert rc == 0, rc
         return t, sec.value, out
