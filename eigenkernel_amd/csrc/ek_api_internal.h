@@ -60,9 +60,10 @@ void release_pipe_streams();       // the staging pipeline's copy streams (ek_so
 void release_batched();            // the batched entries' per-problem status words (ek_batched.hip)
 void release_xbatched();           // the images of ek_hip_eigenpairs_xbatched* (ek_batched_x.hip)
 // orders above EK_HIP_BATCH_NMAX: the chunks' launches on s, status words to dinfo (device); g_mu held
-int xbatched_launch(hipStream_t s, int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
-                    double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
-                    int *dinfo);
+// (itype as DSYGV's, looked at when problem == 1)
+int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
+                    long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                    long long strideZ, int *dinfo);
 void release_batched_check();      // the batched checks' scratch, output words, table and events (ek_batched_check.hip)
 void release_batched_check_x();    // the same of ek_hip_check_xbatched* above EK_HIP_BATCH_NMAX (ek_batched_check_x.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);

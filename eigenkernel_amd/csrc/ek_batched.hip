@@ -763,7 +763,7 @@ static int batched_device_locked(int problem, int itype, int jobz, int n, int ba
   }
   int rc;
   if (n > EK_HIP_BATCH_NMAX) {                      // ek_hip_eigenpairs_xbatched*: the image in device memory
-    rc = xbatched_launch(s, problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
+    rc = xbatched_launch(s, problem, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
                          batched::g_dinfo);
   } else switch (batched::class_of(n)) {
     case 32: rc = batched::launch_class<32, 64>(s, batch, a); break;
@@ -1107,6 +1107,23 @@ int ek_hip_sygv_batched(int itype, int jobz, int n, int batch, const double *A, 
   if (itype < 1 || itype > 3) return -1;
   return batched_host_entry(1, itype, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
                             seconds);
+}
+
+// The same for orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's kernel, CONG for types 2 and 3
+int ek_hip_sygv_xbatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return batched_device_entry(1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                              seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_sygv_xbatched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                         const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                         long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return batched_host_entry(1, itype, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
+                            seconds, EK_HIP_XBATCH_NMAX);
 }
 
 int ek_hip_sygv_vbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,

@@ -4,7 +4,8 @@
 // last store and no launch between the stages -- but the n x n image lies in a device workspace (column-major, leading
 // dimension 257, one slot per workgroup of a launch) and not in LDS: 256 x 257 doubles are 514 KiB.  The vectors stay in
 // LDS (d, e, tau, v, w, the partial sums, the two staged columns: 9 x 256 doubles).  One class: NC = 256, 512 threads,
-// thread t is (row or column t % 256, half t / 256).  Problem 0 and problem 1 (A x = l B x) only.
+// thread t is (row or column t % 256, half t / 256).  Problem 0 and problem 1; problem 1 in DSYGV's three
+// types: A x = l B x (itype 1), A B x = l x (2), B A x = l x (3).
 //
 // Every n^3 loop over the image runs with the lanes of a wave along consecutive rows (consecutive addresses):
 //   1  right-looking Cholesky: lane = row; the scaled column of a step is kept in LDS for the update
@@ -22,6 +23,16 @@
 //      and the last pass stores Z^T's rows as Z's columns
 // Five n^2 passes do have the lanes 257 doubles apart on one side (a cache line per lane): the mirror fill of A's image,
 // the copy of X's lower half, the mirror of C, the transpose of Z, and the reads of the last pass.
+// Types 2 and 3 have an instantiation of their own (CONG), so that the kernel of the standard problem and of type 1 is the
+// code it always was.  Its stages 2 and 5, lane = row in every n^3 loop again:
+//   2  C = L^T A L in two passes of one form: Y = A L in place (the pair t owns row t of the full symmetric image;
+//      S[t, j] <- sum over k >= j of S[t, k] L[k, j] for ascending j reads columns >= j of its own row, which still hold
+//      A), the image transposed in place (a sixth n^2 pass; A is symmetric: Y^T = L^T A), then C = Y^T L by the same pass
+//      on the columns 0 .. t of row t, and type 1's mirror.  The two threads of a pair take every other term of a sum;
+//      the sum is half 0's part plus half 1's
+//   5  type 3: Z <- L Z on the transposed image, column-oriented: for k = n-1 .. 0, z[i] += L[i, k] z[k] for i > k, then
+//      z[k] *= L[k, k]; the two threads of a pair take every other entry i.  z[k] is untouched until its own step: both
+//      halves load it a step ahead and only the half 0 stores it.  Types 1 and 2 keep Z <- L^-T Z
 // Loads from the image are issued eight at a time before the first use: a dependent round trip to L2 / Infinity Cache /
 // HBM is paid once per eight entries.  All traffic to the image between threads is ordered by __syncthreads(); plain
 // loads and stores, no atomics.  The order of every sum depends on n alone: same bits wherever a problem sits.
@@ -51,7 +62,8 @@ struct Args {
   double *Z; int ldz; long long sZ;
   int *info;
   double *ws;
-};
+  int itype;                                        // 1 / 2 / 3 as DSYGV's, looked at when problem == 1; last, so that
+};                                                  // the fields before it keep their offsets
 
 // ek_batched.hip's block_reduce: a sum (or maximum) over the workgroup, the same bits in every thread
 template <bool MAX>
@@ -104,6 +116,34 @@ __device__ __forceinline__ double img_dot(const gdouble *x, const double *l, int
   return acc;
 }
 
+// One pass of the congruence C = L^T A L (CONG, types 2 and 3): S[r, j] <- sum over k >= j of S[r, k] L[k, j] for
+// j = 0 .. n-1 ascending (LOWER: j = 0 .. r), in place: a step reads the columns >= j of its own row and nothing reads
+// column j afterwards.  Column j of L comes from B through the two sl vectors, staged a step ahead.  The two threads of a
+// pair take every other term, each in ascending order; the sum is half 0's part plus half 1's.  The parts of an even step
+// lie in e0 / e1 (half 0's, half 1's), those of an odd step in o0 / o1, so that a step costs one barrier.  Ends behind a
+// barrier.
+template <bool LOWER>
+__device__ __forceinline__ void cong_pass(gdouble *S, const gdouble *B, int ldb, int n, int t, int r, int sub, bool row,
+                                          double *sl, double *e0, double *e1, double *o0, double *o1) {
+  if (t < n) sl[t] = B[t];                          // column 0 of L
+  __syncthreads();
+  const int last = LOWER ? r : n - 1;
+  for (int j = 0; j < n; ++j) {
+    const double *cur = sl + (j & 1) * NC;
+    double *p0 = (j & 1) ? o0 : e0, *p1 = (j & 1) ? o1 : e1;
+    double nx = 0.0;
+    if (j + 1 < n && t > j && t < n) nx = B[t + (size_t)(j + 1) * ldb];
+    if (row && j <= last) (sub ? p1 : p0)[r] = img_dot<LD, P>(S + r, cur, j + sub, n, 0.0);
+    if (t < n) sl[((j + 1) & 1) * NC + t] = nx;
+    __syncthreads();
+    if (sub == 0 && row && j <= last) S[r + j * LD] = p0[r] + p1[r];
+  }
+  __syncthreads();
+}
+
+// CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
+// CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
+template <bool CONG>
 __global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
   __shared__ double sd[NC], se[NC], st[NC];         // d, e, tau: alive from stage 3 to the end
   __shared__ double sv[NC], sw[NC];                 // stage 1: the scaled column; 3: v, w; 4: c, s of a sweep
@@ -168,14 +208,30 @@ __global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
     __syncthreads();
   }
 
-  // ---- 2: A -> full symmetric image; C = L^-1 A L^-T
+  // ---- 2: A -> full symmetric image; C = L^-1 A L^-T (CONG: C = L^T A L)
   if (row)
     for (int j = sub; j <= r; j += P) {
       const double x = ldexp(A[r + (size_t)j * lda], -aex);
       S[r + j * LD] = x;
       S[j + r * LD] = x;
     }
-  if (a.problem) {
+  if (CONG) {
+    __syncthreads();
+    // Y = A L: the pair r owns row r of the full image
+    cong_pass<false>(S, B, ldb, n, t, r, sub, row, sl, sp, sp + NC, sv, sw);
+    // Y^T = L^T A (A is symmetric): the image transposed in place
+    if (row)
+      for (int j = sub; j < r; j += P) {
+        const double lo = S[r + j * LD], up = S[j + r * LD];
+        S[r + j * LD] = up;
+        S[j + r * LD] = lo;
+      }
+    __syncthreads();
+    // C = Y^T L, lower half: the pair r owns row r, columns 0 .. r
+    cong_pass<true>(S, B, ldb, n, t, r, sub, row, sl, sp, sp + NC, sv, sw);
+    if (row)
+      for (int j = sub; j < r; j += P) S[j + r * LD] = S[r + j * LD];
+  } else if (a.problem) {
     if (t < n) sl[t] = B[t];                        // column 0 of L
     __syncthreads();
     // X = L^-1 A, transposed: the pair r owns column r of X = row r of the image
@@ -499,8 +555,28 @@ __global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
       __syncthreads();
     }
   }
-  // Z <- L^-T Z
-  if (a.problem) {
+  if (CONG && a.itype == 3) {
+    // Z <- L Z, a column of L per step from the last: entry i > k sees the steps k = i-1 .. 0 in that order whichever
+    // thread applies them; z[k] is as stage 4 and the reflectors left it until step k, loaded by both halves a step ahead
+    __syncthreads();
+    if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
+    double pv = row ? S[r + (n - 1) * LD] : 0.0;
+    __syncthreads();
+    for (int k = n - 1, s = 0; k >= 0; --k, ++s) {
+      const double *cur = sl + (s & 1) * NC;
+      double nx = 0.0;
+      if (k >= 1 && t >= k - 1 && t < n) nx = B[t + (size_t)(k - 1) * ldb];
+      if (row) {
+        double nv = 0.0;
+        if (k >= 1) nv = S[r + (k - 1) * LD];       // no step before its own writes it
+        if (sub == 0) S[r + k * LD] = pv * cur[k];
+        img_axpy<LD, P>(S + r, cur, -pv, k + 1 + sub, n);
+        pv = nv;
+      }
+      if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+      __syncthreads();
+    }
+  } else if (a.problem) {                           // Z <- L^-T Z
     __syncthreads();
     if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
     __syncthreads();
@@ -564,9 +640,9 @@ void release_xbatched() {
 }
 
 // arguments checked (EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX, batch > 0), g_mu held; dinfo holds `batch` words
-int xbatched_launch(hipStream_t s, int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
-                    double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
-                    int *dinfo) {
+int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
+                    long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                    long long strideZ, int *dinfo) {
   using namespace batchedx;
   const int K = g_chunk;
   { int rc0 = ensure_images((size_t)std::min(batch, K)); if (rc0) return rc0; }
@@ -574,8 +650,9 @@ int xbatched_launch(hipStream_t s, int problem, int jobz, int n, int batch, doub
     const int count = std::min(K, batch - c0);
     Args a{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
            problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
-           jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, dinfo + c0, g_ws};
-    hipLaunchKernelGGL(xbatched_kernel, dim3(count), dim3(T), 0, s, a);
+           jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, dinfo + c0, g_ws, itype};
+    if (problem && itype != 1) hipLaunchKernelGGL(xbatched_kernel<true>, dim3(count), dim3(T), 0, s, a);
+    else hipLaunchKernelGGL(xbatched_kernel<false>, dim3(count), dim3(T), 0, s, a);
     EK_HIP_CHECK(hipGetLastError());
   }
   return 0;

@@ -183,6 +183,10 @@ def load_library(path=None):
                                                       vp, c_int, c_ll, _ip, _dp]),
         "ek_hip_eigenpairs_xbatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp,
                                                _dp, c_int, c_ll, _ip, _dp]),
+        "ek_hip_sygv_xbatched_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp,
+                                                c_int, c_ll, _ip, _dp]),
+        "ek_hip_sygv_xbatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
+                                         c_ll, _ip, _dp]),
         "ek_hip_debug_xbatched_chunk": (c_int, [c_int]),
         "ek_hip_check_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
                                                  c_ll, _ip, _dp, _dp, _dp]),
@@ -237,6 +241,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_sygv_vbatched", "ek_hip_check_sygvx_device", "ek_hip_check_sygvx",
     "ek_hip_eigenpairs_xbatched_device", "ek_hip_eigenpairs_xbatched", "ek_hip_debug_xbatched_chunk",
     "ek_hip_check_xbatched_device", "ek_hip_check_xbatched", "ek_hip_debug_check_xbatched_chunk",
+    "ek_hip_sygv_xbatched_device", "ek_hip_sygv_xbatched",
 )
 
 
@@ -800,6 +805,18 @@ def sygv_batched(A, B, itype=1, vectors=True, seconds=None):
     if B is None:
         raise ValueError("B is required")
     return _batched_call("ek_hip_sygv_batched", int(itype), A, B, vectors, seconds)
+
+
+def sygv_xbatched(A, B, itype=1, vectors=True, seconds=None):
+    """sygv_batched for orders up to XBATCH_NMAX (ek_hip_sygv_xbatched): the same arguments, returns and errors.  Orders
+    up to BATCH_NMAX give sygv_batched's bits; above it itype 1 is eigenpairs_xbatched(A, B) to the bit and types 2 and 3
+    run that kernel class with the reduction and the recovery of the type.  A missing B or an itype outside 1 .. 3
+    raises ValueError before the library is called; an order beyond XBATCH_NMAX raises SolverError with info -3."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if B is None:
+        raise ValueError("B is required")
+    return _batched_call("ek_hip_sygv_xbatched", int(itype), A, B, vectors, seconds)
 
 
 def _vbatched_call(name, first, As, Bs, vectors, seconds):

@@ -277,8 +277,8 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
  * one stream without a host synchronise in between.
  * Workspace: batch ints, and for orders above EK_HIP_BATCH_NMAX min(batch, 1024) images of 256 x 257 doubles (526 336
  * bytes each, 539 MB for 1024 problems or more) of device memory, grown on demand and kept until ek_hip_finalize.
- * Not offered at the new orders: the variable-order form, problem types 2 and 3.  Their acceptance check is
- * ek_hip_check_xbatched* below. */
+ * Not offered at the new orders: the variable-order form.  Problem types 2 and 3 at these orders are
+ * ek_hip_sygv_xbatched* below.  The acceptance check of these entries is ek_hip_check_xbatched* below. */
 #define EK_HIP_XBATCH_NMAX 256
 int ek_hip_eigenpairs_xbatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                       double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
@@ -363,6 +363,33 @@ int ek_hip_sygv_vbatched_device(int itype, int jobz, int batch, const int *n, do
 int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
                          const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
                          int *info, double *seconds);
+
+/* DSYGV's three problem types for orders up to EK_HIP_XBATCH_NMAX: what ek_hip_eigenpairs_xbatched* are to
+ * ek_hip_eigenpairs_batched*, for ek_hip_sygv_batched*.  The same 16 arguments and argument-error codes as
+ * ek_hip_sygv_batched*, decided before any device work and without dereferencing a data pointer, the first offending
+ * argument deciding: -1 for itype outside 1 .. 3 (B always required: -8 / -9 / -10), -3 for n < 0 or n > EK_HIP_XBATCH_NMAX.
+ *   0 <= n <= EK_HIP_BATCH_NMAX : forwarded to the code behind ek_hip_sygv_batched*: the same bits in w, Z, info, dA and dB
+ *   EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX, itype 1 : ek_hip_eigenpairs_xbatched*(problem = 1) to the bit (the same
+ *                   kernel)
+ *   EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX, itype 2, 3 : a second instantiation of that kernel with the reduction
+ *                   C = L^T A L and, for type 3, the recovery x = L y; every other stage is the same code
+ * The contract of ek_hip_sygv_batched* and of ek_hip_eigenpairs_xbatched* holds for types 2 and 3 at the new orders:
+ * info[b] is 0 (always with finite w), the failing pivot k of B (the value type 1 reports), -5 or 100000 + k; A is scaled
+ * from A alone; the device form works IN PLACE, dA[b] <- DSYTD2's lower layout of C = L^T A L (d and e those of the
+ * caller's scaling), dB[b] <- L, type 1's L bit for bit; types 2 and 3 return the same w and the same dA image bit for
+ * bit and Z3 = B Z2 to rounding; jobz = 0 returns the bits of jobz = 1 in w and dA; the same bits alone, at any position of
+ * any batch, in any chunk and in the host and the device form; strictly upper triangles, rows n .. ld-1 and the gaps
+ * between problems are neither read nor written; a failed problem touches its own slots only.  Chunks and workspace are
+ * those of ek_hip_eigenpairs_xbatched*.  ek_hip_sygv_batched* keep answering -3 above EK_HIP_BATCH_NMAX.
+ * Not offered: the variable-order form above EK_HIP_BATCH_NMAX.  ek_hip_check_xbatched* stays a check of type 1; one
+ * problem of types 2 and 3 at a time is checked by ek_hip_check_sygvx*. */
+int ek_hip_sygv_xbatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout; A and B are left untouched (the call works on device copies) */
+int ek_hip_sygv_xbatched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                         const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                         long long strideZ, int *info, double *seconds);
 
 /* The acceptance checks and the inverse participation ratios of EVERY problem of a batch -- what ek_hip_residual_device,
  * ek_hip_orthogonality_device and ek_hip_ipratios_device are to one problem, with the same normalisations (the

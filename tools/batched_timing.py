@@ -6,7 +6,7 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  --itype 2 / 3: the generalized rows solve A B x = l x / B A x = l x
                                                  through ek_hip_sygv_batched_device (the loop stays type 1's: a yardstick)
                                                  sizes above 128 (up to 256) time ek_hip_eigenpairs_xbatched_device
-                                                 against the same host loop
+                                                 (--itype 2 / 3: ek_hip_sygv_xbatched_device) against the same host loop
   python tools/batched_timing.py --once 64g      one batched call (256 generalized pairs of order 64 with vectors)
                                                  after a warm-up: what a kernel trace should look at
   python tools/batched_timing.py --mixed [--mixed-batch 2048] [--mixed-orders 8,128]
@@ -81,9 +81,10 @@ class Case:
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
         fn, first = self.lib.ek_hip_eigenpairs_batched_device, problem
-        if n > solver.BATCH_NMAX:                   # orders 129 .. 256: the image in device memory (type 1 only)
-            assert self.itype == 1, "orders above %d: problem types 2 and 3 are not offered" % solver.BATCH_NMAX
+        if n > solver.BATCH_NMAX:                   # orders 129 .. 256: the image in device memory
             fn = self.lib.ek_hip_eigenpairs_xbatched_device
+            if problem and self.itype != 1:
+                fn, first = self.lib.ek_hip_sygv_xbatched_device, self.itype
         elif problem and self.itype != 1:
             fn, first = self.lib.ek_hip_sygv_batched_device, self.itype
         rc = fn(first, jobz, n, self.batch, self.dA, n, nn, self.dB if problem else None, n, nn, self.dw,
@@ -241,7 +242,8 @@ def main():
     ap.add_argument("--batches", default="1,256,4096")
     ap.add_argument("--loop-max", type=int, default=64)
     ap.add_argument("--itype", type=int, choices=(1, 2, 3), default=1,
-                    help="problem type of the generalized batched rows (2, 3: ek_hip_sygv_batched_device)")
+                    help="problem type of the generalized batched rows (2, 3: ek_hip_sygv_batched_device, "
+                         "ek_hip_sygv_xbatched_device above order 128)")
     ap.add_argument("--once", default=None, help="<n>g or <n>s: one generalized / standard batch of 256 with vectors")
     ap.add_argument("--once-batch", type=int, default=256)
     ap.add_argument("--check", action="store_true", help="time the batched check behind each solve (with vectors)")
@@ -294,7 +296,8 @@ def main():
         lib.ek_hip_finalize()
         return
     if args.itype != 1:
-        print("# generalized rows: itype %d (ek_hip_sygv_batched_device)" % args.itype)
+        print("# generalized rows: itype %d (ek_hip_sygv_batched_device; ek_hip_sygv_xbatched_device above order %d)"
+              % (args.itype, solver.BATCH_NMAX))
     print("# problem jobz     n batch | batched wall ms  device ms  us/problem  problems/s | loop ms (scaled)  "
           "us/problem | ratio")
     for n in (int(x) for x in args.sizes.split(",")):

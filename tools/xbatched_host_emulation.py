@@ -2,13 +2,16 @@
 """ek_batched_x.hip's kernel on the CPU: the kernel's source, unchanged, compiled for the host with one OS thread per GPU
 thread, __syncthreads() as a barrier and __shared__ as static storage; one problem per run (tools, not product).
 
-  python tools/xbatched_host_emulation.py [--n 129] [--problem 1] [--tsan] [--stop 0|1|2]
+  python tools/xbatched_host_emulation.py [--n 129] [--problem 1] [--itype 1|2|3] [--tsan] [--stop 0|1|2]
+      --itype  DSYGV's problem type (problem 1): 2 and 3 run the kernel's CONG instantiation
       --tsan   build with -fsanitize=thread: a missing barrier shows as a data race with both source lines
-      --stop   1: end after X = L^-1 A and compare the image with a forward substitution's X^T; 2: after stage 2 (C)
+      --stop   1: end after X = L^-1 A and compare the image with a forward substitution's X^T (type 1 only); 2: after
+               stage 2 (C = L^-1 A L^-T; types 2 and 3: C = L^T A L formed by plain loops in the kernel's summation order)
 
 --stop compares bit for bit (the reference applies the same updates in the same order) and exits 1 on a difference.
-Prints info, residual and (B-)orthogonality against their bounds and whether the NaNs planted in the strict upper
-triangles of A and B survived; exit status 0 when all hold.  Needs g++ with C++20 (std::barrier).  The butterfly of
+Prints info, residual and (B-)orthogonality against their bounds (types 2 and 3: the normalisations of the type, module
+docstring of tests/test_gpu_sygv_batched.py, type 3 with the factor left in B) and whether the NaNs planted in the strict
+upper triangles of A and B survived; exit status 0 when all hold.  Needs g++ with C++20 (std::barrier).  The butterfly of
 block_reduce is ordered by barriers of the emulation's own, so this says nothing about that function."""
 import argparse
 import os
@@ -20,9 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=129)
 ap.add_argument("--problem", type=int, default=1)
+ap.add_argument("--itype", type=int, default=1, choices=(1, 2, 3))
 ap.add_argument("--tsan", action="store_true")
 ap.add_argument("--stop", type=int, default=0)
 args = ap.parse_args()
+assert args.itype == 1 or (args.problem == 1 and args.stop != 1), "--itype 2|3: problem 1, and --stop 0 or 2"
 src = open(os.path.join(ROOT, "eigenkernel_amd", "csrc", "ek_batched_x.hip")).read()
 def patch(text, old, new):
     assert text.count(old) == 1, "anchor not found exactly once in ek_batched_x.hip: %r" % old
@@ -66,6 +71,8 @@ src += r'''
 using namespace ek::batchedx;
 int main(int argc, char **argv) {
   const int n = argc > 1 ? atoi(argv[1]) : 129, problem = argc > 2 ? atoi(argv[2]) : 1;
+  const int itype = argc > 3 ? atoi(argv[3]) : 1;
+  const bool cong = problem && itype != 1;
   std::vector<double> A((size_t)n * n), B((size_t)n * n), Z((size_t)n * n, -7.0), w(n, -7.0), ws(kSlot, NAN);
   unsigned long long s = 12345 + n;
   auto rnd = [&]() { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return ((double)(s >> 11) / 9007199254740992.0) * 2.0 - 1.0; };
@@ -77,24 +84,31 @@ int main(int argc, char **argv) {
     }
   std::vector<double> A0 = A, B0 = B;
   int info = 777;
-  Args a{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &info, ws.data()};
+  Args a{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &info, ws.data(), itype};
   g_stop2 = getenv("STOP2") ? atoi(getenv("STOP2")) : 0;
   std::barrier<> bar(T);
   g_bar = &bar;
   std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) th.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; xbatched_kernel(a); });
+  for (int t = 0; t < T; ++t) th.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (cong) xbatched_kernel<true>(a); else xbatched_kernel<false>(a); });
   for (auto &x : th) x.join();
   if (g_stop2) {
-    // C = L^-1 A L^-T from the L left in B
+    // C = L^-1 A L^-T (types 2 and 3: L^T A L) from the L left in B
     std::vector<double> X((size_t)n * n), C((size_t)n * n);
     auto Lf = [&](int i, int j) { return B[i + (size_t)j * n]; };
     auto a00 = [&](int i, int j) { return i >= j ? A0[i + (size_t)j * n] : A0[j + (size_t)i * n]; };
+    if (cong) {
+      // a sum over k >= j: the terms j, j + 2, ... and j + 1, j + 3, ... each from 0.0 in ascending order, then added
+      auto halves = [&](auto row, int j) { double p[2] = {0.0, 0.0}; for (int h = 0; h < 2; ++h) for (int k = j + h; k < n; k += 2) p[h] += row(k) * Lf(k, j); return p[0] + p[1]; };
+      for (int r = 0; r < n; ++r) for (int j = 0; j < n; ++j) X[r + (size_t)j * n] = halves([&](int k) { return a00(r, k); }, j);      // Y = A L
+      for (int r = 0; r < n; ++r) for (int i = 0; i <= r; ++i) C[r + (size_t)i * n] = halves([&](int k) { return X[k + (size_t)r * n]; }, i);   // C = Y^T L
+    } else {
     for (int c = 0; c < n; ++c) for (int i = 0; i < n; ++i) { double v = a00(i, c); for (int k = 0; k < i; ++k) v -= Lf(i, k) * X[k + (size_t)c * n]; X[i + (size_t)c * n] = v / Lf(i, i); }
     for (int r = 0; r < n; ++r) for (int j = 0; j < n; ++j) { double v = X[r + (size_t)j * n]; for (int k = 0; k < j; ++k) v -= Lf(j, k) * C[r + (size_t)k * n]; C[r + (size_t)j * n] = v / Lf(j, j); }
     if (g_stop2 == 1) for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) C[i + (size_t)j * n] = X[j + (size_t)i * n];
+    }
     double worst = 0; int wi = -1, wj = -1, bad = 0;
     for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) { if (g_stop2 == 2 && i < j) continue; double e = std::fabs(ws[i + (size_t)j * LD] - C[i + (size_t)j * n]); if (e != 0.0) ++bad; if (e > worst) { worst = e; wi = i; wj = j; } }
-    printf("%s: worst |image - reference| = %.3e at (%d, %d), %d entries differ in their bits\n", g_stop2 == 1 ? "after X = L^-1 A (all entries, against X^T)" : "after stage 2 (lower triangle, against C)", worst, wi, wj, bad);
+    printf("%s: worst |image - reference| = %.3e at (%d, %d), %d entries differ in their bits\n", g_stop2 == 1 ? "after X = L^-1 A (all entries, against X^T)" : cong ? "after stage 2 (lower triangle, against L^T A L)" : "after stage 2 (lower triangle, against C)", worst, wi, wj, bad);
     int shown = 0;
     for (int j = 0; j < n && shown < 12; ++j) for (int i = 0; i < n && shown < 12; ++i) if (!(g_stop2 == 2 && i < j) && ws[i + (size_t)j * LD] != C[i + (size_t)j * n]) { printf("  (%d, %d): %.6e vs %.6e\n", i, j, ws[i + (size_t)j * LD], C[i + (size_t)j * n]); ++shown; }
     return bad ? 1 : 0;
@@ -102,6 +116,36 @@ int main(int argc, char **argv) {
   // residual and orthogonality on the host
   auto a0 = [&](int i, int j) { return i >= j ? A0[i + (size_t)j * n] : A0[j + (size_t)i * n]; };
   auto b0 = [&](int i, int j) { if (!problem) return i == j ? 1.0 : 0.0; return i >= j ? B0[i + (size_t)j * n] : B0[j + (size_t)i * n]; };
+  if (cong) {
+    // the quantities of the type: |M z - w z|_2 / (max|A| |B|_2 |z|_2) with M = A B (2), B A (3); max|Z^T B Z - I| (2),
+    // max|(L^-1 Z)^T (L^-1 Z) - I| (3) with the factor left in B
+    std::vector<double> BZ((size_t)n * n), G((size_t)n * n), x(n, 1.0), y(n);
+    auto mul = [&](auto m, const double *in, double *out) { for (int i = 0; i < n; ++i) { double sacc = 0; for (int j = 0; j < n; ++j) sacc += m(i, j) * in[j]; out[i] = sacc; } };
+    double amax = 0, bnorm = 0, res = 0, orth = 0, wmax = 0; bool asc = true;
+    for (int j = 0; j < n; ++j) for (int i = j; i < n; ++i) amax = std::max(amax, std::fabs(A0[i + (size_t)j * n]));
+    for (int it = 0; it < 300; ++it) { mul(b0, x.data(), y.data()); bnorm = 0; for (int i = 0; i < n; ++i) bnorm += y[i] * y[i]; bnorm = std::sqrt(bnorm); for (int i = 0; i < n; ++i) x[i] = y[i] / bnorm; }
+    for (int k = 0; k < n; ++k) {
+      const double *z = &Z[(size_t)k * n];
+      std::vector<double> u(n), v(n);
+      if (itype == 2) { mul(b0, z, u.data()); mul(a0, u.data(), v.data()); } else { mul(a0, z, u.data()); mul(b0, u.data(), v.data()); }
+      double rn = 0, zn = 0;
+      for (int i = 0; i < n; ++i) { const double d = v[i] - w[k] * z[i]; rn += d * d; zn += z[i] * z[i]; }
+      res = std::max(res, std::sqrt(rn) / (amax * bnorm * std::sqrt(zn)));
+      wmax = std::max(wmax, std::fabs(w[k])); if (k && w[k] < w[k - 1]) asc = false;
+      if (itype == 2) mul(b0, z, &BZ[(size_t)k * n]);
+      else for (int i = 0; i < n; ++i) { double sacc = z[i]; for (int j = 0; j < i; ++j) sacc -= B[i + (size_t)j * n] * BZ[j + (size_t)k * n]; BZ[i + (size_t)k * n] = sacc / B[i + (size_t)i * n]; }
+    }
+    for (int k = 0; k < n; ++k) for (int l = 0; l < n; ++l) {
+      double sacc = 0;
+      for (int i = 0; i < n; ++i) sacc += (itype == 2 ? Z[i + (size_t)k * n] : BZ[i + (size_t)k * n]) * BZ[i + (size_t)l * n];
+      orth = std::max(orth, std::fabs(sacc - (k == l ? 1.0 : 0.0)));
+    }
+    const double lim = 256 * n * 2.220446049250313e-16;
+    printf("n=%d itype=%d info=%d ascending=%d max|w|=%.3f residual %.3e (bound %.3e) orthogonality %.3e (bound %.3e)\n", n, itype, info, (int)asc, wmax, res, lim, orth, lim);
+    bool upper = true; for (int j = 0; j < n; ++j) for (int i = 0; i < j; ++i) upper = upper && std::isnan(A[i + (size_t)j * n]) && std::isnan(B[i + (size_t)j * n]);
+    printf("upper triangles untouched: %d\n", (int)upper);
+    return (info == 0 && asc && res <= lim && orth <= lim && upper) ? 0 : 1;
+  }
   double res = 0, orth = 0, wmax = 0; bool asc = true;
   std::vector<double> BZ((size_t)n * n);
   for (int k = 0; k < n; ++k) for (int i = 0; i < n; ++i) { double sacc = 0; for (int j = 0; j < n; ++j) sacc += b0(i, j) * Z[j + (size_t)k * n]; BZ[i + (size_t)k * n] = sacc; }
@@ -128,4 +172,4 @@ if args.stop:
     env["STOP2"] = str(args.stop)
 if args.tsan:
     env.setdefault("TSAN_OPTIONS", "halt_on_error=1 history_size=4")
-sys.exit(subprocess.call([exe, str(args.n), str(args.problem)], env=env))
+sys.exit(subprocess.call([exe, str(args.n), str(args.problem), str(args.itype)], env=env))
