@@ -193,6 +193,10 @@ def load_library(path=None):
         "ek_hip_check_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
                                           _ip, _dp, _dp, _dp]),
         "ek_hip_debug_check_xbatched_chunk": (c_int, [c_int]),
+        "ek_hip_check_sygv_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
+                                                      c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_sygv_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
+                                               c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
         "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
     }
@@ -242,6 +246,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_eigenpairs_xbatched_device", "ek_hip_eigenpairs_xbatched", "ek_hip_debug_xbatched_chunk",
     "ek_hip_check_xbatched_device", "ek_hip_check_xbatched", "ek_hip_debug_check_xbatched_chunk",
     "ek_hip_sygv_xbatched_device", "ek_hip_sygv_xbatched",
+    "ek_hip_check_sygv_xbatched_device", "ek_hip_check_sygv_xbatched",
 )
 
 
@@ -962,6 +967,19 @@ def check_sygv_batched(A, B, w, Z, itype=1, info=None, ipr=True, seconds=None):
     if B is None:
         raise ValueError("B is required")
     return _check_batched_call("ek_hip_check_sygv_batched", int(itype), A, B, w, Z, info, ipr, seconds)
+
+
+def check_sygv_xbatched(A, B, w, Z, itype=1, info=None, ipr=True, seconds=None):
+    """check_sygv_batched for orders up to XBATCH_NMAX (ek_hip_check_sygv_xbatched), behind sygv_xbatched: the same
+    arguments and returns.  Orders up to BATCH_NMAX run the kernels of check_sygv_batched (the same bits); above it itype 1
+    is check_xbatched(A, B, ...) to the bit, and types 2 and 3 run a kernel class of their own with the products on the
+    matrix cores (for the same B and Z, orthogonality and ipr of type 2 are type 1's bits).  A missing B or an itype outside
+    1 .. 3 raises ValueError before the library is called; an order beyond XBATCH_NMAX raises SolverError with info -2."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if B is None:
+        raise ValueError("B is required")
+    return _check_batched_call("ek_hip_check_sygv_xbatched", int(itype), A, B, w, Z, info, ipr, seconds)
 
 
 def _check_vbatched_call(name, first, As, Bs, ws, Zs, info, ipr, seconds):

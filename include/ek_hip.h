@@ -381,8 +381,8 @@ int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const dou
  * any batch, in any chunk and in the host and the device form; strictly upper triangles, rows n .. ld-1 and the gaps
  * between problems are neither read nor written; a failed problem touches its own slots only.  Chunks and workspace are
  * those of ek_hip_eigenpairs_xbatched*.  ek_hip_sygv_batched* keep answering -3 above EK_HIP_BATCH_NMAX.
- * Not offered: the variable-order form above EK_HIP_BATCH_NMAX.  ek_hip_check_xbatched* stays a check of type 1; one
- * problem of types 2 and 3 at a time is checked by ek_hip_check_sygvx*. */
+ * Not offered: the variable-order form above EK_HIP_BATCH_NMAX.  ek_hip_check_xbatched* stays a check of type 1; the
+ * acceptance check of these entries, all three types, is ek_hip_check_sygv_xbatched* below. */
 int ek_hip_sygv_xbatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                 double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                 long long strideZ, int *info, double *seconds);
@@ -459,7 +459,8 @@ int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda
  * Workspace above EK_HIP_BATCH_NMAX (device memory, grown on demand, kept until ek_hip_finalize): n^2 doubles for each of the
  * min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z; at most 512 MiB; none for problem 0),
  * 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
- * Not offered at these orders: the variable-order form and the checks of types 2 and 3. */
+ * Not offered at these orders: the variable-order form.  The checks of types 2 and 3 at these orders are
+ * ek_hip_check_sygv_xbatched* below. */
 int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                  const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                  int ldz, long long strideZ, const int *info, double *out, double *ipr,
@@ -521,6 +522,44 @@ int ek_hip_check_sygv_batched_device(int itype, int n, int batch, const double *
 int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                               int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                               const int *info, double *out, double *ipr, double *seconds);
+/* The uniform form for orders up to EK_HIP_XBATCH_NMAX, behind ek_hip_sygv_xbatched*.  Argument for argument these are
+ * ek_hip_check_sygv_batched_device / ek_hip_check_sygv_batched -- 17 arguments, the same argument-error codes decided before
+ * any device work and without dereferencing a data pointer, the first offending argument deciding, B always required --
+ * with two differences: -1 is for itype outside 1 .. 3 and comes first, -2 is for n < 0 or n > EK_HIP_XBATCH_NMAX.
+ *   0 <= n <= EK_HIP_BATCH_NMAX : forwarded to the code behind ek_hip_check_sygv_batched*: the same bits in out and ipr
+ *   EK_HIP_BATCH_NMAX < n, itype 1 : ek_hip_check_xbatched*(problem = 1) itself: the same bits
+ *   EK_HIP_BATCH_NMAX < n, itype 2, 3 : a kernel class of its own, one workgroup of 512 threads per problem from first load
+ *                   to last store.  The quantities are the ones tabulated above, in the same slots.  The three n^3
+ *                   products of a type (B Z, A (B Z), Z^T (B Z); A Z, B (A Z), W^T W) run on the fp64 matrix cores over
+ *                   LDS-staged tiles with the operands in device memory; type 3's own factor B = L L^T (from the caller's
+ *                   ORIGINAL B; a pivot takes a square root and a division) and W = L^-1 Z run in device memory with a
+ *                   wave along consecutive rows.  A pivot of B that is not positive and finite gives NaN in out[4 b + 3]
+ *                   and in the problem's ipr slots; its residual slots stay valid and the return value is 0
+ * The whole contract above holds at the new orders: A and B symmetric by their lower triangles (strictly upper triangles,
+ * rows n..ld-1 and the gaps between problems are never read), info = NULL checks every problem and a problem with
+ * info[b] != 0 gets NaN in its four slots, keeps its ipr slots and has its w and Z left unread, ipr = NULL is legal,
+ * out = NULL is -15, n = 0 or batch = 0 returns 0 with nothing referenced or written, plain IEEE divisions, a maximum that
+ * keeps a NaN.  THE SAME BITS WHEREVER A PROBLEM SITS: a problem's outputs depend on (itype, n, A, B, w, Z) alone -- alone,
+ * at any position of any batch, in any chunk, in the host and the device form.  For the same (B, Z), out[4 b + 3] and ipr
+ * of type 2 are the bits of ek_hip_check_xbatched*(problem = 1).  A, B, w and Z are const and come back bit for bit.
+ * NOT COLLECTIVE; the calls synchronise.
+ * A batch of types 2 and 3 above EK_HIP_BATCH_NMAX runs in chunks of at most 1024 checked problems (the value that
+ * ek_hip_debug_check_xbatched_chunk sets governs this entry too), launched one after the other on one stream without a
+ * host synchronise in between; one copy brings the output words to the host, where they are scattered.
+ * Workspace there (device memory, grown on demand, kept until ek_hip_finalize): for each of the min(checked problems, 1024)
+ * problems of a chunk n^2 doubles for type 2 (S = B Z; at most 512 MiB) and 2 n^2 for type 3 (A Z, then L, and W; at most
+ * 1 GiB), 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
+ * ek_hip_check_sygv_batched* and ek_hip_check_batched* keep answering -2 above EK_HIP_BATCH_NMAX.  Not offered: the
+ * variable-order form above EK_HIP_BATCH_NMAX. */
+int ek_hip_check_sygv_xbatched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
+                                      const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
+                                      int ldz, long long strideZ, const int *info, double *out, double *ipr,
+                                      double *seconds);
+/* host arrays A, B, w, Z with the same layout (the call works on device copies; the caller's arrays are untouched) */
+int ek_hip_check_sygv_xbatched(int itype, int n, int batch, const double *A, int lda, long long strideA, const double *B,
+                               int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
+                               const int *info, double *out, double *ipr, double *seconds);
+/* The variable form of ek_hip_check_sygv_batched* (orders up to EK_HIP_BATCH_NMAX) */
 int ek_hip_check_sygv_vbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
                                       const double *const *dB, const int *ldb, const double *const *dw,
                                       const double *const *dZ, const int *ldz, const int *info, double *out,

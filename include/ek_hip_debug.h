@@ -129,9 +129,9 @@ int ek_hip_debug_vbatched_last(double *class_seconds, int *class_count);
    each chunk reusing the same image slots).  0 (or less) restores the default of 1024; returns the previous value.  A
    tuning and test hook: no result depends on it. */
 int ek_hip_debug_xbatched_chunk(int problems);
-/* ek_hip_check_xbatched*, orders above EK_HIP_BATCH_NMAX: checked problems per launch (a batch runs in chunks of that many,
-   each chunk reusing the same scratch for S = B Z).  0 (or less) restores the default of 1024; returns the previous value.
-   A tuning and test hook: no result depends on it. */
+/* ek_hip_check_xbatched* and ek_hip_check_sygv_xbatched*, orders above EK_HIP_BATCH_NMAX: checked problems per launch (a batch
+   runs in chunks of that many, each chunk reusing the same scratch for S = B Z; types 2 and 3: for the products, L and W).
+   0 (or less) restores the default of 1024; returns the previous value.  A tuning and test hook: no result depends on it. */
 int ek_hip_debug_check_xbatched_chunk(int problems);
 
 /* test aid: the next `times` bulge chasings of whole-path calls count as abandoned (exercises the repetition from the

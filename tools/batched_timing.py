@@ -19,6 +19,9 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  (ek_hip_check_batched_device; ek_hip_check_xbatched_device for sizes
                                                  above 128) on its w and Z -- the check's device time
                                                  beside the solve's, the worst res_max and orthogonality of the batch
+                                                 --itype 2 / 3: the generalized rows time the type's own check
+                                                 (ek_hip_check_sygv_batched_device; ek_hip_check_sygv_xbatched_device
+                                                 above 128) behind the type's own solve
   python tools/batched_timing.py --once 64g --once-batch 1024 --check
                                                  one solve and one check after a warm-up of each
 
@@ -106,10 +109,14 @@ class Case:
         dp = ctypes.POINTER(ctypes.c_double)
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
-        fn = self.lib.ek_hip_check_batched_device
+        fn, first = self.lib.ek_hip_check_batched_device, problem
         if n > solver.BATCH_NMAX:                   # orders 129 .. 256: the check of the xbatched solver
             fn = self.lib.ek_hip_check_xbatched_device
-        rc = fn(problem, n, self.batch, self.dA0, n, nn, self.dB0 if problem else None, n, nn, self.dw, self.dZ, n, nn,
+        if problem and self.itype != 1:             # types 2 and 3: the type's own check behind the type's own solve
+            first = self.itype
+            fn = (self.lib.ek_hip_check_sygv_xbatched_device if n > solver.BATCH_NMAX
+                  else self.lib.ek_hip_check_sygv_batched_device)
+        rc = fn(first, n, self.batch, self.dA0, n, nn, self.dB0 if problem else None, n, nn, self.dw, self.dZ, n, nn,
                 self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), out.ctypes.data_as(dp), ipr.ctypes.data_as(dp),
                 ctypes.byref(sec))
         t = time.perf_counter() - t0
@@ -275,11 +282,15 @@ def main():
         lib.ek_hip_finalize()
         return
     if args.check:
+        if args.itype != 1:
+            print("# generalized rows: itype %d (ek_hip_check_sygv_batched_device behind ek_hip_sygv_batched_device; "
+                  "ek_hip_check_sygv_xbatched_device behind ek_hip_sygv_xbatched_device above order %d)"
+                  % (args.itype, solver.BATCH_NMAX))
         print("# problem     n batch | solve device ms | check wall ms  device ms  us/problem | check / solve | "
               "worst res_max  orthogonality")
         for n in (int(x) for x in args.sizes.split(",")):
             for batch in (int(x) for x in args.batches.split(",")):
-                c = Case(lib, n, batch)
+                c = Case(lib, n, batch, itype=args.itype)
                 for problem in (1, 0):
                     ts, tc, worst = [], [], np.zeros(2)
                     c.batched(problem, 1); c.check(problem)                         # warm-up
