@@ -18,6 +18,17 @@
 #include <vector>
 
 namespace ek {
+namespace batched {
+// The variable-order entries' problem table (ek_batched.hip builds it, its kernel and ek_batched_x.hip's read it): one
+// entry per problem of order > 0, a class after the other, descending order inside a class; `index` is the problem's
+// place in the caller's batch, where its status word goes.
+struct Desc {
+  double *A, *B, *w, *Z;
+  int n, lda, ldb, ldz, index, pad;
+};
+static_assert(sizeof(Desc) == 56, "the table's entry");
+}  // namespace batched
+
 namespace api {
 
 struct Context {
@@ -64,7 +75,12 @@ void release_xbatched();           // the images of ek_hip_eigenpairs_xbatched* 
 int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
                     long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                     long long strideZ, int *dinfo);
-void release_batched_check();      // the batched checks' scratch, output words, table and events (ek_batched_check.hip)
+// the same for `count` entries of the variable-order table (device), all of order above EK_HIP_BATCH_NMAX: chunk c
+// takes the entries [c K, c K + K) and the image slots 0 .. K-1; the status word of an entry goes to dinfo[index]
+int xvbatched_prepare(int count);  // its images (min(count, K) slots), to be called before the call's first event
+int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count, const batched::Desc *table,
+                     int *dinfo);
+void release_batched_check();     // the batched checks' scratch, output words, table and events (ek_batched_check.hip)
 void release_batched_check_x();    // the same of ek_hip_check_xbatched* above EK_HIP_BATCH_NMAX (ek_batched_check_x.hip)
 int check_xbatched_chunk();        // checked problems per launch there (ek_hip_debug_check_xbatched_chunk); g_mu held
 void release_batched_check_sygv_x();   // the same of ek_hip_check_sygv_xbatched*, types 2 and 3 (ek_batched_check_sygv_x.hip)

@@ -56,13 +56,8 @@ struct Args {
   int itype;                                        // 1 / 2 / 3 as DSYGV's, looked at when problem == 1; last, so that
 };                                                  // what the kernel of type 1 loads lies where it always lay
 
-// ek_hip_eigenpairs_vbatched*: problems of different orders in one call.  A workgroup finds its problem in a table
-// (one entry per problem of order > 0, a class after the other, descending order inside a class); `index` is the
-// problem's place in the caller's batch, where its status word goes.
-struct Desc {
-  double *A, *B, *w, *Z;
-  int n, lda, ldb, ldz, index, pad;
-};
+// ek_hip_eigenpairs_vbatched*: problems of different orders in one call.  A workgroup finds its problem in a table of
+// Desc (ek_api_internal.h).
 struct VArgs {
   int problem, jobz;
   const Desc *table;
@@ -656,17 +651,18 @@ static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
 static int *g_dinfo = nullptr;
 static size_t g_dinfo_count = 0;
 
-// the variable form's problem table, the streams of the classes of 64 and 32 (the class of 128 runs on the context's
-// stream) and the events that tie them to it: kept like the status words
+// the variable form's problem table, the streams of the classes behind the largest one present (that one runs on the
+// context's stream) and the events that tie them to it: kept like the status words
 static Desc *g_dtable = nullptr;
 static size_t g_dtable_count = 0;
 static std::vector<Desc> g_htable;                 // its host image
-static hipStream_t g_side[2] = {nullptr, nullptr};
-constexpr int kEvents = 10;                         // fork, two joins, start / end of each class, end of the call
+constexpr int kClasses = 4;                         // 256 (ek_batched_x.hip's kernel; ek_hip_*_xvbatched* only), 128, 64, 32
+static hipStream_t g_side[kClasses - 1] = {};
+constexpr int kEvents = 3 * kClasses + 1;           // fork, joins, start / end of each class, end of the call
 static hipEvent_t g_ev[kEvents] = {};
 static int g_streams = 3;                           // 3: a stream per class; 1: one stream (ek_hip_debug_vbatched_streams)
-static double g_class_seconds[3] = {0.0, 0.0, 0.0}; // the last timed variable call's kernels: classes of 128, 64, 32
-static int g_class_count[3] = {0, 0, 0};
+static double g_class_seconds[kClasses] = {};       // the last timed variable call's kernels, by class
+static int g_class_count[kClasses] = {};
 
 static int ensure_info(size_t batch) {
   if (batch <= g_dinfo_count) return 0;
@@ -678,7 +674,7 @@ static int ensure_info(size_t batch) {
   return 0;
 }
 
-static int ensure_variable(size_t entries) {
+static int ensure_variable(size_t entries, int sides) {
   if (entries > g_dtable_count) {
     if (g_dtable) (void)hipFree(g_dtable);
     g_dtable = nullptr;
@@ -686,7 +682,7 @@ static int ensure_variable(size_t entries) {
     EK_HIP_CHECK(hipMalloc((void **)&g_dtable, entries * sizeof(Desc)));
     g_dtable_count = entries;
   }
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < sides; ++k)
     if (!g_side[k]) EK_HIP_CHECK(hipStreamCreateWithFlags(&g_side[k], hipStreamNonBlocking));
   for (int k = 0; k < kEvents; ++k)
     if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
@@ -705,7 +701,7 @@ void release_batched() {
   g_dtable = nullptr;
   g_dtable_count = 0;
   std::vector<Desc>().swap(g_htable);
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < kClasses - 1; ++k) {
     if (g_side[k]) (void)hipStreamDestroy(g_side[k]);
     g_side[k] = nullptr;
   }
@@ -789,7 +785,7 @@ static int batched_device_locked(int problem, int itype, int jobz, int n, int ba
 // All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.
 static int vbatched_check(int problem, int jobz, int batch, const int *n, const void *const *A, const int *lda,
                           const void *const *B, const int *ldb, const void *const *w, const void *const *Z,
-                          const int *ldz, const int *info, bool *nothing) {
+                          const int *ldz, const int *info, bool *nothing, int nmax) {
   *nothing = false;
   if (problem != 0 && problem != 1) return -1;
   if (jobz != 0 && jobz != 1) return -2;
@@ -797,7 +793,7 @@ static int vbatched_check(int problem, int jobz, int batch, const int *n, const 
   if (batch == 0) { *nothing = true; return 0; }
   if (!n) return -4;
   for (int b = 0; b < batch; ++b)
-    if (n[b] < 0 || n[b] > EK_HIP_BATCH_NMAX) return -4;
+    if (n[b] < 0 || n[b] > nmax) return -4;
   auto entries = [&](const void *const *P) {
     if (!P) return false;
     for (int b = 0; b < batch; ++b)
@@ -825,7 +821,9 @@ static int vbatched_check(int problem, int jobz, int batch, const int *n, const 
   return 0;
 }
 
-// arguments checked, context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses
+// arguments checked, context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses.  Orders above
+// EK_HIP_BATCH_NMAX (ek_hip_*_xvbatched* only) make a class of their own in front of the three, which runs
+// ek_batched_x.hip's kernel in chunks (xvbatched_launch)
 static int vbatched_device_locked(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
                                   const int *lda, double *const *dB, const int *ldb, double *const *dw,
                                   double *const *dZ, const int *ldz, int *info, double *seconds) {
@@ -842,57 +840,60 @@ static int vbatched_device_locked(int problem, int itype, int jobz, int batch, c
   }
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
   g_htable.resize(order.size());                    // static: the upload below may still read it when an error returns
-  int count[3] = {0, 0, 0};                         // classes of 128, 64, 32
+  int count[kClasses] = {0, 0, 0, 0};               // classes of 256, 128, 64, 32
   for (size_t i = 0; i < order.size(); ++i) {
     const int b = order[i], c = class_of(n[b]);
-    ++count[c == 128 ? 0 : c == 64 ? 1 : 2];
+    ++count[n[b] > EK_HIP_BATCH_NMAX ? 0 : c == 128 ? 1 : c == 64 ? 2 : 3];
     g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], jobz ? dZ[b] : nullptr, n[b], lda[b],
                        problem ? ldb[b] : 1, jobz ? ldz[b] : 1, b, 0};
   }
+  // the largest class present runs on the context's stream, the others on a stream of their own behind the fork event
+  int side[kClasses] = {-1, -1, -1, -1}, sides = 0; // -1: the context's stream
+  if (g_streams == 3)
+    for (int k = 0, used = 0; k < kClasses; ++k)
+      if (count[k] && used++ > 0) side[k] = sides++;
   { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
-  { int rc0 = ensure_variable(order.size()); if (rc0) return rc0; }
+  { int rc0 = ensure_variable(order.size(), std::max(sides, 2)); if (rc0) return rc0; }   // the third: with four classes
+  if (count[0]) { int rc0 = xvbatched_prepare(count[0]); if (rc0) return rc0; }
   hipStream_t s = g_ctx.stream;
   EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
-  // the largest class present runs on the context's stream, the others on a stream of their own behind the fork event
-  hipStream_t cs[3] = {s, s, s};
-  for (int k = 0, used = 0; k < 3; ++k)
-    if (count[k]) {
-      if (g_streams == 3 && used > 0) cs[k] = g_side[used - 1];
-      ++used;
-    }
+  hipStream_t cs[kClasses];
+  for (int k = 0; k < kClasses; ++k) cs[k] = side[k] < 0 ? s : g_side[side[k]];
   EK_HIP_CHECK(hipEventRecord(g_ev[0], s));         // before the first launch
   int rc = 0, off = 0;
   hipError_t e = hipSuccess;
-  for (int k = 0; k < 3 && !rc && e == hipSuccess; ++k) {
+  for (int k = 0; k < kClasses && !rc && e == hipSuccess; ++k) {
     if (!count[k]) continue;
     if (cs[k] != s) e = hipStreamWaitEvent(cs[k], g_ev[0], 0);
     if (e != hipSuccess) break;
     VArgs a{problem, jobz, g_dtable + off, g_dinfo, itype};
-    if (seconds) (void)hipEventRecord(g_ev[3 + 2 * k], cs[k]);
-    rc = k == 0 ? launch_class<128, 256>(cs[k], count[k], a)
-       : k == 1 ? launch_class<64, 128>(cs[k], count[k], a) : launch_class<32, 64>(cs[k], count[k], a);
-    if (seconds) (void)hipEventRecord(g_ev[4 + 2 * k], cs[k]);
+    if (seconds) (void)hipEventRecord(g_ev[kClasses + 2 * k], cs[k]);
+    rc = k == 0 ? xvbatched_launch(cs[k], problem, itype, jobz, count[k], g_dtable + off, g_dinfo)
+       : k == 1 ? launch_class<128, 256>(cs[k], count[k], a)
+       : k == 2 ? launch_class<64, 128>(cs[k], count[k], a) : launch_class<32, 64>(cs[k], count[k], a);
+    if (seconds) (void)hipEventRecord(g_ev[kClasses + 1 + 2 * k], cs[k]);
     if (cs[k] != s) {                               // join
       e = hipEventRecord(g_ev[k], cs[k]);
       if (e == hipSuccess) e = hipStreamWaitEvent(s, g_ev[k], 0);
     }
     off += count[k];
   }
-  if (seconds) (void)hipEventRecord(g_ev[9], s);    // after the last launch has ended
+  if (seconds) (void)hipEventRecord(g_ev[kEvents - 1], s);   // after the last launch has ended
   if (!rc && e == hipSuccess)
     e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
   hipError_t es = hipStreamSynchronize(s);
   if (e != hipSuccess || rc)                        // an error may have left a class outside the join
-    for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(g_side[k]);
+    for (int k = 0; k < kClasses - 1; ++k)
+      if (g_side[k]) (void)hipStreamSynchronize(g_side[k]);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess && !rc) rc = -1000 - (int)e;
   if (seconds && !rc) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[9]) == hipSuccess) *seconds = (double)ms * 1e-3;
-    for (int k = 0; k < 3; ++k) {
+    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[kEvents - 1]) == hipSuccess) *seconds = (double)ms * 1e-3;
+    for (int k = 0; k < kClasses; ++k) {
       g_class_count[k] = count[k];
       g_class_seconds[k] = 0.0;
-      if (count[k] && hipEventElapsedTime(&ms, g_ev[3 + 2 * k], g_ev[4 + 2 * k]) == hipSuccess)
+      if (count[k] && hipEventElapsedTime(&ms, g_ev[kClasses + 2 * k], g_ev[kClasses + 1 + 2 * k]) == hipSuccess)
         g_class_seconds[k] = (double)ms * 1e-3;
     }
   }
@@ -961,10 +962,11 @@ static int batched_host_entry(int problem, int itype, int jobz, int n, int batch
 
 static int vbatched_device_entry(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
                                  const int *lda, double *const *dB, const int *ldb, double *const *dw,
-                                 double *const *dZ, const int *ldz, int *info, double *seconds) {
+                                 double *const *dZ, const int *ldz, int *info, double *seconds,
+                                 int nmax = EK_HIP_BATCH_NMAX) {
   bool nothing;
   int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)dA, lda, (const void *const *)dB, ldb,
-                          (const void *const *)dw, (const void *const *)dZ, ldz, info, &nothing);
+                          (const void *const *)dw, (const void *const *)dZ, ldz, info, &nothing, nmax);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -981,10 +983,11 @@ static int vbatched_device_entry(int problem, int itype, int jobz, int batch, co
 
 static int vbatched_host_entry(int problem, int itype, int jobz, int batch, const int *n, const double *const *A,
                                const int *lda, const double *const *B, const int *ldb, double *const *w,
-                               double *const *Z, const int *ldz, int *info, double *seconds) {
+                               double *const *Z, const int *ldz, int *info, double *seconds,
+                               int nmax = EK_HIP_BATCH_NMAX) {
   bool nothing;
   int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
-                          (const void *const *)w, (const void *const *)Z, ldz, info, &nothing);
+                          (const void *const *)w, (const void *const *)Z, ldz, info, &nothing, nmax);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -1140,6 +1143,36 @@ int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const dou
   return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds);
 }
 
+// The variable-order entries for orders up to EK_HIP_XBATCH_NMAX: a problem above EK_HIP_BATCH_NMAX runs
+// ek_batched_x.hip's kernel, every other one the kernel ek_hip_*_vbatched* give it
+int ek_hip_eigenpairs_xvbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA,
+                                       const int *lda, double *const *dB, const int *ldb, double *const *dw,
+                                       double *const *dZ, const int *ldz, int *info, double *seconds) {
+  return vbatched_device_entry(problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds,
+                               EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_eigenpairs_xvbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                                const double *const *B, const int *ldb, double *const *w, double *const *Z,
+                                const int *ldz, int *info, double *seconds) {
+  return vbatched_host_entry(problem, 1, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_sygv_xvbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                 double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                 const int *ldz, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return vbatched_device_entry(1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds,
+                               EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_sygv_xvbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                          const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
+                          int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
 int ek_hip_debug_vbatched_streams(int streams) {
   if (streams != 1 && streams != 3) streams = 3;
   std::lock_guard<std::mutex> lk(g_mu);
@@ -1149,7 +1182,16 @@ int ek_hip_debug_vbatched_streams(int streams) {
 
 int ek_hip_debug_vbatched_last(double *class_seconds, int *class_count) {
   std::lock_guard<std::mutex> lk(g_mu);
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < 3; ++k) {                     // classes of 128, 64, 32
+    if (class_seconds) class_seconds[k] = batched::g_class_seconds[k + 1];
+    if (class_count) class_count[k] = batched::g_class_count[k + 1];
+  }
+  return 0;
+}
+
+int ek_hip_debug_xvbatched_last(double *class_seconds, int *class_count) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (int k = 0; k < batched::kClasses; ++k) {     // classes of 256, 128, 64, 32
     if (class_seconds) class_seconds[k] = batched::g_class_seconds[k];
     if (class_count) class_count[k] = batched::g_class_count[k];
   }

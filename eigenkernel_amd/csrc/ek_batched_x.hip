@@ -39,6 +39,10 @@
 //
 // A batch runs in chunks of at most K problems (K = 1024; ek_hip_debug_xbatched_chunk), launched one after the other on
 // the context's stream without a host synchronise; problem i of a chunk works in slot i of the workspace.
+//
+// ek_hip_*_xvbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in entry
+// blockIdx.x of its launch's slice of the variable-order table (ek_batched.hip builds it) instead of at blockIdx.x *
+// stride; the image slot is blockIdx.x either way.
 #include "ek_api_internal.h"
 
 #include <algorithm>
@@ -64,6 +68,47 @@ struct Args {
   double *ws;
   int itype;                                        // 1 / 2 / 3 as DSYGV's, looked at when problem == 1; last, so that
 };                                                  // the fields before it keep their offsets
+
+// The table form: entry blockIdx.x of `table` (this launch's slice), image slot blockIdx.x of ws, status word at
+// info[entry.index]
+using batched::Desc;
+struct XVArgs {
+  int problem, jobz;
+  const Desc *table;
+  int *info;
+  double *ws;
+  int itype;
+};
+
+// What a workgroup works on, whichever way it found it.  The pointers are typed as global (ek_batched.hip's Problem): one
+// loaded from the table is generic to the compiler otherwise.  n is the same in every lane either way (a kernel argument
+// or a load at an address that depends on blockIdx.x alone): every barrier and every loop bound depends on it.
+struct Problem {
+  int n;
+  gdouble *A; int lda;
+  gdouble *B; int ldb;
+  gdouble *w;
+  gdouble *Z; int ldz;                              // Z: the table form's; the uniform form leaves it to vectors()
+  gdouble *S;
+  int *info;
+};
+__device__ __forceinline__ Problem locate(const Args &a) {
+  const long long pb = blockIdx.x;
+  return {a.n, (gdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (gdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (gdouble *)(a.w + pb * a.n), nullptr, a.ldz,
+          (gdouble *)(a.ws + (size_t)pb * kSlot), a.info + pb};
+}
+__device__ __forceinline__ Problem locate(const XVArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz,
+          (gdouble *)(a.ws + (size_t)blockIdx.x * kSlot), a.info + d.index};
+}
+// Z where the kernel first needs it, behind the exit of jobz = 0 (whose callers pass no Z): the uniform form does its
+// address arithmetic only there, as it always did; the table form loaded the pointer with the rest of its entry
+__device__ __forceinline__ gdouble *vectors(const Args &a, const Problem &) {
+  return (gdouble *)(a.Z + (long long)blockIdx.x * a.sZ);
+}
+__device__ __forceinline__ gdouble *vectors(const XVArgs &, const Problem &p) { return p.Z; }
 
 // ek_batched.hip's block_reduce: a sum (or maximum) over the workgroup, the same bits in every thread
 template <bool MAX>
@@ -143,8 +188,9 @@ __device__ __forceinline__ void cong_pass(gdouble *S, const gdouble *B, int ldb,
 
 // CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
 // CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
-template <bool CONG>
-__global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
+// ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or XVArgs (a table entry).
+template <bool CONG, typename ARGS = Args>
+__global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
   __shared__ double sd[NC], se[NC], st[NC];         // d, e, tau: alive from stage 3 to the end
   __shared__ double sv[NC], sw[NC];                 // stage 1: the scaled column; 3: v, w; 4: c, s of a sweep
   __shared__ double sp[P * NC];                     // partial sums of a pair
@@ -153,16 +199,13 @@ __global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
   __shared__ int srank[NC];
   __shared__ int s_state, s_m, s_lo;
 
-  const long long pb = blockIdx.x;
-  const int t = threadIdx.x, n = a.n;
+  const Problem p = locate(a);
+  const int t = threadIdx.x, n = p.n;
   const int r = t % NC, sub = t / NC;
   const bool row = r < n;
-  gdouble *A = (gdouble *)(a.A + pb * a.sA);
-  gdouble *B = a.problem ? (gdouble *)(a.B + pb * a.sB) : nullptr;
-  gdouble *S = (gdouble *)(a.ws + (size_t)pb * kSlot);
-  gdouble *W = (gdouble *)(a.w + pb * a.n);
-  const int lda = a.lda, ldb = a.ldb;
-  int *info = a.info + pb;
+  gdouble *A = p.A, *B = p.B, *S = p.S, *W = p.w;
+  const int lda = p.lda, ldb = p.ldb;
+  int *info = p.info;
   int phase = 0;
 
   // ---- 0: A finite?  max|a| off the same pass (ek_batched.hip's rule: scaled outside 2^-256 .. 2^256)
@@ -519,8 +562,8 @@ __global__ __launch_bounds__(T) void xbatched_kernel(Args a) {
     if (t == 0) *info = 0;
     return;
   }
-  gdouble *Z = (gdouble *)(a.Z + pb * a.sZ);
-  const int ldz = a.ldz;
+  gdouble *Z = vectors(a, p);
+  const int ldz = p.ldz;
 
   // ---- 5: the image becomes Z^T: the pair r owns column r of Z = row r of the image
   if (row)
@@ -651,8 +694,33 @@ int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int 
     Args a{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
            problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
            jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, dinfo + c0, g_ws, itype};
-    if (problem && itype != 1) hipLaunchKernelGGL(xbatched_kernel<true>, dim3(count), dim3(T), 0, s, a);
-    else hipLaunchKernelGGL(xbatched_kernel<false>, dim3(count), dim3(T), 0, s, a);
+    if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, Args>), dim3(count), dim3(T), 0, s, a);
+    else hipLaunchKernelGGL((xbatched_kernel<false, Args>), dim3(count), dim3(T), 0, s, a);
+    EK_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// the images of a variable call with `count` > 0 problems above EK_HIP_BATCH_NMAX, before its first event: growing them
+// frees and allocates, which synchronises the device and belongs neither into `seconds` nor beside a running class
+int xvbatched_prepare(int count) {
+  using namespace batchedx;
+  return ensure_images((size_t)std::min(count, g_chunk));
+}
+
+// arguments checked, g_mu held, xvbatched_prepare(count) done; `table` (device) holds `count` > 0 entries of orders
+// EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX; dinfo holds a word per problem of the caller's batch.  The chunks share the
+// slots 0 .. K-1: the order of the stream is what separates two users of a slot, so every chunk goes on s.
+int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count, const batched::Desc *table,
+                     int *dinfo) {
+  using namespace batchedx;
+  const int K = g_chunk;
+  if ((size_t)std::min(count, K) > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
+  for (int c0 = 0; c0 < count; c0 += K) {
+    const int chunk = std::min(K, count - c0);
+    XVArgs a{problem, jobz, table + c0, dinfo, g_ws, itype};
+    if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XVArgs>), dim3(chunk), dim3(T), 0, s, a);
+    else hipLaunchKernelGGL((xbatched_kernel<false, XVArgs>), dim3(chunk), dim3(T), 0, s, a);
     EK_HIP_CHECK(hipGetLastError());
   }
   return 0;

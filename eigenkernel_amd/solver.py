@@ -199,6 +199,12 @@ def load_library(path=None):
                                                c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_debug_vbatched_streams": (c_int, [c_int]),
         "ek_hip_debug_vbatched_last": (c_int, [_dp, _ip]),
+        "ek_hip_eigenpairs_xvbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip,
+                                                       _dp]),
+        "ek_hip_eigenpairs_xvbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_sygv_xvbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_sygv_xvbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
+        "ek_hip_debug_xvbatched_last": (c_int, [_dp, _ip]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -247,6 +253,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_xbatched_device", "ek_hip_check_xbatched", "ek_hip_debug_check_xbatched_chunk",
     "ek_hip_sygv_xbatched_device", "ek_hip_sygv_xbatched",
     "ek_hip_check_sygv_xbatched_device", "ek_hip_check_sygv_xbatched",
+    "ek_hip_eigenpairs_xvbatched_device", "ek_hip_eigenpairs_xvbatched", "ek_hip_sygv_xvbatched_device",
+    "ek_hip_sygv_xvbatched", "ek_hip_debug_xvbatched_last",
 )
 
 
@@ -879,6 +887,23 @@ def sygv_vbatched(As, Bs, itype=1, vectors=True, seconds=None):
     if Bs is None:
         raise ValueError("Bs is required")
     return _vbatched_call("ek_hip_sygv_vbatched", int(itype), As, Bs, vectors, seconds)
+
+
+def eigenpairs_xvbatched(As, Bs=None, vectors=True, seconds=None):
+    """eigenpairs_vbatched for orders up to XBATCH_NMAX (ek_hip_eigenpairs_xvbatched): the same arguments, returns and
+    errors.  A problem above BATCH_NMAX has the bits of eigenpairs_xbatched on that pair alone, every other one those of
+    eigenpairs_vbatched."""
+    return _vbatched_call("ek_hip_eigenpairs_xvbatched", 0 if Bs is None else 1, As, Bs, vectors, seconds)
+
+
+def sygv_xvbatched(As, Bs, itype=1, vectors=True, seconds=None):
+    """sygv_vbatched for orders up to XBATCH_NMAX (ek_hip_sygv_xvbatched): the same arguments, returns and errors; each
+    problem's bits are those of sygv_xbatched on that pair alone."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if Bs is None:
+        raise ValueError("Bs is required")
+    return _vbatched_call("ek_hip_sygv_xvbatched", int(itype), As, Bs, vectors, seconds)
 
 
 CHECK_NOUT = 4   # EK_HIP_CHECK_NOUT: a_norm, res_ave, res_max, orthogonality

@@ -277,8 +277,8 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
  * one stream without a host synchronise in between.
  * Workspace: batch ints, and for orders above EK_HIP_BATCH_NMAX min(batch, 1024) images of 256 x 257 doubles (526 336
  * bytes each, 539 MB for 1024 problems or more) of device memory, grown on demand and kept until ek_hip_finalize.
- * Not offered at the new orders: the variable-order form.  Problem types 2 and 3 at these orders are
- * ek_hip_sygv_xbatched* below.  The acceptance check of these entries is ek_hip_check_xbatched* below. */
+ * The variable-order form at the new orders is ek_hip_eigenpairs_xvbatched* below.  Problem types 2 and 3 at these
+ * orders are ek_hip_sygv_xbatched* below.  The acceptance check of these entries is ek_hip_check_xbatched* below. */
 #define EK_HIP_XBATCH_NMAX 256
 int ek_hip_eigenpairs_xbatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                       double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
@@ -364,6 +364,46 @@ int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const dou
                          const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
                          int *info, double *seconds);
 
+/* Problems of DIFFERENT orders up to EK_HIP_XBATCH_NMAX in one call ("xvbatched"): what ek_hip_eigenpairs_xbatched* are
+ * to ek_hip_eigenpairs_batched*, for ek_hip_eigenpairs_vbatched* and ek_hip_sygv_vbatched*.  The same 13 arguments, host
+ * and device conventions, argument-error codes (decided before any device work and without dereferencing a pointer of
+ * the pointer arrays, the first offending argument deciding) and contract as the entries they extend, with one
+ * difference: -4 is for n NULL or an order outside 0 .. EK_HIP_XBATCH_NMAX.  ek_hip_eigenpairs_vbatched* and
+ * ek_hip_sygv_vbatched* keep answering -4 above EK_HIP_BATCH_NMAX.  For the sygv forms -1 is for itype outside 1 .. 3 and B
+ * is always required (-7 / -8).
+ * Problem b runs in the kernel its own order picks: n[b] <= 32 / 64 / 128 the classes of ek_hip_*_vbatched*,
+ * EK_HIP_BATCH_NMAX < n[b] <= EK_HIP_XBATCH_NMAX the kernel of ek_hip_*_xbatched* (image in device memory).
+ * THE SAME BITS AS THE UNIFORM CALL: problem b's w, Z, info and in-place images of dA and dB are bit-identical to what
+ * ek_hip_eigenpairs_xbatched_device (ek_hip_sygv_xbatched_device) returns for the same (n, A, B) alone, wherever the
+ * problem sits, whatever surrounds it, in whichever chunk, and in the host and the device form.  So a batch with no order
+ * above EK_HIP_BATCH_NMAX returns the bits of ek_hip_*_vbatched*, and ek_hip_sygv_xvbatched*(itype = 1) those of
+ * ek_hip_eigenpairs_xvbatched*(problem = 1).
+ * Everything else carries over: info[b] is 0 (always with finite w), the failing pivot of B, -5 or 100000 + k; a failed
+ * problem touches only its own slots; strictly upper triangles, rows n[b] .. ld-1 and whatever lies between problems are
+ * neither read nor written; A is scaled from A alone; types 2 and 3 give equal w and equal dA bits for the same (A, B);
+ * the problems must not overlap in memory (not checked); NOT COLLECTIVE; the call synchronises.
+ * The classes are launched largest first, a class's problems in descending order; the class above EK_HIP_BATCH_NMAX runs
+ * on the context's stream in chunks of at most 1024 problems, one after the other, the other classes beside it on
+ * streams of their own.  Workspace: that of ek_hip_*_vbatched* (three streams and thirteen events), and, only when an
+ * order above EK_HIP_BATCH_NMAX is present, min(problems above EK_HIP_BATCH_NMAX, 1024) images as for
+ * ek_hip_eigenpairs_xbatched*; kept until ek_hip_finalize.
+ * Not offered: acceptance checks of the variable form above EK_HIP_BATCH_NMAX (ek_hip_check_*vbatched* stop there). */
+int ek_hip_eigenpairs_xvbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                       double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                       const int *ldz, int *info, double *seconds);
+/* host addresses in A, B, w, Z, as ek_hip_eigenpairs_vbatched: A and B are left untouched, the lower triangles travel
+ * packed (ld = n[b]) in one copy per matrix kind, w and Z come back in one copy each; w[b] and Z[b] of a failed problem
+ * are left as they were */
+int ek_hip_eigenpairs_xvbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                                const double *const *B, const int *ldb, double *const *w, double *const *Z,
+                                const int *ldz, int *info, double *seconds);
+int ek_hip_sygv_xvbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                 double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                 const int *ldz, int *info, double *seconds);
+int ek_hip_sygv_xvbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                          const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
+                          int *info, double *seconds);
+
 /* DSYGV's three problem types for orders up to EK_HIP_XBATCH_NMAX: what ek_hip_eigenpairs_xbatched* are to
  * ek_hip_eigenpairs_batched*, for ek_hip_sygv_batched*.  The same 16 arguments and argument-error codes as
  * ek_hip_sygv_batched*, decided before any device work and without dereferencing a data pointer, the first offending
@@ -381,7 +421,7 @@ int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const dou
  * any batch, in any chunk and in the host and the device form; strictly upper triangles, rows n .. ld-1 and the gaps
  * between problems are neither read nor written; a failed problem touches its own slots only.  Chunks and workspace are
  * those of ek_hip_eigenpairs_xbatched*.  ek_hip_sygv_batched* keep answering -3 above EK_HIP_BATCH_NMAX.
- * Not offered: the variable-order form above EK_HIP_BATCH_NMAX.  ek_hip_check_xbatched* stays a check of type 1; the
+ * The variable-order form above EK_HIP_BATCH_NMAX is ek_hip_sygv_xvbatched* below.  ek_hip_check_xbatched* stays a check of type 1; the
  * acceptance check of these entries, all three types, is ek_hip_check_sygv_xbatched* below. */
 int ek_hip_sygv_xbatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                 double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
@@ -459,7 +499,8 @@ int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda
  * Workspace above EK_HIP_BATCH_NMAX (device memory, grown on demand, kept until ek_hip_finalize): n^2 doubles for each of the
  * min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z; at most 512 MiB; none for problem 0),
  * 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
- * Not offered at these orders: the variable-order form.  The checks of types 2 and 3 at these orders are
+ * Not offered at these orders: a check of the variable-order form (the results of ek_hip_eigenpairs_xvbatched* are
+ * checked one order at a time here).  The checks of types 2 and 3 at these orders are
  * ek_hip_check_sygv_xbatched* below. */
 int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                  const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
@@ -549,8 +590,9 @@ int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int 
  * Workspace there (device memory, grown on demand, kept until ek_hip_finalize): for each of the min(checked problems, 1024)
  * problems of a chunk n^2 doubles for type 2 (S = B Z; at most 512 MiB) and 2 n^2 for type 3 (A Z, then L, and W; at most
  * 1 GiB), 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
- * ek_hip_check_sygv_batched* and ek_hip_check_batched* keep answering -2 above EK_HIP_BATCH_NMAX.  Not offered: the
- * variable-order form above EK_HIP_BATCH_NMAX. */
+ * ek_hip_check_sygv_batched* and ek_hip_check_batched* keep answering -2 above EK_HIP_BATCH_NMAX.  Not offered: a
+ * check of the variable-order form above EK_HIP_BATCH_NMAX (ek_hip_sygv_xvbatched*' results are checked one order at a time
+ * here). */
 int ek_hip_check_sygv_xbatched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
                                       const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                       int ldz, long long strideZ, const int *info, double *out, double *ipr,

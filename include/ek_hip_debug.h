@@ -119,12 +119,16 @@ unsigned long long ek_hip_debug_window_workspace_bytes(int problem, int n, int j
 /* workspace one ek_hip_sygvx* call asks for (host arithmetic, no GPU): ek_hip_debug_window_workspace_bytes(1, n, jobz,
    range, m) for every itype 1..3 (types 2 and 3 keep type 1's plan).  0: bad arguments. */
 unsigned long long ek_hip_debug_sygvx_workspace_bytes(int itype, int n, int jobz, int range, int m);
-/* ek_hip_eigenpairs_vbatched*: 3 (the default, also for any other value) launches every class on a stream of its own,
-   1 launches the classes one behind the other on one stream.  A tuning hook: no result depends on it. */
+/* ek_hip_*_vbatched* and ek_hip_*_xvbatched*: 3 (the default, also for any other value) launches every class on a stream
+   of its own (with an order above EK_HIP_BATCH_NMAX present there are up to four classes), 1 launches the classes one
+   behind the other on one stream.  A tuning hook: no result depends on it. */
 int ek_hip_debug_vbatched_streams(int streams);
 /* the last ek_hip_eigenpairs_vbatched* call that was given `seconds`: device time of the launch of the classes of 128,
    64 and 32 (events around each on its stream) and the problems each took; either pointer may be NULL */
 int ek_hip_debug_vbatched_last(double *class_seconds, int *class_count);
+/* the same with four entries each: the classes of 256 (orders above EK_HIP_BATCH_NMAX, all chunks), 128, 64 and 32 of the
+   last ek_hip_*_vbatched* or ek_hip_*_xvbatched* call that was given `seconds` */
+int ek_hip_debug_xvbatched_last(double *class_seconds, int *class_count);
 /* ek_hip_eigenpairs_xbatched*, orders above EK_HIP_BATCH_NMAX: problems per launch (a batch runs in chunks of that many,
    each chunk reusing the same image slots).  0 (or less) restores the default of 1024; returns the previous value.  A
    tuning and test hook: no result depends on it. */

@@ -14,6 +14,11 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  (ek_hip_eigenpairs_vbatched_device, a stream per class and one stream)
                                                  against a uniform call per distinct order and against one uniform call
                                                  with every problem padded to order 128
+  python tools/batched_timing.py --mixed --mixed-batch 512 --mixed-orders 129,256   (or 8,256)
+                                                 an upper order above 128: the variable call is
+                                                 ek_hip_eigenpairs_xvbatched_device, the baselines go through
+                                                 ek_hip_eigenpairs_xbatched_device, the padding is to order 256, and the
+                                                 class times are those of the classes of 256 / 128 / 64 / 32
   python tools/batched_timing.py --check [--sizes 64,128] [--batches 1024,4096]
                                                  with vectors only: after each timed solve, the batched check
                                                  (ek_hip_check_batched_device; ek_hip_check_xbatched_device for sizes
@@ -169,7 +174,10 @@ def mixed(lib, batch, lo, hi):
     goff = np.concatenate(([0], np.cumsum(orders[by_order].astype(np.int64) ** 2)))
     gwoff = np.concatenate(([0], np.cumsum(orders[by_order].astype(np.int64))))
     distinct, first, counts = np.unique(orders[by_order], return_index=True, return_counts=True)
-    pad = Case(lib, 128, batch)
+    big = hi > solver.BATCH_NMAX                    # the entries for orders up to 256
+    pad = Case(lib, solver.XBATCH_NMAX if big else solver.BATCH_NMAX, batch)
+    f_var = lib.ek_hip_eigenpairs_xvbatched_device if big else lib.ek_hip_eigenpairs_vbatched_device
+    f_uni = lib.ek_hip_eigenpairs_xbatched_device if big else lib.ek_hip_eigenpairs_batched_device
 
     keep = []
 
@@ -196,14 +204,16 @@ def mixed(lib, batch, lo, hi):
         put(dA, hA); put(dB, hB)
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
-        rc = lib.ek_hip_eigenpairs_vbatched_device(1, 1, batch, n32.ctypes.data_as(ip), tA, n32.ctypes.data_as(ip), tB,
-                                                   n32.ctypes.data_as(ip), tw, tZ, n32.ctypes.data_as(ip),
-                                                   info.ctypes.data_as(ip), ctypes.byref(sec))
+        rc = f_var(1, 1, batch, n32.ctypes.data_as(ip), tA, n32.ctypes.data_as(ip), tB, n32.ctypes.data_as(ip), tw, tZ,
+                   n32.ctypes.data_as(ip), info.ctypes.data_as(ip), ctypes.byref(sec))
         t = time.perf_counter() - t0
         assert rc == 0 and not info.any(), (rc, info[info != 0][:4])
-        cls, cnt = np.zeros(3), np.zeros(3, dtype=np.int32)
-        assert lib.ek_hip_debug_vbatched_last(cls.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                              cnt.ctypes.data_as(ip)) == 0
+        cls, cnt = np.zeros(4), np.zeros(4, dtype=np.int32)
+        assert lib.ek_hip_debug_xvbatched_last(cls.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                               cnt.ctypes.data_as(ip)) == 0
+        if not big:                                 # the three classes of ek_hip_eigenpairs_vbatched*
+            assert cnt[0] == 0
+            cls, cnt = cls[1:], cnt[1:]
         return t, sec.value, cls, cnt
 
     def grouped():
@@ -213,16 +223,21 @@ def mixed(lib, batch, lo, hi):
         for n, f, c in zip(distinct, first, counts):
             n, c = int(n), int(c)
             t0 = time.perf_counter()
-            rc = lib.ek_hip_eigenpairs_batched_device(1, 1, n, c, at(dgA, goff[f]), n, n * n, at(dgB, goff[f]), n, n * n,
-                                                      at(dw, gwoff[f]), at(dZ, goff[f]), n, n * n,
-                                                      info.ctypes.data_as(ip), None)
+            rc = f_uni(1, 1, n, c, at(dgA, goff[f]), n, n * n, at(dgB, goff[f]), n, n * n, at(dw, gwoff[f]),
+                       at(dZ, goff[f]), n, n * n, info.ctypes.data_as(ip), None)
             t += time.perf_counter() - t0
             assert rc == 0 and not info[:c].any()
         return t
 
-    print("# mixed: %d generalized problems with vectors, orders %d..%d (%d distinct; classes of 128 / 64 / 32: %d / %d / %d)"
-          % (batch, lo, hi, len(distinct), (orders > 64).sum(), ((orders > 32) & (orders <= 64)).sum(),
-             (orders <= 32).sum()))
+    if big:
+        print("# mixed: %d generalized problems with vectors, orders %d..%d (%d distinct; classes of 256 / 128 / 64 / 32: "
+              "%d / %d / %d / %d)" % (batch, lo, hi, len(distinct), (orders > 128).sum(),
+                                      ((orders > 64) & (orders <= 128)).sum(), ((orders > 32) & (orders <= 64)).sum(),
+                                      (orders <= 32).sum()))
+    else:
+        print("# mixed: %d generalized problems with vectors, orders %d..%d (%d distinct; classes of 128 / 64 / 32: %d / %d / %d)"
+              % (batch, lo, hi, len(distinct), (orders > 64).sum(), ((orders > 32) & (orders <= 64)).sum(),
+                 (orders <= 32).sum()))
     res = {}
     for streams in (3, 1):
         assert lib.ek_hip_debug_vbatched_streams(streams) == 0
@@ -232,9 +247,11 @@ def mixed(lib, batch, lo, hi):
             tv.append(var()); tg.append(grouped()); tp.append(pad.batched(1, 1)[0])
         best = min(tv, key=lambda x: x[0])
         res[streams] = best[0]
-        print("  streams=%d | t_var wall %.3f ms device %.3f ms | class launches 128: %.3f ms  64: %.3f ms  32: %.3f ms | "
+        names = ("256", "128", "64", "32")[-len(best[2]):]
+        print("  streams=%d | t_var wall %.3f ms device %.3f ms | class launches %s | "
               "t_grouped %.3f ms (ratio %.1f) | t_pad %.3f ms (ratio %.2f)"
-              % (streams, best[0] * 1e3, best[1] * 1e3, best[2][0] * 1e3, best[2][1] * 1e3, best[2][2] * 1e3,
+              % (streams, best[0] * 1e3, best[1] * 1e3,
+                 "  ".join("%s: %.3f ms" % (k, v * 1e3) for k, v in zip(names, best[2])),
                  min(tg) * 1e3, min(tg) / best[0], min(tp) * 1e3, min(tp) / best[0]), flush=True)
         print("            all t_var wall ms: %s" % " ".join("%.3f" % (x[0] * 1e3) for x in tv))
     assert lib.ek_hip_debug_vbatched_streams(3) == 0
@@ -254,7 +271,8 @@ def main():
     ap.add_argument("--once", default=None, help="<n>g or <n>s: one generalized / standard batch of 256 with vectors")
     ap.add_argument("--once-batch", type=int, default=256)
     ap.add_argument("--check", action="store_true", help="time the batched check behind each solve (with vectors)")
-    ap.add_argument("--mixed", action="store_true", help="problems of different orders: the variable call")
+    ap.add_argument("--mixed", action="store_true", help="problems of different orders: the variable call "
+                    "(an upper order above 128: ek_hip_eigenpairs_xvbatched_device)")
     ap.add_argument("--mixed-batch", type=int, default=2048)
     ap.add_argument("--mixed-orders", default="8,128", help="lo,hi of the uniformly drawn orders")
     args = ap.parse_args()

@@ -2,7 +2,9 @@
 """ek_batched_x.hip's kernel on the CPU: the kernel's source, unchanged, compiled for the host with one OS thread per GPU
 thread, __syncthreads() as a barrier and __shared__ as static storage; one problem per run (tools, not product).
 
-  python tools/xbatched_host_emulation.py [--n 129] [--problem 1] [--itype 1|2|3] [--tsan] [--stop 0|1|2]
+  python tools/xbatched_host_emulation.py [--n 129] [--problem 1] [--itype 1|2|3] [--table] [--tsan] [--stop 0|1|2]
+      --table  the kernel's table instantiation (ek_hip_*_xvbatched*): the problem as the one entry of a variable-order
+               table, image slot 0, the status word at info[entry.index]
       --itype  DSYGV's problem type (problem 1): 2 and 3 run the kernel's CONG instantiation
       --tsan   build with -fsanitize=thread: a missing barrier shows as a data race with both source lines
       --stop   1: end after X = L^-1 A and compare the image with a forward substitution's X^T (type 1 only); 2: after
@@ -24,6 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=129)
 ap.add_argument("--problem", type=int, default=1)
 ap.add_argument("--itype", type=int, default=1, choices=(1, 2, 3))
+ap.add_argument("--table", action="store_true")
 ap.add_argument("--tsan", action="store_true")
 ap.add_argument("--stop", type=int, default=0)
 args = ap.parse_args()
@@ -35,6 +38,11 @@ def patch(text, old, new):
 
 
 src = src[:src.index("// the images: grown")]
+# the table's entry, shared through ek_api_internal.h: the struct as it stands there
+internal = open(os.path.join(ROOT, "eigenkernel_amd", "csrc", "ek_api_internal.h")).read()
+assert internal.count("struct Desc {") == 1, "struct Desc not found exactly once in ek_api_internal.h"
+desc = internal[internal.index("struct Desc {"):]
+desc = desc[:desc.index("};") + 2]
 hdr = r'''
 #include <barrier>
 #include <thread>
@@ -60,7 +68,8 @@ static inline double __shfl_xor(double x, int o, int) { g_xch[threadIdx.x] = x; 
 static inline double __builtin_amdgcn_rsq(double h) { return 1.0 / std::sqrt(h); }
 using std::min;
 static int g_stop2 = 0;
-'''
+namespace ek { namespace batched { @DESC@ } }
+'''.replace("@DESC@", desc)
 src = patch(src, '#include "ek_api_internal.h"', hdr)
 src = patch(src, "typedef __attribute__((address_space(1))) double gdouble;", "typedef double gdouble;")
 src = patch(src, "  // ---- 3: Householder", "  if (g_stop2) return;\n  // ---- 3: Householder")
@@ -83,14 +92,19 @@ int main(int argc, char **argv) {
       B[i + (size_t)j * n] = (i == j) ? 2.0 + 0.5 * rnd() : rnd() / n;
     }
   std::vector<double> A0 = A, B0 = B;
-  int info = 777;
-  Args a{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &info, ws.data(), itype};
+  const bool table = argc > 4 && atoi(argv[4]);
+  int infos[3] = {777, 777, 777};
+  int &info = infos[table ? 2 : 0];                   // the table form: the status word of the entry's index
+  Args a{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, infos, ws.data(), itype};
+  Desc d{A.data(), problem ? B.data() : nullptr, w.data(), Z.data(), n, n, n, n, 2, 0};
+  XVArgs v{problem, 1, &d, infos, ws.data(), itype};
   g_stop2 = getenv("STOP2") ? atoi(getenv("STOP2")) : 0;
   std::barrier<> bar(T);
   g_bar = &bar;
   std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) th.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (cong) xbatched_kernel<true>(a); else xbatched_kernel<false>(a); });
+  for (int t = 0; t < T; ++t) th.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (table) { if (cong) xbatched_kernel<true>(v); else xbatched_kernel<false>(v); } else if (cong) xbatched_kernel<true>(a); else xbatched_kernel<false>(a); });
   for (auto &x : th) x.join();
+  if (table && (infos[0] != 777 || infos[1] != 777)) { printf("a status word outside the entry's index was written\n"); return 1; }
   if (g_stop2) {
     // C = L^-1 A L^-T (types 2 and 3: L^T A L) from the L left in B
     std::vector<double> X((size_t)n * n), C((size_t)n * n);
@@ -172,4 +186,4 @@ if args.stop:
     env["STOP2"] = str(args.stop)
 if args.tsan:
     env.setdefault("TSAN_OPTIONS", "halt_on_error=1 history_size=4")
-sys.exit(subprocess.call([exe, str(args.n), str(args.problem), str(args.itype)], env=env))
+sys.exit(subprocess.call([exe, str(args.n), str(args.problem), str(args.itype), str(int(args.table))], env=env))
