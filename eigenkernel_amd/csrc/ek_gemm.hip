@@ -143,6 +143,78 @@ __host__ __device__ __forceinline__ bool tile_of(const GemmArgs &p, int tile, in
   return true;
 }
 
+// ---------------------------------------------------------------------------------------
+// Epilogue of the three LDS kernels: C <- alpha acc + beta C for the NI x MI accumulator blocks of a wave.  Element r of
+// acc[ni][mi] is row mw + 16 mi, column nw + 16 ni + 4 r (mw, nw: the lane's first row and column).  Written per element
+// as load, multiply-add, store, the compiler keeps every load behind the previous store to C and a wave makes one
+// dependent trip to memory per accumulator element.  Here the C values of QB blocks (block q = ni * MI + mi, 4 doubles per
+// lane each, in the registers the K loop has released) are fetched back to back, then combined, then stored: one wait
+// per batch (QB is chosen per kernel by measurement: see the calls).  MASK = false (whole tiles): no predicates; MASK = true (edge tiles): every load and store under its own
+// m < M && n < N, as gemm_rankk_kernel does -- no address outside the entry is formed into a load or a store.  Each element
+// is exactly fma(beta, c, alpha * acc) (what the per-element form compiled to); with beta == 0 C is never read.
+template <int MI, int QB, bool MASK>
+__device__ __forceinline__ void load_c(double (&c)[QB][4], int q0, const double *__restrict__ C, int ldc, int mw, int nw,
+                                       int M, int N) {
+#pragma unroll
+  for (int j = 0; j < QB; ++j) {
+    const int m = mw + ((q0 + j) % MI) * 16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = nw + ((q0 + j) / MI) * 16 + 4 * r;
+      c[j][r] = (!MASK || (m < M && n < N)) ? C[(size_t)m + (size_t)n * ldc] : 0.0;
+    }
+  }
+}
+// blocks q0 .. q0 + QB - 1 of acc with the values load_c() fetched for them (BETA = false: c is not looked at)
+template <int NI, int MI, int QB, bool MASK, bool BETA>
+__device__ __forceinline__ void store_c(const double4_t (&acc)[NI][MI], int q0, const double (&c)[QB][4],
+                                        double *__restrict__ C, int ldc, int mw, int nw, int M, int N, double alpha,
+                                        double beta) {
+  double v[QB][4];
+#pragma unroll
+  for (int j = 0; j < QB; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      v[j][r] = alpha * acc[(q0 + j) / MI][(q0 + j) % MI][r];
+      if (BETA) v[j][r] = __builtin_fma(beta, c[j][r], v[j][r]);
+      // the values of a masked batch are complete before the first predicated store: sunk into the stores' own
+      // blocks, each multiply-add would wait there for everything in flight, the previous store included
+      if (MASK && BETA) asm volatile("" : "+v"(v[j][r]));
+    }
+#pragma unroll
+  for (int j = 0; j < QB; ++j) {
+    const int m = mw + ((q0 + j) % MI) * 16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = nw + ((q0 + j) / MI) * 16 + 4 * r;
+      if (!MASK || (m < M && n < N)) C[(size_t)m + (size_t)n * ldc] = v[j][r];
+    }
+  }
+}
+// all NI * MI blocks in batches of QB
+template <int NI, int MI, int QB, bool MASK>
+__device__ __forceinline__ void epilogue_masked(const double4_t (&acc)[NI][MI], double *__restrict__ C, int ldc, int mw,
+                                                int nw, int M, int N, double alpha, double beta) {
+  static_assert((NI * MI) % QB == 0, "whole batches");
+  double c[QB][4];
+  if (beta != 0.0) {
+#pragma unroll
+    for (int q0 = 0; q0 < NI * MI; q0 += QB) {
+      load_c<MI, QB, MASK>(c, q0, C, ldc, mw, nw, M, N);
+      store_c<NI, MI, QB, MASK, true>(acc, q0, c, C, ldc, mw, nw, M, N, alpha, beta);
+    }
+  } else {
+#pragma unroll
+    for (int q0 = 0; q0 < NI * MI; q0 += QB) store_c<NI, MI, QB, MASK, false>(acc, q0, c, C, ldc, mw, nw, M, N, alpha, beta);
+  }
+}
+template <int NI, int MI, int QB>
+__device__ __forceinline__ void epilogue(const double4_t (&acc)[NI][MI], double *__restrict__ C, int ldc, int mw, int nw,
+                                         int M, int N, double alpha, double beta, bool whole) {
+  if (whole) epilogue_masked<NI, MI, QB, false>(acc, C, ldc, mw, nw, M, N, alpha, beta);
+  else epilogue_masked<NI, MI, QB, true>(acc, C, ldc, mw, nw, M, N, alpha, beta);
+}
+
 template <bool TA, bool TB, bool VEC>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
   __shared__ __attribute__((aligned(16))) double smem[2 * TILE_DOUBLES];
@@ -216,24 +288,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
     }
   }
 
-  // D[i][j]: i = n index = (lane>>4) + 4*reg, j = m index = lane&15
-  const double alpha = p.alpha, beta = p.beta;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      const int m = m0 + wm + mi * 16 + l15;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wn + ni * 16 + l4 + 4 * r;
-        if (m < p.M && n < p.N) {
-          double *c = C + (size_t)m + (size_t)n * p.ldc;
-          double v = alpha * acc[ni][mi][r];
-          if (beta != 0.0) v += beta * *c;
-          *c = v;
-        }
-      }
-    }
+  // D[i][j]: i = n index = (lane>>4) + 4*reg, j = m index = lane&15; four batches of 16 doubles
+  epilogue<4, 4, 4>(acc, C, p.ldc, m0 + wm + l15, n0 + wn + l4, p.M, p.N, p.alpha, p.beta, m0 + BM <= p.M && n0 + BN <= p.N);
 }
 
 // (Measured and withdrawn, round 4: the same kernel with K walked in steps of 32 -- half the barrier pairs, 2 x 36 KB of
@@ -369,23 +425,17 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel_w8(GemmArgs p) {
           acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
     }
   }
-  const double alpha = p.alpha, beta = p.beta;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      const int m = m0 + wm + mi * 16 + l15;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wn + ni * 16 + l4 + 4 * r;
-        if (m < p.M && n < p.N) {
-          double *c = C + (size_t)m + (size_t)n * p.ldc;
-          double v = alpha * acc[ni][mi][r];
-          if (beta != 0.0) v += beta * *c;
-          *c = v;
-        }
-      }
-    }
+  // Eight batches of one block (4 doubles per lane), chosen by measurement on the MI355X (lower NT, m = 12288, K = 128:
+  // 0.507 ms element by element, 0.467 in batches of 16, 0.460 of 8, 0.436 of 4; K = 256: 0.733, 0.737, 0.723, 0.704;
+  // DESIGN section 8).  The short-K updates this kernel runs move 256 KB of C per tile and sit near the HBM limit; the
+  // reading of the figures is that sixteen waves of a CU fetching 16 values each at once hold up the operand slabs of
+  // the neighbouring workgroup by more than the fewer waits gain.  The lane's row and column are formed again from the
+  // thread index behind the loop, so that no address of the epilogue occupies a register through it (this kernel lives
+  // on 128).
+  int te = threadIdx.x;
+  asm volatile("" : "+v"(te));
+  const int mw = m0 + ((te >> 6) & 1) * 64 + (te & 15), nw = n0 + (te >> 7) * 32 + ((te & 63) >> 4);
+  epilogue<2, 4, 1>(acc, C, p.ldc, mw, nw, p.M, p.N, p.alpha, p.beta, m0 + BM <= p.M && n0 + BN <= p.N);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -493,6 +543,18 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(GemmArgs p) {
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  // VEC: the C tile (16 doubles per lane) travels beside the first slabs, as in gemm_rankk_kernel -- nothing to wait for
+  // behind the K loop, which in this kernel's launches (a few tiles, short K) is most of its duration.  The scalar
+  // instantiations would leave their occupancy step with 32 registers more (three workgroups per CU: 168): they fetch it
+  // as one batch behind the loop.
+  const double alpha = p.alpha, beta = p.beta;
+  const bool whole = m0 + SM <= p.M && n0 + SN <= p.N;
+  const int mw = m0 + wm + l15, nw = n0 + wn + l4;
+  double cval[4][4];
+  if (VEC && beta != 0.0) {
+    if (whole) load_c<2, 4, false>(cval, 0, C, p.ldc, mw, nw, p.M, p.N);
+    else load_c<2, 4, true>(cval, 0, C, p.ldc, mw, nw, p.M, p.N);
+  }
   double ra[8], rb[8];
   if (VEC) { sload_slab_v<TA>(ra, A, p.lda, m0, p.M, 0, p.K, t); sload_slab_v<!TB>(rb, B, p.ldb, n0, p.N, 0, p.K, t); }
   else { sload_slab<TA>(ra, A, p.lda, m0, p.M, 0, p.K, t); sload_slab<!TB>(rb, B, p.ldb, n0, p.N, 0, p.K, t); }
@@ -520,23 +582,15 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(GemmArgs p) {
           acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
     }
   }
-  const double alpha = p.alpha, beta = p.beta;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const int m = m0 + wm + mi * 16 + l15;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wn + ni * 16 + l4 + 4 * r;
-        if (m < p.M && n < p.N) {
-          double *c = C + (size_t)m + (size_t)n * p.ldc;
-          double v = alpha * acc[ni][mi][r];
-          if (beta != 0.0) v += beta * *c;
-          *c = v;
-        }
-      }
-    }
+  if (!VEC) {
+    epilogue<2, 2, 4>(acc, C, p.ldc, mw, nw, p.M, p.N, alpha, beta, whole);
+  } else if (beta != 0.0) {
+    if (whole) store_c<2, 2, 4, false, true>(acc, 0, cval, C, p.ldc, mw, nw, p.M, p.N, alpha, beta);
+    else store_c<2, 2, 4, true, true>(acc, 0, cval, C, p.ldc, mw, nw, p.M, p.N, alpha, beta);
+  } else {
+    if (whole) store_c<2, 2, 4, false, false>(acc, 0, cval, C, p.ldc, mw, nw, p.M, p.N, alpha, beta);
+    else store_c<2, 2, 4, true, false>(acc, 0, cval, C, p.ldc, mw, nw, p.M, p.N, alpha, beta);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
