@@ -263,8 +263,6 @@ int ek_hip_finalize(void) {
   release_batched();
   release_xbatched();
   release_batched_check();
-  release_batched_check_x();
-  release_batched_check_sygv_x();
   // a communicator does not outlive the library's device state
   comm_teardown();
   return 0;

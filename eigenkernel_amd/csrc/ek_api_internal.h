@@ -80,10 +80,7 @@ int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int 
 int xvbatched_prepare(int count);  // its images (min(count, K) slots), to be called before the call's first event
 int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count, const batched::Desc *table,
                      int *dinfo);
-void release_batched_check();     // the batched checks' scratch, output words, table and events (ek_batched_check.hip)
-void release_batched_check_x();    // the same of ek_hip_check_xbatched* above EK_HIP_BATCH_NMAX (ek_batched_check_x.hip)
-int check_xbatched_chunk();        // checked problems per launch there (ek_hip_debug_check_xbatched_chunk); g_mu held
-void release_batched_check_sygv_x();   // the same of ek_hip_check_sygv_xbatched*, types 2 and 3 (ek_batched_check_sygv_x.hip)
+void release_batched_check();     // every batched check's scratch, output words, table and events (ek_batched_check.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);
 
 // device buffers of one host-array call: released on every exit path

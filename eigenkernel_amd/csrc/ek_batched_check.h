@@ -1,7 +1,11 @@
-// ek_batched_check.h -- what the two translation units of the batched acceptance checks share (not installed):
-//   ek_batched_check.hip       the entries, the host side, the kernel of the standard problem and of type 1
+// ek_batched_check.h -- what the translation units of the batched acceptance checks share (not installed):
+//   ek_batched_check.hip       the entries up to EK_HIP_BATCH_NMAX, the kernel of the standard problem and of type 1, and
+//                              the host side of every uniform-order entry: the argument checker, the device
+//                              pool with its one release function, the run function, the stager of host arrays
 //   ek_batched_check_sygv.hip  the kernel of DSYGV's types 2 and 3
-// The kernels live in two units so that adding the second leaves the code generated for the first as it was.
+//   ek_batched_check_x.hip, ek_batched_check_sygv_x.hip  the kernels above EK_HIP_BATCH_NMAX and their entries
+//                              (ek_batched_check_x.h), which hand the host driver a launch function
+// The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
 #pragma once
 #include "ek_api_internal.h"
 
@@ -116,6 +120,29 @@ constexpr int lds_doubles(int NC) { return NC * (NC + 1) + 8 * NC + NC + 4; }
 // one launch of the kernel of types 2 and 3 (itype) for `count` problems of class nc (32, 64, 128)
 int launch_sygv(hipStream_t s, int itype, int nc, int count, const Args &a);
 int launch_sygv(hipStream_t s, int itype, int nc, int count, const VArgs &a);
+
+// ---- the host driver of the uniform-order entries (ek_batched_check.hip)
+// One call.  itype: 0 the standard problem and type 1 (`problem` says which), 2 or 3 those types (problem = 1).  A, B, w
+// and Z are host or device arrays as the entry says, device arrays when a UniformLaunch sees them; the rest is host
+struct Uniform {
+  int itype, problem, n, batch;
+  const double *A; int lda; long long sA;
+  const double *B; int ldb; long long sB;
+  const double *w;
+  const double *Z; int ldz; long long sZ;
+  const int *info;
+  double *out, *ipr, *seconds;
+};
+// A unit's own part of a call: its Args and one launch of its kernel for the entries first .. first + count - 1 of the map
+// (nullptr: those problems), with the pool's scratch S and output words dout, dipr (nullptr: no IPRs)
+typedef int (*UniformLaunch)(hipStream_t s, const Uniform &u, const int *map, int first, int count, double *S, double *dout,
+                             double *dipr);
+// -1 .. -13, -15 as include/ek_hip.h lists them, n against nmax; *nothing: n == 0 or batch == 0
+int uniform_arguments(const Uniform &u, int nmax, bool *nothing);
+// the rest of an entry whose arguments are checked: *seconds = 0, the context, g_mu, device copies of host arrays, the
+// launches, the fetch and the scatter.  scratch: doubles per problem (chunked = false: one launch, indexed by problem
+// number) or per workgroup of a launch (chunked = true: ek_hip_debug_check_xbatched_chunk problems a launch)
+int uniform_entry(const Uniform &u, bool nothing, bool host, size_t scratch, bool chunked, UniformLaunch launch);
 
 }  // namespace bcheck
 }  // namespace ek

@@ -25,6 +25,11 @@
 // ek_hip_check_sygv_batched* / ek_hip_check_sygv_vbatched*  check DSYGV's types 2 (A B x = l x) and 3
 // (B A x = l x): the same entries, classes, table and scatter, with the kernel of ek_batched_check_sygv.hip in the place of
 // the one below (a translation unit of its own, so that the code generated for this one stays what it was).
+//
+// The host side of EVERY uniform-order check entry lives below the kernel: one argument checker, one device
+// pool with one release function, one run function and one stager of host arrays, declared in ek_batched_check.h.
+// ek_batched_check_x.hip and ek_batched_check_sygv_x.hip (orders above EK_HIP_BATCH_NMAX) keep their kernel, its launch
+// and thin entries, and hand this driver a launch function.  All entries serialise on g_mu, so one pool serves them all.
 #include "ek_batched_check.h"
 
 #include <algorithm>
@@ -175,8 +180,9 @@ static int launch_class(hipStream_t s, int count, const ARGS &a, int itype) {
 
 static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
 
-// Device memory the entries keep (grown, never shrunk, released in ek_hip_finalize): the scratch S, the output words
-// (out, then the IPRs), the table or the map of the problems to check; two events for `seconds`
+// Device memory the entries of all three units keep (grown, never shrunk, released in ek_hip_finalize): the scratch S, the
+// output words (out, then the IPRs), the table or the map of the problems to check; two events for `seconds`.  A call
+// writes what it reads: the map or table is uploaded whenever it is used, the scratch is written before it is read
 static double *g_scratch = nullptr, *g_dout = nullptr;
 static void *g_dtable = nullptr;
 static size_t g_scratch_count = 0, g_dout_count = 0, g_dtable_bytes = 0;
@@ -184,6 +190,8 @@ static hipEvent_t g_ev[2] = {nullptr, nullptr};
 static std::vector<Desc> g_htable;                  // host images: an upload may still read them when an error returns
 static std::vector<int> g_hmap;
 static std::vector<double> g_hout;
+constexpr int kChunk = 1024;                        // problems per launch of the kernels above EK_HIP_BATCH_NMAX, whose
+static int g_chunk = kChunk;                        // scratch is per workgroup (ek_hip_debug_check_xbatched_chunk)
 
 template <typename P>
 static int grow(P **p, size_t *have, size_t want, size_t unit) {
@@ -232,27 +240,28 @@ using namespace ek::api;
 
 static const double kNaN = std::nan("");
 
-static int uniform_check(int problem, int n, int batch, const void *A, int lda, long long strideA, const void *B,
-                         int ldb, long long strideB, const void *w, const void *Z, int ldz, long long strideZ,
-                         const double *out, bool *nothing) {
+// The argument errors of every uniform-order entry: nmax is the entry's largest order, B is looked at when u.problem is 1
+// (the entries of DSYGV's types call with problem = 1, after their own test of itype).  No data pointer is dereferenced.
+int ek::bcheck::uniform_arguments(const Uniform &u, int nmax, bool *nothing) {
+  const int n = u.n;
   *nothing = false;
-  if (problem != 0 && problem != 1) return -1;
-  if (n < 0 || n > EK_HIP_BATCH_NMAX) return -2;
-  if (batch < 0) return -3;
-  if (n == 0 || batch == 0) { *nothing = true; return 0; }
-  if (!A) return -4;
-  if (lda < n) return -5;
-  if (strideA < (long long)lda * n) return -6;
-  if (problem == 1) {
-    if (!B) return -7;
-    if (ldb < n) return -8;
-    if (strideB < (long long)ldb * n) return -9;
+  if (u.problem != 0 && u.problem != 1) return -1;
+  if (n < 0 || n > nmax) return -2;
+  if (u.batch < 0) return -3;
+  if (n == 0 || u.batch == 0) { *nothing = true; return 0; }
+  if (!u.A) return -4;
+  if (u.lda < n) return -5;
+  if (u.sA < (long long)u.lda * n) return -6;
+  if (u.problem == 1) {
+    if (!u.B) return -7;
+    if (u.ldb < n) return -8;
+    if (u.sB < (long long)u.ldb * n) return -9;
   }
-  if (!w) return -10;
-  if (!Z) return -11;
-  if (ldz < n) return -12;
-  if (strideZ < (long long)ldz * n) return -13;
-  if (!out) return -15;                             // 14 is info: NULL means every problem
+  if (!u.w) return -10;
+  if (!u.Z) return -11;
+  if (u.ldz < n) return -12;
+  if (u.sZ < (long long)u.ldz * n) return -13;
+  if (!u.out) return -15;                           // 14 is info: NULL means every problem
   return 0;
 }
 
@@ -298,41 +307,83 @@ static int run_and_fetch(size_t words, double *seconds, LAUNCH launch) {
   return rc;
 }
 
-// arguments checked (n > 0, batch > 0), context up, g_mu held; dA, dB, dw, dZ device, info / out / ipr host.  itype: 0 the
-// standard problem and type 1 (`problem` says which), 2 or 3 those types (problem = 1)
-static int uniform_device_locked(int itype, int problem, int n, int batch, const double *dA, int lda,
-                                 long long strideA, const double *dB, int ldb, long long strideB, const double *dw,
-                                 const double *dZ, int ldz, long long strideZ, const int *info, double *out, double *ipr,
-                                 double *seconds) {
+// arguments checked (n > 0, batch > 0), context up, g_mu held; u.A, u.B, u.w, u.Z device.  Everything of a call but the
+// kernel: the map of the problems to check from info, the pool, the events, the launches, the fetch, the scatter.
+// `chunked` says how the kernel indexes its scratch of `scratch` doubles: by problem number (false: one launch for all),
+// or by workgroup (true: g_chunk problems a launch, one after the other on the stream because they share the scratch)
+static int uniform_run(const bcheck::Uniform &u, size_t scratch, bool chunked, bcheck::UniformLaunch launch) {
   using namespace bcheck;
+  const int n = u.n, batch = u.batch;
   g_hmap.clear();
   bool skip = false;
-  if (info)
+  if (u.info)
     for (int b = 0; b < batch; ++b) {
-      if (info[b] == 0) g_hmap.push_back(b); else skip = true;
+      if (u.info[b] == 0) g_hmap.push_back(b); else skip = true;
     }
   const int count = skip ? (int)g_hmap.size() : batch;
-  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (ipr ? (size_t)batch * n : 0);
+  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (u.ipr ? (size_t)batch * n : 0);
   std::vector<size_t> off((size_t)batch);
   for (int b = 0; b < batch; ++b) off[b] = nout + (size_t)b * n;
-  int rc = 0;
   if (count > 0) {
-    rc = ensure(problem ? (size_t)batch * n * n : 0, words, skip ? g_hmap.size() * sizeof(int) : 0);
+    const int K = chunked ? g_chunk : count;
+    int rc = ensure((size_t)(chunked ? std::min(count, K) : batch) * scratch, words, skip ? g_hmap.size() * sizeof(int) : 0);
     if (rc) return rc;
-    rc = run_and_fetch(words, seconds, [&](hipStream_t s) -> int {
+    rc = run_and_fetch(words, u.seconds, [&](hipStream_t s) -> int {
       if (skip) EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_hmap.data(), g_hmap.size() * sizeof(int), hipMemcpyHostToDevice, s));
-      Args a{problem, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, skip ? (const int *)g_dtable : nullptr,
-             g_scratch, g_dout, ipr ? g_dout + nout : nullptr};
-      switch (class_of(n)) {
-        case 32: return launch_class<32, 64>(s, count, a, itype);
-        case 64: return launch_class<64, 128>(s, count, a, itype);
-        default: return launch_class<128, 256>(s, count, a, itype);
+      for (int c0 = 0; c0 < count; c0 += K) {
+        const int rcl = launch(s, u, skip ? (const int *)g_dtable : nullptr, c0, std::min(K, count - c0), g_scratch, g_dout,
+                               u.ipr ? g_dout + nout : nullptr);
+        if (rcl) return rcl;
       }
+      return 0;
     });
     if (rc) return rc;
   }
-  scatter(batch, [&](int) { return n; }, info, off, out, [&](int b) { return ipr ? ipr + (size_t)b * n : nullptr; });
+  scatter(batch, [&](int) { return n; }, u.info, off, u.out,
+          [&](int b) { return u.ipr ? u.ipr + (size_t)b * n : nullptr; });
   return 0;
+}
+
+// What follows the argument check in every uniform-order entry.  host: A, B, w and Z are host arrays and get device copies
+// with the caller's own layout, as in ek_hip_eigenpairs_batched (B only when the call has one)
+int ek::bcheck::uniform_entry(const Uniform &u, bool nothing, bool host, size_t scratch, bool chunked,
+                              UniformLaunch launch) {
+  if (u.seconds) *u.seconds = 0.0;
+  if (nothing) return 0;
+  int rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!host) return uniform_run(u, scratch, chunked, launch);
+  hipStream_t s = g_ctx.stream;
+  const int n = u.n, batch = u.batch, problem = u.problem;
+  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
+  const size_t cA = span(u.lda, u.sA), cB = problem ? span(u.ldb, u.sB) : 0, cZ = span(u.ldz, u.sZ);
+  const size_t cw = (size_t)batch * n;
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cA * 8);
+  if (!rc) rc = mem.alloc(&uw, cw * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
+  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(uA, u.A, cA * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, u.B, cB * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, u.w, cw * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uZ, u.Z, cZ * 8, hipMemcpyHostToDevice, s));
+  Uniform d = u;
+  d.A = uA; d.B = uB; d.w = uw; d.Z = uZ;
+  return uniform_run(d, scratch, chunked, launch);
+}
+
+// this unit's part of a call: the class kernels (orders up to EK_HIP_BATCH_NMAX) index everything by problem number
+static int launch_uniform(hipStream_t s, const bcheck::Uniform &u, const int *map, int, int count, double *S, double *dout,
+                          double *dipr) {
+  using namespace bcheck;
+  Args a{u.problem, u.n, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z, u.ldz, u.sZ, map, S, dout, dipr};
+  switch (class_of(u.n)) {
+    case 32: return launch_class<32, 64>(s, count, a, u.itype);
+    case 64: return launch_class<64, 128>(s, count, a, u.itype);
+    default: return launch_class<128, 256>(s, count, a, u.itype);
+  }
 }
 
 // All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.
@@ -420,51 +471,13 @@ static int variable_device_locked(int itype, int problem, int batch, const int *
   return 0;
 }
 
-// The four entries behind both families: ek_hip_check_*batched* (itype = 0) and ek_hip_check_sygv_*batched* (itype = 2, 3
+// The entries behind both families: ek_hip_check_*batched* (itype = 0) and ek_hip_check_sygv_*batched* (itype = 2, 3
 // with problem = 1; their itype 1 is problem 1 of the first family)
-static int uniform_device_entry(int itype, int problem, int n, int batch, const double *dA, int lda, long long strideA,
-                                const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
-                                int ldz, long long strideZ, const int *info, double *out, double *ipr,
-                                double *seconds) {
+static int class_entry(const bcheck::Uniform &u, bool host) {
   bool nothing;
-  int rc = uniform_check(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, out, &nothing);
+  int rc = bcheck::uniform_arguments(u, EK_HIP_BATCH_NMAX, &nothing);
   if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return uniform_device_locked(itype, problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                               out, ipr, seconds);
-}
-
-static int uniform_host_entry(int itype, int problem, int n, int batch, const double *A, int lda, long long strideA,
-                              const double *B, int ldb, long long strideB, const double *w, const double *Z, int ldz,
-                              long long strideZ, const int *info, double *out, double *ipr, double *seconds) {
-  bool nothing;
-  int rc = uniform_check(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, out, &nothing);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  // device copies with the caller's own layout, as in ek_hip_eigenpairs_batched
-  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
-  const size_t cA = span(lda, strideA), cB = problem ? span(ldb, strideB) : 0, cZ = span(ldz, strideZ);
-  const size_t cw = (size_t)batch * n;
-  DevMem mem;
-  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cA * 8);
-  if (!rc) rc = mem.alloc(&uw, cw * 8);
-  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
-  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
-  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  return uniform_device_locked(itype, problem, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info,
-                               out, ipr, seconds);
+  return bcheck::uniform_entry(u, nothing, host, u.problem ? (size_t)u.n * u.n : 0, false, launch_uniform);
 }
 
 static int variable_device_entry(int itype, int problem, int batch, const int *n, const double *const *dA,
@@ -559,15 +572,15 @@ int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA,
                                 const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                 int ldz, long long strideZ, const int *info, double *out, double *ipr,
                                 double *seconds) {
-  return uniform_device_entry(0, problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out,
-                              ipr, seconds);
+  return class_entry({0, problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out, ipr, seconds},
+                     false);
 }
 
 int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                          int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                          const int *info, double *out, double *ipr, double *seconds) {
-  return uniform_host_entry(0, problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
-                            seconds);
+  return class_entry({0, problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr, seconds},
+                     true);
 }
 
 int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
@@ -589,16 +602,16 @@ int ek_hip_check_sygv_batched_device(int itype, int n, int batch, const double *
                                      int ldz, long long strideZ, const int *info, double *out, double *ipr,
                                      double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return uniform_device_entry(itype == 1 ? 0 : itype, 1, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz,
-                              strideZ, info, out, ipr, seconds);
+  return class_entry({itype == 1 ? 0 : itype, 1, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                      out, ipr, seconds}, false);
 }
 
 int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                               int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                               const int *info, double *out, double *ipr, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return uniform_host_entry(itype == 1 ? 0 : itype, 1, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ,
-                            info, out, ipr, seconds);
+  return class_entry({itype == 1 ? 0 : itype, 1, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out,
+                      ipr, seconds}, true);
 }
 
 int ek_hip_check_sygv_vbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
@@ -615,6 +628,14 @@ int ek_hip_check_sygv_vbatched(int itype, int batch, const int *n, const double 
                                const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
   return variable_host_entry(itype == 1 ? 0 : itype, 1, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds);
+}
+
+// the problems per launch above EK_HIP_BATCH_NMAX (include/ek_hip_debug.h)
+int ek_hip_debug_check_xbatched_chunk(int problems) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int before = bcheck::g_chunk;
+  bcheck::g_chunk = problems > 0 ? problems : bcheck::kChunk;
+  return before;
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // ek_batched_check_sygv_x.hip -- ek_hip_check_sygv_xbatched*: the batched acceptance checks of DSYGV's types 2
 // (A B x = l x) and 3 (B A x = l x) for the orders EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX that ek_hip_sygv_xbatched*
 // solves.  Orders up to EK_HIP_BATCH_NMAX are forwarded to ek_hip_check_sygv_batched*, type 1 above them to
-// ek_hip_check_xbatched*(problem = 1); both translation units stay as they were.
+// ek_hip_check_xbatched*(problem = 1).  This unit holds the kernel, its launch and the entries; the argument checker, the
+// device pool, the chunk loop, the fetch and the scatter are ek_batched_check.hip's.
 //
 // One workgroup of 512 threads (8 waves) owns a problem from its first load to its last store.  The quantities are those
 // of DESIGN.md 16.  The three n^3 products of a type run on the fp64 matrix cores with the tiles, the loaders, the K step
@@ -27,8 +28,6 @@
 // kernel behind the host and the device form.  A, B, w and Z are read only; nothing strictly above a diagonal, at or
 // beyond row n or between the problems is read.
 #include "ek_batched_check_x.h"
-
-#include <algorithm>
 
 namespace ek {
 namespace xcheck_sygv {
@@ -401,26 +400,7 @@ __global__ __launch_bounds__(T) void xcheck_sygv_kernel(Args a) {
   }
 }
 
-// Device memory the entries keep (grown, never shrunk, released in ek_hip_finalize): the scratch of a launch, the output
-// words (out, then the IPRs), the map of the problems to check; two events for `seconds`
-static double *g_scratch = nullptr, *g_dout = nullptr;
-static int *g_dmap = nullptr;
-static size_t g_scratch_count = 0, g_dout_count = 0, g_dmap_count = 0;
-static hipEvent_t g_ev[2] = {nullptr, nullptr};
-static std::vector<int> g_hmap;                     // host images: an upload may still read them when an error returns
-static std::vector<double> g_hout;
 static bool g_raised[2] = {false, false};
-
-template <typename P>
-static int grow(P **p, size_t *have, size_t want) {
-  if (want <= *have) return 0;
-  if (*p) (void)hipFree((void *)*p);
-  *p = nullptr;
-  *have = 0;
-  EK_HIP_CHECK(hipMalloc((void **)p, want * sizeof(P)));
-  *have = want;
-  return 0;
-}
 
 template <int ITYPE>
 static int launch(hipStream_t s, int count, const Args &a) {
@@ -435,122 +415,34 @@ static int launch(hipStream_t s, int count, const Args &a) {
   return 0;
 }
 
-}  // namespace xcheck_sygv
-
-namespace api {
-void release_batched_check_sygv_x() {
-  using namespace xcheck_sygv;
-  if (g_scratch) (void)hipFree(g_scratch);
-  if (g_dout) (void)hipFree(g_dout);
-  if (g_dmap) (void)hipFree(g_dmap);
-  g_scratch = g_dout = nullptr;
-  g_dmap = nullptr;
-  g_scratch_count = g_dout_count = g_dmap_count = 0;
-  for (int k = 0; k < 2; ++k) {
-    if (g_ev[k]) (void)hipEventDestroy(g_ev[k]);
-    g_ev[k] = nullptr;
-  }
-  std::vector<int>().swap(g_hmap);
-  std::vector<double>().swap(g_hout);
+// this unit's part of a call (bcheck::uniform_entry does the rest): the scratch is indexed by workgroup
+static int launch_uniform(hipStream_t s, const bcheck::Uniform &u, const int *map, int first, int count, double *S,
+                          double *dout, double *dipr) {
+  Args a{u.itype, u.n, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z, u.ldz, u.sZ, map, first, S, dout, dipr};
+  return u.itype == 2 ? launch<2>(s, count, a) : launch<3>(s, count, a);
 }
-}  // namespace api
+
+static int entry(const bcheck::Uniform &u, bool nothing, bool host) {
+  return bcheck::uniform_entry(u, nothing, host, (size_t)(u.itype - 1) * u.n * u.n, true, launch_uniform);
+}
+
+}  // namespace xcheck_sygv
 }  // namespace ek
 
 using namespace ek;
-using namespace ek::api;
-
-// the argument errors of ek_hip_check_sygv_batched* with EK_HIP_XBATCH_NMAX in the place of EK_HIP_BATCH_NMAX; no data
-// pointer is dereferenced
-static int xcheck_sygv_arguments(int itype, int n, int batch, const void *A, int lda, long long strideA, const void *B,
-                                 int ldb, long long strideB, const void *w, const void *Z, int ldz, long long strideZ,
-                                 const double *out, bool *nothing) {
-  *nothing = false;
-  if (itype < 1 || itype > 3) return -1;
-  if (n < 0 || n > EK_HIP_XBATCH_NMAX) return -2;
-  if (batch < 0) return -3;
-  if (n == 0 || batch == 0) { *nothing = true; return 0; }
-  if (!A) return -4;
-  if (lda < n) return -5;
-  if (strideA < (long long)lda * n) return -6;
-  if (!B) return -7;
-  if (ldb < n) return -8;
-  if (strideB < (long long)ldb * n) return -9;
-  if (!w) return -10;
-  if (!Z) return -11;
-  if (ldz < n) return -12;
-  if (strideZ < (long long)ldz * n) return -13;
-  if (!out) return -15;                             // 14 is info: NULL means every problem
-  return 0;
-}
-
-// arguments checked (itype 2 or 3, EK_HIP_BATCH_NMAX < n, batch > 0), context up, g_mu held; dA, dB, dw, dZ device,
-// info / out / ipr host
-static int xcheck_sygv_device_locked(int itype, int n, int batch, const double *dA, int lda, long long strideA,
-                                     const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
-                                     int ldz, long long strideZ, const int *info, double *out, double *ipr,
-                                     double *seconds) {
-  using namespace xcheck_sygv;
-  static const double kNaN = std::nan("");
-  g_hmap.clear();
-  bool skip = false;
-  if (info)
-    for (int b = 0; b < batch; ++b) {
-      if (info[b] == 0) g_hmap.push_back(b); else skip = true;
-    }
-  const int count = skip ? (int)g_hmap.size() : batch;
-  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (ipr ? (size_t)batch * n : 0);
-  if (count > 0) {
-    const int K = check_xbatched_chunk();
-    { int rc = grow(&g_scratch, &g_scratch_count, (size_t)std::min(count, K) * (itype - 1) * n * n); if (rc) return rc; }
-    { int rc = grow(&g_dout, &g_dout_count, words); if (rc) return rc; }
-    { int rc = grow(&g_dmap, &g_dmap_count, skip ? g_hmap.size() : 0); if (rc) return rc; }
-    for (int k = 0; k < 2; ++k)
-      if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
-    hipStream_t s = g_ctx.stream;
-    if (seconds) (void)hipEventRecord(g_ev[0], s);
-    int rc = [&]() -> int {
-      if (skip) EK_HIP_CHECK(hipMemcpyAsync(g_dmap, g_hmap.data(), g_hmap.size() * sizeof(int), hipMemcpyHostToDevice, s));
-      for (int c0 = 0; c0 < count; c0 += K) {       // one after the other on the stream: they share the scratch
-        Args a{itype, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, skip ? g_dmap : nullptr, c0,
-               g_scratch, g_dout, ipr ? g_dout + nout : nullptr};
-        const int rcl = itype == 2 ? launch<2>(s, std::min(K, count - c0), a) : launch<3>(s, std::min(K, count - c0), a);
-        if (rcl) return rcl;
-      }
-      return 0;
-    }();
-    if (seconds) (void)hipEventRecord(g_ev[1], s);
-    g_hout.resize(words);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(g_hout.data(), g_dout, words * sizeof(double), hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess && !rc) rc = -1000 - (int)e;
-    if (rc) return rc;
-    if (seconds) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess) *seconds = (double)ms * 1e-3;
-    }
-  }
-  for (int b = 0; b < batch; ++b) {                 // the scatter: a skipped problem gets NaN and keeps its ipr
-    double *o = out + (size_t)b * EK_HIP_CHECK_NOUT;
-    if (info && info[b] != 0) {
-      o[0] = o[1] = o[2] = o[3] = kNaN;
-    } else {
-      std::memcpy(o, g_hout.data() + (size_t)b * EK_HIP_CHECK_NOUT, EK_HIP_CHECK_NOUT * sizeof(double));
-      if (ipr) std::memcpy(ipr + (size_t)b * n, g_hout.data() + nout + (size_t)b * n, (size_t)n * sizeof(double));
-    }
-  }
-  return 0;
-}
 
 extern "C" {
 
+// the argument errors of ek_hip_check_sygv_batched* with EK_HIP_XBATCH_NMAX in the place of EK_HIP_BATCH_NMAX
 int ek_hip_check_sygv_xbatched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
                                       const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                       int ldz, long long strideZ, const int *info, double *out, double *ipr,
                                       double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  const bcheck::Uniform u{itype, 1, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out, ipr,
+                          seconds};
   bool nothing;
-  int rc = xcheck_sygv_arguments(itype, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, out, &nothing);
+  int rc = bcheck::uniform_arguments(u, EK_HIP_XBATCH_NMAX, &nothing);
   if (rc) return rc;
   if (n <= EK_HIP_BATCH_NMAX)                       // n = 0 included: the same answers, the same kernel, the same bits
     return ek_hip_check_sygv_batched_device(itype, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
@@ -558,19 +450,17 @@ int ek_hip_check_sygv_xbatched_device(int itype, int n, int batch, const double 
   if (itype == 1)                                   // type 1 is problem 1 of the first family
     return ek_hip_check_xbatched_device(1, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out,
                                         ipr, seconds);
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return xcheck_sygv_device_locked(itype, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out,
-                                   ipr, seconds);
+  return xcheck_sygv::entry(u, nothing, false);
 }
 
 int ek_hip_check_sygv_xbatched(int itype, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                                int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                                const int *info, double *out, double *ipr, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  const bcheck::Uniform u{itype, 1, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
+                          seconds};
   bool nothing;
-  int rc = xcheck_sygv_arguments(itype, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, out, &nothing);
+  int rc = bcheck::uniform_arguments(u, EK_HIP_XBATCH_NMAX, &nothing);
   if (rc) return rc;
   if (n <= EK_HIP_BATCH_NMAX)
     return ek_hip_check_sygv_batched(itype, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
@@ -578,28 +468,7 @@ int ek_hip_check_sygv_xbatched(int itype, int n, int batch, const double *A, int
   if (itype == 1)
     return ek_hip_check_xbatched(1, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
                                  seconds);
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  // device copies with the caller's own layout, as in ek_hip_check_xbatched
-  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
-  const size_t cA = span(lda, strideA), cB = span(ldb, strideB), cZ = span(ldz, strideZ);
-  const size_t cw = (size_t)batch * n;
-  DevMem mem;
-  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cA * 8);
-  if (!rc) rc = mem.alloc(&uw, cw * 8);
-  if (!rc) rc = mem.alloc(&uB, cB * 8);
-  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  return xcheck_sygv_device_locked(itype, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info, out,
-                                   ipr, seconds);
+  return xcheck_sygv::entry(u, nothing, true);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 //   ek_batched_check_sygv_x.hip  ek_hip_check_sygv_xbatched*: DSYGV's types 2 and 3
 // Everything here is inlined into its caller; the code generated for the first unit is what it was before the second
 // existed (DESIGN.md 20 records the comparison).
+// Both units hold a kernel, its launch and thin entries; their host side is the driver of ek_batched_check.h.
 #pragma once
 #include "ek_batched_check.h"
 

@@ -1,6 +1,7 @@
 // ek_batched_check_x.hip -- ek_hip_check_xbatched*: the batched acceptance checks for the orders
 // EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX that ek_hip_eigenpairs_xbatched* solves.  Orders up to
-// EK_HIP_BATCH_NMAX are forwarded to ek_hip_check_batched*, whose translation unit this one leaves as it was.
+// EK_HIP_BATCH_NMAX are forwarded to ek_hip_check_batched*.  This unit holds the kernel, its launch and the entries; the
+// argument checker, the device pool, the chunk loop, the fetch and the scatter are ek_batched_check.hip's.
 //
 // One workgroup of 512 threads (8 waves) owns a problem from its first load to its last store.  At these orders neither Z
 // nor S = B Z nor A Z fits in LDS (512 KB each at n = 256), so the three products run on the fp64 matrix cores
@@ -24,13 +25,10 @@
 // kernel behind the host and the device form.  A, B, w and Z are read only.
 #include "ek_batched_check_x.h"
 
-#include <algorithm>
-
 namespace ek {
 namespace xcheck {
 
 constexpr int kBuf = 2 * kTileP + kTileQ;           // A, B, Z of one step (step 2: Z^T, unused, S)
-constexpr int kChunk = 1024;                        // problems per launch
 
 // LDS doubles: two buffers, the waves' column sums of r^2, z s and z^4, 1 / sqrt(G_jj), a word per wave
 constexpr int kLdsDoubles = 2 * kBuf + 3 * NW * TN + EK_HIP_XBATCH_NMAX + NW;
@@ -220,27 +218,7 @@ __global__ __launch_bounds__(T) void xcheck_kernel(Args a) {
   }
 }
 
-// Device memory the entries keep (grown, never shrunk, released in ek_hip_finalize): the scratch S of a launch, the output
-// words (out, then the IPRs), the map of the problems to check; two events for `seconds`
-static double *g_scratch = nullptr, *g_dout = nullptr;
-static int *g_dmap = nullptr;
-static size_t g_scratch_count = 0, g_dout_count = 0, g_dmap_count = 0;
-static hipEvent_t g_ev[2] = {nullptr, nullptr};
-static std::vector<int> g_hmap;                     // host images: an upload may still read them when an error returns
-static std::vector<double> g_hout;
-static int g_chunk = kChunk;
 static bool g_raised[2] = {false, false};
-
-template <typename P>
-static int grow(P **p, size_t *have, size_t want) {
-  if (want <= *have) return 0;
-  if (*p) (void)hipFree((void *)*p);
-  *p = nullptr;
-  *have = 0;
-  EK_HIP_CHECK(hipMalloc((void **)p, want * sizeof(P)));
-  *have = want;
-  return 0;
-}
 
 template <bool GEN>
 static int launch(hipStream_t s, int count, const Args &a) {
@@ -255,173 +233,52 @@ static int launch(hipStream_t s, int count, const Args &a) {
   return 0;
 }
 
-}  // namespace xcheck
-
-namespace api {
-int check_xbatched_chunk() { return xcheck::g_chunk; }
-
-void release_batched_check_x() {
-  using namespace xcheck;
-  if (g_scratch) (void)hipFree(g_scratch);
-  if (g_dout) (void)hipFree(g_dout);
-  if (g_dmap) (void)hipFree(g_dmap);
-  g_scratch = g_dout = nullptr;
-  g_dmap = nullptr;
-  g_scratch_count = g_dout_count = g_dmap_count = 0;
-  for (int k = 0; k < 2; ++k) {
-    if (g_ev[k]) (void)hipEventDestroy(g_ev[k]);
-    g_ev[k] = nullptr;
-  }
-  std::vector<int>().swap(g_hmap);
-  std::vector<double>().swap(g_hout);
+// this unit's part of a call (bcheck::uniform_entry does the rest): the scratch is indexed by workgroup
+static int launch_uniform(hipStream_t s, const bcheck::Uniform &u, const int *map, int first, int count, double *S,
+                          double *dout, double *dipr) {
+  Args a{u.problem, u.n, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z, u.ldz, u.sZ, map, first, S, dout, dipr};
+  return u.problem ? launch<true>(s, count, a) : launch<false>(s, count, a);
 }
-}  // namespace api
+
+static int entry(const bcheck::Uniform &u, bool nothing, bool host) {
+  return bcheck::uniform_entry(u, nothing, host, u.problem ? (size_t)u.n * u.n : 0, true, launch_uniform);
+}
+
+}  // namespace xcheck
 }  // namespace ek
 
 using namespace ek;
-using namespace ek::api;
-
-// the argument errors of ek_hip_check_batched* with EK_HIP_XBATCH_NMAX in the place of EK_HIP_BATCH_NMAX
-static int xcheck_arguments(int problem, int n, int batch, const void *A, int lda, long long strideA, const void *B,
-                            int ldb, long long strideB, const void *w, const void *Z, int ldz, long long strideZ,
-                            const double *out, bool *nothing) {
-  *nothing = false;
-  if (problem != 0 && problem != 1) return -1;
-  if (n < 0 || n > EK_HIP_XBATCH_NMAX) return -2;
-  if (batch < 0) return -3;
-  if (n == 0 || batch == 0) { *nothing = true; return 0; }
-  if (!A) return -4;
-  if (lda < n) return -5;
-  if (strideA < (long long)lda * n) return -6;
-  if (problem == 1) {
-    if (!B) return -7;
-    if (ldb < n) return -8;
-    if (strideB < (long long)ldb * n) return -9;
-  }
-  if (!w) return -10;
-  if (!Z) return -11;
-  if (ldz < n) return -12;
-  if (strideZ < (long long)ldz * n) return -13;
-  if (!out) return -15;                             // 14 is info: NULL means every problem
-  return 0;
-}
-
-// arguments checked (EK_HIP_BATCH_NMAX < n, batch > 0), context up, g_mu held; dA, dB, dw, dZ device, info / out / ipr host
-static int xcheck_device_locked(int problem, int n, int batch, const double *dA, int lda, long long strideA,
-                                const double *dB, int ldb, long long strideB, const double *dw, const double *dZ, int ldz,
-                                long long strideZ, const int *info, double *out, double *ipr, double *seconds) {
-  using namespace xcheck;
-  static const double kNaN = std::nan("");
-  g_hmap.clear();
-  bool skip = false;
-  if (info)
-    for (int b = 0; b < batch; ++b) {
-      if (info[b] == 0) g_hmap.push_back(b); else skip = true;
-    }
-  const int count = skip ? (int)g_hmap.size() : batch;
-  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (ipr ? (size_t)batch * n : 0);
-  if (count > 0) {
-    const int K = g_chunk;
-    { int rc = grow(&g_scratch, &g_scratch_count, problem ? (size_t)std::min(count, K) * n * n : 0); if (rc) return rc; }
-    { int rc = grow(&g_dout, &g_dout_count, words); if (rc) return rc; }
-    { int rc = grow(&g_dmap, &g_dmap_count, skip ? g_hmap.size() : 0); if (rc) return rc; }
-    for (int k = 0; k < 2; ++k)
-      if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
-    hipStream_t s = g_ctx.stream;
-    if (seconds) (void)hipEventRecord(g_ev[0], s);
-    int rc = [&]() -> int {
-      if (skip) EK_HIP_CHECK(hipMemcpyAsync(g_dmap, g_hmap.data(), g_hmap.size() * sizeof(int), hipMemcpyHostToDevice, s));
-      for (int c0 = 0; c0 < count; c0 += K) {       // one after the other on the stream: they share the scratch
-        Args a{problem, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, skip ? g_dmap : nullptr, c0,
-               g_scratch, g_dout, ipr ? g_dout + nout : nullptr};
-        const int rcl = problem ? launch<true>(s, std::min(K, count - c0), a) : launch<false>(s, std::min(K, count - c0), a);
-        if (rcl) return rcl;
-      }
-      return 0;
-    }();
-    if (seconds) (void)hipEventRecord(g_ev[1], s);
-    g_hout.resize(words);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(g_hout.data(), g_dout, words * sizeof(double), hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess && !rc) rc = -1000 - (int)e;
-    if (rc) return rc;
-    if (seconds) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess) *seconds = (double)ms * 1e-3;
-    }
-  }
-  for (int b = 0; b < batch; ++b) {                 // the scatter: a skipped problem gets NaN and keeps its ipr
-    double *o = out + (size_t)b * EK_HIP_CHECK_NOUT;
-    if (info && info[b] != 0) {
-      o[0] = o[1] = o[2] = o[3] = kNaN;
-    } else {
-      std::memcpy(o, g_hout.data() + (size_t)b * EK_HIP_CHECK_NOUT, EK_HIP_CHECK_NOUT * sizeof(double));
-      if (ipr) std::memcpy(ipr + (size_t)b * n, g_hout.data() + nout + (size_t)b * n, (size_t)n * sizeof(double));
-    }
-  }
-  return 0;
-}
 
 extern "C" {
 
+// the argument errors of ek_hip_check_batched* with EK_HIP_XBATCH_NMAX in the place of EK_HIP_BATCH_NMAX
 int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                  const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                  int ldz, long long strideZ, const int *info, double *out, double *ipr,
                                  double *seconds) {
+  const bcheck::Uniform u{0, problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out, ipr,
+                          seconds};
   bool nothing;
-  int rc = xcheck_arguments(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, out, &nothing);
+  int rc = bcheck::uniform_arguments(u, EK_HIP_XBATCH_NMAX, &nothing);
   if (rc) return rc;
   if (n <= EK_HIP_BATCH_NMAX)                       // n = 0 included: the same answers, the same kernel, the same bits
     return ek_hip_check_batched_device(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
                                        out, ipr, seconds);
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return xcheck_device_locked(problem, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info, out, ipr,
-                              seconds);
+  return xcheck::entry(u, nothing, false);
 }
 
 int ek_hip_check_xbatched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                           int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                           const int *info, double *out, double *ipr, double *seconds) {
+  const bcheck::Uniform u{0, problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
+                          seconds};
   bool nothing;
-  int rc = xcheck_arguments(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, out, &nothing);
+  int rc = bcheck::uniform_arguments(u, EK_HIP_XBATCH_NMAX, &nothing);
   if (rc) return rc;
   if (n <= EK_HIP_BATCH_NMAX)
     return ek_hip_check_batched(problem, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info, out, ipr,
                                 seconds);
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  // device copies with the caller's own layout, as in ek_hip_check_batched
-  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
-  const size_t cA = span(lda, strideA), cB = problem ? span(ldb, strideB) : 0, cZ = span(ldz, strideZ);
-  const size_t cw = (size_t)batch * n;
-  DevMem mem;
-  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cA * 8);
-  if (!rc) rc = mem.alloc(&uw, cw * 8);
-  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
-  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
-  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  return xcheck_device_locked(problem, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ, info, out, ipr,
-                              seconds);
-}
-
-int ek_hip_debug_check_xbatched_chunk(int problems) {
-  std::lock_guard<std::mutex> lk(ek::api::g_mu);
-  const int before = ek::xcheck::g_chunk;
-  ek::xcheck::g_chunk = problems > 0 ? problems : ek::xcheck::kChunk;
-  return before;
+  return xcheck::entry(u, nothing, true);
 }
 
 }  // extern "C"

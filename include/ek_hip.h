@@ -589,7 +589,8 @@ int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int 
  * host synchronise in between; one copy brings the output words to the host, where they are scattered.
  * Workspace there (device memory, grown on demand, kept until ek_hip_finalize): for each of the min(checked problems, 1024)
  * problems of a chunk n^2 doubles for type 2 (S = B Z; at most 512 MiB) and 2 n^2 for type 3 (A Z, then L, and W; at most
- * 1 GiB), 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
+ * 1 GiB), 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.  All
+ * ek_hip_check_*batched* entries draw on ONE such set of buffers, as large as the largest call so far needed.
  * ek_hip_check_sygv_batched* and ek_hip_check_batched* keep answering -2 above EK_HIP_BATCH_NMAX.  Not offered: a
  * check of the variable-order form above EK_HIP_BATCH_NMAX (ek_hip_sygv_xvbatched*' results are checked one order at a time
  * here). */

@@ -178,14 +178,15 @@ def _same(a, b):
 
 # ------------------------------------------------------------------------------------------------------- the calls
 def _uniform(lib, form, first, A, B, w, Z, info=None, ipr=True, pad=0, fill=SENTINEL, entry=NEW):
-    """entry[_device](first, ...) on strided images of A[b], B[b], Z[b] (full matrices: both triangles as given); `first`
-    is the entry's first argument (itype, or problem for ek_hip_check_xbatched): pad = 0 the compact layout, pad > 0 leading
+    """entry[_device](first, ...) on strided images of A[b], B[b], Z[b] (full matrices: both triangles as given; B = None: a
+    null pointer, for the standard problem of the first family); `first` is the entry's first argument (itype, or problem
+    for ek_hip_check_[x]batched): pad = 0 the compact layout, pad > 0 leading
     dimensions n + pad .. and strides beyond ld * n, the gaps holding `fill`.  o.untouched: the images of A, B, w, Z after
     the call equal those before it, byte for byte."""
     batch, n = A.shape[0], A.shape[1]
     lda, ldb, ldz = (n + pad, n + 2 * pad, n + 3 * pad) if pad else (n, n, n)
     sA, sB, sZ = lda * n + (5 if pad else 0), ldb * n + (3 if pad else 0), ldz * n + (7 if pad else 0)
-    h = [_pack(A, lda, sA, fill), _pack(B, ldb, sB, fill),
+    h = [_pack(A, lda, sA, fill), _pack(B, ldb, sB, fill) if B is not None else np.zeros(1),
          np.ascontiguousarray(w).reshape(-1).copy() if w.size else np.zeros(1), _pack(Z, ldz, sZ, fill)]
     out = np.full(batch * 4 + 2, SENTINEL)
     q = np.full(batch * n + 3, SENTINEL)
@@ -197,12 +198,14 @@ def _uniform(lib, form, first, A, B, w, Z, info=None, ipr=True, pad=0, fill=SENT
     if form == "device":
         with _Dev(lib) as dev:
             d = [dev.up(x) for x in h]
-            o.rc = getattr(lib, entry + "_device")(first, n, batch, d[0], lda, sA, d[1], ldb, sB, d[2], d[3], ldz, sZ, *tail)
+            o.rc = getattr(lib, entry + "_device")(first, n, batch, d[0], lda, sA, d[1] if B is not None else None, ldb, sB,
+                                                   d[2], d[3], ldz, sZ, *tail)
             o.untouched = all(_same(dev.down(p, x), x) for p, x in zip(d, h))
     else:
         g = [x.copy() for x in h]
         P = [x.ctypes.data_as(_dp) for x in g]
-        o.rc = getattr(lib, entry)(first, n, batch, P[0], lda, sA, P[1], ldb, sB, P[2], P[3], ldz, sZ, *tail)
+        o.rc = getattr(lib, entry)(first, n, batch, P[0], lda, sA, P[1] if B is not None else None, ldb, sB, P[2], P[3],
+                                   ldz, sZ, *tail)
         o.untouched = all(_same(y, x) for y, x in zip(g, h))
     o.seconds = sec.value
     o.out, o.ipr = out[:batch * 4].reshape(batch, 4), q[:batch * n].reshape(batch, n)
@@ -588,3 +591,99 @@ def test_the_check_against_the_solve_and_the_host_loop(hip, n, itype):
           % (n, itype, batch, ts * 1e3, tc * 1e3, wc * 1e3, tc / ts, tc / t1, wl * 1e3, wl / wc))
     assert 0.0 < tc <= ts, (tc, ts)
     assert wc < wl, (wc, wl)
+
+
+# ------------------------------------------------------------------------ 12: one device pool behind every family
+def _mirror1(A, B, w, Z):
+    """The mirror of the standard problem (B = None) and of type 1."""
+    a_norm, ave, mx = verifier.eval_residual_norm(A, w, Z, B)
+    return np.array([a_norm, ave, mx, verifier.eval_orthogonality(Z, B)]), verifier.get_ipratios(Z, B)
+
+
+@functools.lru_cache(maxsize=None)
+def _pool_inputs():
+    """The fixed inputs of the five calls below, from _pairs and SciPy's pairs perturbed as in _cases.  Read only."""
+    def solved(seed, batch, n, itype, with_b=True):
+        A, B = _pairs(seed, batch, n) if n else (np.zeros((batch, 0, 0)), np.zeros((batch, 0, 0)))
+        w, Z = np.zeros((batch, n)), np.zeros((batch, n, n))
+        for b in range(batch if n else 0):
+            w[b], Z[b] = sl.eigh(A[b], B[b], type=itype, lower=True) if with_b else sl.eigh(A[b], lower=True)
+        Zp = Z + 1e-3 * np.random.default_rng(seed + 7).standard_normal(Z.shape) / np.sqrt(n)
+        for a in (A, B, w, Zp):
+            a.setflags(write=False)
+        return A, (B if with_b else None), w, Zp
+
+    c = _Out()
+    c.gen40 = solved(31040, 5, 40, 1)
+    c.x129 = tuple(a[:3] for a in (_cases(129, 3).A, _cases(129, 3).B, _cases(129, 3).w, _cases(129, 3).Zp))
+    c.std130 = solved(31130, 3, 130, 1, with_b=False)
+    c.var = [solved(31200 + n, 1, n, 1) for n in (0, 33, 64)]
+    c.t2_40 = solved(32040, 5, 40, 2)
+    return c
+
+
+def _pool_round(hip, lib):
+    """The entries of all three units and the variable form one after the other, host forms: each call finds in the pool
+    what the call before it left there."""
+    c = _pool_inputs()
+    r = []
+    # an int map in the table buffer, a small scratch
+    r.append(_uniform(lib, "host", 1, *c.gen40, info=[0, 3, 0, 0, 0], entry="ek_hip_check_batched"))
+    # the scratch grows to 2 * 2 * 129^2 doubles, two launches, no map
+    try:
+        hip.check_xbatched_chunk(2)
+        r.append(_uniform(lib, "host", 3, *c.x129))
+    finally:
+        hip.check_xbatched_chunk(0)
+    # no scratch asked for while the pool holds a large one, a map shorter than the first call's, no IPRs
+    r.append(_uniform(lib, "host", 0, *c.std130, info=[0, 0, 2], ipr=False, entry="ek_hip_check_xbatched"))
+    # a table of descriptors where the map was
+    v = _Out()
+    v.out, v.iprs = hip.check_vbatched([x[0][0] for x in c.var], [x[1][0] for x in c.var], [x[2][0] for x in c.var],
+                                       [x[3][0] for x in c.var])
+    r.append(v)
+    r.append(_uniform(lib, "host", 2, *c.t2_40, entry="ek_hip_check_sygv_batched"))
+    return r
+
+
+def test_one_pool_serves_every_family_in_turn(hip):
+    """ek_hip_check_batched (generalized, n = 40, a skipped problem), ek_hip_check_sygv_xbatched (type 3, n = 129, chunks of
+    2), ek_hip_check_xbatched (standard, n = 130, a skipped problem, no IPRs), ek_hip_check_vbatched (orders 0, 33, 64) and
+    ek_hip_check_sygv_batched (type 2, n = 40) share one scratch, one buffer of output words, one table / map buffer and
+    two events.  The sequence runs twice: the second round's words are the first round's bit for bit, NaN
+    slots included; a skipped problem has NaN in its four slots and its IPR row untouched; every call of the first round
+    agrees with the host mirror within the bounds of the tests above (4 max(n, 8) eps, max(1, cond_2(B)) wider for slot 3
+    and the IPRs of type 3)."""
+    lib = hip.load_library()
+    c = _pool_inputs()
+    first, second = _pool_round(hip, lib), _pool_round(hip, lib)
+    for k, (a, b) in enumerate(zip(first, second)):
+        if k == 3:
+            assert _same(a.out, b.out) and all(_same(x, y) for x, y in zip(a.iprs, b.iprs))
+        else:
+            _clean(a, a.out.shape[0])
+            _clean(b, b.out.shape[0])
+            assert _same(a.out, b.out) and _same(a.ipr, b.ipr), k
+    g40, x129, s130, var, t40 = first
+    # the skipped problems
+    assert np.all(np.isnan(g40.out[1])) and np.all(g40.ipr[1] == SENTINEL)
+    assert np.all(np.isnan(s130.out[2])) and np.all(s130.ipr == SENTINEL)
+    # the mirror
+    A, B, w, Z = c.gen40
+    _assert_shares([_shares(1, g40.out[b], g40.ipr[b], *_mirror1(A[b], B[b], w[b], Z[b]), 40, 1.0) for b in (0, 2, 3, 4)],
+                   ("pool", "check_batched", 40))
+    ref, cond = _mirror_cases(129, 3), _cases(129, 3).cond
+    _assert_shares([_shares(3, x129.out[b], x129.ipr[b], ref[b][0], ref[b][1], 129, cond[b]) for b in range(3)],
+                   ("pool", "check_sygv_xbatched", 129))
+    A, _, w, Z = c.std130
+    for b in (0, 1):
+        m_out, m_ipr = _mirror1(A[b], None, w[b], Z[b])
+        _assert_shares([_shares(1, s130.out[b], m_ipr, m_out, m_ipr, 130, 1.0)], ("pool", "check_xbatched", 130, b))
+    assert var.out[0, 0] == 0.0 and np.all(np.isnan(var.out[0, 1:])) and var.iprs[0].size == 0
+    for b, n in ((1, 33), (2, 64)):
+        A, B, w, Z = (x[0] for x in c.var[b])
+        _assert_shares([_shares(1, var.out[b], var.iprs[b], *_mirror1(A, B, w, Z), n, 1.0)],
+                       ("pool", "check_vbatched", n))
+    A, B, w, Z = c.t2_40
+    _assert_shares([_shares(2, t40.out[b], t40.ipr[b], *_mirror(2, A[b], B[b], w[b], Z[b]), 40, 1.0) for b in range(5)],
+                   ("pool", "check_sygv_batched", 40))
