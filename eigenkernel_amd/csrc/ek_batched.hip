@@ -1,9 +1,10 @@
 // ek_batched.hip -- ek_hip_eigenpairs_batched*: many small problems (order <= EK_HIP_BATCH_NMAX) in ONE launch.
 //
 // One workgroup owns a problem from its first load to its last store, and the matrix it works on lives in LDS the
-// whole time: there is no launch and no host synchronise between the stages.
+// whole time: there is no launch and no host synchronise between the stages.  block_reduce, stage 0 and
+// the rank sort are those of ek_batched_stages.h, which ek_batched_x.hip uses too.
 //
-//   0  the lower triangle of A is read once for NaN / Inf (info -5) and for max|a|: outside 2^-256 .. 2^256 the image
+//   0  scan_a: A's lower triangle is read once for NaN / Inf (info -5) and for max|a|: outside 2^-256 .. 2^256 the image
 //      of stage 2 is A times an exact power of two, and d, e, w go out multiplied back
 //   1  B's lower triangle -> LDS, right-looking Cholesky in LDS, L -> dB (lower triangle); a pivot that is not
 //      positive (or outside 1e-290 .. 1e290, or NaN) ends the problem with info = its 1-based index
@@ -38,13 +39,13 @@
 // ek_hip_eigenpairs_vbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in
 // a table instead of at blockIdx.x * stride; every problem runs in the class its own order picks (the uniform call's
 // bits), the classes as one launch each, the problems of a class in descending order.
-#include "ek_api_internal.h"
+#include "ek_batched_stages.h"
 
 #include <algorithm>
-#include <cfloat>
 
 namespace ek {
 namespace batched {
+using namespace bstages;
 
 struct Args {
   int problem, jobz, n;
@@ -65,10 +66,7 @@ struct VArgs {
   int itype;
 };
 
-// What a workgroup works on, whichever way it found it.  The pointers are typed as global: one that arrives as a kernel
-// argument is known to be, but one loaded from the table is generic to the compiler, which would emit flat loads and
-// stores for it (64-bit addresses in VGPRs, waits shared with LDS).
-typedef __attribute__((address_space(1))) double gdouble;
+// What a workgroup works on, whichever way it found it.  The pointers are typed as global (gdouble, ek_batched_stages.h)
 struct Problem {
   int n;
   gdouble *A; int lda;
@@ -85,26 +83,6 @@ __device__ __forceinline__ Problem locate(const Args &a) {
 __device__ __forceinline__ Problem locate(const VArgs &a) {
   const Desc &d = a.table[blockIdx.x];
   return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz, a.info + d.index};
-}
-
-// Sum (or maximum) over the workgroup, the same bits in every thread.  `red` holds 2 * NW doubles; the two halves
-// alternate so that a call needs one barrier: between two uses of a half lies the barrier of the call between them.
-template <int NW, bool MAX>
-__device__ __forceinline__ double block_reduce(double x, double *red, int &phase) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double y = __shfl_xor(x, o, 64);
-    x = MAX ? fmax(x, y) : x + y;
-  }
-  if (NW == 1) return x;
-  double *rr = red + phase * NW;
-  phase ^= 1;
-  if ((threadIdx.x & 63) == 0) rr[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double s = rr[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) s = MAX ? fmax(s, rr[w]) : s + rr[w];
-  return s;
 }
 
 // y[i * SY] -= a * x[i] for i0 <= i < i1, x and y in LDS: four elements' loads go out before the first store, so that
@@ -231,28 +209,9 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   int *info = p.info;
   int phase = 0;
 
-  // ---- 0: A finite?  max|a| comes off the same pass: an A whose squares would leave the normal range is scaled
-  int aex = 0;                                      // the image holds 2^-aex A; d, e and w go out times 2^aex
-  {
-    double mx = 0.0;
-    if (row)
-      for (int j = sub; j <= r; j += P) {
-        const double ax = fabs(A[r + (size_t)j * lda]);
-        mx = (ax <= DBL_MAX) ? fmax(mx, ax) : INFINITY;   // a NaN counts as Inf: fmax would drop it
-      }
-    const double amax = block_reduce<NW, true>(mx, red, phase);
-    if (!(amax <= DBL_MAX)) {                       // uniform: amax has the same bits in every thread
-      if (t == 0) *info = -5;
-      return;
-    }
-    // Stage 3 forms plain sums of squares (DSYEV scales for the same reason, and so does ek_solve.hip's stage_in_A).
-    // Inside 2^-256 .. 2^256 nothing is done and the arithmetic is the unscaled kernel's to the bit: there the square
-    // of every entry down to eps / n of max|a| is a normal number (>= 2^-632) and n^1.5 max|a|^2 is finite (<= 2^523),
-    // and the other half of the exponent range is left to what L^-1 . L^-T amplifies (1 / lambda_min(B) up to 2^250).
-    // Outside, max|a| goes to [1/2, 1) by an exact power of two (not by rmin / anrm as DSYEV does), so that the
-    // result is that of the scaled matrix to the bit.
-    if (amax > 0.0 && (amax < 0x1p-256 || amax > 0x1p256)) (void)frexp(amax, &aex);
-  }
+  // ---- 0: A finite?  max|a|: the image holds 2^-aex A; d, e and w go out times 2^aex
+  int aex;
+  if (!scan_a<NC, NW>(A, lda, n, red, phase, info, aex)) return;
 
   if (a.problem) {
     // ---- 1: B = L L^T in the image
@@ -548,26 +507,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
       return;
     }
   }
-  // ascending order: rank sort (ties by index; a NaN sorts last so that the ranks stay a permutation)
-  {
-    int rank = 0, bad = 0;
-    double wr = 0.0;
-    if (sub == 0 && row) {
-      const double di = sd[r], ki = (di == di) ? di : INFINITY;
-      for (int j = 0; j < n; ++j) {
-        const double dj = sd[j], kj = (dj == dj) ? dj : INFINITY;
-        rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
-      }
-      srank[r] = rank;
-      wr = ldexp(di, wex);                          // one rounding at most (a denormal result), as di * 2^ex had
-      bad = !(fabs(wr) <= DBL_MAX);
-    }
-    if (__syncthreads_or(bad)) {                    // an eigenvalue beyond the range of a double (or a NaN that QL made):
-      if (t == 0) *info = 100000 + n + 1;           // reported like a reduction that overflowed, and nothing is written
-      return;
-    }
-    if (sub == 0 && row) p.w[rank] = wr;
-  }
+  if (!rank_sort<NC>(n, wex, sd, srank, p.w, info)) return;
   if (!a.jobz) {
     if (t == 0) *info = 0;
     return;

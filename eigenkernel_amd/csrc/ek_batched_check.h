@@ -7,7 +7,7 @@
 //                              (ek_batched_check_x.h), which hand the host driver a launch function
 // The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
 #pragma once
-#include "ek_api_internal.h"
+#include "ek_batched_stages.h"
 
 #include <cmath>
 
@@ -38,9 +38,9 @@ struct VArgs {
   double *out;
 };
 
-// global address space, as in ek_batched.hip: a pointer loaded from the table would otherwise cost flat accesses
-typedef __attribute__((address_space(1))) double gdouble;
-typedef const __attribute__((address_space(1))) double cgdouble;
+// global address space, the solver's own types: a pointer loaded from the table would otherwise cost flat accesses
+using bstages::gdouble;
+using bstages::cgdouble;
 struct Problem {
   int n;
   cgdouble *A; int lda;

@@ -1,11 +1,14 @@
 // ek_batched_x.hip -- ek_hip_eigenpairs_xbatched*: orders EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX of the batched solver.
 //
-// The six stages of ek_batched.hip with the same arithmetic rules, one workgroup per problem from its first load to its
-// last store and no launch between the stages -- but the n x n image lies in a device workspace (column-major, leading
-// dimension 257, one slot per workgroup of a launch) and not in LDS: 256 x 257 doubles are 514 KiB.  The vectors stay in
-// LDS (d, e, tau, v, w, the partial sums, the two staged columns: 9 x 256 doubles).  One class: NC = 256, 512 threads,
-// thread t is (row or column t % 256, half t / 256).  Problem 0 and problem 1; problem 1 in DSYGV's three
-// types: A x = l B x (itype 1), A B x = l x (2), B A x = l x (3).
+// The six stages of ek_batched.hip, one workgroup per problem from its first load to its last store and no launch between
+// the stages -- but the n x n image lies in a device workspace (column-major, leading dimension 257, one slot per workgroup
+// of a launch) and not in LDS: 256 x 257 doubles are 514 KiB.  The vectors stay in LDS (d, e, tau, v, w, the partial sums,
+// the two staged columns: 9 x 256 doubles).  One class: NC = 256, 512 threads, thread t is (row or column t % 256, half
+// t / 256).  Problem 0 and problem 1; problem 1 in DSYGV's three types: A x = l B x (itype 1), A B x = l x
+// (2), B A x = l x (3).
+// block_reduce, stage 0 (scan_a) and the rank sort that ends stage 4 (rank_sort) are those of ek_batched_stages.h, which
+// ek_batched.hip uses too.  The rest is written here with ek_batched.hip's arithmetic rules: eight loads from
+// the image ahead of the first store where that file has four, and in stages 1, 2 and 5 another owner for every entry.
 //
 // Every n^3 loop over the image runs with the lanes of a wave along consecutive rows (consecutive addresses):
 //   1  right-looking Cholesky: lane = row; the scaled column of a step is kept in LDS for the update
@@ -43,15 +46,14 @@
 // ek_hip_*_xvbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in entry
 // blockIdx.x of its launch's slice of the variable-order table (ek_batched.hip builds it) instead of at blockIdx.x *
 // stride; the image slot is blockIdx.x either way.
-#include "ek_api_internal.h"
+#include "ek_batched_stages.h"
 
 #include <algorithm>
-#include <cfloat>
 
 namespace ek {
 namespace batchedx {
 
-typedef __attribute__((address_space(1))) double gdouble;
+using namespace bstages;
 
 constexpr int NC = 256, T = 512, LD = NC + 1, P = T / NC, NW = T / 64;
 constexpr size_t kSlot = (size_t)NC * LD;           // doubles of one image
@@ -80,9 +82,9 @@ struct XVArgs {
   int itype;
 };
 
-// What a workgroup works on, whichever way it found it.  The pointers are typed as global (ek_batched.hip's Problem): one
-// loaded from the table is generic to the compiler otherwise.  n is the same in every lane either way (a kernel argument
-// or a load at an address that depends on blockIdx.x alone): every barrier and every loop bound depends on it.
+// What a workgroup works on, whichever way it found it.  The pointers are typed as global (gdouble).  n is the same in
+// every lane either way (a kernel argument or a load at an address that depends on blockIdx.x alone): every barrier and
+// every loop bound depends on it.
 struct Problem {
   int n;
   gdouble *A; int lda;
@@ -109,24 +111,6 @@ __device__ __forceinline__ gdouble *vectors(const Args &a, const Problem &) {
   return (gdouble *)(a.Z + (long long)blockIdx.x * a.sZ);
 }
 __device__ __forceinline__ gdouble *vectors(const XVArgs &, const Problem &p) { return p.Z; }
-
-// ek_batched.hip's block_reduce: a sum (or maximum) over the workgroup, the same bits in every thread
-template <bool MAX>
-__device__ __forceinline__ double block_reduce(double x, double *red, int &phase) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double y = __shfl_xor(x, o, 64);
-    x = MAX ? fmax(x, y) : x + y;
-  }
-  double *rr = red + phase * NW;
-  phase ^= 1;
-  if ((threadIdx.x & 63) == 0) rr[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double s = rr[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) s = MAX ? fmax(s, rr[w]) : s + rr[w];
-  return s;
-}
 
 // y[i * SY] -= x[i] * a for i = i0, i0 + STEP, ... < i1; y in the image, x in LDS: eight loads before the first store
 template <int SY, int STEP>
@@ -208,22 +192,9 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
   int *info = p.info;
   int phase = 0;
 
-  // ---- 0: A finite?  max|a| off the same pass (ek_batched.hip's rule: scaled outside 2^-256 .. 2^256)
-  int aex = 0;
-  {
-    double mx = 0.0;
-    if (row)
-      for (int j = sub; j <= r; j += P) {
-        const double ax = fabs(A[r + (size_t)j * lda]);
-        mx = (ax <= DBL_MAX) ? fmax(mx, ax) : INFINITY;
-      }
-    const double amax = block_reduce<true>(mx, red, phase);
-    if (!(amax <= DBL_MAX)) {
-      if (t == 0) *info = -5;
-      return;
-    }
-    if (amax > 0.0 && (amax < 0x1p-256 || amax > 0x1p256)) (void)frexp(amax, &aex);
-  }
+  // ---- 0: A finite?  max|a|: the image holds 2^-aex A (scan_a)
+  int aex;
+  if (!scan_a<NC, NW>(A, lda, n, red, phase, info, aex)) return;
 
   if (a.problem) {
     // ---- 1: B = L L^T in the image
@@ -329,7 +300,7 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
   for (int k = 0; k + 1 < n; ++k) {
     double x = 0.0;
     if (sub == 0 && row && r >= k + 2) x = S[r + k * LD];
-    const double xn2 = block_reduce<false>(x * x, red, phase);
+    const double xn2 = block_reduce<NW, false>(x * x, red, phase);
     const double alpha = S[k + 1 + k * LD], dk = S[k + k * LD];
     double tau = 0.0, beta = alpha, scal = 0.0;
     if (xn2 != 0.0) {
@@ -361,7 +332,7 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
       pr = tau * (sp[r] + sp[NC + r]);
       vr = sv[r];
     }
-    const double dot = block_reduce<false>(pr * vr, red, phase);
+    const double dot = block_reduce<NW, false>(pr * vr, red, phase);
     const double al2 = -0.5 * tau * dot;
     if (sub == 0 && row && r > k) sw[r] = pr + al2 * vr;
     __syncthreads();
@@ -408,7 +379,7 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
       if (t == 0) *info = 100000 + n + 1;
       return;
     }
-    const double anorm = block_reduce<true>(mx, red, phase);
+    const double anorm = block_reduce<NW, true>(mx, red, phase);
     if (anorm > 0.0) {
       int ex;
       (void)frexp(anorm, &ex);
@@ -538,26 +509,7 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
       return;
     }
   }
-  // ascending order: rank sort (ties by index; a NaN sorts last so that the ranks stay a permutation)
-  {
-    int rank = 0, bad = 0;
-    double wr = 0.0;
-    if (sub == 0 && row) {
-      const double di = sd[r], ki = (di == di) ? di : INFINITY;
-      for (int j = 0; j < n; ++j) {
-        const double dj = sd[j], kj = (dj == dj) ? dj : INFINITY;
-        rank += (kj < ki || (kj == ki && j < r)) ? 1 : 0;
-      }
-      srank[r] = rank;
-      wr = ldexp(di, wex);
-      bad = !(fabs(wr) <= DBL_MAX);
-    }
-    if (__syncthreads_or(bad)) {
-      if (t == 0) *info = 100000 + n + 1;
-      return;
-    }
-    if (sub == 0 && row) W[rank] = wr;
-  }
+  if (!rank_sort<NC>(n, wex, sd, srank, W, info)) return;
   if (!a.jobz) {
     if (t == 0) *info = 0;
     return;
