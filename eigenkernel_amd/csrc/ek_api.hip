@@ -332,6 +332,34 @@ int ek_hip_dgemm(int transa, int transb, int m, int n, int k, double alpha, cons
   return 0;
 }
 
+// Test hooks of the stage entries below (include/ek_hip_debug.h).  g_stage_leaves: ek_hip_sygst and ek_hip_trtrs solve
+// through the explicit inverses of L's 256 x 256 diagonal blocks, as the whole-path call does (ek_solve.hip).
+static int g_stage_leaves = 0;
+int ek_hip_debug_stage_leaves256(int mode) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int before = g_stage_leaves;
+  g_stage_leaves = mode == 1 ? 1 : 0;
+  return before;
+}
+int ek_hip_debug_set_sygst_direct(int order) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return sygst_set_direct(order);
+}
+unsigned long long ek_hip_debug_sygst_scratch(int n, unsigned long long *need) {
+  if (n < 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  size_t nd[2] = {0, 0};
+  sygst_scratch_need(n, nd);
+  if (need) { need[0] = nd[0]; need[1] = nd[1]; }
+  return sygst_scratch_doubles(n);
+}
+namespace {
+struct Inv256Guard { ~Inv256Guard() { trsm_register_inv256(nullptr, nullptr, 0); } };   // (whichever way the call ends)
+inline bool stage_leaves(int n) { return g_stage_leaves == 1 && n >= 2 * kDiagNB; }
+inline size_t inv256_doubles(int n) { return (size_t)(n / 256) * 256 * 256; }
+inline size_t inv256_scratch_doubles(int n) { return (size_t)(n / 256) * 128 * 128; }
+}  // namespace
+
 int ek_hip_potrf(int n, double *B_loc, const int desc_B[9]) {
   if (n < 0) return -1;
   if (!B_loc && n > 0) return -2;
@@ -376,18 +404,26 @@ int ek_hip_sygst(int n, double *A_loc, const int desc_A[9], const double *L_loc,
   hipStream_t s = g_ctx.stream;
   const int ld = pad_ld(n), nblk = ceil_div(n, kDiagNB);
   void *ws;
+  const bool leaves = stage_leaves(n);          // (a 256-leaf writes its m x 256 result to `work`)
+  const size_t wrows = leaves ? 256 : 128, i2 = leaves ? inv256_doubles(n) : 0, i2s = leaves ? inv256_scratch_doubles(n) : 0;
   rc = workspace(2 * al((size_t)ld * n * 8) + al((size_t)nblk * kDiagNB * kDiagNB * 8) +
-                 al((size_t)128 * ld * 8) + al(sygst_scratch_doubles(n) * 8), &ws);
+                 al(wrows * ld * 8) + al(sygst_scratch_doubles(n) * 8) + al(i2 * 8) + al(i2s * 8), &ws);
   if (rc) return rc;
   Arena a(ws, g_ctx.ws_bytes);
   double *dA = a.get<double>((size_t)ld * n);
   double *dL = a.get<double>((size_t)ld * n);
   double *dInv = a.get<double>((size_t)nblk * kDiagNB * kDiagNB);
-  double *work = a.get<double>((size_t)128 * ld);
+  double *work = a.get<double>(wrows * ld);
   double *scr = a.get<double>(sygst_scratch_doubles(n));
+  double *inv256 = a.get<double>(i2), *inv256_scr = a.get<double>(i2s);
   rc = h2d_matrix(n, n, A_loc, desc_A[8], dA, ld, s); if (rc) return rc;
   rc = h2d_matrix(n, n, L_loc, desc_B[8], dL, ld, s); if (rc) return rc;
   trtri_diag_blocks(s, n, dL, ld, dInv);
+  Inv256Guard inv256_guard;
+  if (leaves) {
+    trtri256_blocks(s, n, dL, ld, dInv, inv256, inv256_scr);
+    trsm_register_inv256(dInv, inv256, n);
+  }
   sygst_lower(s, n, dA, ld, dL, ld, dInv, work, scr);
   EK_HIP_CHECK(hipGetLastError());
   rc = d2h_matrix(n, n, dA, ld, A_loc, desc_A[8], s); if (rc) return rc;
@@ -413,17 +449,26 @@ int ek_hip_trtrs(int n, int nrhs, const double *L_loc, const int desc_B[9], doub
   hipStream_t s = g_ctx.stream;
   const int ld = pad_ld(n), nblk = ceil_div(n, kDiagNB);
   void *ws;
+  const bool leaves = stage_leaves(n);          // (a 256-leaf writes its 256 x nrhs result to `work`)
+  const size_t wrows = leaves ? 256 : 128, i2 = leaves ? inv256_doubles(n) : 0, i2s = leaves ? inv256_scratch_doubles(n) : 0;
   rc = workspace(al((size_t)ld * n * 8) + al((size_t)ld * nrhs * 8) +
-                 al((size_t)nblk * kDiagNB * kDiagNB * 8) + al((size_t)128 * (ld > nrhs ? ld : nrhs) * 8), &ws);
+                 al((size_t)nblk * kDiagNB * kDiagNB * 8) + al(wrows * (ld > nrhs ? ld : nrhs) * 8) +
+                 al(i2 * 8) + al(i2s * 8), &ws);
   if (rc) return rc;
   Arena a(ws, g_ctx.ws_bytes);
   double *dL = a.get<double>((size_t)ld * n);
   double *dZ = a.get<double>((size_t)ld * nrhs);
   double *dInv = a.get<double>((size_t)nblk * kDiagNB * kDiagNB);
-  double *work = a.get<double>((size_t)128 * (ld > nrhs ? ld : nrhs));
+  double *work = a.get<double>(wrows * (ld > nrhs ? ld : nrhs));
+  double *inv256 = a.get<double>(i2), *inv256_scr = a.get<double>(i2s);
   rc = h2d_matrix(n, n, L_loc, desc_B[8], dL, ld, s); if (rc) return rc;
   rc = h2d_matrix(n, nrhs, Z_loc, desc_Z[8], dZ, ld, s); if (rc) return rc;
   trtri_diag_blocks(s, n, dL, ld, dInv);
+  Inv256Guard inv256_guard;
+  if (leaves) {
+    trtri256_blocks(s, n, dL, ld, dInv, inv256, inv256_scr);
+    trsm_register_inv256(dInv, inv256, n);
+  }
   trsm_llt(s, n, nrhs, dL, ld, dInv, dZ, ld, work);
   EK_HIP_CHECK(hipGetLastError());
   rc = d2h_matrix(n, nrhs, dZ, ld, Z_loc, desc_Z[8], s); if (rc) return rc;

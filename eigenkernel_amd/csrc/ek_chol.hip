@@ -443,7 +443,26 @@ static void trsm_rlt_lower(hipStream_t s, int n, const double *L, int ldl, const
 // and largest GEMMs); above it the blocked recursion (n^3).  Measured on MI355X at N = 16384
 // (sygst stage), round 1: no recursion 0.133 s, threshold 2048 -> 0.115 s, 1024 -> 0.120 s, 512 -> 0.126 s;
 // with the 16-byte-load GEMM of round 2: 1024 -> 0.110, 2048 -> 0.103, 4096 -> 0.099, 8192 -> 0.099, none 0.115.
-static int sygst_direct() { return 4096; }      // (the scan above; the tuning switch went in round 6)
+constexpr int kSygstDirect = 4096;              // (the scan above; the tuning switch went in round 6)
+static int g_sygst_direct = kSygstDirect;       // a test hook moves it (sygst_set_direct): the recursion at small orders
+static int sygst_direct() { return g_sygst_direct; }
+int sygst_set_direct(int order) {
+  const int before = g_sygst_direct;
+  g_sygst_direct = order <= 0 ? kSygstDirect : (order < 2 * NB ? 2 * NB : order);
+  return before;
+}
+// what the two recursions below take from `scratch` at order n with the direct order as it stands (host arithmetic):
+// need[0] type 1 (C11 in full and L21 C11: n1^2 + n1 n2), need[1] types 2 and 3 (T and the larger of A22 and the
+// SYR2K's product: max(n1, n2) n), each the largest over all levels
+void sygst_scratch_need(int n, size_t need[2]) {
+  if (n <= sygst_direct()) return;
+  const size_t n1 = (size_t)split_t(n), n2 = (size_t)n - n1;
+  const size_t t1 = n1 * n1 + n1 * n2, t2 = (n1 > n2 ? n1 : n2) * (size_t)n;
+  if (t1 > need[0]) need[0] = t1;
+  if (t2 > need[1]) need[1] = t2;
+  sygst_scratch_need((int)n1, need);
+  sygst_scratch_need((int)n2, need);
+}
 
 // Recursive blocked DSYGST(itype = 1, 'L'):  with A = [A11 .; A21 A22], L = [L11 0; L21 L22]
 //   C11 = sygst(A11, L11)

@@ -132,6 +132,10 @@ void trtri256_blocks(hipStream_t s, int n, const double *L, int ldl, const doubl
 void trsm_register_inv256(const double *invdiag, const double *inv256, int n);
 void sygst_lower(hipStream_t s, int n, double *A, int lda, const double *L, int ldl,
                  const double *invdiag, double *work, double *scratch);
+// test hook: the order at or below which sygst_lower and sygst2_lower reduce directly (<= 0: the default, 4096; at least
+// 256); returns the previous one.  sygst_scratch_need: the scratch both recursions take at that setting.
+int sygst_set_direct(int order);
+void sygst_scratch_need(int n, size_t need[2]);
 // Triangular multiplies (PDTRMM 'L', 'N'-unit) and the reduction of ITYPE 2 / 3.  Their leaves (order <= 256) are GEMMs
 // against zero-masked lower copies of L's diagonal blocks, so the strict upper triangle of L's array is never read:
 // diag receives trmm_diag_doubles(n) doubles (ceil(n / ldd) blocks of ldd x ldd, ldd = trmm_block_ld(n): 256, or 128

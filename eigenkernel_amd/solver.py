@@ -205,6 +205,9 @@ def load_library(path=None):
         "ek_hip_sygv_xvbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_sygv_xvbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_debug_xvbatched_last": (c_int, [_dp, _ip]),
+        "ek_hip_debug_stage_leaves256": (c_int, [c_int]),
+        "ek_hip_debug_set_sygst_direct": (c_int, [c_int]),
+        "ek_hip_debug_sygst_scratch": (c_ull, [c_int, ctypes.POINTER(c_ull)]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -255,6 +258,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_sygv_xbatched_device", "ek_hip_check_sygv_xbatched",
     "ek_hip_eigenpairs_xvbatched_device", "ek_hip_eigenpairs_xvbatched", "ek_hip_sygv_xvbatched_device",
     "ek_hip_sygv_xvbatched", "ek_hip_debug_xvbatched_last",
+    "ek_hip_debug_stage_leaves256", "ek_hip_debug_set_sygst_direct", "ek_hip_debug_sygst_scratch",
 )
 
 
@@ -598,6 +602,26 @@ def trmm(L, Z):
     Z = np.array(_farr(Z), order="F", copy=True)
     info = lib.ek_hip_trmm(L.shape[0], Z.shape[1], _P(L), _I(_desc_for(L)), _P(Z), _I(_desc_for(Z)))
     return Z, info
+
+
+def stage_leaves256(mode):
+    """1: sygst, sygst_ibtype(.., 1) and trtrs solve through the 256-block inverses for n >= 256, as the whole path does;
+    0: the default (ek_hip_debug_stage_leaves256).  Returns the previous mode."""
+    return int(load_library().ek_hip_debug_stage_leaves256(int(mode)))
+
+
+def set_sygst_direct(order=0):
+    """Order at or below which the reductions reduce a block directly (ek_hip_debug_set_sygst_direct): <= 0 restores the
+    default of 4096, values below 256 are raised to 256.  Returns the previous order."""
+    return int(load_library().ek_hip_debug_set_sygst_direct(int(order)))
+
+
+def sygst_scratch(n):
+    """(doubles of scratch a reduction of order n is given, what type 1's recursion takes, what types 2 / 3's takes) at
+    the direct order as it stands (ek_hip_debug_sygst_scratch; host arithmetic)."""
+    need = (ctypes.c_ulonglong * 2)(0, 0)
+    have = load_library().ek_hip_debug_sygst_scratch(int(n), need)
+    return int(have), int(need[0]), int(need[1])
 
 
 BAND_W = 64   # half bandwidth of the two-stage tridiagonalisation (kBandW in csrc/ek_common.h)

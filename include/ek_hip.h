@@ -720,7 +720,10 @@ int ek_hip_comm_destroy(void);
 int ek_hip_comm_allreduce_device(double *dbuf, long long count);
 
 /* Stage-level entry points: one per ScaLAPACK call of the reference, host arrays,
- * 1x1 grid descriptors.  They exist so the path can be replaced (and tested) call by call. */
+ * 1x1 grid descriptors.  They exist so the path can be replaced call by call.  By default ek_hip_sygst and
+ * ek_hip_trtrs solve through the 128-block inverses alone; the production form of the solves (the explicit inverses of
+ * the 256 x 256 diagonal blocks that the whole-path call registers) is selected by the hook
+ * ek_hip_debug_stage_leaves256 of include/ek_hip_debug.h, which is how the stages are tested as the path runs them. */
 /* PDPOTRF('L', n, B, 1, 1, desc_B, info)        generalized_to_standard.f90:24 */
 int ek_hip_potrf(int n, double *B_loc, const int desc_B[9]);
 /* PDSYGST(1, 'L', n, A, 1,1, desc_A, B, 1,1, desc_B, scale, info)   :37 (B holds L) */

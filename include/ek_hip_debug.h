@@ -138,6 +138,23 @@ int ek_hip_debug_xbatched_chunk(int problems);
    0 (or less) restores the default of 1024; returns the previous value.  A tuning and test hook: no result depends on it. */
 int ek_hip_debug_check_xbatched_chunk(int problems);
 
+/* Test hooks of the stage entries of the generalized path (ek_hip_sygst, ek_hip_sygst_ibtype, ek_hip_trtrs; ek_chol.hip).
+ *   _stage_leaves256 : 0 (the default, also for any value but 1): the solves of ek_hip_sygst, of type 1 of
+ *            ek_hip_sygst_ibtype and of ek_hip_trtrs go through the 128-block inverses alone.  1: for n >= 256 they form
+ *            the explicit inverses of L's 256 x 256 diagonal blocks and register them for the call, exactly as the
+ *            whole-path call does, so that every solve takes the 256-leaves the whole path takes; the call's workspace
+ *            grows by that array and its scratch.  Returns the previous mode.
+ *   _set_sygst_direct : the order at or below which the reduction of every type (sygst_rec, sygst2_rec) reduces a block
+ *            directly instead of recursing; <= 0 restores the default of 4096, values below 256 are raised to 256.
+ *            Returns the previous order.  It governs the whole-path calls too.
+ *   _sygst_scratch : returns the doubles of scratch a reduction of order n is given (sygst_scratch_doubles) and, in
+ *            need[0..1] (optional), what the recursion of type 1 and of types 2 / 3 takes from it at the direct order
+ *            as it stands (host arithmetic, no GPU).
+ * No result's contract depends on either hook; the last bits may. */
+int ek_hip_debug_stage_leaves256(int mode);
+int ek_hip_debug_set_sygst_direct(int order);
+unsigned long long ek_hip_debug_sygst_scratch(int n, unsigned long long *need /* 2 */);
+
 /* test aid: the next `times` bulge chasings of whole-path calls count as abandoned (exercises the repetition from the
    saved band and the -992 exit of ek_solve.hip) */
 int ek_hip_debug_fail_next_chase(int times);
