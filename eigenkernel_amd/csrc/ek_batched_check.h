@@ -1,10 +1,13 @@
 // ek_batched_check.h -- what the translation units of the batched acceptance checks share (not installed):
 //   ek_batched_check.hip       the entries up to EK_HIP_BATCH_NMAX, the kernel of the standard problem and of type 1, and
 //                              the host side of every uniform-order entry: the argument checker, the device
-//                              pool with its one release function, the run function, the stager of host arrays
+//                              pool with its one release function, the run function, the stager of host arrays; the
+//                              driver of every variable-order entry, ek_hip_check_*xvbatched* included:
+//                              four classes (256, 128, 64, 32) from one table, the class of 256 in chunks
 //   ek_batched_check_sygv.hip  the kernel of DSYGV's types 2 and 3
-//   ek_batched_check_x.hip, ek_batched_check_sygv_x.hip  the kernels above EK_HIP_BATCH_NMAX and their entries
-//                              (ek_batched_check_x.h), which hand the host driver a launch function
+//   ek_batched_check_x.hip, ek_batched_check_sygv_x.hip  the kernels above EK_HIP_BATCH_NMAX and their uniform entries
+//                              (ek_batched_check_x.h), which hand the host driver a launch function, and the launches of
+//                              their table form for the variable driver (launch_x, launch_sygv_x)
 // The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
 #pragma once
 #include "ek_batched_stages.h"
@@ -26,7 +29,9 @@ struct Args {
   double *ipr;          // n doubles per problem, or nullptr
 };
 
-// the variable form's table: one entry per problem to check, a class after the other, descending order inside a class
+// the variable form's table: one entry per problem to check, a class after the other, descending order inside a class.
+// S: the entry's own scratch -- n^2 doubles per problem in the classes up to 128; in the class of 256 a slot of the
+// entry's chunk (n^2 doubles, 2 n^2 for type 3), reused by the next chunk
 struct Desc {
   const double *A, *B, *w, *Z;
   double *S, *ipr;
@@ -120,6 +125,10 @@ constexpr int lds_doubles(int NC) { return NC * (NC + 1) + 8 * NC + NC + 4; }
 // one launch of the kernel of types 2 and 3 (itype) for `count` problems of class nc (32, 64, 128)
 int launch_sygv(hipStream_t s, int itype, int nc, int count, const Args &a);
 int launch_sygv(hipStream_t s, int itype, int nc, int count, const VArgs &a);
+// one launch of the kernels above EK_HIP_BATCH_NMAX for `count` entries of the table, each of such an order:
+// ek_batched_check_x.hip's (the standard problem and type 1, a.problem says which), ek_batched_check_sygv_x.hip's (itype 2, 3)
+int launch_x(hipStream_t s, int count, const VArgs &a);
+int launch_sygv_x(hipStream_t s, int itype, int count, const VArgs &a);
 
 // ---- the host driver of the uniform-order entries (ek_batched_check.hip)
 // One call.  itype: 0 the standard problem and type 1 (`problem` says which), 2 or 3 those types (problem = 1).  A, B, w

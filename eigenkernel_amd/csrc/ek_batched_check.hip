@@ -30,6 +30,10 @@
 // pool with one release function, one run function and one stager of host arrays, declared in ek_batched_check.h.
 // ek_batched_check_x.hip and ek_batched_check_sygv_x.hip (orders above EK_HIP_BATCH_NMAX) keep their kernel, its launch
 // and thin entries, and hand this driver a launch function.  All entries serialise on g_mu, so one pool serves them all.
+//
+// The variable-order entries for orders up to EK_HIP_XBATCH_NMAX (ek_hip_check_xvbatched*, ek_hip_check_sygv_xvbatched*,
+// DESIGN.md 24) are this unit's too: the variable driver with a fourth class in front, whose launches are those two units'
+// table instantiations (bcheck::launch_x, bcheck::launch_sygv_x).
 #include "ek_batched_check.h"
 
 #include <algorithm>
@@ -179,6 +183,7 @@ static int launch_class(hipStream_t s, int count, const ARGS &a, int itype) {
 }
 
 static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
+constexpr int kClasses = 4;                         // the variable form's: 256 (orders above EK_HIP_BATCH_NMAX), 128, 64, 32
 
 // Device memory the entries of all three units keep (grown, never shrunk, released in ek_hip_finalize): the scratch S, the
 // output words (out, then the IPRs), the table or the map of the problems to check; two events for `seconds`.  A call
@@ -187,6 +192,11 @@ static double *g_scratch = nullptr, *g_dout = nullptr;
 static void *g_dtable = nullptr;
 static size_t g_scratch_count = 0, g_dout_count = 0, g_dtable_bytes = 0;
 static hipEvent_t g_ev[2] = {nullptr, nullptr};
+// the variable form's last call that was given `seconds` (ek_hip_debug_check_xvbatched_last): an event before each class
+// and one behind the last, created by the first such call
+static hipEvent_t g_cev[kClasses + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+static double g_class_seconds[kClasses] = {0.0, 0.0, 0.0, 0.0};
+static int g_class_count[kClasses] = {0, 0, 0, 0};
 static std::vector<Desc> g_htable;                  // host images: an upload may still read them when an error returns
 static std::vector<int> g_hmap;
 static std::vector<double> g_hout;
@@ -227,6 +237,10 @@ void release_batched_check() {
   for (int k = 0; k < 2; ++k) {
     if (g_ev[k]) (void)hipEventDestroy(g_ev[k]);
     g_ev[k] = nullptr;
+  }
+  for (int k = 0; k <= kClasses; ++k) {
+    if (g_cev[k]) (void)hipEventDestroy(g_cev[k]);
+    g_cev[k] = nullptr;
   }
   std::vector<Desc>().swap(g_htable);
   std::vector<int>().swap(g_hmap);
@@ -386,17 +400,18 @@ static int launch_uniform(hipStream_t s, const bcheck::Uniform &u, const int *ma
   }
 }
 
-// All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.
+// All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.  nmax is the
+// entry's largest order (EK_HIP_BATCH_NMAX, or EK_HIP_XBATCH_NMAX for ek_hip_check_*xvbatched*).
 static int variable_check(int problem, int batch, const int *n, const void *const *A, const int *lda,
                           const void *const *B, const int *ldb, const void *const *w, const void *const *Z,
-                          const int *ldz, const double *out, bool *nothing) {
+                          const int *ldz, const double *out, int nmax, bool *nothing) {
   *nothing = false;
   if (problem != 0 && problem != 1) return -1;
   if (batch < 0) return -2;
   if (batch == 0) { *nothing = true; return 0; }
   if (!n) return -3;
   for (int b = 0; b < batch; ++b)
-    if (n[b] < 0 || n[b] > EK_HIP_BATCH_NMAX) return -3;
+    if (n[b] < 0 || n[b] > nmax) return -3;
   auto entries = [&](const void *const *P) {
     if (!P) return false;
     for (int b = 0; b < batch; ++b)
@@ -422,49 +437,87 @@ static int variable_check(int problem, int batch, const int *n, const void *cons
   return 0;
 }
 
-// arguments checked (batch > 0), context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses; itype as above
+// arguments checked (batch > 0), context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses; itype as above.
+// The orders above EK_HIP_BATCH_NMAX (ek_hip_check_*xvbatched* alone let them through) form a class of their own in front
+// of the other three: chunk c of at most g_chunk entries runs over the table's slice [c g_chunk, ...) with the kernels of
+// ek_batched_check_x.hip / ek_batched_check_sygv_x.hip, and every entry of a chunk names its own slot of the chunk's
+// scratch (prefix sums inside the chunk), which the next chunk uses again.  Everything runs on the context's stream, a
+// launch behind the other, so the classes up to 128 lay their n^2 per problem over the same buffer from its start.
 static int variable_device_locked(int itype, int problem, int batch, const int *n, const double *const *dA,
                                   const int *lda, const double *const *dB, const int *ldb, const double *const *dw,
                                   const double *const *dZ, const int *ldz, const int *info, double *out,
                                   double *const *ipr, double *seconds) {
   using namespace bcheck;
-  // the solver's order (DESIGN.md 13): a class after the other, the largest first, descending order inside a class
+  // the solver's order (DESIGN.md 13, 21): a class after the other, the largest first, descending order inside a class
   std::vector<int> order;
   order.reserve((size_t)batch);
   for (int b = 0; b < batch; ++b)
     if (n[b] > 0 && !(info && info[b] != 0)) order.push_back(b);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
   const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT;
+  const int K = g_chunk;
+  const size_t slots = itype == 3 ? 2 : problem ? 1 : 0;   // of n^2 doubles, per entry of the class of 256
   std::vector<size_t> off((size_t)batch, 0), offs((size_t)batch, 0);
-  size_t words = nout, scratch = 0;
+  size_t words = nout, scratch = 0, small = 0, chunk = 0;
+  int count[kClasses] = {0, 0, 0, 0};               // classes of 256, 128, 64, 32
   for (int b : order) {
     if (ipr && ipr[b]) { off[b] = words; words += (size_t)n[b]; }
-    if (problem) { offs[b] = scratch; scratch += (size_t)n[b] * n[b]; }
+    if (n[b] > EK_HIP_BATCH_NMAX) {
+      if (count[0] % K == 0) chunk = 0;             // a chunk's first entry
+      offs[b] = chunk;
+      chunk += slots * (size_t)n[b] * n[b];
+      scratch = std::max(scratch, chunk);
+      ++count[0];
+    } else {
+      const int c = class_of(n[b]);
+      ++count[c == 128 ? 1 : c == 64 ? 2 : 3];
+      if (problem) { offs[b] = small; small += (size_t)n[b] * n[b]; }
+    }
   }
+  scratch = std::max(scratch, small);
+  if (seconds)
+    for (int k = 0; k < kClasses; ++k) { g_class_seconds[k] = 0.0; g_class_count[k] = count[k]; }
   if (!order.empty()) {
     int rc = ensure(scratch, words, order.size() * sizeof(Desc));
     if (rc) return rc;
+    if (seconds)
+      for (int k = 0; k <= kClasses; ++k)
+        if (!g_cev[k]) EK_HIP_CHECK(hipEventCreate(&g_cev[k]));
     g_htable.resize(order.size());
-    int count[3] = {0, 0, 0};                       // classes of 128, 64, 32
     for (size_t i = 0; i < order.size(); ++i) {
-      const int b = order[i], c = class_of(n[b]);
-      ++count[c == 128 ? 0 : c == 64 ? 1 : 2];
-      g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], dZ[b], problem ? g_scratch + offs[b] : nullptr,
+      const int b = order[i];
+      const bool has_s = n[b] > EK_HIP_BATCH_NMAX ? slots != 0 : problem != 0;
+      g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], dZ[b], has_s ? g_scratch + offs[b] : nullptr,
                          (ipr && ipr[b]) ? g_dout + off[b] : nullptr, n[b], lda[b], problem ? ldb[b] : 1, ldz[b], b, 0};
     }
     rc = run_and_fetch(words, seconds, [&](hipStream_t s) -> int {
       EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
       int rcl = 0, at = 0;
-      for (int k = 0; k < 3 && !rcl; ++k) {
+      for (int k = 0; k < kClasses && !rcl; ++k) {
+        if (seconds) (void)hipEventRecord(g_cev[k], s);
         if (!count[k]) continue;
-        VArgs a{problem, (const Desc *)g_dtable + at, g_dout};
-        rcl = k == 0 ? launch_class<128, 256>(s, count[k], a, itype)
-            : k == 1 ? launch_class<64, 128>(s, count[k], a, itype) : launch_class<32, 64>(s, count[k], a, itype);
+        if (k == 0) {
+          for (int c0 = 0; c0 < count[0] && !rcl; c0 += K) {
+            VArgs a{problem, (const Desc *)g_dtable + c0, g_dout};
+            const int cnt = std::min(K, count[0] - c0);
+            rcl = itype ? launch_sygv_x(s, itype, cnt, a) : launch_x(s, cnt, a);
+          }
+        } else {
+          VArgs a{problem, (const Desc *)g_dtable + at, g_dout};
+          rcl = k == 1 ? launch_class<128, 256>(s, count[k], a, itype)
+              : k == 2 ? launch_class<64, 128>(s, count[k], a, itype) : launch_class<32, 64>(s, count[k], a, itype);
+        }
         at += count[k];
       }
+      if (seconds && !rcl) (void)hipEventRecord(g_cev[kClasses], s);
       return rcl;
     });
     if (rc) return rc;
+    if (seconds)
+      for (int k = 0; k < kClasses; ++k) {
+        float ms = 0.f;
+        if (count[k] && hipEventElapsedTime(&ms, g_cev[k], g_cev[k + 1]) == hipSuccess) g_class_seconds[k] = (double)ms * 1e-3;
+      }
   }
   scatter(batch, [&](int b) { return n[b]; }, info, off, out,
           [&](int b) { return (ipr && ipr[b]) ? ipr[b] : nullptr; });
@@ -483,10 +536,10 @@ static int class_entry(const bcheck::Uniform &u, bool host) {
 static int variable_device_entry(int itype, int problem, int batch, const int *n, const double *const *dA,
                                  const int *lda, const double *const *dB, const int *ldb, const double *const *dw,
                                  const double *const *dZ, const int *ldz, const int *info, double *out,
-                                 double *const *ipr, double *seconds) {
+                                 double *const *ipr, double *seconds, int nmax) {
   bool nothing;
   int rc = variable_check(problem, batch, n, (const void *const *)dA, lda, (const void *const *)dB, ldb,
-                          (const void *const *)dw, (const void *const *)dZ, ldz, out, &nothing);
+                          (const void *const *)dw, (const void *const *)dZ, ldz, out, nmax, &nothing);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -502,10 +555,10 @@ static int variable_device_entry(int itype, int problem, int batch, const int *n
 static int variable_host_entry(int itype, int problem, int batch, const int *n, const double *const *A,
                                const int *lda, const double *const *B, const int *ldb, const double *const *w,
                                const double *const *Z, const int *ldz, const int *info, double *out,
-                               double *const *ipr, double *seconds) {
+                               double *const *ipr, double *seconds, int nmax) {
   bool nothing;
   int rc = variable_check(problem, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
-                          (const void *const *)w, (const void *const *)Z, ldz, out, &nothing);
+                          (const void *const *)w, (const void *const *)Z, ldz, out, nmax, &nothing);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -587,13 +640,14 @@ int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const dou
                                  const double *const *dB, const int *ldb, const double *const *dw,
                                  const double *const *dZ, const int *ldz, const int *info, double *out,
                                  double *const *ipr, double *seconds) {
-  return variable_device_entry(0, problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds);
+  return variable_device_entry(0, problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds,
+                               EK_HIP_BATCH_NMAX);
 }
 
 int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
                           const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
                           const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
-  return variable_host_entry(0, problem, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds);
+  return variable_host_entry(0, problem, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds, EK_HIP_BATCH_NMAX);
 }
 
 // DSYGV's types: -1 for an itype outside 1 .. 3, then the family above with problem = 1 (type 1 is that problem itself)
@@ -620,14 +674,58 @@ int ek_hip_check_sygv_vbatched_device(int itype, int batch, const int *n, const 
                                       double *const *ipr, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
   return variable_device_entry(itype == 1 ? 0 : itype, 1, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr,
-                               seconds);
+                               seconds, EK_HIP_BATCH_NMAX);
 }
 
 int ek_hip_check_sygv_vbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
                                const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
                                const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return variable_host_entry(itype == 1 ? 0 : itype, 1, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds);
+  return variable_host_entry(itype == 1 ? 0 : itype, 1, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds,
+                             EK_HIP_BATCH_NMAX);
+}
+
+// The variable forms for orders up to EK_HIP_XBATCH_NMAX: the entries above with the larger bound; the
+// driver puts the orders above EK_HIP_BATCH_NMAX into a class of their own
+int ek_hip_check_xvbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                  const double *const *dB, const int *ldb, const double *const *dw,
+                                  const double *const *dZ, const int *ldz, const int *info, double *out,
+                                  double *const *ipr, double *seconds) {
+  return variable_device_entry(0, problem, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr, seconds,
+                               EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_check_xvbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                           const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                           const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
+  return variable_host_entry(0, problem, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_check_sygv_xvbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
+                                       const double *const *dB, const int *ldb, const double *const *dw,
+                                       const double *const *dZ, const int *ldz, const int *info, double *out,
+                                       double *const *ipr, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return variable_device_entry(itype == 1 ? 0 : itype, 1, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, out, ipr,
+                               seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_check_sygv_xvbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
+                                const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                                const int *ldz, const int *info, double *out, double *const *ipr, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return variable_host_entry(itype == 1 ? 0 : itype, 1, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds,
+                             EK_HIP_XBATCH_NMAX);
+}
+
+// the classes of the last variable-order check that was given `seconds` (include/ek_hip_debug.h)
+int ek_hip_debug_check_xvbatched_last(double *class_seconds, int *class_count) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (int k = 0; k < bcheck::kClasses; ++k) {      // classes of 256, 128, 64, 32
+    if (class_seconds) class_seconds[k] = bcheck::g_class_seconds[k];
+    if (class_count) class_count[k] = bcheck::g_class_count[k];
+  }
+  return 0;
 }
 
 // the problems per launch above EK_HIP_BATCH_NMAX (include/ek_hip_debug.h)

@@ -3,6 +3,8 @@
 // solves.  Orders up to EK_HIP_BATCH_NMAX are forwarded to ek_hip_check_sygv_batched*, type 1 above them to
 // ek_hip_check_xbatched*(problem = 1).  This unit holds the kernel, its launch and the entries; the argument checker, the
 // device pool, the chunk loop, the fetch and the scatter are ek_batched_check.hip's.
+// The kernel has a second instantiation per type that finds its problem in the variable form's table
+// (bcheck::launch_sygv_x, behind ek_hip_check_sygv_xvbatched*: DESIGN.md 24); the passes exist once.
 //
 // One workgroup of 512 threads (8 waves) owns a problem from its first load to its last store.  The quantities are those
 // of DESIGN.md 16.  The three n^3 products of a type run on the fp64 matrix cores with the tiles, the loaders, the K step
@@ -215,8 +217,22 @@ __device__ __forceinline__ void img_axpy(gdouble *y, int sy, const double *x, do
   for (; i < i1; i += 2) y[i * sy] -= x[i] * a;
 }
 
+// the uniform launch's problem: entry first + workgroup of the map (or that problem), the scratch by workgroup
 template <int ITYPE>
-__global__ __launch_bounds__(T) void xcheck_sygv_kernel(Args a) {
+__device__ __forceinline__ bcheck::Problem locate_sygv(const Args &a) {
+  const int n = a.n;
+  const long long pb = a.map ? a.map[a.first + (int)blockIdx.x] : a.first + (int)blockIdx.x;
+  return {n, (cgdouble *)(a.A + pb * a.sA), a.lda, (cgdouble *)(a.B + pb * a.sB), a.ldb, (cgdouble *)(a.w + pb * n),
+          (cgdouble *)(a.Z + pb * a.sZ), a.ldz, (gdouble *)(a.S + (long long)blockIdx.x * (ITYPE - 1) * n * n),
+          (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT), a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr};
+}
+template <int ITYPE>
+__device__ __forceinline__ bcheck::Problem locate_sygv(const bcheck::VArgs &a) { return bcheck::locate(a); }
+
+// ARGS: Args (one order, strided; the scratch by workgroup) or bcheck::VArgs (entry blockIdx.x of the launch's slice of the
+// table, which names the entry's own scratch of (ITYPE - 1) n^2 doubles)
+template <int ITYPE, typename ARGS>
+__global__ __launch_bounds__(T) void xcheck_sygv_kernel(ARGS a) {
   static_assert(ITYPE == 2 || ITYPE == 3, "type 1 is ek_batched_check_x.hip's");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double *buf = smem;                               // [2][kBuf]
@@ -228,16 +244,16 @@ __global__ __launch_bounds__(T) void xcheck_sygv_kernel(Args a) {
   double *red = p4 + NX;                            // a word per wave
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, l4 = lane >> 4;
-  const int n = a.n;
-  const long long pb = a.map ? a.map[a.first + (int)blockIdx.x] : a.first + (int)blockIdx.x;
-  cgdouble *A = (cgdouble *)(a.A + pb * a.sA);
-  cgdouble *B = (cgdouble *)(a.B + pb * a.sB);
-  cgdouble *w = (cgdouble *)(a.w + pb * n);
-  cgdouble *Z = (cgdouble *)(a.Z + pb * a.sZ);
-  gdouble *S = (gdouble *)(a.S + (long long)blockIdx.x * (ITYPE - 1) * n * n);
-  gdouble *out = (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT);
-  gdouble *ipr = a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr;
-  const int lda = a.lda, ldb = a.ldb, ldz = a.ldz;
+  const bcheck::Problem p = locate_sygv<ITYPE>(a);
+  const int n = p.n;
+  cgdouble *A = p.A;
+  cgdouble *B = p.B;
+  cgdouble *w = p.w;
+  cgdouble *Z = p.Z;
+  gdouble *S = p.S;
+  gdouble *out = p.out;
+  gdouble *ipr = p.ipr;
+  const int lda = p.lda, ldb = p.ldb, ldz = p.ldz;
   cgdouble *M1 = ITYPE == 2 ? B : A, *M2 = ITYPE == 2 ? A : B;   // the first product's matrix, the second's
   const int ld1 = ITYPE == 2 ? ldb : lda, ld2 = ITYPE == 2 ? lda : ldb;
 
@@ -400,17 +416,16 @@ __global__ __launch_bounds__(T) void xcheck_sygv_kernel(Args a) {
   }
 }
 
-static bool g_raised[2] = {false, false};
-
-template <int ITYPE>
-static int launch(hipStream_t s, int count, const Args &a) {
+template <int ITYPE, typename ARGS>
+static int launch(hipStream_t s, int count, const ARGS &a) {
   constexpr size_t lds = (size_t)kLdsDoubles * sizeof(double);
-  if (!g_raised[ITYPE - 2]) {
-    EK_HIP_CHECK(hipFuncSetAttribute((const void *)xcheck_sygv_kernel<ITYPE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-    g_raised[ITYPE - 2] = true;
+  static bool raised = false;                       // one per instantiation
+  if (!raised) {
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)xcheck_sygv_kernel<ITYPE, ARGS>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised = true;
   }
-  hipLaunchKernelGGL((xcheck_sygv_kernel<ITYPE>), dim3(count), dim3(T), lds, s, a);
+  hipLaunchKernelGGL((xcheck_sygv_kernel<ITYPE, ARGS>), dim3(count), dim3(T), lds, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -427,6 +442,13 @@ static int entry(const bcheck::Uniform &u, bool nothing, bool host) {
 }
 
 }  // namespace xcheck_sygv
+
+// the variable form's launch (ek_batched_check.h): `count` entries of the table, every one of an order above
+// EK_HIP_BATCH_NMAX, itype 2 or 3
+int bcheck::launch_sygv_x(hipStream_t s, int itype, int count, const VArgs &a) {
+  return itype == 2 ? xcheck_sygv::launch<2>(s, count, a) : xcheck_sygv::launch<3>(s, count, a);
+}
+
 }  // namespace ek
 
 using namespace ek;

@@ -2,6 +2,8 @@
 // EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX that ek_hip_eigenpairs_xbatched* solves.  Orders up to
 // EK_HIP_BATCH_NMAX are forwarded to ek_hip_check_batched*.  This unit holds the kernel, its launch and the entries; the
 // argument checker, the device pool, the chunk loop, the fetch and the scatter are ek_batched_check.hip's.
+// The kernel has a second instantiation per problem kind that finds its problem in the variable form's table
+// (bcheck::launch_x, behind ek_hip_check_xvbatched*: DESIGN.md 24); the passes exist once.
 //
 // One workgroup of 512 threads (8 waves) owns a problem from its first load to its last store.  At these orders neither Z
 // nor S = B Z nor A Z fits in LDS (512 KB each at n = 256), so the three products run on the fp64 matrix cores
@@ -46,8 +48,23 @@ struct Args {
   double *ipr;          // n doubles per problem, or nullptr
 };
 
+// the uniform launch's problem: entry first + workgroup of the map (or that problem), the scratch by workgroup
 template <bool GEN>
-__global__ __launch_bounds__(T) void xcheck_kernel(Args a) {
+__device__ __forceinline__ bcheck::Problem locate_x(const Args &a) {
+  const int n = a.n;
+  const long long pb = a.map ? a.map[a.first + (int)blockIdx.x] : a.first + (int)blockIdx.x;
+  return {n, (cgdouble *)(a.A + pb * a.sA), a.lda, GEN ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (cgdouble *)(a.w + pb * n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
+          GEN ? (gdouble *)(a.S + (long long)blockIdx.x * n * n) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
+          a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr};
+}
+template <bool GEN>
+__device__ __forceinline__ bcheck::Problem locate_x(const bcheck::VArgs &a) { return bcheck::locate(a); }
+
+// ARGS: how the workgroup finds its problem -- Args (one order, strided; the scratch by workgroup) or bcheck::VArgs (entry
+// blockIdx.x of the launch's slice of the table, which names the entry's own scratch)
+template <bool GEN, typename ARGS>
+__global__ __launch_bounds__(T) void xcheck_kernel(ARGS a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double *buf = smem;                               // [2][kBuf]
   double *cs = buf + 2 * kBuf;                      // [3][NW][TN]: the waves' column sums
@@ -55,16 +72,16 @@ __global__ __launch_bounds__(T) void xcheck_kernel(Args a) {
   double *red = sg + EK_HIP_XBATCH_NMAX;            // a word per wave
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, l4 = lane >> 4;
-  const int n = a.n;
-  const long long pb = a.map ? a.map[a.first + (int)blockIdx.x] : a.first + (int)blockIdx.x;
-  cgdouble *A = (cgdouble *)(a.A + pb * a.sA);
-  cgdouble *B = GEN ? (cgdouble *)(a.B + pb * a.sB) : nullptr;
-  cgdouble *w = (cgdouble *)(a.w + pb * n);
-  cgdouble *Z = (cgdouble *)(a.Z + pb * a.sZ);
-  gdouble *S = GEN ? (gdouble *)(a.S + (long long)blockIdx.x * n * n) : nullptr;
-  gdouble *out = (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT);
-  gdouble *ipr = a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr;
-  const int lda = a.lda, ldb = a.ldb, ldz = a.ldz;
+  const bcheck::Problem p = locate_x<GEN>(a);
+  const int n = p.n;
+  cgdouble *A = p.A;
+  cgdouble *B = GEN ? p.B : nullptr;
+  cgdouble *w = p.w;
+  cgdouble *Z = p.Z;
+  gdouble *S = GEN ? p.S : nullptr;
+  gdouble *out = p.out;
+  gdouble *ipr = p.ipr;
+  const int lda = p.lda, ldb = p.ldb, ldz = p.ldz;
   const int nk = (n + KT - 1) / KT;
 
   // ---- 1: A Z, S = B Z, per column ||r_j||^2, G_jj, sum z^4; ||A||_F^2
@@ -218,17 +235,16 @@ __global__ __launch_bounds__(T) void xcheck_kernel(Args a) {
   }
 }
 
-static bool g_raised[2] = {false, false};
-
-template <bool GEN>
-static int launch(hipStream_t s, int count, const Args &a) {
+template <bool GEN, typename ARGS>
+static int launch(hipStream_t s, int count, const ARGS &a) {
   constexpr size_t lds = (size_t)kLdsDoubles * sizeof(double);
-  if (!g_raised[GEN]) {
-    EK_HIP_CHECK(hipFuncSetAttribute((const void *)xcheck_kernel<GEN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  static bool raised = false;                       // one per instantiation
+  if (!raised) {
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)xcheck_kernel<GEN, ARGS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds));
-    g_raised[GEN] = true;
+    raised = true;
   }
-  hipLaunchKernelGGL((xcheck_kernel<GEN>), dim3(count), dim3(T), lds, s, a);
+  hipLaunchKernelGGL((xcheck_kernel<GEN, ARGS>), dim3(count), dim3(T), lds, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -245,6 +261,13 @@ static int entry(const bcheck::Uniform &u, bool nothing, bool host) {
 }
 
 }  // namespace xcheck
+
+// the variable form's launch (ek_batched_check.h): `count` entries of the table, every one of an order above
+// EK_HIP_BATCH_NMAX, a.problem says which instantiation
+int bcheck::launch_x(hipStream_t s, int count, const VArgs &a) {
+  return a.problem ? xcheck::launch<true>(s, count, a) : xcheck::launch<false>(s, count, a);
+}
+
 }  // namespace ek
 
 using namespace ek;

@@ -205,6 +205,12 @@ def load_library(path=None):
         "ek_hip_sygv_xvbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_sygv_xvbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_debug_xvbatched_last": (c_int, [_dp, _ip]),
+        "ek_hip_check_xvbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
+        "ek_hip_check_xvbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
+        "ek_hip_check_sygv_xvbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp,
+                                                       _dp]),
+        "ek_hip_check_sygv_xvbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
+        "ek_hip_debug_check_xvbatched_last": (c_int, [_dp, _ip]),
         "ek_hip_debug_stage_leaves256": (c_int, [c_int]),
         "ek_hip_debug_set_sygst_direct": (c_int, [c_int]),
         "ek_hip_debug_sygst_scratch": (c_ull, [c_int, ctypes.POINTER(c_ull)]),
@@ -258,6 +264,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_sygv_xbatched_device", "ek_hip_check_sygv_xbatched",
     "ek_hip_eigenpairs_xvbatched_device", "ek_hip_eigenpairs_xvbatched", "ek_hip_sygv_xvbatched_device",
     "ek_hip_sygv_xvbatched", "ek_hip_debug_xvbatched_last",
+    "ek_hip_check_xvbatched_device", "ek_hip_check_xvbatched", "ek_hip_check_sygv_xvbatched_device",
+    "ek_hip_check_sygv_xvbatched", "ek_hip_debug_check_xvbatched_last",
     "ek_hip_debug_stage_leaves256", "ek_hip_debug_set_sygst_direct", "ek_hip_debug_sygst_scratch",
 )
 
@@ -1086,6 +1094,33 @@ def check_sygv_vbatched(As, Bs, ws, Zs, itype=1, info=None, ipr=True, seconds=No
     if Bs is None:
         raise ValueError("Bs is required")
     return _check_vbatched_call("ek_hip_check_sygv_vbatched", int(itype), As, Bs, ws, Zs, info, ipr, seconds)
+
+
+def check_xvbatched(As, Bs, ws, Zs, info=None, ipr=True, seconds=None):
+    """check_vbatched for orders up to XBATCH_NMAX (ek_hip_check_xvbatched), behind eigenpairs_xvbatched: the same
+    arguments and returns.  Each problem's bits are those of check_xbatched on it alone; an order beyond XBATCH_NMAX raises
+    SolverError with info -3."""
+    return _check_vbatched_call("ek_hip_check_xvbatched", 0 if Bs is None else 1, As, Bs, ws, Zs, info, ipr, seconds)
+
+
+def check_sygv_xvbatched(As, Bs, ws, Zs, itype=1, info=None, ipr=True, seconds=None):
+    """check_sygv_vbatched for orders up to XBATCH_NMAX (ek_hip_check_sygv_xvbatched), behind sygv_xvbatched: the same
+    arguments and returns, each problem's bits those of check_sygv_xbatched on it alone (itype 1 is check_xvbatched(As,
+    Bs, ...) to the bit)."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if Bs is None:
+        raise ValueError("Bs is required")
+    return _check_vbatched_call("ek_hip_check_sygv_xvbatched", int(itype), As, Bs, ws, Zs, info, ipr, seconds)
+
+
+def check_xvbatched_last():
+    """(seconds, problems) of the classes of 256, 128, 64 and 32 in the last variable-order check call that was given
+    `seconds` (ek_hip_debug_check_xvbatched_last)."""
+    sec = np.zeros(4)
+    cnt = np.zeros(4, dtype=np.int32)
+    load_library().ek_hip_debug_check_xvbatched_last(_P(sec), _I(cnt))
+    return sec, cnt
 
 
 def check_sygvx(A, B, w, Z, itype=1):

@@ -387,7 +387,8 @@ int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const dou
  * streams of their own.  Workspace: that of ek_hip_*_vbatched* (three streams and thirteen events), and, only when an
  * order above EK_HIP_BATCH_NMAX is present, min(problems above EK_HIP_BATCH_NMAX, 1024) images as for
  * ek_hip_eigenpairs_xbatched*; kept until ek_hip_finalize.
- * Not offered: acceptance checks of the variable form above EK_HIP_BATCH_NMAX (ek_hip_check_*vbatched* stop there). */
+ * The acceptance checks of these entries' results, in the form they come in, are ek_hip_check_xvbatched* and
+ * ek_hip_check_sygv_xvbatched* below (ek_hip_check_*vbatched* stop at EK_HIP_BATCH_NMAX). */
 int ek_hip_eigenpairs_xvbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
                                        double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
                                        const int *ldz, int *info, double *seconds);
@@ -499,9 +500,8 @@ int ek_hip_check_batched(int problem, int n, int batch, const double *A, int lda
  * Workspace above EK_HIP_BATCH_NMAX (device memory, grown on demand, kept until ek_hip_finalize): n^2 doubles for each of the
  * min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z; at most 512 MiB; none for problem 0),
  * 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.
- * Not offered at these orders: a check of the variable-order form (the results of ek_hip_eigenpairs_xvbatched* are
- * checked one order at a time here).  The checks of types 2 and 3 at these orders are
- * ek_hip_check_sygv_xbatched* below. */
+ * The variable-order form at these orders is ek_hip_check_xvbatched* below (the results of ek_hip_eigenpairs_xvbatched* in
+ * one call).  The checks of types 2 and 3 at these orders are ek_hip_check_sygv_xbatched* below. */
 int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                  const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                  int ldz, long long strideZ, const int *info, double *out, double *ipr,
@@ -528,6 +528,33 @@ int ek_hip_check_vbatched_device(int problem, int batch, const int *n, const dou
 int ek_hip_check_vbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
                           const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
                           const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
+/* The variable form for orders up to EK_HIP_XBATCH_NMAX, behind ek_hip_eigenpairs_xvbatched*: what ek_hip_check_xbatched* are
+ * to ek_hip_check_batched*, for ek_hip_check_vbatched*.  Prototype for prototype the 14 arguments of
+ * ek_hip_check_vbatched_device / ek_hip_check_vbatched, and their whole contract: host arrays of `batch` entries, device
+ * (device form) or host (host form) addresses IN dA, dB, dw, dZ, host addresses in ipr (ipr == NULL or a NULL entry: not
+ * wanted); A, B, w and Z const and back bit for bit; strictly upper triangles, rows n[b] .. ld-1 and the gaps between
+ * problems never read; the same argument-error codes, decided before any device work and without dereferencing any pointer
+ * of the pointer arrays, the first offender deciding -- with one difference: -3 is for n == NULL or an order outside
+ * 0 .. EK_HIP_XBATCH_NMAX.  n[b] == 0: a_norm = 0 and NaN in the other three slots; info[b] != 0: NaN in the four slots, the
+ * ipr row left alone, w and Z not read (host form: nothing of that problem is staged); batch == 0: 0, nothing referenced or
+ * written.  ek_hip_check_vbatched* keep answering -3 above EK_HIP_BATCH_NMAX.
+ * THE SAME BITS AS THE UNIFORM CALL: problem b's four words and IPRs are those of ek_hip_check_xbatched_device for the same
+ * (n, A, B, w, Z) alone -- wherever it sits, whatever surrounds it, in whichever chunk, in the host and the device form (a
+ * batch without an order above EK_HIP_BATCH_NMAX returns the bits of ek_hip_check_vbatched*).
+ * One stable sort by descending order; the orders above EK_HIP_BATCH_NMAX form a class of their own that runs first, in
+ * chunks of at most 1024 checked problems (ek_hip_debug_check_xbatched_chunk governs it), with the kernel of
+ * ek_hip_check_xbatched* reading its problem from the table; then the classes of 128, 64 and 32 as in ek_hip_check_vbatched*.
+ * Everything runs on one stream: one table upload, the launches, one fetch, one synchronise.  NOT COLLECTIVE.
+ * Workspace: that of ek_hip_check_vbatched*; only when an order above EK_HIP_BATCH_NMAX is present, the scratch is at least
+ * the largest chunk's sum of n[b]^2 doubles of a generalized batch (at most 512 MiB; the other classes lie over the same
+ * buffer). */
+int ek_hip_check_xvbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                  const double *const *dB, const int *ldb, const double *const *dw,
+                                  const double *const *dZ, const int *ldz, const int *info, double *out,
+                                  double *const *ipr, double *seconds);
+int ek_hip_check_xvbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                           const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                           const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
 
 /* The same checks for DSYGV's three problem types -- what ek_hip_check_batched* / ek_hip_check_vbatched* are to
  * ek_hip_eigenpairs_*batched*, these are to ek_hip_sygv_batched* / ek_hip_sygv_vbatched*.  With B = L L^T (B SPD), A and B
@@ -591,9 +618,8 @@ int ek_hip_check_sygv_batched(int itype, int n, int batch, const double *A, int 
  * problems of a chunk n^2 doubles for type 2 (S = B Z; at most 512 MiB) and 2 n^2 for type 3 (A Z, then L, and W; at most
  * 1 GiB), 4 + n doubles per problem for the outputs, 4 bytes per checked problem when some are skipped, two events.  All
  * ek_hip_check_*batched* entries draw on ONE such set of buffers, as large as the largest call so far needed.
- * ek_hip_check_sygv_batched* and ek_hip_check_batched* keep answering -2 above EK_HIP_BATCH_NMAX.  Not offered: a
- * check of the variable-order form above EK_HIP_BATCH_NMAX (ek_hip_sygv_xvbatched*' results are checked one order at a time
- * here). */
+ * ek_hip_check_sygv_batched* and ek_hip_check_batched* keep answering -2 above EK_HIP_BATCH_NMAX.  The variable-order form
+ * above EK_HIP_BATCH_NMAX is ek_hip_check_sygv_xvbatched* below (ek_hip_sygv_xvbatched*' results in one call). */
 int ek_hip_check_sygv_xbatched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
                                       const double *dB, int ldb, long long strideB, const double *dw, const double *dZ,
                                       int ldz, long long strideZ, const int *info, double *out, double *ipr,
@@ -610,6 +636,23 @@ int ek_hip_check_sygv_vbatched_device(int itype, int batch, const int *n, const 
 int ek_hip_check_sygv_vbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
                                const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
                                const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
+/* The variable form for orders up to EK_HIP_XBATCH_NMAX, behind ek_hip_sygv_xvbatched*: the 14 arguments and the contract of
+ * ek_hip_check_sygv_vbatched*, with -3 for n == NULL or an order outside 0 .. EK_HIP_XBATCH_NMAX (-1 for itype outside 1 .. 3
+ * comes first; B always required: -6 / -7).  Problem b's four words and IPRs are the bits of
+ * ek_hip_check_sygv_xbatched_device for the same (itype, n, A, B, w, Z) alone, wherever it sits, in whichever chunk, in the
+ * host and the device form; itype 1 IS ek_hip_check_xvbatched*(problem = 1); slot 3 and the IPRs of type 2 are type 1's
+ * bits; a B that is not SPD under type 3 gives NaN in slot 3 and the IPRs, valid residual slots and the return value 0.
+ * Classes, chunks, stream and copies are those of ek_hip_check_xvbatched*, with the kernel of ek_hip_check_sygv_xbatched* in
+ * the class above EK_HIP_BATCH_NMAX; its scratch is n[b]^2 doubles per entry of a chunk for type 2 and 2 n[b]^2 for type 3
+ * (at most 512 MiB and 1 GiB).  ek_hip_check_sygv_vbatched* keep answering -3 above EK_HIP_BATCH_NMAX.  NOT COLLECTIVE; the
+ * calls synchronise once. */
+int ek_hip_check_sygv_xvbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
+                                       const double *const *dB, const int *ldb, const double *const *dw,
+                                       const double *const *dZ, const int *ldz, const int *info, double *out,
+                                       double *const *ipr, double *seconds);
+int ek_hip_check_sygv_xvbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
+                                const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
+                                const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
 /* One problem of ANY order: the quantities above for the first n_cols columns of Z (what a window of ek_hip_sygvx*
  * returns; sum_j rho_j / n_cols, G of order n_cols), out[0 .. 3] and ipr_host[0 .. n_cols-1] (host; ipr_host may be NULL).
  * dA, dB: the ORIGINAL column-major matrices (lda, ldb >= max(1, n); lower triangles referenced), dw: n_cols eigenvalues,

@@ -137,6 +137,10 @@ int ek_hip_debug_xbatched_chunk(int problems);
    runs in chunks of that many, each chunk reusing the same scratch for S = B Z; types 2 and 3: for the products, L and W).
    0 (or less) restores the default of 1024; returns the previous value.  A tuning and test hook: no result depends on it. */
 int ek_hip_debug_check_xbatched_chunk(int problems);
+/* the last ek_hip_check_*vbatched* or ek_hip_check_*xvbatched* call that was given `seconds`: device time of the classes of
+   256 (orders above EK_HIP_BATCH_NMAX, all chunks), 128, 64 and 32 (events between them on the one stream) and the problems
+   each took; either pointer may be NULL.  The shape of ek_hip_debug_xvbatched_last. */
+int ek_hip_debug_check_xvbatched_last(double class_seconds[4], int class_count[4]);
 
 /* Test hooks of the stage entries of the generalized path (ek_hip_sygst, ek_hip_sygst_ibtype, ek_hip_trtrs; ek_chol.hip).
  *   _stage_leaves256 : 0 (the default, also for any value but 1): the solves of ek_hip_sygst, of type 1 of

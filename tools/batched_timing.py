@@ -19,6 +19,11 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  ek_hip_eigenpairs_xvbatched_device, the baselines go through
                                                  ek_hip_eigenpairs_xbatched_device, the padding is to order 256, and the
                                                  class times are those of the classes of 256 / 128 / 64 / 32
+  python tools/batched_timing.py --mixed --check --mixed-batch 512 --mixed-orders 129,256   (or 8,256)
+                                                 the variable acceptance check (ek_hip_check_xvbatched_device;
+                                                 ek_hip_check_vbatched_device up to order 128) on the variable solve's w
+                                                 and Z, against one uniform check call per distinct order and against the
+                                                 solve's device time; the classes' times and counts of the check
   python tools/batched_timing.py --check [--sizes 64,128] [--batches 1024,4096]
                                                  with vectors only: after each timed solve, the batched check
                                                  (ek_hip_check_batched_device; ek_hip_check_xbatched_device for sizes
@@ -150,10 +155,12 @@ class Case:
             self.lib.ek_hip_free(p)
 
 
-def mixed(lib, batch, lo, hi):
+def mixed(lib, batch, lo, hi, check=False):
     """Generalized with vectors, orders drawn i.i.d. uniformly from lo..hi (seeded).  Best of 3 after a warm-up, the kinds
     alternated, inputs restored outside the clock.  Wall times; for the variable call also the device time and the time of
-    every class's launch (events on its stream)."""
+    every class's launch (events on its stream).  check: the variable acceptance check (ek_hip_check_xvbatched_device, or
+    ek_hip_check_vbatched_device up to order 128) of the variable solve's results against one uniform check call per
+    distinct order and against the solve itself, on the same workload."""
     ip = ctypes.POINTER(ctypes.c_int)
     orders = np.random.default_rng(2048).integers(lo, hi + 1, batch)
     mats = {}
@@ -229,6 +236,13 @@ def mixed(lib, batch, lo, hi):
             assert rc == 0 and not info[:c].any()
         return t
 
+    if check:
+        mixed_check(lib, batch, orders, by_order, (distinct, first, counts), (off, woff, goff, gwoff), (hA, hB, gA, gB),
+                    (dA, dB, dgA, dgB, dw, dZ), (tw, tZ), var, up, put, table, big)
+        for p in keep:
+            lib.ek_hip_free(p)
+        pad.close()
+        return
     if big:
         print("# mixed: %d generalized problems with vectors, orders %d..%d (%d distinct; classes of 256 / 128 / 64 / 32: "
               "%d / %d / %d / %d)" % (batch, lo, hi, len(distinct), (orders > 128).sum(),
@@ -260,6 +274,85 @@ def mixed(lib, batch, lo, hi):
     pad.close()
 
 
+def mixed_check(lib, batch, orders, by_order, groups, offsets, host, device, tables, var, up, put, table, big):
+    """--mixed --check: the rest of mixed() for the checks.  The solve runs once per round (its device time is the
+    yardstick of the "no dearer than the solve" rule); its w and Z stay where the variable call left them and are copied
+    once, ordered by order, for the uniform calls."""
+    ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+    distinct, first, counts = groups
+    off, woff, goff, gwoff = offsets
+    hA, hB, gA, gB = host
+    dA, dB, dgA, dgB, dw, dZ = device
+    tw, tZ = tables
+    c_var = lib.ek_hip_check_xvbatched_device if big else lib.ek_hip_check_vbatched_device
+    c_uni = lib.ek_hip_check_xbatched_device if big else lib.ek_hip_check_batched_device
+    dA0, dB0 = up(hA), up(hB)                       # the originals, the variable call's layout
+    put(dA0, hA); put(dB0, hB)
+    tA0, tB0 = table(dA0, off), table(dB0, off)
+    n32 = orders.astype(np.int32)
+    info = np.zeros(batch, dtype=np.int32)
+    out = np.zeros(batch * 4)
+    q = np.zeros(int(woff[-1]))
+    tq = (ctypes.c_void_p * batch)(*[q.ctypes.data + int(woff[b]) * 8 for b in range(batch)])
+    gout, gq = np.zeros(batch * 4), np.zeros(int(gwoff[-1]))
+    var()                                           # warm-up of the solve; its w and Z feed every check below
+    hw, hZ = np.zeros(int(woff[-1])), np.zeros(int(off[-1]))
+    assert lib.ek_hip_memcpy_d2h(hw.ctypes.data, dw, hw.nbytes) == 0
+    assert lib.ek_hip_memcpy_d2h(hZ.ctypes.data, dZ, hZ.nbytes) == 0
+    gw = np.concatenate([hw[woff[b]:woff[b + 1]] for b in by_order])
+    gZ = np.concatenate([hZ[off[b]:off[b + 1]] for b in by_order])
+    dgw, dgZ = up(gw), up(gZ)
+    put(dgw, gw); put(dgZ, gZ)
+    put(dgA, gA); put(dgB, gB)
+
+    def check_var():
+        sec = ctypes.c_double(0.0)
+        t0 = time.perf_counter()
+        rc = c_var(1, batch, n32.ctypes.data_as(ip), tA0, n32.ctypes.data_as(ip), tB0, n32.ctypes.data_as(ip), tw, tZ,
+                   n32.ctypes.data_as(ip), info.ctypes.data_as(ip), out.ctypes.data_as(dp), tq, ctypes.byref(sec))
+        t = time.perf_counter() - t0
+        assert rc == 0, rc
+        cls, cnt = np.zeros(4), np.zeros(4, dtype=np.int32)
+        assert lib.ek_hip_debug_check_xvbatched_last(cls.ctypes.data_as(dp), cnt.ctypes.data_as(ip)) == 0
+        return t, sec.value, cls, cnt
+
+    def check_grouped():
+        t = 0.0
+        at = lambda p, o: ctypes.c_void_p(p.value + int(o) * 8)  # noqa: E731
+        for n, f, c in zip(distinct, first, counts):
+            n, f, c = int(n), int(f), int(c)
+            t0 = time.perf_counter()
+            rc = c_uni(1, n, c, at(dgA, goff[f]), n, n * n, at(dgB, goff[f]), n, n * n, at(dgw, gwoff[f]),
+                       at(dgZ, goff[f]), n, n * n, None, gout[4 * f:].ctypes.data_as(dp), gq[gwoff[f]:].ctypes.data_as(dp),
+                       None)
+            t += time.perf_counter() - t0
+            assert rc == 0, rc
+        return t
+
+    print("# mixed check: %d generalized problems, orders %d..%d (%d distinct; classes of 256 / 128 / 64 / 32: "
+          "%d / %d / %d / %d), IPRs wanted, device-resident"
+          % (batch, orders.min(), orders.max(), len(distinct), (orders > 128).sum(),
+             ((orders > 64) & (orders <= 128)).sum(), ((orders > 32) & (orders <= 64)).sum(), (orders <= 32).sum()))
+    check_var(); check_grouped()                    # warm-up
+    tv, tg, ts = [], [], []
+    for _ in range(3):
+        ts.append(var()[1])                         # the same bits every time: the checks' inputs do not move
+        tv.append(check_var()); tg.append(check_grouped())
+    best = min(tv, key=lambda x: x[0])
+    dev = min(x[1] for x in tv)
+    o, g = out.reshape(batch, 4), gout.reshape(batch, 4)
+    same = all(np.array_equal(o[b].view(np.uint64), g[k].view(np.uint64))
+               and np.array_equal(q[woff[b]:woff[b + 1]].view(np.uint64), gq[gwoff[k]:gwoff[k + 1]].view(np.uint64))
+               for k, b in enumerate(by_order))
+    print("  t_var wall %.3f ms device %.3f ms | classes %s | t_grouped (%d calls) %.3f ms (ratio %.1f) | solve device "
+          "%.3f ms (check / solve %.3f) | same bits both ways: %s | worst res_max %.2e orthogonality %.2e"
+          % (best[0] * 1e3, dev * 1e3,
+             "  ".join("%s: %d, %.3f ms" % (k, c, v * 1e3) for k, c, v in zip(("256", "128", "64", "32"), best[3], best[2])),
+             len(distinct), min(tg) * 1e3, min(tg) / best[0], min(ts) * 1e3, dev / min(ts), same, o[:, 2].max(),
+             o[:, 3].max()), flush=True)
+    print("            all t_var wall ms: %s" % " ".join("%.3f" % (x[0] * 1e3) for x in tv))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="30,64,128")
@@ -270,7 +363,8 @@ def main():
                          "ek_hip_sygv_xbatched_device above order 128)")
     ap.add_argument("--once", default=None, help="<n>g or <n>s: one generalized / standard batch of 256 with vectors")
     ap.add_argument("--once-batch", type=int, default=256)
-    ap.add_argument("--check", action="store_true", help="time the batched check behind each solve (with vectors)")
+    ap.add_argument("--check", action="store_true", help="time the batched check behind each solve (with vectors); with "
+                    "--mixed: the variable check against a uniform check call per distinct order and against its solve")
     ap.add_argument("--mixed", action="store_true", help="problems of different orders: the variable call "
                     "(an upper order above 128: ek_hip_eigenpairs_xvbatched_device)")
     ap.add_argument("--mixed-batch", type=int, default=2048)
@@ -280,7 +374,7 @@ def main():
     assert lib.ek_hip_init(0) == 0
     if args.mixed:
         lo, hi = (int(x) for x in args.mixed_orders.split(","))
-        mixed(lib, args.mixed_batch, lo, hi)
+        mixed(lib, args.mixed_batch, lo, hi, check=args.check)
         lib.ek_hip_finalize()
         return
     if args.once:
