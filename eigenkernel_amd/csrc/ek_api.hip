@@ -96,9 +96,7 @@ void release_scratch_choice() {
 
 // returns the scratch to use for the tridiagonalisation of order n on matrix wA (arena_work if nothing better)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need) {
-  static int enabled = -1;
-  if (enabled < 0) { const char *e = getenv("EK_HIP_PLACEMENT"); enabled = e ? atoi(e) : 1; }
-  if (!enabled || n < 8192) return arena_work;
+  if (!switch_int(kSwPlacement) || n < 8192) return arena_work;
   if (g_scratch.for_ws == g_ctx.ws_alloc && g_scratch.for_n == n && g_scratch.bytes >= need)
     return g_scratch.buf ? g_scratch.buf : arena_work;
   release_scratch_choice();
@@ -140,7 +138,7 @@ void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *
   for (int c = 1; c < ncand; ++c) if (c != best && cand[c]) (void)hipFree(cand[c]);
   g_scratch.buf = best > 0 ? cand[best] : nullptr;
   g_scratch.bytes = need; g_scratch.for_ws = g_ctx.ws_alloc; g_scratch.for_n = n;
-  if (getenv("EK_HIP_PLACEMENT_VERBOSE"))
+  if (switch_text(kSwPlacementVerbose))
     fprintf(stderr, "[ek_hip] scratch placement: first-panel probes (ms; first = inside the arena):%s -> %s\n", msg,
             best ? "a separate allocation" : "the arena's own");
   return g_scratch.buf ? g_scratch.buf : arena_work;
@@ -209,11 +207,7 @@ void count_mismatch(hipStream_t s, int m, int n, const double *X, int ldx, const
                      lower, count);
 }
 
-int pad_ld(int n) {
-  static int extra = -1;
-  if (extra < 0) { const char *e = getenv("EK_HIP_LDPAD"); extra = e ? atoi(e) : 0; }
-  return round_up(n > 0 ? n : 1, 128) + extra;
-}
+int pad_ld(int n) { return round_up(n > 0 ? n : 1, 128); }
 
 int h2d_matrix(int m, int n, const double *h, int ldh, double *d, int ldd, hipStream_t s) {
   EK_HIP_CHECK(hipMemcpy2DAsync(d, (size_t)ldd * sizeof(double), h, (size_t)ldh * sizeof(double),

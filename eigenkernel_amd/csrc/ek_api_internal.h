@@ -8,6 +8,7 @@
 #include "../../include/ek_hip.h"
 #include "../../include/ek_hip_debug.h"
 #include "ek_common.h"
+#include "ek_switch.h"
 
 #include <rccl/rccl.h>   // types only: the library is bound at run time (dlopen), see ek_comm.hip
 

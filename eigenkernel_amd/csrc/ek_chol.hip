@@ -496,9 +496,7 @@ static void sygst_rec(hipStream_t s, int n, double *A, int lda, const double *L,
   // A22 -= A21 L21^T + L21 A21^T.  As two lower-only products each loses a fifth to its tail (2080 tiles of 2 ms on
   // 512 workgroup slots at n2 = 8192: 45 TFLOP/s); the same flops as ONE full product P = A21 L21^T (68 TFLOP/s, into
   // the space of C11, which is spent) and a pass A22 -= P + P^T over the lower triangle.
-  static int fold = -1;
-  if (fold < 0) { const char *e = getenv("EK_SYGST_FOLD"); fold = e ? atoi(e) : 1; }
-  if (fold && n2 <= n1) {
+  if (n2 <= n1) {
     double *P = C11;
     gemm(s, false, true, n2, n2, n1, 1.0, A21, lda, L21, ldl, 0.0, P, n2);
     hipLaunchKernelGGL(syr2k_fold_kernel, dim3(ceil_div(n2, 32), ceil_div(n2, 32)), dim3(256), 0, s, n2, P, n2, A22, lda);
@@ -921,8 +919,7 @@ void potrf_lower_rl(hipStream_t s, hipStream_t s2, int n, double *B, int ldb, do
   // then takes ONE rank-512 update on stream s -- the next panel's columns first, so that its factorisation
   // runs beside the rest of the update.  With rank-128 updates of the whole trailing matrix (ob = 1, the earlier
   // form) every 128 columns read and wrote the whole trailing triangle: 92 GB of C traffic at N = 16384.
-  static int ob = -1;
-  if (ob < 0) { const char *e = getenv("EK_POTRF_OB"); ob = e ? atoi(e) : 4; if (ob < 1) ob = 1; }
+  constexpr int ob = 4;
   const int NOB = ceil_div(NRB, ob);
   auto factor_outer = [&](hipStream_t st, int o) {
     const int k0 = o * ob, k1 = (k0 + ob < NRB) ? k0 + ob : NRB;

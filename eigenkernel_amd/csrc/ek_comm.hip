@@ -27,7 +27,7 @@ struct Rccl {
   ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
   int load() {
     if (h) return 0;
-    const char *names[] = {getenv("EK_HIP_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+    const char *names[] = {switch_text(kSwRcclLib), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
     for (const char *nm : names) {
       if (!nm || !*nm) continue;
       h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
@@ -97,17 +97,13 @@ void rccl_allgatherv(hipStream_t s, int nmem, int, double *const *bufs, const si
 int g_two_stage_min = -1;
 int two_stage_min() {
   if (g_two_stage_min >= 0) return g_two_stage_min;
-  static int env = -2;
-  if (env == -2) { const char *e = getenv("EK_HIP_TWO_STAGE_MIN"); env = e ? atoi(e) : -1; }
+  const int env = switch_int(kSwTwoStageMin);
   return env >= 0 ? env : 512;
 }
 
 // From how many ranks on the Cholesky factor and the reduction to standard form are distributed
 // as well (below that their replicated forms are cheaper); EK_HIP_DIST_MIN_RANKS overrides (tests).
-int dist_min_ranks() {
-  const char *e = getenv("EK_HIP_DIST_MIN_RANKS");
-  return e ? atoi(e) : 3;
-}
+int dist_min_ranks() { return switch_int(kSwDistMinRanks); }
 
 // ---- the same two exchanges through the host's allgatherv hook (ek_hip_set_allgatherv): for
 // hosts that have MPI but no RCCL-capable node, and for multi-process tests on one GPU.  Every

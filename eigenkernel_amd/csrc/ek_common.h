@@ -48,8 +48,8 @@ struct GemmDesc {
 };
 void gemm(hipStream_t s, const GemmDesc &g);
 
-// What gemm() launches for a descriptor: a pure host function of it (and of EK_GEMM_VEC / EK_GEMM_W8 / EK_GEMM_RANKK, read
-// once), no GPU.  gemm() itself launches by it; the test hooks of ek_debug.hip report it.
+// What gemm() launches for a descriptor: a pure host function of it, no GPU.  gemm() itself launches by it; the test
+// hooks of ek_debug.hip report it.
 enum { kGemmNone = -1, kGemmSmall = 0, kGemmW4 = 1, kGemmW8 = 2, kGemmRankK = 3 };
 struct GemmPlan {
   int kernel;            // kGemm*: gemm_small_kernel, gemm_kernel, gemm_kernel_w8, gemm_rankk_kernel; None: nothing to do

@@ -159,7 +159,7 @@ int ek_hip_sytrd_team(int n, double *A_loc, const int desc_A[9], double *d, doub
     EK_HIP_CHECK(hipMemsetAsync(dd, 0, 3 * al((size_t)ld * 8), s));
     rc = h2d_matrix(n, n, A_loc, desc_A[8], dA, ld, s); if (rc) return rc;
     mem[m] = SytrdMember{dA, ld, dd, de, dt, nullptr, 0, work, nteam > 0 ? m : g_comm.rank};
-    const char *poison = getenv("EK_HIP_TEAM_POISON");
+    const char *poison = switch_text(kSwTeamPoison);
     if (poison && poison[0] == '1' && P > 1)
       poison_foreign_strips(s, n, dA, ld, P, mem[m].rank);
   }
@@ -284,7 +284,7 @@ int ek_hip_debug_sy2sb_team(int n, double *A, int lda, double *V, int ldv, doubl
     EK_HIP_CHECK(hipMemsetAsync(dt, 0, (size_t)ld * 8, s));
     rc = h2d_matrix(n, n, A, lda, dA, ld, s); if (rc) return rc;
     mem[m] = Sy2sbMember{dA, ld, dV, ld, dt, d_flags + m, work, nteam > 0 ? m : g_comm.rank};
-    const char *poison = getenv("EK_HIP_TEAM_POISON");
+    const char *poison = switch_text(kSwTeamPoison);
     if (poison && poison[0] == '1' && P > 1)
       poison_foreign_strips(s, n, dA, ld, P, mem[m].rank);
   }
@@ -438,7 +438,7 @@ int ek_hip_debug_two_stage_timing(int n, int ncols, int reps, double *seconds, i
 
 // Tuning hook (not part of the drop-in surface): tridiagonalise a device-generated synthetic
 // matrix of order n held with leading dimension ld, `reps` times; seconds[0] = stage time per
-// repetition.  Honour EK_SYTRD_MAXCOLS to time only the first panels.
+// repetition.  ek_hip_debug_set_sytrd_maxcols makes it time only the first panels.
 int ek_hip_debug_sytrd(int n, int ld, int reps, double *seconds) {
   int rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);

@@ -726,10 +726,8 @@ GemmPlan gemm_plan(const GemmDesc &g) {
   // lower-only products of one batch entry: a grid of the tiles on and below the diagonal only
   const bool compact = g.lower_only && g.batch == 1 && !g.d_dims && !g.d_offs;
   // 16-byte operand fetch: every slab start must be 16-byte aligned -- even leading dimensions, aligned bases,
-  // even batch strides, no per-batch offsets from device memory (EK_GEMM_VEC=0 turns the variants off)
-  static int vec_env = -1;
-  if (vec_env < 0) { const char *e = getenv("EK_GEMM_VEC"); vec_env = e ? atoi(e) : 1; }
-  pl.vec = vec_env && (!g.d_offs || g.even_offs) && ((g.lda | g.ldb) & 1) == 0 &&
+  // even batch strides, no per-batch offsets from device memory
+  pl.vec = (!g.d_offs || g.even_offs) && ((g.lda | g.ldb) & 1) == 0 &&
            ((((size_t)g.A | (size_t)g.B) & 15) == 0) && (g.batch == 1 || ((g.strideA | g.strideB) & 1) == 0);
   const bool small = (big_tiles < 256 && !g.lower_only) || (g.lower_only && g.small_tiles);
   pl.tile = small ? SM : BM;
@@ -743,15 +741,10 @@ GemmPlan gemm_plan(const GemmDesc &g) {
   // Rank-k updates (short K, C read-modify-write) run on the 8-wave variant: twice the resident
   // waves hide the operand and C latency that the 4-wave kernel exposes when there are only a few
   // k-steps per tile (measured: SYR2K of the tridiagonalisation -25 %); long-K products stay on
-  // the 4-wave kernel (measured 3 % faster there).  EK_GEMM_W8=0/1 forces one of them.
-  static int w8 = -2;
-  if (w8 == -2) { const char *e = getenv("EK_GEMM_W8"); w8 = e ? atoi(e) : -1; }
-  // rank-k updates with short K: the staged 8-wave kernel (EK_GEMM_RANKK=0 turns it off)
-  static int rankk = -1;
-  if (rankk < 0) { const char *e = getenv("EK_GEMM_RANKK"); rankk = e ? atoi(e) : 1; }
-  if (rankk && g.staged_rank_k && !g.transA && g.transB && g.K <= 256 && g.K >= 32 && w8 < 0) { pl.kernel = kGemmRankK; return pl; }
-  const bool use_w8 = (w8 >= 0) ? (w8 != 0) : (g.K <= 512 && g.beta != 0.0);
-  pl.kernel = use_w8 ? kGemmW8 : kGemmW4;
+  // the 4-wave kernel (measured 3 % faster there).
+  // rank-k updates with short K: the staged 8-wave kernel
+  if (g.staged_rank_k && !g.transA && g.transB && g.K <= 256 && g.K >= 32) { pl.kernel = kGemmRankK; return pl; }
+  pl.kernel = (g.K <= 512 && g.beta != 0.0) ? kGemmW8 : kGemmW4;
   return pl;
 }
 

@@ -29,6 +29,7 @@
 // sweeps the factors are applied with k ascending, blocks of sweeps descending; reflectors of
 // different blocks commute unless their row ranges overlap, which this order respects.
 #include "ek_common.h"
+#include "ek_switch.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -118,7 +119,6 @@ struct ChaseArgs {
   unsigned *prog;        // [nsweeps] tasks completed per sweep
   unsigned *ctl;         // [0] ticket, [1] abort, [3] "the position-owned kernel gave up" (this kernel then runs), [4] census
   double *mail; int kmax;   // mailbox lines [4][kmax][MAILW]
-  long long *prof;       // optional: [0..5] shader cycles per phase of a task summed over workgroup 0's tasks, [6] tasks
   int only_if_abandoned; // run only if ctl[3] is set (the fall-back behind chase_pos_kernel)
   const int *skip;       // device: non-zero = the band is not valid (the first stage raised its flag): do nothing
 };
@@ -307,9 +307,6 @@ __global__ __launch_bounds__(64 * NW) void chase_kernel(ChaseArgs p) {
       const int i0 = s + 1 + k * SB;                       // first index of I_k
       const int L = (n - i0 < SB) ? n - i0 : SB;           // its length (>= 2)
       int L1 = n - i0 - SB; if (L1 > SB) L1 = SB; if (L1 < 0) L1 = 0;
-      long long tc0 = 0, tc1 = 0, tc2 = 0, tc3 = 0, tc4 = 0;
-      const bool prof = p.prof && blockIdx.x == 0 && t == 0;
-      if (prof) tc0 = clock64();
       // the previous sweep's task k+1, if it has one: its late numbers come through the mailbox
       const bool lead = s > 0 && k + 1 < Kprev;
       double *mail = p.mail + ((size_t)((s - 1) & 3) * p.kmax + (k + 1)) * MAILW;
@@ -333,7 +330,6 @@ __global__ __launch_bounds__(64 * NW) void chase_kernel(ChaseArgs p) {
         m_a = ld_sc1(mail + ((lane < 63) ? lane + 1 : 64));
         if (lane == 63) m_b = ld_sc1(mail);
       }
-      if (prof) tc1 = clock64();
       // ---- (a) the reflector of task 0: x = A(I_0, s) (final: the previous sweep's task 0 is complete).  Those of
       // the later tasks were made at the end of the previous task (below).
       const int cur = k & 1;
@@ -346,7 +342,6 @@ __global__ __launch_bounds__(64 * NW) void chase_kernel(ChaseArgs p) {
         }
         __syncthreads();                                                     // #1 (first task only)
       }
-      if (prof) tc2 = clock64();
       const double tau = s_tau[cur];
       const double v_r = s_v[cur][lane];
       double vc[CW];
@@ -384,7 +379,6 @@ __global__ __launch_bounds__(64 * NW) void chase_kernel(ChaseArgs p) {
       }
       __syncthreads();                                                       // #2
       if (!s_ok) return;
-      if (prof) tc3 = clock64();
       // ---- partial sums of p = D v and q = B_k v
       double dd[CW];
       {
@@ -395,7 +389,6 @@ __global__ __launch_bounds__(64 * NW) void chase_kernel(ChaseArgs p) {
         s_p[wave][lane] = pp; s_q[wave][lane] = qq;
       }
       __syncthreads();                                                       // #3
-      if (prof) tc4 = clock64();
       // ---- the reflector of task k+1 first: it needs column 0 of the new B_k = B_k H only (first wave), and the
       // next sweep is waiting for its beta.  The column goes to memory at once as (beta, 0, ..., 0), beta into
       // the mailbox (in the last task: entry (0,0) of the final B_k, or nothing).
@@ -456,11 +449,6 @@ __global__ __launch_bounds__(64 * NW) void chase_kernel(ChaseArgs p) {
           }
         }
       }
-      if (prof) {
-        const long long tc5 = clock64();
-        p.prof[0] += tc1 - tc0; p.prof[1] += tc2 - tc1; p.prof[2] += tc3 - tc2; p.prof[3] += tc4 - tc3;
-        p.prof[4] += tc5 - tc4; p.prof[6] += 1;
-      }
       if (k + 1 < K) {
         __syncthreads();                                                     // #4: the new reflector is in LDS
         // ---- (b) B_k <- H' B_k with the NEW reflector (rows I_{k+1}): the block is final for this sweep
@@ -494,11 +482,9 @@ struct PosArgs {
   double *fwd, *bwd;     // [K0 + 1][4][MAILW]: line (k, s & 3) is written by position k-1 (fwd) / k+1 (bwd) for position k
   unsigned *retired;     // [K0 + 1]: position k has finished its last task and left A(n-1, n-1) in the band array
   unsigned *ctl;         // [3] abandoned, [4] census of the workgroups
-  int per;               // 0: workgroup b holds position b; > 0: position (b & 7) * per + (b >> 3), neighbours mostly on one XCD
   unsigned census_spins;
   const int *skip;       // device: non-zero = the band is not valid (the first stage raised its flag): do nothing
   unsigned jitter;       // test aid (EK_SB2ST_JITTER): pseudo-random pauses of single positions, to shake the timing
-  long long *trace; int trace_k;   // EK_SB2ST_TRACE=<position>: wall-clock stamps (10 ns) of that position's first 2048 sweeps
 };
 
 template <int CTRL>
@@ -518,7 +504,7 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
   __shared__ int s_ok;
   constexpr int RW = 1;                                    // the wave that makes the reflectors
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int k = p.per > 0 ? (int)(blockIdx.x & 7) * p.per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  const int k = (int)blockIdx.x;                           // workgroup b holds position b
   if (k >= p.K0) return;
   if (p.skip && (*p.skip & 0xff)) return;
   const int n = p.n;
@@ -586,13 +572,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
     const bool lead = s > 0 && k + 1 < Kprev;              // position k+1 had a task in sweep s-1: its late numbers come by mail
     // every store of the previous task (mail, emptied lines) has completed before this task sends anything
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef EK_POS_TRACE      // diagnostic build only: the stamps cost 15 % of the stage even when no position is traced
-    const bool tr = p.trace && k == p.trace_k && s < 2048 && lane == 0;
-    auto stamp = [&](int slot) { if (tr) p.trace[16 * s + slot] = (long long)wall_clock64(); };
-#else
-    auto stamp = [](int) {};
-#endif
-    if (wave == 0) stamp(0);
     if (p.jitter) {                                        // (uniform per workgroup and sweep)
       const unsigned h = ((unsigned)s * 2654435761u) ^ ((unsigned)k * 40503u * p.jitter);
       if (((h >> 9) & 15u) == 0u) for (unsigned q = 0; q < ((h >> 3) & 63u); ++q) __builtin_amdgcn_s_sleep(64);
@@ -612,7 +591,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
         s_v[0][lane] = (lane == 0) ? 1.0 : a;
         if (lane == 0) s_tau[0] = a;
       }
-      stamp(1);
     }
     // ---- the entering column: the late numbers of position k+1's task of the previous sweep
     if (wave == NW - 1 && s > 0) {
@@ -625,7 +603,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
         const double col = (lane < 63) ? up : beta;
         bk[CW - 1] = (lane < L1 && SB - 1 < L) ? col : 0.0;
         if (lane == 63 && SB - 1 < L) dd[CW - 1] = corner;
-        stamp(2);
       } else if (L == SB) {
         // the one sweep after position k+1 has retired (or never existed): the corner is A(n-1, n-1) in the band array
         int ok = 1;
@@ -645,7 +622,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
     }
     __syncthreads();                                                         // #1
     if (!s_ok) return;
-    if (wave == 0) stamp(3);
     const double tau = s_tau[0];
     const double v_r = s_v[0][lane];
     double vc[CW];
@@ -658,7 +634,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
       if (wave == 0) s_b0[lane] = bk[0];
     }
     __syncthreads();                                                         // #2
-    if (wave == 0) stamp(7);
     // ---- the reflector of position k+1: position k+1 is waiting for it.  Made by wave RW from column 0 of B_k (which
     // wave 0 has put into LDS) while wave 0 updates column 0 of D_k, the late numbers position k-1 is waiting for.
     if (wave == RW) {
@@ -671,7 +646,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
         const Reflector r = reflector_of(col0, lane);
         double *line = p.fwd + ((size_t)(k + 1) * 4 + (s & 3)) * PMAILW;
         st_sc1(line + lane, (lane == 0) ? r.tau : r.v);
-        stamp(4);
         s_v[1][lane] = r.v;
         if (lane == 0) { s_tau[1] = r.tau; p.tau2[(size_t)(k + 1) + (size_t)s * p.ldt] = r.tau; }
         if (lane < L1) p.V2[(size_t)(i0 + SB + lane) + (size_t)s * p.ldv2] = r.v;
@@ -690,7 +664,7 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
     if (wave == 0) {
       // column 0 of D_k leaves the position: the late numbers of position k-1, or (position 0) d and the next column
       dd[0] = task_rank2(dd[0], v_r, lane_value(w_r, 0), w_r, vc[0]);
-      if (k > 0) { st_sc1(p.bwd + ((size_t)(k - 1) * 4 + (s & 3)) * PMAILW + lane, dd[0]); stamp(5); }
+      if (k > 0) st_sc1(p.bwd + ((size_t)(k - 1) * 4 + (s & 3)) * PMAILW + lane, dd[0]);
       else if (lane == 0) AB[(size_t)(s + 1) * LDAB] = dd[0];              // d(s+1): read after the kernel -- a plain store: the
                                                                             // wait at the top of the next sweep would sit out an sc1 store's way to memory
     }
@@ -707,13 +681,10 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
 #pragma unroll
       for (int j = 0; j < CW; ++j) bp[j] = (L1 > 0) ? task_right(bk[j], q_r, vc[j]) : 0.0;
     }
-    if (wave == 0) stamp(8);
     if (k + 1 < K) {
       __syncthreads();                                                       // #3: the new reflector is in LDS
-      if (wave == 0) stamp(9);
       task_left<CW>(bp, s_v[1][lane], s_tau[1], s_t[wave], lane, wave == 0);
     }
-    if (wave == 0) stamp(6);
     if (s == s_last) break;
     // ---- the blocks of the next sweep: one row and one column further down the band
     if (lane == 0) {
@@ -722,7 +693,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
     }
     s_x[wave][lane] = dd[0]; s_y[wave][lane] = bp[0];
     __syncthreads();                                                         // #4
-    if (wave == 0) stamp(10);
     if (k == 0 && wave == 0) {
       const double up = dpp_shift<0x130>(dd[0]);
       xnext = (lane < 63) ? up : s_b00;
@@ -739,7 +709,6 @@ __global__ __launch_bounds__(512) void chase_pos_kernel(PosArgs p) {
       bk[j] = (lane == 63) ? 0.0 : bu;
     }
     if (wave == NW - 1) dd[CW - 1] = (lane < 63) ? s_row[lane + 1] : 0.0;    // the corner and B's last column: next sweep's mail
-    if (wave == 0) stamp(11);
   }
   // ---- retirement: the last task had L = 2; what is left of D_k is A(n-1, n-1) (position 0: also e(n-2))
   if (wave == 0) {
@@ -908,7 +877,6 @@ struct Q2ApplyArgs {
   int nslab, npass, npair;   // npair = ceil(nS / NBLK) bundles of blocks of sweeps (NBLK q ..); bundle q = 0 is the lowest
   unsigned *prog;        // [npass] chunks stored by pass (bundle, slab) at index (npair-1-bundle) * nslab + slab
   unsigned *ctl;         // [2] ticket, [1] abort (shared with the chase)
-  int extra;             // chunks a pass keeps behind its predecessor beyond the two it must
 };
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -1127,7 +1095,7 @@ __global__ __launch_bounds__(256, 2) void q2_apply_nb_kernel(Q2ApplyArgs p) {
       return rec_of(nb, nk);
     };
     // ---- prologue: the window at step 0; its rows from 32 NBLK on are chunk 0 of the bundle above (+ slack)
-    if (t == 0) s_ok = wait_for((unsigned)(1 + p.extra)) ? 1 : 0;
+    if (t == 0) s_ok = wait_for(1u) ? 1 : 0;
     __syncthreads();
     if (!s_ok) { if (t == 0) __hip_atomic_store(&p.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
 #pragma unroll
@@ -1148,7 +1116,7 @@ __global__ __launch_bounds__(256, 2) void q2_apply_nb_kernel(Q2ApplyArgs p) {
     for (int k = 0; k < KS; ++k) {
       // gate of this step: the 64 rows fetched below are chunk k + 1 of the bundle above
       if (t == 0) {
-        const unsigned need = (unsigned)(k + 2 + p.extra);
+        const unsigned need = (unsigned)(k + 2);
         s_ok = (!pprog || early >= need || wait_for(need)) ? 1 : 0;
       }
       __syncthreads();
@@ -1279,88 +1247,35 @@ void sb2st_lower(hipStream_t s, int n, const double *A, int lda, double *d, doub
     // which kernel: 1 = sweeps through memory (chase_kernel), 2 = positions in registers (chase_pos_kernel, with
     // chase_kernel behind it in case its workgroups cannot all become resident); default 2 where the chip holds K0
     int mode = 2;
-    static int env_mode = -1;
-    if (env_mode < 0) { const char *ev = getenv("EK_SB2ST_CHASE"); env_mode = ev ? atoi(ev) : 0; }
-    if (env_mode > 0) mode = env_mode;
+    if (switch_int(kSwChase) > 0) mode = switch_int(kSwChase);
     if (chase_mode > 0) mode = chase_mode;
     const int K0 = (n - 3) / SB + 1;
-    const bool pos = mode == 2 && K0 <= pos_capacity() && !getenv("EK_SB2ST_WGS") && !getenv("EK_SB2ST_PROF");
+    const bool pos = mode == 2 && K0 <= pos_capacity() && !switch_text(kSwChaseWgs);
     kprof_begin(s, kProfChase);
     if (pos) {
       hipLaunchKernelGGL(mail_init_kernel, dim3(ceil_div(npmail, 256)), dim3(256), 0, s, pmail, npmail);
       (void)hipMemsetAsync(retired, 0, (size_t)(L.kmax + 2) * 4, s);
       hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, s, retired + K0, 1u);   // there is no position K0
-      // neighbours on one XCD (EK_SB2ST_XCDMAP=1) buy nothing at one workgroup per CU (N = 16384: 52.0 vs 51.6 ms) and
-      // cost at two (N = 32768: 143 vs 125 ms: the two workgroups of a CU are then close in the pipeline and busy together)
-      int per = 0;
-      if (const char *ev = getenv("EK_SB2ST_XCDMAP")) { if (atoi(ev) != 0) per = ceil_div(K0, 8); }
-      unsigned census = 1u << 16;                            // x ~0.3 us: what a workgroup waits for the others to arrive
-      if (const char *ev = getenv("EK_SB2ST_CENSUS_SPINS")) census = (unsigned)atoi(ev);
-      PosArgs a{n, K0, AB, V2, ldv2, tau2, L.ldt, pmail, pmail + (size_t)4 * (L.kmax + 2) * PMAILW, retired, ctl, per, census, d_flag,
-                getenv("EK_SB2ST_JITTER") ? (unsigned)atoi(getenv("EK_SB2ST_JITTER")) : 0u, nullptr, -1};
-#ifdef EK_POS_TRACE
-      static long long *trace_buf = nullptr;
-      if (const char *ev = getenv("EK_SB2ST_TRACE")) {
-        if (!trace_buf) (void)hipMalloc((void **)&trace_buf, 2048 * 16 * sizeof(long long));
-        (void)hipMemsetAsync(trace_buf, 0, 2048 * 16 * sizeof(long long), s);
-        a.trace = trace_buf; a.trace_k = atoi(ev);
-      }
-#endif
-      hipLaunchKernelGGL(chase_pos_kernel, dim3(per > 0 ? per * 8 : K0), dim3(512), 0, s, a);
+      // (workgroup b holds position b: neighbours on one XCD instead buy nothing at one workgroup per CU (N = 16384: 52.0 vs
+      // 51.6 ms) and cost at two (N = 32768: 143 vs 125 ms: the two workgroups of a CU are then close in the pipeline and busy
+      // together))
+      const unsigned census = (unsigned)switch_int(kSwCensusSpins);   // x ~0.3 us: what a workgroup waits for the others to arrive
+      PosArgs a{n, K0, AB, V2, ldv2, tau2, L.ldt, pmail, pmail + (size_t)4 * (L.kmax + 2) * PMAILW, retired, ctl, census, d_flag,
+                (unsigned)switch_int(kSwChaseJitter)};
+      hipLaunchKernelGGL(chase_pos_kernel, dim3(K0), dim3(512), 0, s, a);
       hipLaunchKernelGGL(repack_band_kernel, dim3(n), dim3(LDAB), 0, s, n, AB0, AB, ctl);
-#ifdef EK_POS_TRACE
-      if (a.trace) {                                         // diagnostic: average gaps between the stamps, sweeps 256 .. 2047
-        static long long h[2048 * 16];
-        (void)hipMemcpyAsync(h, a.trace, sizeof(h), hipMemcpyDeviceToHost, s);
-        (void)hipStreamSynchronize(s);
-        double acc[16] = {0}; int cnt = 0;
-        for (int q = 256; q + 1 < 2048 && q + 1 <= L.nsweeps - 64 * (a.trace_k + 2); ++q) {
-          const long long *r = h + 16 * q, *r1 = h + 16 * (q + 1);
-          if (!r[0] || !r1[0]) continue;
-          acc[0] += (double)(r1[0] - r[0]);                 // period
-          for (int j = 1; j < 16; ++j) acc[j] += r[j] ? (double)(r[j] - r[0]) : 0.0;
-          ++cnt;
-        }
-        if (cnt)
-          fprintf(stderr, "[sb2st trace] position %d, %d sweeps: period %.0f ns; from the top of a sweep: forward mail taken %.0f, "
-                  "backward mail taken %.0f, barrier #1 passed %.0f, #2 passed %.0f, backward sent %.0f, forward sent %.0f, "
-                  "D and B H done %.0f, #3 passed %.0f, H B done %.0f, #4 passed %.0f, shifted %.0f ns\n",
-                  a.trace_k, cnt, 10 * acc[0] / cnt, 10 * acc[1] / cnt, 10 * acc[2] / cnt, 10 * acc[3] / cnt, 10 * acc[7] / cnt,
-                  10 * acc[5] / cnt, 10 * acc[4] / cnt, 10 * acc[8] / cnt, 10 * acc[9] / cnt, 10 * acc[6] / cnt, 10 * acc[10] / cnt,
-                  10 * acc[11] / cnt);
-      }
-#endif
     }
     hipLaunchKernelGGL(mail_init_kernel, dim3(ceil_div(nmail, 256)), dim3(256), 0, s, mail, nmail);
-    ChaseArgs c{n, L.nsweeps, AB, V2, ldv2, tau2, L.ldt, prog, ctl, mail, L.kmax + 1, nullptr, pos ? 1 : 0, d_flag};
-    if (getenv("EK_SB2ST_PROF")) { c.prof = (long long *)(ctl + 16); }
+    ChaseArgs c{n, L.nsweeps, AB, V2, ldv2, tau2, L.ldt, prog, ctl, mail, L.kmax + 1, pos ? 1 : 0, d_flag};
     // enough workgroups for the pipeline (a sweep starts one task behind its predecessor)
     int nwg = n / SB + 8;
     if (nwg > 256) nwg = 256;
     if (nwg > L.nsweeps) nwg = L.nsweeps;
-    if (const char *ev = getenv("EK_SB2ST_WGS")) { const int v = atoi(ev); if (v > 0) nwg = v; }
-    static int nw = -1;
-    if (nw < 0) { const char *ev = getenv("EK_SB2ST_WAVES"); nw = ev ? atoi(ev) : 8; }
-    if (nw == 16) hipLaunchKernelGGL(chase_kernel<16>, dim3(nwg), dim3(1024), 0, s, c);
-    else if (nw == 8) hipLaunchKernelGGL(chase_kernel<8>, dim3(nwg), dim3(512), 0, s, c);
-    else hipLaunchKernelGGL(chase_kernel<4>, dim3(nwg), dim3(256), 0, s, c);
+    if (switch_int(kSwChaseWgs) > 0) nwg = switch_int(kSwChaseWgs);
+    hipLaunchKernelGGL(chase_kernel<8>, dim3(nwg), dim3(512), 0, s, c);
     kprof_end(s, kProfChase);
   }
   hipLaunchKernelGGL(unpack_de_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, n, AB, d, e);
-  if (getenv("EK_SB2ST_PROF")) {
-    long long h[8];
-    (void)hipMemcpyAsync(h, ctl + 16, sizeof(h), hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[sb2st prof] tasks %lld; cycles per task: gate+loads %.0f, reflector %.0f, left-apply+fill %.0f, "
-            "partials %.0f, updates %.0f\n", h[6], (double)h[0] / h[6], (double)h[1] / h[6], (double)h[2] / h[6],
-            (double)h[3] / h[6], (double)h[4] / h[6]);
-  }
-  if (getenv("EK_SB2ST_VERBOSE")) {
-    unsigned h[8];
-    (void)hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[sb2st] n %d: abort %u, positions abandoned %u, census %u\n", n, h[1], h[3], h[4]);
-  }
   hipLaunchKernelGGL(forward_abort_kernel, dim3(1), dim3(1), 0, s, ctl, d_flag);   // abort word -> caller's flag
 }
 
@@ -1388,20 +1303,17 @@ void sb2st_apply_q2(hipStream_t s, int n, int ncols, const double *V2, int ldv2,
   // blocks of sweeps per pass: 4 from order 8192 on, 3 below (N = 16384: 0.194 / 0.199 / 0.212 s with 4 / 3 / 2,
   // N = 4096: 4.9 / 4.7 / 4.9 ms); EK_Q2_NBLK = 2, 3, 4 forces one (all give the same bits)
   int nblk = (n >= 8192) ? 4 : 3;
-  if (const char *ev = getenv("EK_Q2_NBLK")) { const int v = atoi(ev); if (v >= 2 && v <= 4) nblk = v; }
+  { const int v = switch_int(kSwQ2Nblk); if (v >= 2 && v <= 4) nblk = v; }
   const int per = nblk;
   const int nslab = ceil_div(ncols, QNC), npair = ceil_div(L.nS, per), npass = npair * nslab;
   (void)hipMemsetAsync(qprog, 0, (size_t)npass * 4, s);
   (void)hipMemsetAsync(ctl + 2, 0, 4, s);
-  // extra: how many further steps a pass stays behind its predecessor in the slab (fetch distance).  With few slabs
-  // the passes of a slab are one dependent chain and every step of distance is paid npair times: 0 / 1 / 2 / 3 give
+  // (A pass stays no further behind its predecessor in the slab than the two steps it must.  With few slabs
+  // the passes of a slab are one dependent chain and every step of distance is paid npair times:
   // 21.0 / 22.2 / 24.2 / 26.2 ms for 1024 columns at N = 16384, 5.1 / 5.4 / 5.6 / 6.0 ms at N = 4096, and the same
-  // 227 ms for all 16384 columns.
-  Q2ApplyArgs a{g, Rec, Z, ldz, ncols, nslab, npass, npair, qprog, ctl, 0};
-  if (const char *ev = getenv("EK_Q2_EXTRA")) a.extra = atoi(ev);
-  int nwg = 512;
-  if (const char *ev = getenv("EK_Q2_WGS")) { const int v = atoi(ev); if (v > 0) nwg = v; }
-  if (nwg > npass) nwg = npass;
+  // 227 ms for all 16384 columns with 0 / 1 / 2 / 3 further steps of fetch distance.)
+  Q2ApplyArgs a{g, Rec, Z, ldz, ncols, nslab, npass, npair, qprog, ctl};
+  const int nwg = npass < 512 ? npass : 512;
   kprof_begin(s, kProfQ2Apply);
   if (nblk == 3) hipLaunchKernelGGL(q2_apply_nb_kernel<3>, dim3(nwg), dim3(256), lds, s, a);
   else if (nblk == 4) hipLaunchKernelGGL(q2_apply_nb_kernel<4>, dim3(nwg), dim3(256), lds, s, a);

@@ -141,7 +141,7 @@ struct HostPipe {
   struct Job { double *dev; int ldd; double *host; int ldh; int m, n; hipEvent_t after; int tag; bool to_host; bool tri = false; };
   static constexpr int kMaxThreads = 8;
   static constexpr int kTri = 512;           // columns of a diagonal block on the way out (2 MiB of scratch per worker)
-  int kThreads = 2;                          // per direction (EK_HIP_PIPE_THREADS; default by the cores the process has)
+  int kThreads = 2;                          // per direction (by the cores the process has)
   int kOutThreads = 2;                       // of them on the way out (see start())
   bool lower_only = true;                    // EK_HIP_PIPE_LOWER=0: whole matrices both ways, as round 3
   std::mutex mu;
@@ -190,7 +190,7 @@ struct HostPipe {
         fprintf(stderr, "[pipe] main thread waited %.4f s (%s) at t = %.4f\n", r.t1 - r.t0, r.kind == 2 ? "input" : "drain", r.t0);
       }
     }
-    if (getenv("EK_HIP_PIPE_TRACE") && atoi(getenv("EK_HIP_PIPE_TRACE")) >= 2)       // every job
+    if (switch_int(kSwPipeTrace) >= 2)       // every job
       for (const auto &r : trace_log)
         if (r.kind < 2) fprintf(stderr, "[pipe] job %s %8.1f MB  t = %.4f .. %.4f  (%.1f GB/s)\n", r.kind ? "out" : "in ", r.bytes / 1e6, r.t0, r.t1,
                                 r.bytes / 1e9 / (r.t1 - r.t0 > 1e-9 ? r.t1 - r.t0 : 1e-9));
@@ -204,20 +204,17 @@ struct HostPipe {
   int start(int dev) {
     device = dev;
     t_origin = std::chrono::steady_clock::now();
-    { static int tr = -1; if (tr < 0) { const char *e = getenv("EK_HIP_PIPE_TRACE"); tr = (e && atoi(e) != 0) ? 1 : 0; } trace = tr != 0; }
-    static int env_threads = -2;
-    { static int lo = -1; if (lo < 0) { const char *e = getenv("EK_HIP_PIPE_LOWER"); lo = (e && atoi(e) == 0) ? 0 : 1; } lower_only = lo != 0; }
+    trace = switch_once(kSwPipeTrace) != 0;
+    lower_only = switch_int(kSwPipeLower) != 0;
     const int cores = usable_cores();
     kThreads = cores >= 16 ? 6 : cores >= 8 ? 4 : 2;      // (both directions are rarely busy at once)
-    if (env_threads >= 1 && env_threads <= kMaxThreads) kThreads = env_threads;
     { const int rc = g_pipe_streams.ensure(2 * kThreads); if (rc) return rc; }
     for (int i = 0; i < 2 * kThreads; ++i) cs[i] = g_pipe_streams.cs[i];
     // The way out hands pageable memory to the runtime: two threads saturate the link (30 GB/s
     // each), and MORE than two collapse under the HIP runtime PyTorch bundles (2.10: 1.7 GB/s per thread with three, 0.9
     // with six, beside running kernels; the system's runtime does 10 - 20 with any number) -- which is the runtime that
     // serves a process that imported torch first.  EK_HIP_PIPE_THREADS_OUT overrides.
-    static int env_out = -2;
-    if (env_out == -2) { const char *e = getenv("EK_HIP_PIPE_THREADS_OUT"); env_out = e ? atoi(e) : -1; }
+    const int env_out = switch_int(kSwPipeThreadsOut);
     kOutThreads = kThreads < 2 ? kThreads : 2;
     if (env_out >= 1 && env_out <= kThreads) kOutThreads = env_out;
     for (int i = 0; i < kThreads + kOutThreads; ++i) th.emplace_back([this, i]() { run(i < kThreads, cs[i]); });
@@ -512,8 +509,7 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
   // leading dimension = order, 256-byte aligned: the bench's and the host path's arrays at the BASELINE orders): the
   // stage-in / stage-out copies of A, B and Z -- five passes over 2 GiB at N = 16384, 4.4 ms of a 0.86 s solve -- are
   // then not made (EK_HIP_ALIAS=0: always copy).  The plan above keeps its sizes: an upper bound.
-  const char *alias_e = getenv("EK_HIP_ALIAS");          // (read per call: the tests switch it)
-  const int alias_env = (alias_e && atoi(alias_e) == 0) ? 0 : 1;
+  const int alias_env = switch_int(kSwAlias);            // (read per call: the tests switch it)
   auto alias_ok = [&](const double *p, int ldu) {
     return alias_env && p && n % 128 == 0 && ldu == ld && (((size_t)p) & 255) == 0;
   };
@@ -583,8 +579,7 @@ int solve_device_locked(int problem, int n, int n_vec, double *dA, int lda, doub
     for (int q = 0; q < 256; ++q) { if (part[q] > anrm) anrm = part[q]; if (!(part[256 + q] <= offband)) offband = part[256 + q]; }
     // the reference's own inputs are sparse Hamiltonians, often banded: a matrix with nothing below its 64th subdiagonal
     // IS the output of the dense -> band stage (EK_HIP_BAND_INPUT=0 turns the short cut off)
-    const char *band_env = getenv("EK_HIP_BAND_INPUT");
-    band_input = !(band_env && atoi(band_env) == 0) && problem == 0 && !dist && offband == 0.0;
+    band_input = switch_int(kSwBandInput) != 0 && problem == 0 && !dist && offband == 0.0;
     if (!(anrm <= 1.7e308)) return -4;   // NaN / Inf in A: illegal value, as XERBLA
     // the tridiagonalisation forms x^T A x of the unscaled column (|A|^3 n^2): keep cubes in range
     const double rmin = 1e-90, rmax = 1e90;
@@ -1467,8 +1462,7 @@ int ek_hip_solve(int problem, int n, int n_vec, double *A_loc, const int desc_A[
     uw = (double *)((char *)uZ + nnal);
     if (problem == 1) uB = (double *)((char *)uw + al((size_t)n * 8));
   }
-  int pipe_min = 2048;           // EK_HIP_PIPE_MIN: order from which the host path stages through the pipeline (0: never)
-  if (const char *e = getenv("EK_HIP_PIPE_MIN")) pipe_min = atoi(e);
+  const int pipe_min = switch_int(kSwPipeMin);   // order from which the host path stages through the pipeline (0: never)
   if (pipe_min > 0 && n >= pipe_min) {
     // staging pipeline: the copies overlap the stages (HostPipe): what remains exposed is B's way in, the rest of A's
     // behind the Cholesky factorisation, and the last slab of Z

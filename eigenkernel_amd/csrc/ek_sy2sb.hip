@@ -25,6 +25,7 @@
 // The band is left in the lower band of A, R (with the signs of the reconstruction) in the panel.
 #include "ek_common.h"
 #include "ek_block64.h"
+#include "ek_switch.h"
 
 #include <chrono>
 #include <cstdlib>
@@ -347,7 +348,6 @@ struct HrArgs {
   const double *G2; const double *Qt; int ldq; const double *R1;
   double *M2, *T, *L1, *Rband, *tau;
   int *flag;
-  long long *prof;   // optional: shader cycles per phase
 };
 // LDS: THREE 64 x 64 images (round 5; four until round 4).  With 135 KB the workgroup could only start on a CU that BOTH
 // resident workgroups of a trailing update had left, and a freed slot went to the update's next workgroup first: beside
@@ -363,9 +363,6 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
   __shared__ double s_red[4];
   __shared__ double s_inv[kScratch];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  long long tc[10]; int nt = 0;
-  const bool prof = p.prof && t == 0;
-  if (prof) tc[nt++] = clock64();
   // G2 and its distance from the identity: the loss of orthogonality of the first pass
   double dev = 0.0;
   double gv[16], qv[16];
@@ -395,7 +392,6 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
     // random triangles of kappa ~ 1e7, came out with eigenvalues 1.5e-9 off.)  The rest goes to the rescue.
     if (!(dmax <= EK_CHOLQR_MAXDEV)) atomicOr(p.flag, 2);
   }
-  if (prof) tc[nt++] = clock64();
   if (dmax <= 1e-10) {                                                   // (uniform)
     // G2 = I + E with |E| <= 1e-10: the factor is R2 = I + U, U = striu(E) + diag(E) / 2, and R2^-1 = I - U, both to
     // O(E^2) = 64 x 1e-20 entrywise, far below the rounding of the products they enter -- the 64 serial steps of a
@@ -408,12 +404,9 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
       sB[i * LD + j] = one - u;                                          // sB = R2^-1
     }
     __syncthreads();
-    if (prof) { tc[nt++] = clock64(); tc[nt++] = clock64(); }
   } else {
     if (chol64_upper_wg(sA, s_inv) >= 0 && t == 0) atomicOr(p.flag, 1);      // sA = R2
-    if (prof) tc[nt++] = clock64();
     triinv64_upper_wg(sA, sB, s_inv);                                    // sB = R2^-1
-    if (prof) tc[nt++] = clock64();
   }
   // Q top = Qt_top R2^-1 into the accumulators; then R1 takes the place of Qt's top block and R2 R1 is formed while R2
   // is still there (the signs it is scaled by come from the LU below); then Q top takes R2's place
@@ -441,9 +434,7 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
   double *sD = sA;                                                       // (R2 has served)
   mm64_store(qacc, sD);                                                 // sD = Q top
   __syncthreads();
-  if (prof) tc[nt++] = clock64();
   lu64_signed_wg(sD, s_sign, s_inv);                               // sD = L1 \ U of (Q_top - S)
-  if (prof) tc[nt++] = clock64();
   for (int idx = t; idx < SB * SB; idx += 256) {
     const int i = idx & 63, j = idx >> 6;
     p.L1[idx] = (i > j) ? sD[i * LD + j] : (i == j ? 1.0 : 0.0);
@@ -457,7 +448,6 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
   }
   __syncthreads();
   triinv64_upper_wg(sD, sC, s_inv);                                      // sC = U^-1
-  if (prof) { tc[nt++] = clock64(); tc[nt++] = clock64(); }
   __syncthreads();
   mm64(sB, false, sC, false, nullptr, p.M2);                            // M2 = R2^-1 U^-1
   {                                                                     // S R2 R1
@@ -470,7 +460,6 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
         p.Rband[i + SB * j] = s_sign[i] * p.Rband[i + SB * j];
       }
   }
-  if (prof) { tc[nt++] = clock64(); for (int q = 0; q + 1 < nt; ++q) p.prof[q] += tc[q + 1] - tc[q]; p.prof[9] += 1; }
 }
 
 // ---------------------------------------------------------------- panel with few rows: Householder
@@ -1283,7 +1272,7 @@ struct Layout {
     off_ypart = o; o += al256((size_t)maxsplit * mpad * SB * 8);
     off_gpart = o; o += al256((size_t)nparts * SB * SB * 8);
     off_gpart2 = o; o += al256((size_t)nparts * SB * SB * 8);
-    off_small = o; o += al256((size_t)24 * SB * SB * 8);   // [10 * 4096 ..): profile counters
+    off_small = o; o += al256((size_t)24 * SB * SB * 8);   // (slot 10 is free)
     if (P == 0) {
       // the trailing update's operands for up to two pending panels: A-operand [W1 | V1 | W2 | V2], B-operand
       // [V1 | W1 | V2 | W2], double-buffered for the look-ahead (in place of the two [W | V | W] images)
@@ -1309,7 +1298,6 @@ struct Layout {
 struct ChainBufs {
   int n, mpad;
   double *Qt, *Gpart2, *Gred2, *R1, *R1inv, *M2, *L1, *Rband;
-  long long *prof;
   int *pflag;               // the flag of the panel in flight (device)
   int *nzrows;              // [panel]: 1 + the last non-zero 64-row chunk of the panel (zeroed at the start of the stage)
 };
@@ -1346,7 +1334,7 @@ void panel_chain(hipStream_t st, const ChainBufs &b, double *A, int lda, double 
   pa.M = b.R1; pa.dst = b.Qt; pa.ldd = b.mpad;           // (Q1 = A R1^-1 by substitution against R1 itself)
   hipLaunchKernelGGL(panel_kernel<1>, dim3(nch), dim3(256), 0, st, pa);
   hipLaunchKernelGGL(reduce_parts_kernel, dim3(128), dim3(256), 0, st, nch, b.Gpart2, b.Gred2);
-  HrArgs ha{b.Gred2, b.Qt, b.mpad, b.R1, b.M2, Tp, b.L1, b.Rband, tau1 + c0, b.pflag, b.prof};
+  HrArgs ha{b.Gred2, b.Qt, b.mpad, b.R1, b.M2, Tp, b.L1, b.Rband, tau1 + c0, b.pflag};
   hipLaunchKernelGGL(hr_kernel, dim3(1), dim3(256), 3 * IMG * sizeof(double), st, ha);
   // the rescue of a panel CholeskyQR2 could not factor (one workgroup; it leaves at once otherwise), then the final pass
   hipLaunchKernelGGL(house_tall_kernel, dim3(1), dim3(HT), 0, st, m, Ap, lda, tau1 + c0, b.pflag, d_flag,
@@ -1476,23 +1464,20 @@ void sy2sb_lower(hipStream_t s, hipStream_t s2, int n, double *A, int lda, doubl
   // panel-chain scratch of the look-ahead stream (its Gram partials must not meet those of yred)
   double *Gpart2 = (double *)(w + L.off_gpart2), *Gred2 = sm + 11 * 4096;
   const int ldi = L.mpad;
-  const bool prof = getenv("EK_SY2SB_PROF") != nullptr;
-  if (prof) (void)hipMemsetAsync(sm + 10 * 4096, 0, 128, s);
   // rest of the trailing update: below 8192 rows the staged rank-k kernel (one workgroup per CU: the panel chain
   // of the look-ahead finds room beside it), above the plain 8-wave GEMM (two per CU, 33 against 27 - 32 TFLOP/s
   // alone; the chain is short against the update there).  N = 16384: 0.2025 -> 0.1949 s, N = 32768: 1.364 -> 1.278 s.
-  static int staged_max = -1;
-  if (staged_max < 0) { const char *e = getenv("EK_SY2SB_STAGED_MAX"); staged_max = e ? atoi(e) : 8192; }
-  static int la_min = -1;
-  if (la_min < 0) { const char *e = getenv("EK_SY2SB_LOOKAHEAD_MIN"); la_min = e ? atoi(e) : 5120; }
+  constexpr int staged_max = 8192;
+  const int la_min = switch_int(kSwLookaheadMin);
   constexpr int small_max = 4096;  // (N = 4096: stage 14.6 -> 13.9 ms)
-  int pair_min = 5120;             // rows of the first panel's trailing matrix from which panels go in pairs (0: never)
-  { const char *e = getenv("EK_SY2SB_PAIR_MIN"); if (e) pair_min = atoi(e); }      // (read per call: the tests force pairs at small orders)
+  // rows of the first panel's trailing matrix from which panels go in pairs (0: never; read per call: the tests force
+  // pairs at small orders)
+  const int pair_min = switch_int(kSwPairMin);
 
   int *nzrows = (int *)(sm + 13 * 4096);               // one word per panel (room for 8192)
   (void)hipMemsetAsync(nzrows, 0, (size_t)ceil_div(n, SB) * sizeof(int), s);
   (void)hipMemsetAsync(sm + 12 * 4096, 0, 128, s);      // the panel's flag and the arrival counter of a rescued panel's outputs
-  const ChainBufs cb{n, L.mpad, Qt, Gpart2, Gred2, R1, R1inv, M2, L1, Rband, prof ? (long long *)(sm + 10 * 4096) : nullptr,
+  const ChainBufs cb{n, L.mpad, Qt, Gpart2, Gred2, R1, R1inv, M2, L1, Rband,
                      (int *)(sm + 12 * 4096), nzrows};
   // block j (0..3) of an operand image, from image row `row` on
   auto blk = [&](double *img, int j, int row) -> double * { return img + (size_t)row + (size_t)j * SB * ldi; };
@@ -1582,15 +1567,6 @@ void sy2sb_lower(hipStream_t s, hipStream_t s2, int n, double *A, int lda, doubl
     }
     pb ^= 1;
   }
-  if (getenv("EK_SY2SB_PROF")) {
-    long long h[10];
-    (void)hipMemcpyAsync(h, sm + 10 * 4096, sizeof(h), hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    if (h[9] > 0)
-      fprintf(stderr, "[hr_kernel prof] calls %lld; cycles: load %.0f chol %.0f inv %.0f qtop-mm %.0f lu %.0f tsolve+uinv %.0f "
-              "r1-load %.0f mm2 %.0f\n", h[9], (double)h[0] / h[9], (double)h[1] / h[9], (double)h[2] / h[9], (double)h[3] / h[9],
-              (double)h[4] / h[9], (double)h[5] / h[9], (double)h[6] / h[9], (double)h[7] / h[9]);
-  }
 }
 
 
@@ -1659,8 +1635,7 @@ void sy2sb_lower_dist(hipStream_t s, hipStream_t s2, int n, int nmem, const Sy2s
     }
     evs = true;
   }
-  int la_env = -1;      // (read per call: the multi-process test compares both forms inside one process group)
-  { const char *e = getenv("EK_SY2SB_DIST_LOOKAHEAD_MIN"); if (e) la_env = atoi(e); }
+  const int la_env = switch_int(kSwDistLookaheadMin);   // (read per call: the multi-process test compares both forms inside one process group)
   const int la_min = g_dist_la_min >= 0 ? g_dist_la_min : (la_env >= 0 ? la_env : 1024);
   const bool la_on = s2 != nullptr && la_min > 0;
   const int P = x.nranks;
@@ -1680,7 +1655,7 @@ void sy2sb_lower_dist(hipStream_t s, hipStream_t s2, int n, int nmem, const Sy2s
     double *sm = m.sm;
     m.Tm[0] = sm + 4 * 4096; m.Tm[1] = sm + 9 * 4096;
     m.cb = ChainBufs{n, L.mpad, m.Qt, (double *)(w + L.off_gpart2), sm + 11 * 4096, sm + 4096, sm + 2 * 4096, sm + 3 * 4096,
-                     sm + 5 * 4096, sm + 6 * 4096, nullptr, (int *)(sm + 12 * 4096), (int *)(sm + 13 * 4096)};
+                     sm + 5 * 4096, sm + 6 * 4096, (int *)(sm + 12 * 4096), (int *)(sm + 13 * 4096)};
     (void)hipMemsetAsync(sm + 13 * 4096, 0, (size_t)ceil_div(n, SB) * sizeof(int), s);
     (void)hipMemsetAsync(sm + 12 * 4096, 0, 128, s);
     msgs[q] = m.msg; ys[q] = m.Y;

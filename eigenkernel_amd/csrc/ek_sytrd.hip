@@ -665,16 +665,9 @@ struct SymvProfile {
   double seconds = 0.0;
 } g_prof;
 
-// bring-up / tuning knobs (environment), read once
+// tuning knob (sytrd_set_max_cols: the placement probes, ek_hip_debug_set_sytrd_maxcols)
 struct Knobs {
-  int max_cols = -1;   // EK_SYTRD_MAXCOLS: stop after this many columns (micro-benchmarks only)
-  int G = 0;           // EK_SYMV_G: minimum tiles per symv workgroup (0 = none)
-  int wgs = 0;         // EK_SYMV_WGS: symv workgroups to aim for (0 = 512)
-  Knobs() {
-    if (const char *e = getenv("EK_SYMV_WGS")) wgs = atoi(e);
-    if (const char *e = getenv("EK_SYTRD_MAXCOLS")) max_cols = atoi(e);
-    if (const char *e = getenv("EK_SYMV_G")) G = atoi(e);
-  }
+  int max_cols = -1;   // stop after this many columns (micro-benchmarks only)
 };
 Knobs &knobs_rw() { static Knobs k; return k; }
 const Knobs &knobs() { return knobs_rw(); }
@@ -746,7 +739,7 @@ void sytrd_lower(hipStream_t s, int n, double *A, int lda, double *d, double *e,
     hipLaunchKernelGGL(colupd_kernel<false>, dim3(nblk), dim3(256), 0, s, c);
     return nblk;
   };
-  const int wg_target = knobs().wgs > 0 ? knobs().wgs : 512;   // 2 resident workgroups per CU
+  constexpr int wg_target = 512;   // 2 resident workgroups per CU
 
   int nchunks_cur = 0;
   for (int j0 = 0; j0 < n - 1; j0 += NBP) {
@@ -763,9 +756,8 @@ void sytrd_lower(hipStream_t s, int n, double *A, int lda, double *d, double *e,
       sv.ntiles = T * (T + 1) / 2;
       // ~2 resident workgroups per CU for large trailing matrices; one per CU once the matrix is
       // small enough that per-workgroup fixed costs dominate (measured: T <= 40 strips)
-      const int target = (knobs().wgs > 0) ? wg_target : (T <= 40 ? 256 : wg_target);
+      const int target = T <= 40 ? 256 : wg_target;
       sv.q = ceil_div(sv.ntiles, target);
-      if (knobs().G > 0 && sv.q < knobs().G) sv.q = knobs().G;
       sv.nwg = ceil_div(sv.ntiles, sv.q);
       sv.ndot = (i > 0) ? NDOT : 0;
       sv.nchunks = nchunks_cur;
@@ -932,9 +924,8 @@ void sytrd_lower_dist(hipStream_t s, int n, int nmem, const SytrdMember *mem, co
           // a member streams 1/P of the triangle per launch, so per-workgroup fixed costs weigh
           // more than on one GPU: one workgroup per CU (measured, team of 8, s per rank: N=16384
           // 0.470 / 0.460 / 0.474 / 0.472 at 192 / 256 / 384 / 512; N=32768 1.70 / 1.72 at 256 / 512)
-          const int target = (knobs().wgs > 0) ? knobs().wgs : 256;
+          constexpr int target = 256;
           sv.q = ceil_div(sv.ntiles, target);
-          if (knobs().G > 0 && sv.q < knobs().G) sv.q = knobs().G;
           sv.nwg = ceil_div(sv.ntiles, sv.q);
         } else { sv.q = 1; sv.nwg = 0; }
         sv.ndot = (i > 0) ? NDOT : 0;

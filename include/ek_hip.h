@@ -856,7 +856,32 @@ int ek_hip_check(int what, int problem, int n, int n_cols, int index1, int index
  * deallocates A without reading it, solver_scalapack_all.f90:19-124).  The library times a one-off
  * placement probe inside the first large one-stage solve (EK_HIP_PLACEMENT=0 turns it off; it prints
  * nothing unless EK_HIP_PLACEMENT_VERBOSE is set).
- * Tuning, profiling and test hooks are declared in ek_hip_debug.h, not here. */
+ * Tuning, profiling and test hooks are declared in ek_hip_debug.h, not here.
+ *
+ * Run-time switches: every environment variable the library reads (csrc/ek_switch.h is the one reader; INTEGRATION.md 7
+ * says more about each).  A set variable counts as atoi() of its text.  once: the first read is kept for the life of
+ * the process; each call: read at every use.
+ *   name | default | read | meaning
+ *   EK_HIP_TWO_STAGE_MIN | 512 | once | order from which two stages tridiagonalise (0: never)
+ *   EK_HIP_DIST_MIN_RANKS | 3 | each call | ranks from which the Cholesky factor and the reduction are distributed
+ *   EK_HIP_RCCL_LIB | none | each call | text: the RCCL library to load before the usual names
+ *   EK_HIP_PIPE_MIN | 2048 | each call | order from which ek_hip_solve stages through its pipeline (0: never)
+ *   EK_HIP_PIPE_TRACE | 0 | once and each call | not 0: the pipeline's report (once), 2: with every job (each call)
+ *   EK_HIP_PIPE_LOWER | 1 | once | 0: whole matrices cross PCIe both ways
+ *   EK_HIP_PIPE_THREADS_OUT | 2 | once | copy threads on the way out
+ *   EK_HIP_ALIAS | 1 | each call | 0: always copy the caller's device arrays
+ *   EK_HIP_BAND_INPUT | 1 | each call | 0: no short cut for a matrix that is a band already
+ *   EK_HIP_PLACEMENT | 1 | once | 0: no placement probe
+ *   EK_HIP_PLACEMENT_VERBOSE | unset | each call | set: the probe's timings on stderr
+ *   EK_HIP_TEAM_POISON | unset | each call | test aid: NaN into the strips a rehearsed member does not own
+ *   EK_SY2SB_PAIR_MIN | 5120 | each call | rows from which dense -> band takes its panels in pairs (0: never)
+ *   EK_SY2SB_LOOKAHEAD_MIN | 5120 | once | rows from which the next panel is factored beside the update
+ *   EK_SY2SB_DIST_LOOKAHEAD_MIN | 1024 | each call | the same for a team (0: never)
+ *   EK_SB2ST_CHASE | 2 | once | 1: band -> tridiagonal by sweeps through memory only
+ *   EK_SB2ST_WGS | unset | each call | test aid: sweeps through memory with this many workgroups
+ *   EK_SB2ST_JITTER | 0 | each call | test aid: seed of pauses that shake the position kernel's timing
+ *   EK_SB2ST_CENSUS_SPINS | 65536 | each call | polls the position kernel's workgroups wait for each other
+ *   EK_Q2_NBLK | by order | each call | blocks of sweeps per pass of Q2: 2, 3 or 4 */
 
 #ifdef __cplusplus
 }

@@ -13,5 +13,5 @@ solver.eigen_solver("general_hip", A[:512, :512].copy(), B[:512, :512].copy())
 for rep in range(2):
     t = time.time(); ep, _ = solver.eigen_solver("general_hip", A, B); dt = time.time() - t
     dev = sum(v for k, v in ep.stage_seconds.items() if "copies" not in k)
-    print("pin=%s N=%d GEP: wall %.3f s (incl. numpy copies), device stages %.3f s, reported copies %.3f s"
-          % (os.environ.get("EK_HIP_PIN", "1"), n, dt, dev, ep.stage_seconds["ek_hip:host_device_copies"]))
+    print("N=%d GEP: wall %.3f s (incl. numpy copies), device stages %.3f s, reported copies %.3f s"
+          % (n, dt, dev, ep.stage_seconds["ek_hip:host_device_copies"]))
