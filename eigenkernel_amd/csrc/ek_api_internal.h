@@ -2,7 +2,8 @@
 //   ek_api.hip    boundary: context, memory, the stage-level entries (one per ScaLAPACK call), acceptance checks
 //   ek_comm.hip   the communicator that stands where the reference has its BLACS context: RCCL (bound at run time),
 //                 the host-hook exchange, the team's agreements
-//   ek_solve.hip  the whole-path driver (solve_device_locked), the staging pipeline of the host path, ek_hip_solve*
+//   ek_solve.hip  the whole-path driver (the Path behind solve_device_locked), its plan, the device and window entries
+//   ek_solve_host.hip  the entries on host arrays (ek_hip_solve, ..._replicated, ...) and their staging pipeline
 //   ek_debug.hip  tuning / profiling / rehearsal hooks of include/ek_hip_debug.h and the *_team entries
 #pragma once
 #include "../../include/ek_hip.h"
@@ -68,7 +69,7 @@ inline size_t al(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 void release_scratch_choice();
 int user_images(size_t bytes, void **p);   // device images of host arrays, kept between calls (ek_api.hip)
 void release_user_images();
-void release_pipe_streams();       // the staging pipeline's copy streams (ek_solve.hip)
+void release_pipe_streams();       // the staging pipeline's copy streams (ek_solve_host.hip)
 void release_batched();            // the batched entries' per-problem status words (ek_batched.hip)
 void release_xbatched();           // the images of ek_hip_eigenpairs_xbatched* (ek_batched_x.hip)
 // orders above EK_HIP_BATCH_NMAX: the chunks' launches on s, status words to dinfo (device); g_mu held
@@ -140,6 +141,62 @@ const char *comm_error_string();
 
 // ---- whole path (ek_solve.hip)
 void gather_band_strips(hipStream_t s, int n, int nmem, int rank0, double *const *ABs, const SytrdExchange &x);
+
+// the library's return code for a runtime error (0 for hipSuccess); EK_TRY passes a stage's nonzero code on
+inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -1000 - (int)e; }
+#define EK_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
+// a window of the spectrum (ek_hip_eigenvalues*, ek_hip_eigenpairs*, ek_hip_sygvx*): see the Path of ek_solve.hip
+struct Window {
+  int jobz, range, il, iu;
+  double vl, vu;
+  int zcap;
+  int m, first;            // out
+};
+constexpr int kWindowTooSmall = -990;
+
+// One call of the whole path on device arrays (column-major, any ld >= n); callers fill in the fields they use.
+struct HostPipe;
+struct PathCall {
+  int problem = 0, itype = 1, n = 0, n_vec = 0;
+  double *dA = nullptr; int lda = 0;
+  double *dB = nullptr; int ldb = 0;
+  double *dw = nullptr, *dZ = nullptr; int ldz = 0;
+  double *stage_seconds = nullptr; int n_stages = 0;
+  const GridCell *cell = nullptr;       // a grid cell's share of the eigenvectors
+  HostPipe *pipe = nullptr;             // the host path's staging pipeline
+  Window *win = nullptr;
+};
+// the arguments of ek_hip_solve_device, in its order, as a request (cell, pipe, win and itype are the caller's to add)
+inline PathCall path_call(int problem, int n, int n_vec, double *dA, int lda, double *dB, int ldb, double *dw, double *dZ,
+                          int ldz, double *stage_seconds, int n_stages) {
+  PathCall c;
+  c.problem = problem; c.n = n; c.n_vec = n_vec;
+  c.dA = dA; c.lda = lda; c.dB = dB; c.ldb = ldb; c.dw = dw; c.dZ = dZ; c.ldz = ldz;
+  c.stage_seconds = stage_seconds; c.n_stages = n_stages;
+  return c;
+}
+int solve_device_locked(const PathCall &call);      // g_mu held
+// arguments 1 .. 9 of ek_hip_solve_device, ..._device_grid and ..._replicated, and of ek_hip_eigenvalues*, in order (LAPACK -k)
+int solve_args(int problem, int n, int n_vec, const void *A, int lda, const void *B, int ldb, const void *w, const void *Z);
+int eigenvalues_args(int problem, int n, int il, int iu, const void *A, int lda, const void *B, int ldb, const void *w);
+// both entries of ek_hip_eigenvalues* under the lock (the arrays are the device's)
+int eigenvalues_locked(int problem, int n, int il, int iu, double *dA, int lda, double *dB, int ldb, double *dw,
+                       double *stage_seconds, int n_stages);
+// the argument checks of ek_hip_eigenpairs* / ek_hip_sygvx* in argument order, and both entries under the lock
+int eigenpairs_args(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, const void *A, int lda,
+                    const void *B, int ldb, const int *m, const int *ifirst, const void *w, const void *Z, int ldz,
+                    int zcap);
+int eigenpairs_locked(int problem, int jobz, int range, int n, double vl, double vu, int il, int iu, double *dA, int lda,
+                      double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ, int ldz, int zcap,
+                      double *stage_seconds, int n_stages, int itype);
+
+// ---- host entries and their staging pipeline (ek_solve_host.hip); what the Path asks of a pipeline:
+int pipe_wait_in(HostPipe *p, int tag);           // B (tag 0) or A (1) is in HBM; the pipeline's error, if any
+int pipe_z_slab(const HostPipe *p);               // columns of Z per slab on the way out
+// what stream s has made final leaves for the host: the lower triangle of A ('A') or L ('B') from the caller's device
+// array dev (ldd), or columns c0 .. c0 + nc - 1 of Z ('Z')
+void pipe_out(HostPipe *p, hipStream_t s, char which, double *dev, int ldd, int n, int c0, int nc);
 
 }  // namespace api
 }  // namespace ek
