@@ -257,6 +257,7 @@ int ek_hip_finalize(void) {
   release_batched();
   release_xbatched();
   release_batched_check();
+  release_sparse_host();
   // a communicator does not outlive the library's device state
   comm_teardown();
   return 0;

@@ -191,6 +191,22 @@ int eigenpairs_locked(int problem, int jobz, int range, int n, double vl, double
                       double *dB, int ldb, int *m, int *ifirst, double *dw, double *dZ, int ldz, int zcap,
                       double *stage_seconds, int n_stages, int itype);
 
+// ---- triplet inputs (ek_sparse.hip); sparse::Csr is the host form of ek_sparse_csr.h
+}  // namespace api
+namespace sparse { struct Csr; }
+namespace api {
+// (nnz, suffix, value) at argument positions pos, pos + 1, pos + 2: -position of the first offender (a negative count; a
+// NULL suffix or an index outside 1 .. n; a NULL value), or 0
+int triplet_args(int n, long long nnz, const int *suf, const double *val, int pos);
+// the host CSRs of A and, with_b, of B (built side by side on two threads) in storage the library keeps between calls:
+// g_mu held; valid until the next call; never throws
+int csr_build(int n, long long nnzA, const int *sufA, const double *valA, const sparse::Csr **hA, bool with_b,
+              long long nnzB, const int *sufB, const double *valB, const sparse::Csr **hB);
+void release_sparse_host();                          // that storage (ek_hip_finalize)
+size_t csr_device_bytes(int n, long long nnz);       // device bytes of a CSR, bounded by the list: 2 nnz entries
+// the CSR into dst (csr_device_bytes(n, nnz_list) bytes of device memory) on stream s; h must outlive the stream's work
+int csr_upload(hipStream_t s, const sparse::Csr &h, long long nnz_list, void *dst, DevCsr *d);
+
 // ---- host entries and their staging pipeline (ek_solve_host.hip); what the Path asks of a pipeline:
 int pipe_wait_in(HostPipe *p, int tag);           // B (tag 0) or A (1) is in HBM; the pipeline's error, if any
 int pipe_z_slab(const HostPipe *p);               // columns of Z per slab on the way out

@@ -362,4 +362,24 @@ size_t sygv_check_work_bytes(int itype, int n, int ncols);
 void sygv_check(hipStream_t s, int itype, int n, int ncols, const double *A, int lda, const double *B, int ldb,
                 const double *w, const double *Z, int ldz, double *d_out, double *d_ipr, int *d_info, void *work);
 
+// ---------------------------------------------------------------- triplet inputs (ek_sparse.hip, ek_verify.hip)
+// the CSR of a mirrored symmetric matrix (ek_sparse_csr.h builds it on the host) in device memory
+struct DevCsr { const long long *rowptr; const int *col; const double *val; long long nnz; };
+// M (n x n, ld) <- the dense mirrored matrix: zero fill, then both triangles from the CSR (no duplicates, no races)
+void sparse_densify(hipStream_t s, int n, const DevCsr &m, double *M, int ld);
+// The three acceptance quantities from the CSRs of A and B: residual over the first n_check columns, orthogonality over
+// the n_orth columns from c0 on, n_ipr ratios; a count of 0 skips its part.  hi_orth = c0 + n_orth.  Byte offsets into work:
+struct SparseCheckLayout {
+  size_t Zt, St, S, G, part, vec, total;
+  int ncu, ldt, rows, chunks;   // columns of Z the pass takes, their padded count, rows per wave, chunks of rows
+  SparseCheckLayout(int problem, int n, int n_check, int n_orth, int hi_orth, int n_ipr);
+};
+size_t sparse_check_work_bytes(int problem, int n, int n_check, int n_orth, int hi_orth, int n_ipr);
+// phases: kSparseMetric (S, the orthogonality and the IPRs: B alone is read), kSparseResidual (A is read; after the other,
+// on the same stream: A's CSR need not be in device memory before), or both, one after the other
+enum { kSparseMetric = 1, kSparseResidual = 2 };
+void sparse_check(hipStream_t s, int phases, int problem, int n, const DevCsr &A, const DevCsr &B, const double *w,
+                  const double *Z, int ldz, int n_check, int c0, int n_orth, int n_ipr, double *d_out /* 8 */,
+                  double *d_ipr, void *work);
+
 }  // namespace ek

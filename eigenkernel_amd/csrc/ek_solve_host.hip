@@ -1,8 +1,10 @@
 // ek_solve_host.hip -- the whole path on host arrays: the C entries ek_hip_solve (1 x 1 through the staging pipeline or
-// plain; grids through a communicator or the host's allgatherv hook), ek_hip_solve_replicated, ek_hip_eigenvalues,
+// plain; grids through a communicator or the host's allgatherv hook), ek_hip_solve_replicated, ek_hip_solve_sparse
+// (the same on triplets: the images are densified in HBM, ek_sparse.hip), ek_hip_eigenvalues,
 // ek_hip_eigenpairs and ek_hip_sygvx of include/ek_hip.h.  Each stages device images of its arrays (HostImages) around
 // one call of the Path (ek_solve.hip: solve_device_locked).
 #include "ek_api_internal.h"
+#include "ek_sparse_csr.h"
 
 #include <condition_variable>
 #include <sched.h>
@@ -409,6 +411,50 @@ int replicated_host_locked(int problem, int n, int n_vec, double *A, int lda, do
   return im.finish(info, stage_seconds, n_stages);
 }
 
+// Replicated TRIPLETS (the reference's own matrix arguments) -> this cell's block-cyclic piece of Z: the images of
+// replicated_host_locked, built in HBM from the CSRs of the mirrored matrices instead of crossing PCIe, then the same
+// call of the Path.  A and B are not returned (the reference deallocates them unread).  The CSR build, the upload and
+// the densification are the way in: EK_STAGE_COPY.
+int sparse_host_locked(int problem, int n, int n_vec, long long nnzA, const int *sufA, const double *valA,
+                       long long nnzB, const int *sufB, const double *valB, double *w, double *Z_loc, int lldz,
+                       const GridCell &cell, double *stage_seconds, int n_stages) {
+  const int nr_loc = numroc0(n, cell.nb, cell.myrow, cell.nprow);
+  const int nc_loc = numroc0(n_vec, cell.nb, cell.mycol, cell.npcol);
+  const int ldzl = nr_loc > 1 ? nr_loc : 1;
+  HostImages im;
+  const sparse::Csr *hA = nullptr, *hB = nullptr;
+  EK_TRY(csr_build(n, nnzA, sufA, valA, &hA, problem == 1, nnzB, sufB, valB, &hB));
+  // the images and the CSRs in the one allocation the library keeps between calls (HostImages::alloc says why)
+  const size_t nn = al((size_t)n * n * 8), zb = al((size_t)ldzl * (nc_loc > 0 ? nc_loc : 1) * 8), wb = al((size_t)n * 8);
+  const size_t ca = csr_device_bytes(n, nnzA), cb = problem == 1 ? csr_device_bytes(n, nnzB) : 0;
+  char *base = nullptr;
+  EK_TRY(user_images((problem == 1 ? 2 : 1) * nn + zb + wb + ca + cb, (void **)&base));
+  im.uA = (double *)base;
+  im.uZ = (double *)(base + nn);
+  im.uw = (double *)(base + nn + zb);
+  char *cA = base + nn + zb + wb, *cB = cA + ca;
+  if (problem == 1) im.uB = (double *)(cB + cb);
+  DevCsr dA{}, dB{};
+  int info = csr_upload(im.s, *hA, nnzA, cA, &dA);
+  if (!info && problem == 1) info = csr_upload(im.s, *hB, nnzB, cB, &dB);
+  if (!info) {
+    sparse_densify(im.s, n, dA, im.uA, n);
+    if (problem == 1) sparse_densify(im.s, n, dB, im.uB, n);
+    info = hip_rc(hipGetLastError());
+  }
+  if (!info) info = hip_rc(hipStreamSynchronize(im.s));
+  im.t1 = Clock::now();
+  PathCall c = im.call(problem, n, n_vec, ldzl, stage_seconds, n_stages);
+  c.cell = &cell;
+  if (!info) info = solve_device_locked(c);
+  if (info == -4) info = -6;                 // NaN / Inf in A: the value argument of this prototype
+  if (im.back(info)) {
+    if (nr_loc > 0 && nc_loc > 0) im.out(nr_loc, nc_loc, im.uZ, ldzl, Z_loc, lldz);
+    im.out_w(w, n);
+  }
+  return im.finish(info, stage_seconds, n_stages);
+}
+
 int eigenpairs_host(int problem, int itype, int jobz, int range, int n, double vl, double vu, int il, int iu,
                     const double *A, int lda, const double *B, int ldb, int *m, int *ifirst, double *w, double *Z,
                     int ldz, int zcap, double *stage_seconds, int n_stages) {
@@ -689,6 +735,32 @@ int ek_hip_solve_replicated(int problem, int n, int n_vec, double *A, int lda, d
   const GridCell cell{desc_Z[4], nprow, npcol, myrow, mycol};
   return replicated_host_locked(problem, n, n_vec, A, lda, B, ldb, w, Z_loc, desc_Z[8], cell, stage_seconds,
                                 n_stages);
+}
+
+int ek_hip_solve_sparse(int problem, int n, int n_vec, long long nnzA, const int *sufA, const double *valA,
+                        long long nnzB, const int *sufB, const double *valB, double *w, double *Z_loc,
+                        const int desc_Z[9], int nprow, int npcol, int myrow, int mycol, double *stage_seconds,
+                        int n_stages) {
+  if (problem != 0 && problem != 1) return -1;
+  if (n < 0) return -2;
+  if (n == 0) return 0;
+  if (n_vec < 0 || n_vec > n) return -3;
+  int rc = triplet_args(n, nnzA, sufA, valA, 4); if (rc) return rc;
+  if (problem == 1) { rc = triplet_args(n, nnzB, sufB, valB, 7); if (rc) return rc; }
+  if (!w) return -10;
+  if (!Z_loc) return -11;
+  if (nprow < 1) return -13;
+  if (npcol < 1) return -14;
+  if (myrow < 0 || myrow >= nprow) return -15;
+  if (mycol < 0 || mycol >= npcol) return -16;
+  if (!desc_Z) return -12;
+  if (desc_Z[4] < 1) return -(12 * 100 + 5);
+  rc = check_desc(desc_Z, 12, n, n, numroc0(n, desc_Z[4], myrow, nprow)); if (rc) return rc;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  const GridCell cell{desc_Z[4], nprow, npcol, myrow, mycol};
+  return sparse_host_locked(problem, n, n_vec, nnzA, sufA, valA, nnzB, sufB, valB, w, Z_loc, desc_Z[8], cell,
+                            stage_seconds, n_stages);
 }
 
 int ek_hip_solve(int problem, int n, int n_vec, double *A_loc, const int desc_A[9], double *B_loc,

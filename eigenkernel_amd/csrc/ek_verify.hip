@@ -147,7 +147,161 @@ __global__ void sygv_not_spd_kernel(const int *__restrict__ d_info, int nc, doub
 
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// ---- the check from the triplets (sparse_check below)
+// out[b] = the sum of the squares of block b's slice of the CSR values; the slices are cut by the entry count alone
+__global__ __launch_bounds__(256) void csr_sumsq_kernel(long long nnz, long long per_block, const double *__restrict__ val,
+                                                        double *__restrict__ out) {
+  __shared__ double red[4];
+  const long long k0 = (long long)blockIdx.x * per_block, k1 = k0 + per_block < nnz ? k0 + per_block : nnz;
+  double s = 0.0;
+  for (long long k = k0 + threadIdx.x; k < k1; k += 256) s += val[k] * val[k];
+  s = wg_sum(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+// One pass over the rows for the columns j < ncu of Z, held transposed (Zt(j, c) = z(c, j), ld ldt, a multiple of 64): a
+// lane owns a column, a wave a chunk of `rows` consecutive rows.  Per row i: a = sum_c A(i,c) z(c,j) and s = sum_c B(i,c)
+// z(c,j) (GEN; else s = z(i,j)), both in ascending c by this one lane; St(j, i) = s (GEN); the lane's running sum takes
+// (a - w_j s)^2 for j < n_check.  part(j, chunk) receives the running sum: sparse_colsq_kernel adds the chunks in order.
+// The CSR arrays are read at wave-uniform addresses; every load of z(c, .) is one line of 64 doubles.
+// The pass runs as two launches so that the host can sort A's triplets while the device already works on what needs B
+// alone -- mode kPassS: s and St for the columns j < ncu (A is not looked at); mode kPassRes: a and the running sums for the
+// columns j < n_check, s read back from St (GEN) or z.
+enum { kPassS = 1, kPassRes = 2 };
+template <bool GEN>
+__global__ __launch_bounds__(256) void sparse_residual_kernel(
+    int mode, int n, int ncu, int n_check, int ldt, int rows, const long long *__restrict__ rpA,
+    const int *__restrict__ ciA, const double *__restrict__ vA, const long long *__restrict__ rpB,
+    const int *__restrict__ ciB, const double *__restrict__ vB, const double *__restrict__ w,
+    const double *__restrict__ Zt, double *__restrict__ St, double *__restrict__ part) {
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int chunk = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int r0 = chunk * rows;
+  const bool do_s = GEN && mode == kPassS, do_res = mode == kPassRes;
+  if (r0 >= n || j >= (do_s ? ncu : n_check)) return;
+  const int r1 = r0 + rows < n ? r0 + rows : n;
+  const bool res = do_res && j < n_check;
+  const double wj = res ? w[j] : 0.0;
+  const double *z = Zt + j;
+  double acc = 0.0;
+  for (int i = r0; i < r1; ++i) {
+    double a = 0.0, sv;
+    if (do_res) {
+      const long long k1 = rpA[i + 1];
+#pragma unroll 4
+      for (long long k = rpA[i]; k < k1; ++k) a += vA[k] * z[(size_t)ciA[k] * ldt];
+    }
+    if (do_s) {
+      sv = 0.0;
+      const long long k1 = rpB[i + 1];
+#pragma unroll 4
+      for (long long k = rpB[i]; k < k1; ++k) sv += vB[k] * z[(size_t)ciB[k] * ldt];
+      St[(size_t)i * ldt + j] = sv;
+    } else {
+      sv = GEN ? St[(size_t)i * ldt + j] : z[(size_t)i * ldt];
+    }
+    if (res) { const double r = a - wj * sv; acc += r * r; }
+  }
+  if (do_res) part[(size_t)chunk * ldt + j] = acc;
+}
+
+// colsq[j] = the chunks' sums of column j, in ascending chunk order
+__global__ void sparse_colsq_kernel(int n_check, int chunks, int ldt, const double *__restrict__ part,
+                                    double *__restrict__ colsq) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_check) return;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += part[(size_t)c * ldt + j];
+  colsq[j] = s;
+}
+
+constexpr int kCsrSumBlocks = 512;
+
 }  // namespace
+
+// rows of a wave's chunk in sparse_residual_kernel: at most 128 chunks, so that the partial sums stay a sliver of Z
+static inline int sparse_chunk_rows(int n) { const int r = ceil_div(n, 128); return r > 8 ? r : 8; }
+
+SparseCheckLayout::SparseCheckLayout(int problem, int n, int n_check, int n_orth, int hi_orth, int n_ipr) {
+  ncu = n_check;
+  if (problem == 1) { if (hi_orth > ncu) ncu = hi_orth; if (n_ipr > ncu) ncu = n_ipr; }
+  ldt = round_up(ncu > 0 ? ncu : 1, 64);
+  rows = sparse_chunk_rows(n);
+  chunks = ceil_div(n > 0 ? n : 1, rows);
+  size_t o = 0;
+  auto take = [&](size_t doubles) { const size_t at = o; o += al256(doubles * 8); return at; };
+  Zt = take(ncu > 0 ? (size_t)ldt * n : 0);
+  St = take(problem == 1 && ncu > 0 ? (size_t)ldt * n : 0);
+  S = take(problem == 1 ? (size_t)n * ncu : 0);
+  G = take((size_t)n_orth * n_orth);
+  part = take(ncu > 0 ? (size_t)chunks * ldt : 0);
+  vec = take((size_t)(n_check > n_orth ? n_check : n_orth) + kCsrSumBlocks + 8);
+  total = o;
+}
+
+size_t sparse_check_work_bytes(int problem, int n, int n_check, int n_orth, int hi_orth, int n_ipr) {
+  return SparseCheckLayout(problem, n, n_check, n_orth, hi_orth, n_ipr).total;
+}
+
+// d_out (device, 8 doubles): [0] sum_j ||r_j||, [1] max_j ||r_j||, [2] ||A||_F over the first n_check columns (n_check > 0);
+// [6] the orthogonality of the columns c0 .. c0 + n_orth - 1 (n_orth > 0); d_ipr (device): n_ipr ratios (n_ipr > 0).
+// B is looked at for problem 1 only.  The products with A and B are sparse; G = V^T S, the scaling of G, the finish and the
+// IPR are the calls and kernels of orthogonality() and ipratios() above -- for problem 0 with their very operands.
+static void sparse_check_metric_tail(hipStream_t s, bool gen, int n, const double *Z, int ldz, const double *S, double *G,
+                                     double *colsq, int c0, int n_orth, int n_ipr, double *d_out, double *d_ipr);
+
+// phases: kSparseMetric: what needs B alone (S, the orthogonality, the IPRs); kSparseResidual: what needs A (to be
+// launched after the other, on the same stream; the caller uploads A's CSR in between); both: one after the other.
+void sparse_check(hipStream_t s, int phases, int problem, int n, const DevCsr &A, const DevCsr &B, const double *w,
+                  const double *Z, int ldz, int n_check, int c0, int n_orth, int n_ipr, double *d_out, double *d_ipr,
+                  void *work) {
+  const SparseCheckLayout lay(problem, n, n_check, n_orth, c0 + n_orth, n_ipr);
+  char *p = (char *)work;
+  double *Zt = (double *)(p + lay.Zt), *St = (double *)(p + lay.St), *S = (double *)(p + lay.S);
+  double *G = (double *)(p + lay.G), *part = (double *)(p + lay.part), *colsq = (double *)(p + lay.vec);
+  double *asq = colsq + (n_check > n_orth ? n_check : n_orth);
+  const bool gen = problem == 1, metric = (phases & kSparseMetric) != 0, residual = (phases & kSparseResidual) != 0;
+  const dim3 grid(lay.ldt / 64, ceil_div(lay.chunks, 4));
+  // Z^T belongs to whichever phase first reads it: the metric's for problem 1, the residual's for problem 0
+  if (lay.ncu > 0 && (gen ? metric : residual)) transpose_rows(s, lay.ncu, n, Z, ldz, 0, Zt, lay.ldt);
+  if (gen && metric && lay.ncu > 0) {
+    hipLaunchKernelGGL(sparse_residual_kernel<true>, grid, dim3(256), 0, s, kPassS, n, lay.ncu, n_check, lay.ldt, lay.rows,
+                       nullptr, nullptr, nullptr, B.rowptr, B.col, B.val, w, Zt, St, part);
+    transpose_rows(s, n, lay.ncu, St, lay.ldt, 0, S, n);
+  }
+  if (metric) sparse_check_metric_tail(s, gen, n, Z, ldz, S, G, colsq, c0, n_orth, n_ipr, d_out, d_ipr);
+  if (residual && n_check > 0) {
+    const dim3 rgrid(ceil_div(n_check, 64), grid.y);
+    if (gen)
+      hipLaunchKernelGGL(sparse_residual_kernel<true>, rgrid, dim3(256), 0, s, kPassRes, n, lay.ncu, n_check, lay.ldt,
+                         lay.rows, A.rowptr, A.col, A.val, B.rowptr, B.col, B.val, w, Zt, St, part);
+    if (!gen)
+      hipLaunchKernelGGL(sparse_residual_kernel<false>, rgrid, dim3(256), 0, s, kPassRes, n, lay.ncu, n_check, lay.ldt,
+                         lay.rows, A.rowptr, A.col, A.val, nullptr, nullptr, nullptr, w, Zt, St, part);
+    hipLaunchKernelGGL(sparse_colsq_kernel, dim3(ceil_div(n_check, 256)), dim3(256), 0, s, n_check, lay.chunks, lay.ldt,
+                       part, colsq);
+    const long long per = (A.nnz + kCsrSumBlocks - 1) / kCsrSumBlocks > 1024 ? (A.nnz + kCsrSumBlocks - 1) / kCsrSumBlocks : 1024;
+    const int nb = A.nnz > 0 ? (int)((A.nnz + per - 1) / per) : 1;
+    hipLaunchKernelGGL(csr_sumsq_kernel, dim3(nb), dim3(256), 0, s, A.nnz, per, A.val, asq);
+    hipLaunchKernelGGL(finish_residual_kernel, dim3(1), dim3(256), 0, s, n_check, colsq, nb, asq, d_out);
+  }
+}
+
+// G = V^T S (problem 0: V^T V), its scaling and finish, and the IPRs: the calls and kernels of orthogonality() and ipratios()
+static void sparse_check_metric_tail(hipStream_t s, bool gen, int n, const double *Z, int ldz, const double *S, double *G,
+                                     double *colsq, int c0, int n_orth, int n_ipr, double *d_out, double *d_ipr) {
+  if (n_orth > 0) {
+    const double *Vs = Z + (size_t)c0 * ldz;
+    if (gen) gemm(s, true, false, n_orth, n_orth, n, 1.0, Vs, ldz, S + (size_t)c0 * n, n, 0.0, G, n_orth);
+    else gemm(s, true, false, n_orth, n_orth, n, 1.0, Vs, ldz, Vs, ldz, 0.0, G, n_orth);
+    hipLaunchKernelGGL(ortho_scale_kernel, dim3(n_orth), dim3(256), 0, s, n_orth, G, n_orth, colsq);
+    hipLaunchKernelGGL(finish_residual_kernel, dim3(1), dim3(256), 0, s, 0, colsq, n_orth, colsq, d_out + 4);
+  }
+  if (n_ipr > 0) {
+    if (gen) hipLaunchKernelGGL(ipr_kernel, dim3(n_ipr), dim3(256), 0, s, n, Z, ldz, S, n, d_ipr);
+    else hipLaunchKernelGGL(ipr_kernel, dim3(n_ipr), dim3(256), 0, s, n, Z, ldz, Z, ldz, d_ipr);
+  }
+}
 
 size_t verify_work_bytes(int n, int ncols) {
   const size_t nn = (size_t)n * (n > 0 ? n : 1), nc = (size_t)n * (ncols > 0 ? ncols : 1);

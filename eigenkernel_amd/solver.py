@@ -214,6 +214,16 @@ def load_library(path=None):
         "ek_hip_debug_stage_leaves256": (c_int, [c_int]),
         "ek_hip_debug_set_sygst_direct": (c_int, [c_int]),
         "ek_hip_debug_sygst_scratch": (c_ull, [c_int, ctypes.POINTER(c_ull)]),
+        # a triplet list is (nnz, suffix, value)
+        "ek_hip_solve_sparse": (c_int, [c_int, c_int, c_int, c_ll, _ip, _dp, c_ll, _ip, _dp, _dp, _dp, _ip,
+                                        c_int, c_int, c_int, c_int, _dp, c_int]),
+        "ek_hip_check_sparse_device": (c_int, [c_int, c_int, c_ll, _ip, _dp, c_ll, _ip, _dp, vp, vp, c_int,
+                                               c_int, c_int, c_int, c_int, _dp, _dp]),
+        "ek_hip_check_sparse": (c_int, [c_int, c_int, c_ll, _ip, _dp, c_ll, _ip, _dp, _dp, _dp, c_int,
+                                        c_int, c_int, c_int, c_int, _dp, _dp]),
+        "ek_hip_sparse_to_dense": (c_int, [c_int, c_ll, _ip, _dp, _dp, c_int]),
+        "ek_hip_debug_sparse_check_workspace_bytes": (c_ull, [c_int, c_int, c_ll, c_ll, c_int, c_int, c_int, c_int]),
+        "ek_hip_debug_sparse_csr": (c_ll, [c_int, c_ll, _ip, _dp, _llp, _ip, _dp]),
     }
     for name, (res, args) in sigs.items():
         try:
@@ -267,6 +277,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_xvbatched_device", "ek_hip_check_xvbatched", "ek_hip_check_sygv_xvbatched_device",
     "ek_hip_check_sygv_xvbatched", "ek_hip_debug_check_xvbatched_last",
     "ek_hip_debug_stage_leaves256", "ek_hip_debug_set_sygst_direct", "ek_hip_debug_sygst_scratch",
+    "ek_hip_solve_sparse", "ek_hip_check_sparse_device", "ek_hip_check_sparse", "ek_hip_sparse_to_dense",
+    "ek_hip_debug_sparse_check_workspace_bytes", "ek_hip_debug_sparse_csr",
 )
 
 
@@ -1203,6 +1215,108 @@ def dgemm(transa, transb, alpha, A, B, beta, C, lower_only=False):
     return C
 
 
+# ----------------------------------------------------------------------------- triplet inputs
+def _triplets(M):
+    """(nnz, suffix, value) of a SparseMat as the C-ABI takes them: suffix interleaved (i_k, j_k) int32 pairs -- the
+    memory of the Fortran suffix(2, nnz) -- and float64 values.  The arrays must outlive the call."""
+    suf = np.ascontiguousarray(np.asarray(M.suffix, dtype=np.int32).T)
+    val = np.ascontiguousarray(M.value, dtype=np.float64)
+    if suf.shape != (val.shape[0], 2):
+        raise ValueError("SparseMat: suffix must be (2, nnz) and value (nnz,)")
+    return int(val.shape[0]), suf, val
+
+
+def _tp(t):
+    nnz, suf, val = t
+    return nnz, (_I(suf) if nnz else None), (_P(val) if nnz else None)
+
+
+def sparse_csr(A):
+    """The canonical form the sparse entries work on (ek_hip_debug_sparse_csr; host arithmetic, no GPU): (rowptr, col,
+    val) of the CSR of the mirrored matrix, columns 0-based and ascending inside a row, the last of the entries that
+    name one unordered pair surviving.  Raises SolverError for an index outside 1 .. n."""
+    lib = load_library()
+    t = _triplets(A)
+    n, nnz = int(A.size), t[0]
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    col = np.zeros(max(2 * nnz, 1), dtype=np.int32)
+    val = np.zeros(max(2 * nnz, 1))
+    m = lib.ek_hip_debug_sparse_csr(n, *_tp(t), rowptr.ctypes.data_as(_llp), _I(col), _P(val))
+    if m < 0:
+        raise SolverError("ek_hip_debug_sparse_csr failed", int(m))
+    return rowptr, col[:m].copy(), val[:m].copy()
+
+
+def sparse_to_dense(A):
+    """The mirrored dense matrix of a SparseMat, densified on the GPU (ek_hip_sparse_to_dense): what the reference's loop
+    builds (distribute_matrix.f90:411-418), a later entry replacing an earlier one of the same unordered pair."""
+    lib = load_library()
+    t = _triplets(A)
+    n = int(A.size)
+    M = np.zeros((n, n), order="F")
+    info = lib.ek_hip_sparse_to_dense(n, *_tp(t), _P(M), max(1, n))
+    if info != 0:
+        raise SolverError("ek_hip_sparse_to_dense failed", info)
+    return M
+
+
+def solve_sparse(A, B=None, n_vec=None, proc=None, block_size=None):
+    """ek_hip_solve_sparse: the whole path on the reference's own arguments, SparseMat A (and B: generalized).  No dense
+    matrix is formed on the host; every rank of a grid passes the same triplets and receives its block-cyclic piece of
+    the eigenvectors, as with replicated dense inputs.  Returns EigenpairsBlacs; raises SolverError on info != 0."""
+    lib = load_library()
+    proc = proc or Process()
+    n = int(A.size)
+    n_vec = n if n_vec is None else int(n_vec)
+    ta = _triplets(A)
+    tb = _triplets(B) if B is not None else (0, None, None)
+    desc_Z, Z_loc = _d.setup_distributed_matrix(n, n, proc.n_procs_row, proc.n_procs_col, proc.my_proc_row,
+                                                proc.my_proc_col, block_size=block_size, ctxt=proc.context)
+    w = np.zeros(max(n, 1))
+    stage = np.zeros(N_STAGES)
+    info = lib.ek_hip_solve_sparse(1 if B is not None else 0, n, n_vec, *_tp(ta), *_tp(tb), _P(w), _P(Z_loc),
+                                   _I(desc_Z), proc.n_procs_row, proc.n_procs_col, proc.my_proc_row, proc.my_proc_col,
+                                   _P(stage), N_STAGES)
+    if info != 0:
+        raise SolverError("solve_sparse: libek_hip failed", info)
+    ep = EigenpairsBlacs(values=w[:n], desc=desc_Z, Vectors=Z_loc, info=info)
+    ep.stage_seconds = {lib.ek_hip_stage_name(i).decode(): float(stage[i]) for i in range(N_STAGES)}
+    ep.n_vec = n_vec
+    return ep
+
+
+def check_sparse(A, B, w, Z, n_check=None, index1=1, index2=None, n_ipr=None):
+    """ek_hip_check_sparse: the reference's acceptance quantities from the triplets of A (and B, None: standard) and
+    host arrays w, Z (n x columns).  n_check, index2 and n_ipr default to the columns of Z; n_check = 0, index2 < index1
+    or n_ipr = 0 skip a part (its values come back NaN / empty).  Returns (a_norm, res_ave, res_max, orthogonality,
+    ipratios)."""
+    lib = load_library()
+    Z = _farr(Z)
+    n, nc = Z.shape
+    n_check = nc if n_check is None else int(n_check)
+    index2 = nc if index2 is None else int(index2)
+    n_ipr = nc if n_ipr is None else int(n_ipr)
+    ta = _triplets(A)
+    tb = _triplets(B) if B is not None else (0, None, None)
+    wv = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+    out = np.full(4, np.nan)
+    ipr = np.zeros(max(n_ipr, 1))
+    info = lib.ek_hip_check_sparse(1 if B is not None else 0, n, *_tp(ta), *_tp(tb), _P(wv), _P(Z),
+                                   max(1, Z.strides[1] // 8 if nc > 1 else n), n_check, int(index1), index2, n_ipr,
+                                   _P(out), _P(ipr))
+    if info != 0:
+        raise SolverError("ek_hip_check_sparse failed", info)
+    return float(out[0]), float(out[1]), float(out[2]), float(out[3]), ipr[:max(n_ipr, 0)].copy()
+
+
+def sparse_check_workspace_bytes(problem, n, nnzA, nnzB=0, n_check=None, index1=1, index2=None, n_ipr=None):
+    """Bytes of the cached device workspace one ek_hip_check_sparse_device call asks for (host arithmetic: works without
+    a GPU); include/ek_hip_debug.h states the formula."""
+    return int(load_library().ek_hip_debug_sparse_check_workspace_bytes(
+        int(problem), int(n), int(nnzA), int(nnzB), int(n if n_check is None else n_check), int(index1),
+        int(n if index2 is None else index2), int(n if n_ipr is None else n_ipr)))
+
+
 # ----------------------------------------------------------------------------- the dispatch
 def eigen_solver(solver_type, matrix_A, matrix_B=None, n_vec=None, block_size=None, proc=None,
                  inputs="replicated"):
@@ -1216,6 +1330,8 @@ def eigen_solver(solver_type, matrix_A, matrix_B=None, n_vec=None, block_size=No
     inputs="distributed" reproduces the reference's own data flow instead: A and B are cut into
     block-cyclic pieces (setup_distributed_matrix + distribute_global_sparse_matrix) and handed
     to ek_hip_solve, which reassembles them through the hook of set_allgatherv().
+    inputs="triplets" hands SparseMat matrices on as they are (ek_hip_solve_sparse, on any grid): the dense
+    images are built in device memory, the results are those of "replicated" bit for bit.
     Raises SolverError where the reference terminates (info != 0 from the Cholesky,
     reduction or recovery stage), ValueError for an unknown solver
     ('eigen_solver: Unknown solver', solver_main.f90:98).
@@ -1228,6 +1344,18 @@ def eigen_solver(solver_type, matrix_A, matrix_B=None, n_vec=None, block_size=No
         raise ValueError("eigen_solver: matrix_B is required for %s" % solver_type)
     lib = load_library()
     proc = proc or Process()
+    if inputs == "triplets":
+        # the reference's own arguments, handed on as they are (ek_hip_solve_sparse): no dense matrix on the host
+        if not hasattr(matrix_A, "suffix") or (generalized and not hasattr(matrix_B, "suffix")):
+            raise ValueError("eigen_solver: inputs='triplets' takes SparseMat matrices")
+        if n_vec is not None and n_vec != matrix_A.size and not select:
+            raise ValueError("-n is only legal for *_select solvers (command_argument.f90:186-200)")
+        try:
+            ep = solve_sparse(matrix_A, matrix_B if generalized else None, n_vec=n_vec if select else None, proc=proc,
+                              block_size=block_size)
+        except SolverError as e:
+            raise SolverError("eigen_solver(%s): libek_hip failed" % solver_type, e.info) from None
+        return ep, proc
     gridded = proc.n_procs_row * proc.n_procs_col != 1
 
     def dense(m):

@@ -14,6 +14,8 @@
 !     --binary    one unformatted sequential record of N doubles per file (else `i j value` lines)
 !     --block-size <nb>   block size recorded in the descriptors
 !     --dry-run   read the matrices and stop                             main.f90:89-93
+!     --triplets  keep the matrices as the reference's ek_sparse_mat_t (suffix, value): no dense host array but Z;
+!                 ek_hip_solve_sparse, and one ek_hip_check_sparse for -c, -t and the IPRs
 !     --synthetic <N> [--seed-a 1] [--seed-b 2]   no matrix files: the dense SPD test matrices of
 !                 SURVEY.md 8(d) (the generator of bench.py and of the oracle), made on the GPU by the
 !                 library and fetched into the host arrays; general_* solvers get the pair (A, B).
@@ -67,6 +69,26 @@ module ek_hip_binding
       real(c_double) :: w(*), Z_loc(*), res(*)
       integer(c_int) :: desc_Z(9)
     end function
+    ! the reference's own matrix arguments: matrix%num_non_zeros, matrix%suffix, matrix%value (INTEGRATION.md 1c)
+    integer(c_int) function ek_hip_solve_sparse(problem, n, n_vec, nnz_a, suf_a, val_a, nnz_b, suf_b, val_b, w, Z_loc, &
+         desc_Z, nprow, npcol, myrow, mycol, stage_seconds, n_stages) bind(C, name='ek_hip_solve_sparse')
+      import :: c_int, c_double, c_ptr, c_long_long
+      integer(c_int), value :: problem, n, n_vec, nprow, npcol, myrow, mycol, n_stages
+      integer(c_long_long), value :: nnz_a, nnz_b
+      integer(c_int) :: suf_a(2, *)
+      real(c_double) :: val_a(*), w(*), Z_loc(*), stage_seconds(*)
+      type(c_ptr), value :: suf_b, val_b
+      integer(c_int) :: desc_Z(9)
+    end function
+    integer(c_int) function ek_hip_check_sparse(problem, n, nnz_a, suf_a, val_a, nnz_b, suf_b, val_b, w, Z, ldz, &
+         n_check, index1, index2, n_ipr, res, ipr) bind(C, name='ek_hip_check_sparse')
+      import :: c_int, c_double, c_ptr, c_long_long
+      integer(c_int), value :: problem, n, ldz, n_check, index1, index2, n_ipr
+      integer(c_long_long), value :: nnz_a, nnz_b
+      integer(c_int) :: suf_a(2, *)
+      real(c_double) :: val_a(*), w(*), Z(*), res(4), ipr(*)
+      type(c_ptr), value :: suf_b, val_b
+    end function
   end interface
 end module ek_hip_binding
 
@@ -88,6 +110,14 @@ program eigenkernel_hip_app
   real(c_double), allocatable :: z(:, :), w(:), ipr(:)
   real(c_double) :: stage(EK_HIP_N_STAGES), chk(3)
   real(c_double), allocatable :: chk_ipr(:)
+  ! --triplets: the matrices stay what the reference's ek_sparse_mat_t holds (matrix_io.f90:11-15)
+  logical :: triplets
+  integer(c_long_long) :: nnz_a, nnz_b
+  integer(c_int), allocatable, target :: suf_a(:, :), suf_b(:, :)
+  real(c_double), allocatable, target :: val_a(:), val_b(:)
+  type(c_ptr) :: p_suf_b, p_val_b
+  real(c_double) :: chk4(4)
+  integer :: t_a, t_b
   integer(8) :: clock0, clock1, clock_rate
   double precision :: t_read, t_solve, t_total
   character(len=40), parameter :: stage_names(EK_HIP_N_STAGES) = [character(len=40) :: &
@@ -106,6 +136,7 @@ program eigenkernel_hip_app
   dry_run = .false.; n_files = 0; n_events = 0
   synth_n = 0; seed_a = 1; seed_b = 2
   vec_dir = '.'; vec_ranges = ''; binary_out = .false.; n_ranges = 0
+  triplets = .false.; nnz_a = 0; nnz_b = 0
   call get_command(cmdline)
 
   nargs = command_argument_count()
@@ -124,6 +155,7 @@ program eigenkernel_hip_app
     case ('-p'); call next_arg(vec_ranges)
     case ('-d'); call next_arg(vec_dir)
     case ('--binary'); binary_out = .true.
+    case ('--triplets'); triplets = .true.
     case ('--synthetic'); call next_int(synth_n)
     case ('--seed-a'); call next_int(seed_a)
     case ('--seed-b'); call next_int(seed_b)
@@ -163,7 +195,14 @@ program eigenkernel_hip_app
   if (n_vec >= 0 .and. .not. is_select) call die('-n is only legal for *_select solvers', 1)
 
   call system_clock(clock0, clock_rate)
-  if (synth_n > 0) then
+  if (triplets .and. synth_n > 0) call die('--triplets reads matrix files (--synthetic makes dense matrices)', 1)
+  if (triplets) then
+    call read_triplets(trim(file_a), n, nnz_a, suf_a, val_a)
+    if (generalized) then
+      call read_triplets(trim(file_b), i, nnz_b, suf_b, val_b)
+      if (i /= n) call die('matrix dimensions differ', 1)
+    end if
+  else if (synth_n > 0) then
     n = synth_n
     call synthetic_matrix(n, seed_a, a_orig)
     if (generalized) call synthetic_matrix(n, seed_b, b_orig)
@@ -200,20 +239,31 @@ program eigenkernel_hip_app
   desc_a = [1, 0, n, n, nb, nb, 0, 0, max(1, n)]
   desc_b = desc_a; desc_z = desc_a
   print '("Creating distributed matrix A with M, N, MB, NB: ", i0, ", ", i0, ", ", i0, ", ", i0)', n, n, nb, nb
-  allocate (a_work(n, n), z(n, n), w(n), ipr(n))
-  a_work = a_orig
+  allocate (z(n, n), w(n), ipr(n))
   z = 0.0d0
   problem = 0
-  if (generalized) then
-    allocate (b_work(n, n))
-    b_work = b_orig
-    problem = 1
+  if (generalized) problem = 1
+  if (.not. triplets) then
+    allocate (a_work(n, n))
+    a_work = a_orig
+    if (generalized) then
+      allocate (b_work(n, n))
+      b_work = b_orig
+    end if
   end if
 
   info = ek_hip_init(0_c_int)
   if (info /= 0) call die('ek_hip_init failed (no GPU? there is no CPU fallback)', info)
   call system_clock(clock0)
-  if (generalized) then
+  if (triplets) then
+    ! solve_with_hip on matrix_A%suffix / %value: no dense matrix on the host but Z
+    p_suf_b = c_null_ptr; p_val_b = c_null_ptr
+    if (generalized) then
+      p_suf_b = c_loc(suf_b); p_val_b = c_loc(val_b)
+    end if
+    info = ek_hip_solve_sparse(problem, n, n_vec, nnz_a, suf_a, val_a, nnz_b, p_suf_b, p_val_b, w, z, desc_z, &
+         1, 1, 0, 0, stage, EK_HIP_N_STAGES)
+  else if (generalized) then
     info = ek_hip_solve(problem, n, n_vec, a_work, desc_a, c_loc(b_work), c_loc(desc_b), w, z, desc_z, &
          1, 1, 0, 0, stage, EK_HIP_N_STAGES)
   else
@@ -241,7 +291,17 @@ program eigenkernel_hip_app
   ! ipratios.dat: always n lines (main.f90:138-142); columns beyond n_vec were not computed
   allocate (chk_ipr(max(n, 3)))
   chk_ipr = 0.0d0
-  if (generalized) then
+  if (triplets) then
+    ! the three acceptance quantities from the triplets, one call: IPRs of the computed vectors, the residual of
+    ! -c and the orthogonality of -t (an empty range skips a part)
+    t_a = 1; t_b = 0
+    if (ortho_a >= 1 .and. ortho_b >= ortho_a) then
+      t_a = ortho_a; t_b = ortho_b
+    end if
+    chk4 = 0.0d0
+    info = ek_hip_check_sparse(problem, n, nnz_a, suf_a, val_a, nnz_b, p_suf_b, p_val_b, w, z, max(1, n), &
+         n_check, t_a, t_b, n_vec, chk4, chk_ipr)
+  else if (generalized) then
     info = ek_hip_check(2, problem, n, n_vec, 1, 1, c_null_ptr, c_null_ptr, c_loc(b_orig), c_loc(desc_b), &
          w, z, desc_z, chk_ipr)
   else
@@ -267,7 +327,10 @@ program eigenkernel_hip_app
   end do
 
   if (n_check > 0) then
-    if (generalized) then
+    if (triplets) then
+      chk(1:3) = chk4(1:3)
+      info = 0
+    else if (generalized) then
       info = ek_hip_check(0, problem, n, n_check, 1, 1, c_loc(a_orig), c_loc(desc_a), c_loc(b_orig), &
            c_loc(desc_b), w, z, desc_z, chk)
     else
@@ -280,7 +343,10 @@ program eigenkernel_hip_app
     print '("residual norm (max): ", E26.16e3)', chk(3)
   end if
   if (ortho_a >= 1 .and. ortho_b >= ortho_a) then
-    if (generalized) then
+    if (triplets) then
+      chk(1) = chk4(4)
+      info = 0
+    else if (generalized) then
       info = ek_hip_check(1, problem, n, 0, ortho_a, ortho_b, c_null_ptr, c_null_ptr, c_loc(b_orig), &
            c_loc(desc_b), w, z, desc_z, chk)
     else
@@ -386,7 +452,7 @@ contains
   subroutine usage()
     print '(a)', 'usage: eigenkernel_hip_app -s <hip|hip_select|general_hip|general_hip_select> [-n num]'
     print '(a)', '       [-c num] [-t a,b] [-o file] [-i file] [-l file] [-p ranges] [-d dir] [--binary]'
-    print '(a)', '       [--block-size nb] [--dry-run] A.mtx [B.mtx]'
+    print '(a)', '       [--block-size nb] [--dry-run] [--triplets] A.mtx [B.mtx]'
   end subroutine usage
 
   subroutine die(msg, code)
@@ -442,6 +508,40 @@ contains
     end do
     close (11)
   end subroutine read_matrix_market
+
+  ! the same file as the reference keeps it: ek_sparse_mat_t's suffix(2, nnz) and value(nnz), one triangle, nothing
+  ! mirrored and nothing dense (matrix_io.f90:91-144)
+  subroutine read_triplets(path, dim, nnz, suf, val)
+    character(len=*), intent(in) :: path
+    integer, intent(out) :: dim
+    integer(c_long_long), intent(out) :: nnz
+    integer(c_int), allocatable, target, intent(out) :: suf(:, :)
+    real(c_double), allocatable, target, intent(out) :: val(:)
+    character(len=1024) :: line
+    integer :: rows, cols, cnt, k, st
+    open (unit=11, file=path, status='old', action='read', iostat=st)
+    if (st /= 0) call die('cannot open '//trim(path), 1)
+    read (11, '(a)', iostat=st) line
+    if (st /= 0) call die('empty matrix file '//trim(path), 1)
+    call lower_case(line)
+    if (index(line, '%%matrixmarket matrix coordinate real symmetric') /= 1) &
+         call die('unsupported MatrixMarket banner in '//trim(path), 1)
+    do
+      read (11, '(a)', iostat=st) line
+      if (st /= 0) call die('missing size line in '//trim(path), 1)
+      if (line(1:1) /= '%') exit
+    end do
+    read (line, *, iostat=st) rows, cols, cnt
+    if (st /= 0 .or. rows /= cols .or. cnt < 0) call die('bad size line in '//trim(path), 1)
+    dim = rows
+    nnz = int(cnt, c_long_long)
+    allocate (suf(2, max(1, cnt)), val(max(1, cnt)))
+    do k = 1, cnt
+      read (11, *, iostat=st) suf(1, k), suf(2, k), val(k)
+      if (st /= 0) call die('truncated matrix file '//trim(path), 1)
+    end do
+    close (11)
+  end subroutine read_triplets
 
   subroutine lower_case(sline)
     character(len=*), intent(inout) :: sline

@@ -72,7 +72,9 @@ int ek_hip_version(void);                       /* 100*major + minor.  2: round 
                                                  * and ek_hip_check_vbatched*, and with
                                                  * ek_hip_sygv_batched_device, ek_hip_sygv_batched,
                                                  * ek_hip_sygv_vbatched_device and
-                                                 * ek_hip_sygv_vbatched: their symbols are the signal */
+                                                 * ek_hip_sygv_vbatched, and with the triplet entries
+                                                 * ek_hip_solve_sparse, ek_hip_check_sparse* and
+                                                 * ek_hip_sparse_to_dense: their symbols are the signal */
 int ek_hip_init(int device);                    /* bind this process (rank) to a GPU        */
 int ek_hip_finalize(void);                      /* release cached workspaces / device images */
 const char *ek_hip_stage_name(int stage);       /* reference event name of a stage index    */
@@ -847,6 +849,65 @@ int ek_hip_ipratios_device(int problem, int n, int n_vec, const double *dB, int 
 int ek_hip_check(int what, int problem, int n, int n_cols, int index1, int index2,
                  const double *A_loc, const int desc_A[9], const double *B_loc, const int desc_B[9],
                  const double *w, const double *Z_loc, const int desc_Z[9], double *out);
+
+/* ---- The reference's own matrix arguments: ek_sparse_mat_t, replicated 1-based triplets (matrix_io.f90:11-15), as
+ * eigen_solver and solve_with_general_scalapack receive them (solver_main.f90:22, :65) and as the verifier rebuilds A
+ * and B from (verifier.f90:122-131).  A matrix is (nnz, suf, val): suf = the memory of the Fortran suffix(2, nnz), i.e.
+ * interleaved (i_k, j_k) pairs, val = value(nnz).  Entry k stands for (i, j) and (j, i); either triangle may appear; of the
+ * entries that name the same unordered pair {i, j} the LAST of the list counts, as in the reference's serial pdelset loop
+ * (distribute_matrix.f90:411-418).  The library sorts the list into the CSR of the mirrored matrix on the host (counting
+ * sort by row, columns ascending), uploads that, and no dense n x n array exists on the host except Z.  A result depends
+ * on the set of surviving entries alone: permuting a duplicate-free list changes no bit.  The lists are const.
+ * Argument errors, all entries: -k for argument k of the prototype, decided before any device work, the first offender
+ * deciding: a negative nnz; with nnz > 0 a NULL suf or an index outside 1 .. n (the suf argument's code) or a NULL val;
+ * the counts, index ranges and pointers outside their ranges.  (nnzB, sufB, valB) are not looked at for problem 0.
+ * n = 0: 0, nothing referenced.  Non-finite values pass through to the computation.
+ *
+ * ek_hip_solve_sparse: ek_hip_solve_replicated with A and B built in HBM (zero fill, then both triangles written from
+ * the CSR) -- the meaning of problem, n_vec, w, Z_loc, desc_Z, the grid and stage_seconds, the behaviour on a grid with
+ * or without a communicator, and the info values are those of ek_hip_solve_replicated, numbered by this prototype (NaN /
+ * Inf in A: -6); w and Z_loc are bit-identical to ek_hip_solve_replicated on the mirrored dense matrices at every grid
+ * cell.  A and B as reflectors and L are not returned (the reference deallocates them unread).  The CSR build, the
+ * upload and the densification are reported in EK_STAGE_COPY. */
+int ek_hip_solve_sparse(int problem, int n, int n_vec,
+                        long long nnzA, const int *sufA, const double *valA,
+                        long long nnzB, const int *sufB, const double *valB,
+                        double *w, double *Z_loc, const int desc_Z[9],
+                        int nprow, int npcol, int myrow, int mycol,
+                        double *stage_seconds, int n_stages);
+/* The three acceptance quantities from the triplets in one call, with the normalisations of ek_hip_residual_device,
+ * ek_hip_orthogonality_device and ek_hip_ipratios_device:
+ *   out[0..2]  a_norm, res_ave, res_max over the first n_check columns     (skipped when n_check = 0)
+ *   out[3]     orthogonality over the columns index1 .. index2, 1-based     (skipped when index2 < index1)
+ *   ipr_host   n_ipr inverse participation ratios                          (skipped when n_ipr = 0 or ipr_host = NULL)
+ * A skipped part leaves its outputs as they were.  dw: n_check eigenvalues, dZ: n x (the largest column a part uses),
+ * ldz >= max(1, n), both in device memory.  A V and S = B V are sparse-times-dense products, a pass over the rows each
+ * (a thread sums a row's entries in ascending column order; the sums over rows, waves and workgroups have a fixed
+ * order; no atomics), ||A||_F comes from the CSR values; only G = V^T S is a GEMM.  For problem 0, out[3] and the IPRs
+ * are the bits of ek_hip_orthogonality_device / ek_hip_ipratios_device (the same GEMM call, the same kernels); the rest
+ * agrees with the dense entries to rounding.  Divisions are plain IEEE: an empty A gives a_norm = 0 and Inf / NaN in the
+ * residual slots.  Repeated calls and permuted duplicate-free lists give the same bits.
+ * -9 / -10: dw / dZ NULL where a part needs it, -11 ldz, -12 n_check outside 0 .. n, -13 / -14 index1 < 1 / index2 > n
+ * (when index2 >= index1), -15 n_ipr outside 0 .. n, -16 out NULL with a residual or orthogonality part.
+ * NOT COLLECTIVE; the calls synchronise; every input is const.  Workspace: the library's cached device workspace; it
+ * holds the CSRs, Z^T, for problem 1 S^T and S, G and vectors -- no n x n image of A or B
+ * (ek_hip_debug_sparse_check_workspace_bytes of ek_hip_debug.h states the formula). */
+int ek_hip_check_sparse_device(int problem, int n,
+                               long long nnzA, const int *sufA, const double *valA,
+                               long long nnzB, const int *sufB, const double *valB,
+                               const double *dw, const double *dZ, int ldz,
+                               int n_check, int index1, int index2, int n_ipr,
+                               double out[4], double *ipr_host);
+/* the same with w and Z host arrays (Z: n x the largest column a part uses, ldz); device copies of them are added */
+int ek_hip_check_sparse(int problem, int n,
+                        long long nnzA, const int *sufA, const double *valA,
+                        long long nnzB, const int *sufB, const double *valB,
+                        const double *w, const double *Z, int ldz,
+                        int n_check, int index1, int index2, int n_ipr,
+                        double out[4], double *ipr_host);
+/* The stage alone, for tests and hosts: M (host, n x n, ldm >= n) <- the mirrored dense matrix, densified on the GPU;
+ * bit for bit what the reference's loop builds.  What lies between the columns of M (rows n .. ldm-1) is not written. */
+int ek_hip_sparse_to_dense(int n, long long nnz, const int *suf, const double *val, double *M, int ldm);
 
 /* Which tridiagonalisation the whole-path calls use is an implementation detail behind the results
  * contract: orders >= 512 (EK_HIP_TWO_STAGE_MIN overrides, 0 = never) go dense -> band -> tridiagonal

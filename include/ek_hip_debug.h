@@ -119,6 +119,22 @@ unsigned long long ek_hip_debug_window_workspace_bytes(int problem, int n, int j
 /* workspace one ek_hip_sygvx* call asks for (host arithmetic, no GPU): ek_hip_debug_window_workspace_bytes(1, n, jobz,
    range, m) for every itype 1..3 (types 2 and 3 keep type 1's plan).  0: bad arguments. */
 unsigned long long ek_hip_debug_sygvx_workspace_bytes(int itype, int n, int jobz, int range, int m);
+/* workspace one ek_hip_check_sparse_device call asks for (host arithmetic, no GPU), with a256(x) = x rounded up to a
+   multiple of 256 bytes, csr(nnz) = a256(8 (n + 1)) + a256(8 nnz) + a256(16 nnz) (two entries per triplet, 4 + 8 bytes),
+   n_orth = index2 - index1 + 1 (0 when index2 < index1), U = n_check for problem 0 and max(n_check, index2 if n_orth,
+   n_ipr) for problem 1, ldt = U rounded up to 64 (at least 64), chunks = ceil(n / max(8, ceil(n / 128))):
+     csr(nnzA) [+ csr(nnzB)] + a256(8 ldt n if U) [+ a256(8 ldt n if U) + a256(8 n U)] + a256(8 n_orth^2)
+     + a256(8 chunks ldt if U) + a256(8 (max(n_check, n_orth) + 520)) + a256(8 (n_ipr + 8))
+   with the bracketed terms for problem 1 only: Z^T, (B Z)^T, B Z, G, the chunks' partial sums, vectors, outputs.  No term
+   is an n x n image of A or B.  0: bad arguments, n = 0, or nothing to do. */
+unsigned long long ek_hip_debug_sparse_check_workspace_bytes(int problem, int n, long long nnzA, long long nnzB,
+                                                             int n_check, int index1, int index2, int n_ipr);
+/* the canonical form the sparse entries work on (host arithmetic, no GPU): the CSR of the mirrored symmetric matrix of a
+   1-based triplet list -- rowptr (n + 1), col (0-based, ascending inside a row) and csr_val, the latter two with room for
+   2 nnz entries.  Of the entries naming one unordered pair {i, j} the last of the list survives.  Returns the number of
+   CSR entries, or -k for argument k (-3 also for an index outside 1 .. n). */
+long long ek_hip_debug_sparse_csr(int n, long long nnz, const int *suf, const double *val, long long *rowptr, int *col,
+                                  double *csr_val);
 /* ek_hip_*_vbatched* and ek_hip_*_xvbatched*: 3 (the default, also for any other value) launches every class on a stream
    of its own (with an order above EK_HIP_BATCH_NMAX present there are up to four classes), 1 launches the classes one
    behind the other on one stream.  A tuning hook: no result depends on it. */
