@@ -288,6 +288,9 @@ void sb2st_apply_q2(hipStream_t s, int n, int ncols, const double *V2, int ldv2,
 // ---------------------------------------------------------------- tridiagonal D&C (ek_stedc.hip)
 size_t stedc_work_bytes(int n, int nsel = -1);     // nsel: eigenvector columns wanted (-1: all); <= n - n/2: compact bases
 bool stedc_compact(int n, int nsel);               // whether stedc keeps its bases compact for that selection (no wscratch, Z n x nsel)
+// test hook: the merges in plan order as {off, n1, n} (the top merge last; returns how many, fills tri when cap holds them)
+// and the byte offsets in the workspace of every merge's k, nrot and {M, N, K} x 2 after a solve
+int stedc_merge_plan(int n, int nsel, int *tri, int cap, size_t offs[3]);
 // d(n), e(n-1) -> eigenvalues ascending in w(n), eigenvectors in Z (n x n, ldz).
 // With a selection only the eigenvectors of ranks r(l) = ((l / nb) * npcol + mycol) * nb + l % nb,
 // l = 0..nsel-1, are formed (the block-cyclic share of a process column; nb >= n, npcol = 1 gives

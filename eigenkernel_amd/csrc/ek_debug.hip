@@ -359,6 +359,87 @@ int ek_hip_debug_sb2st(int n, const double *A, int lda, double *d, double *e, do
   return 0;
 }
 
+// The divide & conquer in every storage form (ek_stedc.hip), on host arrays: nsel < 0 the full form (sel = nullptr, what
+// ek_hip_stedc runs), otherwise StedcSelect{nsel, nb, npcol, mycol, first} with Z shaped as the whole path shapes it -- n x n
+// (Z doubles as the scratch of the permuted bases) unless stedc_compact(n, nsel), then n x nsel.  Out: all n eigenvalues,
+// the columns the form produces (n, or nsel), info, and one record {off, n1, n, k, nrot, k1} per merge in plan order (the
+// top merge last) read from the workspace after the solve.  k1, the top-only survivors, is what the two products' K
+// dimensions tell: exact when the merge rotated nothing (no dense column), -1 otherwise (a dense column and an odd last
+// top-only column give the products the same operands).  Returns the number of merges, or -k for the k-th argument.
+// columns of the array that entry hands the stage for nsel selected columns (host arithmetic, no GPU)
+int ek_hip_debug_stedc_zcols(int n, int nsel) {
+  if (n < 0 || nsel > n) return -1;
+  return (nsel >= 0 && stedc_compact(n, nsel)) ? (nsel > 0 ? nsel : 1) : n;
+}
+
+int ek_hip_debug_stedc(int n, const double *d, const double *e, int nsel, int first, int nb, int npcol, int mycol,
+                       double *w, double *Z, int ldz, int *merges, int merge_cap, int *info) {
+  if (n < 0) return -1;
+  if (n > 0 && !d) return -2;
+  if (n > 1 && !e) return -3;
+  if (nsel > n) return -4;
+  const bool pick = nsel >= 0;
+  if (pick) {
+    if (nb < 1) return -6;
+    if (npcol < 1) return -7;
+    if (mycol < 0 || mycol >= npcol) return -8;
+    if (first < 0 || (first > 0 && (npcol != 1 || nb < n))) return -5;
+    // the last selected rank (sel_rank of ek_stedc.hip) must be an eigenvalue's
+    const long long l = nsel - 1;
+    if (nsel > 0 && first + ((l / nb) * npcol + mycol) * nb + l % nb >= n) return -4;
+  }
+  const int ncols = pick ? nsel : n;
+  if (n > 0 && !w) return -9;
+  if (n > 0 && ncols > 0 && !Z) return -10;
+  if (ldz < (n > 0 ? n : 1)) return -11;
+  if (merge_cap > 0 && !merges) return -12;
+  if (merge_cap < 0) return -13;
+  if (!info) return -14;
+  *info = 0;
+  if (n == 0) return 0;
+  size_t offs[3];
+  const int nmerge = stedc_merge_plan(n, nsel, nullptr, 0, offs);
+  if (merges && merge_cap < nmerge) return -13;
+  int rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n);
+  const size_t zc = (size_t)ek_hip_debug_stedc_zcols(n, nsel);
+  const size_t wb = stedc_work_bytes(n, nsel);
+  void *ws;
+  rc = workspace(al((size_t)ld * zc * 8) + al(wb) + 3 * al((size_t)ld * 8), &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  double *dZ = a.get<double>((size_t)ld * zc);
+  char *work = a.get<char>(wb);
+  double *dd = a.get<double>(ld), *de = a.get<double>(ld), *dw = a.get<double>(ld);
+  EK_HIP_CHECK(hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemsetAsync(de, 0, (size_t)ld * 8, s));
+  if (n > 1) EK_HIP_CHECK(hipMemcpyAsync(de, e, (size_t)(n - 1) * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemsetAsync(g_ctx.d_info, 0, 4 * sizeof(int), s));
+  const StedcSelect sel{nsel, nb, npcol, mycol, first};
+  stedc(s, n, dd, de, dw, dZ, ld, work, g_ctx.d_info, pick ? &sel : nullptr);
+  EK_HIP_CHECK(hipGetLastError());
+  if (ncols > 0) { rc = d2h_matrix(n, ncols, dZ, ld, Z, ldz, s); if (rc) return rc; }
+  EK_HIP_CHECK(hipMemcpyAsync(w, dw, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  std::vector<int> tri, cnt;
+  if (merges && nmerge > 0) {
+    tri.resize((size_t)3 * nmerge); cnt.resize((size_t)8 * nmerge);
+    (void)stedc_merge_plan(n, nsel, tri.data(), nmerge, offs);
+    EK_HIP_CHECK(hipMemcpyAsync(cnt.data(), work + offs[0], (size_t)nmerge * 4, hipMemcpyDeviceToHost, s));
+    EK_HIP_CHECK(hipMemcpyAsync(cnt.data() + nmerge, work + offs[1], (size_t)nmerge * 4, hipMemcpyDeviceToHost, s));
+    EK_HIP_CHECK(hipMemcpyAsync(cnt.data() + 2 * (size_t)nmerge, work + offs[2], (size_t)nmerge * 24, hipMemcpyDeviceToHost, s));
+  }
+  rc = fetch_info(info); if (rc) return rc;          // (synchronises)
+  for (int m = 0; merges && m < nmerge; ++m) {
+    const int k = cnt[m], nrot = cnt[(size_t)nmerge + m], k_top = cnt[2 * (size_t)nmerge + 6 * (size_t)m + 2];
+    int *r = merges + 6 * (size_t)m;
+    r[0] = tri[3 * (size_t)m]; r[1] = tri[3 * (size_t)m + 1]; r[2] = tri[3 * (size_t)m + 2];
+    r[3] = k; r[4] = nrot; r[5] = nrot == 0 ? k_top : -1;
+  }
+  return nmerge;
+}
+
 int ek_hip_debug_set_two_stage(int min_order) { g_two_stage_min = min_order; return 0; }   // -1: default
 
 // HIP-event brackets around the kernels of the two-stage path bench.py reports a roofline for

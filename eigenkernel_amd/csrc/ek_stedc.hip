@@ -731,6 +731,26 @@ struct WorkLayout {
 size_t stedc_work_bytes(int n, int nsel) { return WorkLayout(n > 0 ? n : 1, nsel).total; }
 bool stedc_compact(int n, int nsel) { return WorkLayout(n > 0 ? n : 1, nsel).compact; }
 
+// Test hook (ek_hip_debug_stedc): the merges of order n in plan order -- height by height, the top merge last, the order of
+// DcBufs::merges -- as {off, n1, n} in tri (when it holds `cap` >= the count of them), and where in the workspace a finished
+// solve leaves every merge's counts: byte offsets of DcBufs::k, ::nrot and ::gdims (the carving of stedc() below).
+int stedc_merge_plan(int n, int nsel, int *tri, int cap, size_t offs[3]) {
+  if (n <= 0) return 0;
+  const WorkLayout L(n, nsel);
+  Plan plan;
+  plan.height(0, n);
+  int cnt = 0;
+  for (auto &lv : plan.levels)
+    for (auto &m : lv) {
+      if (tri && cnt < cap) { tri[3 * cnt] = m.off; tri[3 * cnt + 1] = m.n1; tri[3 * cnt + 2] = m.n; }
+      ++cnt;
+    }
+  offs[0] = L.off_int + 8 * al256((size_t)(n + 8) * 4);
+  offs[1] = offs[0] + al256((size_t)L.nmerge_cap * 4);
+  offs[2] = L.off_dims;
+  return cnt;
+}
+
 namespace {
 // flops of the eigenvector products this solve really ran: 2 M N K over the two GEMMs of every merge, with the
 // dimensions the deflation (and the column selection of the top merge) left on the device

@@ -130,6 +130,9 @@ def load_library(path=None):
         "ek_hip_debug_potrf_team_profile": (c_int, [c_int, c_int]),
         "ek_hip_debug_potrf_team_profile_get": (c_int, [c_int, _dp]),
         "ek_hip_debug_stedc_team_get": (c_int, [_dp]),
+        "ek_hip_debug_stedc": (c_int, [c_int, _dp, _dp, c_int, c_int, c_int, c_int, c_int, _dp, _dp, c_int, _ip, c_int,
+                                       _ip]),
+        "ek_hip_debug_stedc_zcols": (c_int, [c_int, c_int]),
         "ek_hip_debug_last_pipe_stats": (c_int, [_dp, c_int]),
         "ek_hip_debug_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
         "ek_hip_eigenvalues_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, vp, _dp, c_int]),
@@ -255,7 +258,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_sy2sb", "ek_hip_debug_sb2st", "ek_hip_debug_two_stage_timing", "ek_hip_debug_set_two_stage",
     "ek_hip_profile_kernels", "ek_hip_profile_kernels_get", "ek_hip_debug_last_solve_stats",
     "ek_hip_debug_sy2sb_team", "ek_hip_debug_sy2sb_team_timing", "ek_hip_debug_sy2sb_team_profile", "ek_hip_debug_workspace_bytes", "ek_hip_debug_fail_next_chase", "ek_hip_debug_last_pipe_stats",
-    "ek_hip_debug_stedc_team", "ek_hip_debug_stedc_team_get",
+    "ek_hip_debug_stedc_team", "ek_hip_debug_stedc_team_get", "ek_hip_debug_stedc",
+    "ek_hip_debug_stedc_zcols",
     "ek_hip_debug_potrf_team_profile", "ek_hip_debug_potrf_team_profile_get",
     "ek_hip_eigenvalues_device", "ek_hip_eigenvalues", "ek_hip_stebz",
     "ek_hip_debug_values_workspace_bytes", "ek_hip_debug_set_stebz",
@@ -549,6 +553,37 @@ def stedc(d, e):
     Z = np.zeros((n, n), order="F")
     info = lib.ek_hip_stedc(n, _P(d), _P(ee), _P(Z), _I(_desc_for(Z)))
     return d, Z, info
+
+
+def stedc_select(d, e, nsel=-1, first=0, nb=None, npcol=1, mycol=0):
+    """The divide & conquer stage in every storage form (ek_hip_debug_stedc): nsel < 0 the full form; otherwise the
+    eigenvectors of ranks first + ((l // nb) * npcol + mycol) * nb + l % nb, l = 0..nsel-1 (nb=None: n, a window on a 1x1
+    grid).  Returns (w, Z, info, merges): all n eigenvalues, the n x (n or nsel) columns the form produces, the stage's
+    info and an (nmerge, 6) int array of {off, n1, n, k, nrot, k1} per merge, the top merge last (k1 = -1 where nrot > 0).
+    Raises SolverError on an argument or runtime error."""
+    lib = load_library()
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    n = d.shape[0]
+    ee = np.zeros(max(n, 1)); ee[:max(n - 1, 0)] = np.asarray(e, dtype=np.float64)[:max(n - 1, 0)]
+    nsel = int(nsel)
+    nb = max(n, 1) if nb is None else int(nb)
+    ncols = n if nsel < 0 else nsel
+    w = np.zeros(max(n, 1))
+    Z = np.zeros((max(n, 1), max(ncols, 1)), order="F")
+    cap = n // 16 + 2
+    merges = np.zeros((cap, 6), dtype=np.int32)
+    info = ctypes.c_int(0)
+    rc = lib.ek_hip_debug_stedc(n, _P(d), _P(ee), nsel, int(first), nb, int(npcol), int(mycol), _P(w), _P(Z),
+                                max(n, 1), _I(merges), cap, ctypes.byref(info))
+    if rc < 0:
+        raise SolverError("ek_hip_debug_stedc: %d" % rc, rc)
+    return w[:n], Z[:n, :max(ncols, 0)], info.value, merges[:rc].copy()
+
+
+def stedc_zcols(n, nsel=-1):
+    """Columns of the n-row array stedc_select gives the stage (ek_hip_debug_stedc_zcols; no GPU): nsel where the stage
+    keeps its bases compact, n otherwise."""
+    return load_library().ek_hip_debug_stedc_zcols(int(n), int(nsel))
 
 
 def stebz(d, e, il=1, iu=None):

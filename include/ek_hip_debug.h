@@ -189,6 +189,26 @@ int ek_hip_debug_fail_next_chase(int times);
 int ek_hip_debug_stedc_team(int nranks, int levels, int profile);
 int ek_hip_debug_stedc_team_get(double *seconds);
 
+/* The divide & conquer stage (ek_stedc.hip) in every storage form, on host arrays.  d (n), e (n - 1) -> all n eigenvalues
+   ascending in w and eigenvector columns in Z (ldz >= n):
+     nsel < 0   the full form: n columns (what ek_hip_stedc runs; first, nb, npcol, mycol are not referenced);
+     nsel >= 0  the columns of ranks first + ((l / nb) * npcol + mycol) * nb + l % nb, l = 0 .. nsel - 1 (0-based), in
+                columns 0 .. nsel - 1 of Z: a window on a 1 x 1 grid (npcol = 1, nb >= n; first > 0 there only) or a grid
+                cell's block-cyclic share (first = 0).  The stage's own array is shaped as the whole path shapes it: n x n,
+                or n x nsel with the compact bases when n > 32 and nsel <= n - n / 2.
+   merges (optional, 6 * merge_cap ints): one record {off, n1, n, k, nrot, k1} per merge of the tree in plan order, height
+   by height, the top merge last -- k poles survived the deflation, nrot pairs were rotated, k1 of the survivors are
+   non-zero in the top n1 rows only (-1 when nrot > 0: the stage keeps no count of them that tells a dense column from an
+   odd one).  The top merge is the one whose record has off = 0 and n = n.  *info: the stage's info.
+   Returns the number of merges of the tree (0 for n <= 32; the records are filled when merge_cap holds them, -13
+   otherwise), or -k for an illegal k-th argument (-4 also: a selected rank beyond n - 1; -5 also: first > 0 on a grid)
+   -- decided before any device work -- or <= -1000. */
+int ek_hip_debug_stedc(int n, const double *d, const double *e, int nsel, int first, int nb, int npcol, int mycol,
+                       double *w, double *Z, int ldz, int *merges, int merge_cap, int *info);
+/* columns of the n-row array ek_hip_debug_stedc gives the stage for that selection (host arithmetic, no GPU): nsel
+   (at least 1) where the stage keeps its bases compact, n otherwise (nsel < 0: the full form).  -1: bad arguments. */
+int ek_hip_debug_stedc_zcols(int n, int nsel);
+
 /* Team Cholesky (ek_chol.hip potrf_lower_dist): look-ahead 0 off / 1 on / -1 default; profile != 0: HIP events around every
    owner's chain and every rest-of-update section of the next rehearsals (meaningful with the look-ahead OFF).  _get (after the
    rehearsal): parts[0] all chains, [1] all update sections, [2] first chain + sum over the strips of max(next chain, update / nteam):
