@@ -440,6 +440,53 @@ int ek_hip_debug_stedc(int n, const double *d, const double *e, int nsel, int fi
   return nmerge;
 }
 
+// The back-transformation Z <- Q Z (ek_ormtr.hip) as the whole path reaches it, on host arrays: explicit reflectors V
+// (n x n, column j = v_j, zero above its unit entry: what sytrd_lower and sy2sb_lower leave in wV) and tau (n - 1);
+// ormtr_prepare ONCE, then ormtr_apply on column slabs of `slab` columns (<= 0: one call over all ncols), every call
+// with ncols_global (<= 0: ncols).  The workspace is sized as plan_path sizes it: ormtr_prep_bytes(n) and, for the
+// widest slab w, ormtr_work_bytes(n, w, ncols_global) - ormtr_prep_bytes(n).  Returns 0, -k for the k-th argument
+// -- decided before any device work -- or <= -1000.
+int ek_hip_debug_ormtr(int n, int ncols, const double *V, int ldv, const double *tau, double *Z, int ldz,
+                       int ncols_global, int slab) {
+  if (n < 0) return -1;
+  if (ncols < 0) return -2;
+  if (n > 0 && !V) return -3;
+  if (ldv < (n > 0 ? n : 1)) return -4;
+  if (n > 1 && !tau) return -5;
+  if (n > 0 && ncols > 0 && !Z) return -6;
+  if (ldz < (n > 0 ? n : 1)) return -7;
+  int rc = ensure_init(); if (rc) return rc;
+  if (n <= 1 || ncols == 0) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n);
+  const int ncg = ncols_global > 0 ? ncols_global : ncols;
+  const int w = (slab > 0 && slab < ncols) ? slab : ncols;
+  const size_t pb = ormtr_prep_bytes(n), ab = ormtr_work_bytes(n, w, ncg) - pb;
+  void *ws;
+  rc = workspace(al((size_t)ld * ld * 8) + al((size_t)ld * ncols * 8) + al(pb) + al(ab) + al((size_t)ld * 8), &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  double *dV = a.get<double>((size_t)ld * ld);
+  double *dZ = a.get<double>((size_t)ld * ncols);
+  char *prep = a.get<char>(pb), *work = a.get<char>(ab);
+  double *dt = a.get<double>(ld);
+  EK_HIP_CHECK(hipMemsetAsync(dV, 0, (size_t)ld * ld * 8, s));
+  EK_HIP_CHECK(hipMemsetAsync(dt, 0, (size_t)ld * 8, s));
+  rc = h2d_matrix(n, n, V, ldv, dV, ld, s); if (rc) return rc;
+  rc = h2d_matrix(n, ncols, Z, ldz, dZ, ld, s); if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(dt, tau, (size_t)(n - 1) * 8, hipMemcpyHostToDevice, s));
+  ormtr_prepare(s, n, dV, ld, dt, prep);
+  for (int c0 = 0; c0 < ncols; c0 += w) {
+    const int nc = ncols - c0 < w ? ncols - c0 : w;
+    ormtr_apply(s, n, nc, dV, ld, prep, dZ + (size_t)c0 * ld, ld, work, ncg);
+  }
+  EK_HIP_CHECK(hipGetLastError());
+  rc = d2h_matrix(n, ncols, dZ, ld, Z, ldz, s); if (rc) return rc;
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
 int ek_hip_debug_set_two_stage(int min_order) { g_two_stage_min = min_order; return 0; }   // -1: default
 
 // HIP-event brackets around the kernels of the two-stage path bench.py reports a roofline for

@@ -133,6 +133,7 @@ def load_library(path=None):
         "ek_hip_debug_stedc": (c_int, [c_int, _dp, _dp, c_int, c_int, c_int, c_int, c_int, _dp, _dp, c_int, _ip, c_int,
                                        _ip]),
         "ek_hip_debug_stedc_zcols": (c_int, [c_int, c_int]),
+        "ek_hip_debug_ormtr": (c_int, [c_int, c_int, _dp, c_int, _dp, _dp, c_int, c_int, c_int]),
         "ek_hip_debug_last_pipe_stats": (c_int, [_dp, c_int]),
         "ek_hip_debug_workspace_bytes": (ctypes.c_ulonglong, [c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
         "ek_hip_eigenvalues_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, vp, _dp, c_int]),
@@ -259,7 +260,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_profile_kernels", "ek_hip_profile_kernels_get", "ek_hip_debug_last_solve_stats",
     "ek_hip_debug_sy2sb_team", "ek_hip_debug_sy2sb_team_timing", "ek_hip_debug_sy2sb_team_profile", "ek_hip_debug_workspace_bytes", "ek_hip_debug_fail_next_chase", "ek_hip_debug_last_pipe_stats",
     "ek_hip_debug_stedc_team", "ek_hip_debug_stedc_team_get", "ek_hip_debug_stedc",
-    "ek_hip_debug_stedc_zcols",
+    "ek_hip_debug_stedc_zcols", "ek_hip_debug_ormtr",
     "ek_hip_debug_potrf_team_profile", "ek_hip_debug_potrf_team_profile_get",
     "ek_hip_eigenvalues_device", "ek_hip_eigenvalues", "ek_hip_stebz",
     "ek_hip_debug_values_workspace_bytes", "ek_hip_debug_set_stebz",
@@ -627,6 +628,22 @@ def ormtr(Ar, tau, Z):
     t = np.zeros(max(n, 1)); t[:max(n - 1, 0)] = np.asarray(tau, dtype=np.float64)[:max(n - 1, 0)]
     info = lib.ek_hip_ormtr(n, Z.shape[1], _P(Ar), _I(_desc_for(Ar)), _P(t), _P(Z), _I(_desc_for(Z)))
     return Z, info
+
+
+def debug_ormtr(V, tau, Z, ncols_global=0, slab=0):
+    """The back-transformation as the whole path reaches it (ek_hip_debug_ormtr): V the explicit n x n reflectors (column
+    j = v_j, zero above its unit entry), tau (n - 1); the T factors formed once, then applied to column slabs of `slab`
+    columns (<= 0: one call over all), every call with ncols_global (<= 0: the columns of Z).  Returns Q Z; raises
+    SolverError on an argument or runtime error."""
+    lib = load_library()
+    V = _farr(V)
+    Z = np.array(_farr(Z), order="F", copy=True)
+    n = V.shape[0]
+    t = np.zeros(max(n, 1)); t[:max(n - 1, 0)] = np.asarray(tau, dtype=np.float64)[:max(n - 1, 0)]
+    rc = lib.ek_hip_debug_ormtr(n, Z.shape[1], _P(V), max(n, 1), _P(t), _P(Z), max(n, 1), int(ncols_global), int(slab))
+    if rc:
+        raise SolverError("ek_hip_debug_ormtr: %d" % rc, rc)
+    return Z
 
 
 def trtrs(L, Z):

@@ -209,6 +209,18 @@ int ek_hip_debug_stedc(int n, const double *d, const double *e, int nsel, int fi
    (at least 1) where the stage keeps its bases compact, n otherwise (nsel < 0: the full form).  -1: bad arguments. */
 int ek_hip_debug_stedc_zcols(int n, int nsel);
 
+/* The back-transformation Z <- Q Z, Q = H(0) ... H(n-2) (ek_ormtr.hip), as the whole path reaches it, on host arrays.
+   V (n x n, ldv): the EXPLICIT reflectors, column j = v_j, zero above its unit entry (row j + 1 after the one-stage
+   tridiagonalisation, row j + 64 after the dense -> band stage; a column of zeros with tau = 0 is the identity); tau
+   (n - 1); Z (n x ncols, ldz) <- Q Z.  The T factors are formed ONCE (ormtr_prepare), then applied (ormtr_apply) to column
+   slabs of `slab` columns (<= 0: one call over all ncols), every call with ncols_global (<= 0: ncols), the width the
+   slicing of the inner dimension follows: a slab, or a grid cell's columns, given the whole Z's width carry the bits of
+   the one call over the whole Z.  The workspace is the whole path's: ormtr_prep_bytes(n) and, for the widest slab w,
+   ormtr_work_bytes(n, w, ncols_global) - ormtr_prep_bytes(n).  Returns 0, -k for an illegal k-th argument -- decided
+   before any device work -- or <= -1000. */
+int ek_hip_debug_ormtr(int n, int ncols, const double *V, int ldv, const double *tau, double *Z, int ldz,
+                       int ncols_global, int slab);
+
 /* Team Cholesky (ek_chol.hip potrf_lower_dist): look-ahead 0 off / 1 on / -1 default; profile != 0: HIP events around every
    owner's chain and every rest-of-update section of the next rehearsals (meaningful with the look-ahead OFF).  _get (after the
    rehearsal): parts[0] all chains, [1] all update sections, [2] first chain + sum over the strips of max(next chain, update / nteam):
