@@ -284,6 +284,9 @@ void sb2st_lower(hipStream_t s, int n, const double *A, int lda, double *d, doub
 // Z(:, 0:ncols) <- Q2 Z (Z 16-byte aligned, ldz even); *d_flag |= 4 if the pipeline had to be abandoned
 void sb2st_apply_q2(hipStream_t s, int n, int ncols, const double *V2, int ldv2, double *Z, int ldz, int *d_flag,
                     void *work, double *records = nullptr);
+// test hook: the stage's tau (device; entry [k + s * *ldt] for task (s, k)) and control words (device; [3] != 0: the
+// position kernel gave up, [4]: the workgroups of it that arrived) inside work, in either layout
+void sb2st_debug_view(int n, void *work, const double **tau2, int *ldt, const unsigned **ctl);
 
 // ---------------------------------------------------------------- tridiagonal D&C (ek_stedc.hip)
 size_t stedc_work_bytes(int n, int nsel = -1);     // nsel: eigenvector columns wanted (-1: all); <= n - n/2: compact bases

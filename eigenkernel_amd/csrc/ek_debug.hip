@@ -359,6 +359,78 @@ int ek_hip_debug_sb2st(int n, const double *A, int lda, double *d, double *e, do
   return 0;
 }
 
+// The bulge chasing and the application of Q2 as a stage, on host arrays, with what the stage leaves behind.
+// form 0: the layout of ek_hip_debug_sb2st (the stage packs the band, the records of Q2 inside the workspace); form 1: what
+// the whole path does (Path::tridiagonalise / back_transform in ek_solve.hip): pack_band into sb2st_band(work, n) of a
+// workspace of sb2st_work_bytes(n, false), band_packed = true, the records lent as an array of sb2st_record_bytes(n).
+// chase_mode goes to sb2st_lower (0 default, 1 sweeps through memory, 2 positions in registers).  Optional outputs: V2
+// (n x n, ldv2: reflector (s, k) in rows s+1+64k .. of column s), tau2 ((kmax+1) x max(n-2, 1), ldtau, entry [k + s ldtau],
+// kmax = (n-3)/64 + 1), *ran from the control words after the run (0: no sweep at all, 1: the sweep kernel alone, 2: the
+// position kernel to the end, 3: it gave up and the sweep kernel redid the stage).  Returns 0, -k for the k-th argument
+// (before any device work), or <= -1000.
+int ek_hip_debug_sb2st_stage(int n, const double *A, int lda, int form, int chase_mode, double *d, double *e, double *V2,
+                             int ldv2, double *tau2, int ldtau, double *Z, int ldz, int ncols, int *ran, int *flag) {
+  if (n < 1) return -1;
+  if (!A) return -2;
+  if (lda < n) return -3;
+  if (form != 0 && form != 1) return -4;
+  if (chase_mode < 0 || chase_mode > 2) return -5;
+  if (!d) return -6;
+  if (n > 1 && !e) return -7;
+  const int kmax = (n - 3) / kBandW + 1, ncs = n > 2 ? n - 2 : 1;
+  if (V2 && ldv2 < n) return -9;
+  if (tau2 && ldtau < kmax + 1) return -11;
+  if (ncols < 0) return -14;
+  if (ncols > 0 && !Z) return -12;
+  if (ncols > 0 && ldz < n) return -13;
+  int rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  const int ld = pad_ld(n);
+  const size_t wb = sb2st_work_bytes(n, form == 0), rb = form == 1 ? sb2st_record_bytes(n) : 0;
+  const size_t zc = ncols > 0 ? ncols : 1;
+  void *ws;
+  rc = workspace(2 * al((size_t)ld * ld * 8) + al((size_t)ld * zc * 8) + al(wb) + al(rb) + 2 * al((size_t)ld * 8) + 256, &ws);
+  if (rc) return rc;
+  Arena a(ws, g_ctx.ws_bytes);
+  double *dA = a.get<double>((size_t)ld * ld), *dV2 = a.get<double>((size_t)ld * ld);
+  double *dZ = a.get<double>((size_t)ld * zc);
+  char *work = a.get<char>(wb);
+  double *rec = rb ? a.get<double>(rb / 8) : nullptr;
+  double *dd = a.get<double>(ld), *de = a.get<double>(ld);
+  EK_HIP_CHECK(hipMemsetAsync(dA, 0, (size_t)ld * ld * 8, s));
+  EK_HIP_CHECK(hipMemsetAsync(dV2, 0, (size_t)ld * ld * 8, s));
+  EK_HIP_CHECK(hipMemsetAsync(dd, 0, 2 * al((size_t)ld * 8), s));
+  EK_HIP_CHECK(hipMemsetAsync(g_ctx.d_info, 0, 4 * sizeof(int), s));
+  rc = h2d_matrix(n, n, A, lda, dA, ld, s); if (rc) return rc;
+  if (form == 1) {
+    pack_band(s, n, dA, ld, sb2st_band(work, n));
+    sb2st_lower(s, n, nullptr, 0, dd, de, dV2, ld, g_ctx.d_info + 2, work, /*band_packed=*/true, chase_mode);
+  } else {
+    sb2st_lower(s, n, dA, ld, dd, de, dV2, ld, g_ctx.d_info + 2, work, /*band_packed=*/false, chase_mode);
+  }
+  const double *dtau; int ldt; const unsigned *dctl;
+  sb2st_debug_view(n, work, &dtau, &ldt, &dctl);
+  unsigned ctl[8] = {0};
+  EK_HIP_CHECK(hipMemcpyAsync(ctl, dctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+  if (ncols > 0) {
+    rc = h2d_matrix(n, ncols, Z, ldz, dZ, ld, s); if (rc) return rc;
+    sb2st_apply_q2(s, n, ncols, dV2, ld, dZ, ld, g_ctx.d_info + 2, work, rec);
+    rc = d2h_matrix(n, ncols, dZ, ld, Z, ldz, s); if (rc) return rc;
+  }
+  EK_HIP_CHECK(hipGetLastError());
+  if (V2) { rc = d2h_matrix(n, n, dV2, ld, V2, ldv2, s); if (rc) return rc; }
+  if (tau2) { rc = d2h_matrix(kmax + 1, ncs, dtau, ldt, tau2, ldtau, s); if (rc) return rc; }
+  EK_HIP_CHECK(hipMemcpyAsync(d, dd, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (n > 1) EK_HIP_CHECK(hipMemcpyAsync(e, de, (size_t)(n - 1) * 8, hipMemcpyDeviceToHost, s));
+  int f = 0;
+  EK_HIP_CHECK(hipMemcpyAsync(&f, g_ctx.d_info + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  if (ran) *ran = n < 3 ? 0 : (ctl[3] ? 3 : (ctl[4] ? 2 : 1));
+  if (flag) *flag = f;
+  return 0;
+}
+
 // The divide & conquer in every storage form (ek_stedc.hip), on host arrays: nsel < 0 the full form (sel = nullptr, what
 // ek_hip_stedc runs), otherwise StedcSelect{nsel, nb, npcol, mycol, first} with Z shaped as the whole path shapes it -- n x n
 // (Z doubles as the scratch of the permuted bases) unless stedc_compact(n, nsel), then n x nsel.  Out: all n eigenvalues,

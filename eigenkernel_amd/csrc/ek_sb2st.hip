@@ -1217,6 +1217,14 @@ int pos_capacity() {
 
 size_t sb2st_work_bytes(int n, bool with_records) { return Layout(n, with_records).total; }
 size_t sb2st_record_bytes(int n) { return al256((Layout(n).nrec + 1) * QREC * 8); }
+// test aid (ek_hip_debug_sb2st_stage): where the stage keeps tau (leading dimension *ldt, entry [k + s ldt], nsweeps + 1
+// columns) and its control words ([3] the position kernel gave up, [4] its census) -- the same place in both layouts
+void sb2st_debug_view(int n, void *work, const double **tau2, int *ldt, const unsigned **ctl) {
+  const Layout L(n, false);
+  *tau2 = (const double *)((char *)work + L.off_tau);
+  *ldt = L.ldt;
+  *ctl = (const unsigned *)((char *)work + L.off_ctl);
+}
 
 // Band (lower band of A, half bandwidth 64) -> d, e; the reflectors go to V2 (n x n, ldv2, zero on
 // entry; column s = the reflectors of sweep s stacked) and into the workspace (tau).  *d_flag |= 4
@@ -1305,7 +1313,20 @@ void sb2st_apply_q2(hipStream_t s, int n, int ncols, const double *V2, int ldv2,
   int nblk = (n >= 8192) ? 4 : 3;
   { const int v = switch_int(kSwQ2Nblk); if (v >= 2 && v <= 4) nblk = v; }
   const int per = nblk;
-  const int nslab = ceil_div(ncols, QNC), npair = ceil_div(L.nS, per), npass = npair * nslab;
+  const int npair = ceil_div(L.nS, per);
+  // The workspace holds one progress word per pass for up to nS x ceil(n / 64) passes (Layout::off_qprog): every call of
+  // the whole path (ncols <= n).  More columns than that many slabs go in pieces of whole slabs, one launch after the
+  // other -- columns do not meet, so the bits are those of one launch.  (Before, the words of such a call ran over the
+  // table of the records' offsets behind them.)
+  const size_t qcap = al256((size_t)L.nS * ceil_div(n, QNC) * 4) / 4;
+  const int slabs_max = (int)(qcap / (size_t)npair);
+  if (ceil_div(ncols, QNC) > slabs_max) {
+    const int piece = slabs_max * QNC;
+    for (int c0 = 0; c0 < ncols; c0 += piece)
+      sb2st_apply_q2(s, n, (ncols - c0 < piece) ? ncols - c0 : piece, V2, ldv2, Z + (size_t)c0 * ldz, ldz, d_flag, work, records);
+    return;
+  }
+  const int nslab = ceil_div(ncols, QNC), npass = npair * nslab;
   (void)hipMemsetAsync(qprog, 0, (size_t)npass * 4, s);
   (void)hipMemsetAsync(ctl + 2, 0, 4, s);
   // (A pass stays no further behind its predecessor in the slab than the two steps it must.  With few slabs

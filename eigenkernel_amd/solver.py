@@ -117,6 +117,8 @@ def load_library(path=None):
         "ek_hip_profile_symv_get": (c_int, [_dp, ctypes.POINTER(ctypes.c_longlong), _dp]),
         "ek_hip_debug_sy2sb": (c_int, [c_int, _dp, c_int, _dp, c_int, _dp, _ip]),
         "ek_hip_debug_sb2st": (c_int, [c_int, _dp, c_int, _dp, _dp, _dp, c_int, c_int, _ip]),
+        "ek_hip_debug_sb2st_stage": (c_int, [c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, c_int, _dp, c_int, _dp, c_int,
+                                             c_int, _ip, _ip]),
         "ek_hip_debug_two_stage_timing": (c_int, [c_int, c_int, c_int, _dp, _ip]),
         "ek_hip_debug_set_two_stage": (c_int, [c_int]),
         "ek_hip_profile_kernels": (c_int, [c_int]),
@@ -256,7 +258,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_potrf_team", "ek_hip_debug_reduce_team", "ek_hip_comm_attach_host",
     "ek_hip_debug_set_sytrd_maxcols", "ek_hip_debug_sytrd_work_bytes", "ek_hip_debug_sytrd_at", "ek_hip_debug_sytrd_split", "ek_hip_debug_gemm_at",
     "ek_hip_debug_gemm_desc", "ek_hip_debug_gemm_plan", "ek_hip_debug_gemm_compact_map",
-    "ek_hip_debug_sy2sb", "ek_hip_debug_sb2st", "ek_hip_debug_two_stage_timing", "ek_hip_debug_set_two_stage",
+    "ek_hip_debug_sy2sb", "ek_hip_debug_sb2st", "ek_hip_debug_sb2st_stage", "ek_hip_debug_two_stage_timing", "ek_hip_debug_set_two_stage",
     "ek_hip_profile_kernels", "ek_hip_profile_kernels_get", "ek_hip_debug_last_solve_stats",
     "ek_hip_debug_sy2sb_team", "ek_hip_debug_sy2sb_team_timing", "ek_hip_debug_sy2sb_team_profile", "ek_hip_debug_workspace_bytes", "ek_hip_debug_fail_next_chase", "ek_hip_debug_last_pipe_stats",
     "ek_hip_debug_stedc_team", "ek_hip_debug_stedc_team_get", "ek_hip_debug_stedc",
@@ -1252,6 +1254,48 @@ def sb2st(Bd, Z=None):
     if rc:
         raise RuntimeError("ek_hip_debug_sb2st info=%d" % rc)
     return d[:n], e[:max(n - 1, 0)], Z, flag.value
+
+
+def sb2st_stage(Bd, Z=None, form=0, chase_mode=0, reflectors=True, pad=0):
+    """Stage 2 with what it leaves behind (ek_hip_debug_sb2st_stage): the lower band of Bd -> a dict with d, e, V2 (n x n:
+    reflector (s, k) in rows s+1+64k .. of column s), tau2 ((kmax+1) x max(n-2, 1), entry [k, s]), Z (Q2 Z, or None), ran
+    (which chase kernel ran: 1 sweeps through memory, 2 positions in registers, 3 the second after the first gave up, 0
+    none) and flag.  form 0: the layout of sb2st; form 1: the workspace, packed band and lent records of a whole-path
+    solve.  pad > 0: every host array gets that many more rows than it needs, filled with NaN (never to be read).
+    reflectors=False: V2 and tau2 are not asked for.  Raises SolverError on an argument or runtime error."""
+    lib = load_library()
+    Bd = _farr(Bd)
+    n = Bd.shape[0]
+    pad = int(pad)
+
+    def padded(rows, cols, src=None):
+        M = np.full((rows + pad, max(cols, 1)), np.nan, order="F")
+        M[:rows] = 0.0 if src is None else src
+        return M
+
+    A = padded(n, n, Bd)
+    kmax = max(n - 3, 0) // 64 + 1
+    d = np.zeros(max(n, 1)); e = np.zeros(max(n, 1)); flag = ctypes.c_int(-1); ran = ctypes.c_int(-1)
+    V2 = padded(n, n) if reflectors else None
+    tau2 = padded(kmax + 1, max(n - 2, 1)) if reflectors else None
+    ncols = 0 if Z is None else _farr(Z).shape[1]
+    Zp = padded(n, ncols, _farr(Z)) if ncols > 0 else None
+    rc = lib.ek_hip_debug_sb2st_stage(n, _P(A), n + pad, int(form), int(chase_mode), _P(d), _P(e),
+                                      _P(V2) if reflectors else None, n + pad, _P(tau2) if reflectors else None,
+                                      kmax + 1 + pad, _P(Zp) if ncols > 0 else None, n + pad, ncols, ctypes.byref(ran),
+                                      ctypes.byref(flag))
+    if rc:
+        raise SolverError("ek_hip_debug_sb2st_stage: %d" % rc, rc)
+    if pad:
+        for M in (A, V2, tau2, Zp):
+            if M is not None and not np.isnan(M[M.shape[0] - pad:]).all():
+                raise SolverError("ek_hip_debug_sb2st_stage wrote into the padding of a host array", -1)
+    def cut(M, rows):
+        return None if M is None else np.array(M[:rows], order="F")
+
+    return {"d": d[:n], "e": e[:max(n - 1, 0)], "V2": cut(V2, n), "tau2": cut(tau2, kmax + 1),
+            "Z": (cut(Zp, n) if ncols > 0 else (None if Z is None else np.zeros((n, 0)))), "ran": ran.value,
+            "flag": flag.value}
 
 
 def dgemm(transa, transb, alpha, A, B, beta, C, lower_only=False):

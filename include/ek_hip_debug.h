@@ -79,6 +79,16 @@ int ek_hip_debug_sy2sb(int n, double *A, int lda, double *V, int ldv, double *ta
 int ek_hip_debug_sb2st(int n, const double *A, int lda, double *d, double *e, double *Z, int ldz, int ncols, int *flag);
 int ek_hip_debug_two_stage_timing(int n, int ncols, int reps, double *seconds, int *flag);
 int ek_hip_debug_set_two_stage(int min_order);
+/*   _sb2st_stage : _sb2st with what the stage leaves behind, in either workspace form.  form 0: the layout of _sb2st;
+ *            form 1: what a whole-path solve does (the band packed by the caller into the stage's workspace without
+ *            records, the records of Q2 lent as a separate array).  chase_mode 0: default, 1: sweeps through memory, 2:
+ *            positions in registers.  Optional outputs (NULL: not wanted): V2 (n x n, ldv2; reflector (s, k) in rows
+ *            s+1+64k .. min(s+64(k+1), n-1) of column s), tau2 ((kmax+1) x max(n-2, 1), ldtau; entry [k + s ldtau], kmax =
+ *            (n-3)/64 + 1), *ran = which chase kernel ran (0: none, n < 3; 1: the sweep kernel alone; 2: the position
+ *            kernel to the end; 3: it gave up and the sweep kernel redid the stage).  Z: any ncols >= 0, also above n.
+ *            Returns 0, -k for an illegal k-th argument (before any device work), or <= -1000. */
+int ek_hip_debug_sb2st_stage(int n, const double *A, int lda, int form, int chase_mode, double *d, double *e, double *V2,
+                             int ldv2, double *tau2, int ldtau, double *Z, int ldz, int ncols, int *ran, int *flag);
 /*   _sy2sb_team : the first stage over a 1 x P team (128-wide column strips, strip S on rank S mod P; per panel one
  *            broadcast of [V | T | tau] and one all-reduce of Y): nteam >= 1 rehearses the whole team inside this
  *            process (every member with its own copy of A -- NaN outside its strips when EK_HIP_TEAM_POISON=1), nteam = 0

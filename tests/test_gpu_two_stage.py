@@ -191,19 +191,19 @@ def test_bulge_chasing_does_not_depend_on_the_width_of_the_pipeline(hip, n):
 @pytest.mark.parametrize("n", [3, 4, 66, 130, 193, 777, 1500, 4200])
 def test_both_bulge_chasing_kernels_give_the_same_bits(hip, n):
     """ek_sb2st.hip has two kernels for the chase: positions of the band held in registers, sweeps passing
-    through them by mail (the default), and sweeps walking through memory (EK_SB2ST_CHASE=1; the fall-back).
+    through them by mail (the default), and sweeps walking through memory (the fall-back).
     They share the arithmetic of a task, so d, e, the reflectors (seen through the applied Q2) must agree bit
-    for bit -- which also shows that no hand-off of either protocol delivered a stale or a misplaced number."""
+    for bit -- which also shows that no hand-off of either protocol delivered a stale or a misplaced number.
+    (The kernel is chosen through sb2st_lower's chase_mode, by ek_hip_debug_sb2st_stage: the switch EK_SB2ST_CHASE is
+    read once per process, so flipping it between calls compared one kernel with itself.  The stage's control words
+    say which kernel ran; tests/test_gpu_sb2st_stages.py compares the reflectors themselves, on more classes.)"""
     Bd = _random_band(n, 3 * n + 1)
     Z0 = np.eye(n)[:, ::max(n // 16, 1)][:, :16].copy()
-    try:
-        os.environ["EK_SB2ST_CHASE"] = "1"
-        d1, e1, Z1, f1 = hip.sb2st(Bd, Z0)
-        os.environ["EK_SB2ST_CHASE"] = "2"
-        d2, e2, Z2, f2 = hip.sb2st(Bd, Z0)
-        d3, e3, Z3, f3 = hip.sb2st(Bd, Z0)
-    finally:
-        os.environ.pop("EK_SB2ST_CHASE", None)
+    r1 = hip.sb2st_stage(Bd, Z0, chase_mode=1, reflectors=False)
+    r2 = hip.sb2st_stage(Bd, Z0, chase_mode=2, reflectors=False)
+    r3 = hip.sb2st_stage(Bd, Z0, chase_mode=2, reflectors=False)
+    assert r1["ran"] == 1 and r2["ran"] == 2 and r3["ran"] == 2
+    (d1, e1, Z1, f1), (d2, e2, Z2, f2), (d3, e3, Z3, f3) = ((r["d"], r["e"], r["Z"], r["flag"]) for r in (r1, r2, r3))
     assert f1 == 0 and f2 == 0 and f3 == 0
     assert np.array_equal(d1, d2) and np.array_equal(e1, e2) and np.array_equal(Z1, Z2)
     assert np.array_equal(d3, d2) and np.array_equal(e3, e2) and np.array_equal(Z3, Z2)
