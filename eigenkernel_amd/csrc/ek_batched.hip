@@ -29,6 +29,11 @@
 // problem and of type 1 holds nothing of them.  Scaling of A is stage 0's; what is amplified here is lambda_max(B),
 // not 1 / lambda_min(B).
 //
+// ek_hip_eigenpairs_window_batched*: a window of eigenpairs (RANGE 'I' / 'V') per problem.  A third argument type, WArgs,
+// selects stage 4W of ek_batched_window.h in place of stage 4's QL -- Sturm bisection of the wanted values, inverse
+// iteration for their vectors -- and stage 5 then runs on the window's columns only.  Stages 0 to 3 are
+// the same lines for every argument type, and the instantiations of Args and VArgs hold nothing of the window.
+//
 // Image layout: column-major with leading dimension NC + 1 (odd), NC the class size 32 / 64 / 128.  A wave that walks
 // down a column (consecutive rows) and a wave that walks along a row (stride NC + 1, odd) both hit 32 different
 // 64-bit banks per 32 lanes.  Threads: T = 2 NC; thread t is (row or column t % NC, half t / NC).
@@ -40,8 +45,10 @@
 // a table instead of at blockIdx.x * stride; every problem runs in the class its own order picks (the uniform call's
 // bits), the classes as one launch each, the problems of a class in descending order.
 #include "ek_batched_stages.h"
+#include "ek_batched_window.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace ek {
 namespace batched {
@@ -64,6 +71,12 @@ struct VArgs {
   const Desc *table;
   int *info;
   int itype;
+};
+
+// ek_hip_eigenpairs_window_batched*: Args and the window.  The type is what selects stage 4W (ek_batched_window.h) in
+// place of the QL of stage 4: the instantiations of Args and VArgs hold nothing of it.
+struct WArgs : Args {
+  bwindow::Window win;
 };
 
 // What a workgroup works on, whichever way it found it.  The pointers are typed as global (gdouble, ek_batched_stages.h)
@@ -184,9 +197,11 @@ __device__ __forceinline__ void multiply_by_l(double *S, double *sl, const gdoub
 // ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or VArgs (a table entry)
 // CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
 // CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
+// WIN (ARGS = WArgs): stage 4W for QL, and stage 5 on the window's columns.
 template <int NC, int T, typename ARGS = Args, bool CONG = false>
 __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   constexpr int LD = NC + 1, P = T / NC, NW = T / 64;
+  constexpr bool WIN = std::is_same<ARGS, WArgs>::value;
   static_assert(P == 2 && T % 64 == 0, "two threads per row");
   extern __shared__ double smem[];
   double *S = smem;                       // NC x NC image, leading dimension LD
@@ -386,7 +401,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   __syncthreads();
   // QL converges fast towards a small top; a matrix graded the other way (rank one: everything in d[0]) is taken
   // upside down, T' = P T P, which QL sees as DSTEQR's QR sees T.  Z starts as P, so that Z' comes out as P Z'.
-  const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
+  const bool flip = !WIN && fabs(sd[0]) > fabs(sd[n - 1]);
   {
     double dr = 0.0, er = 0.0;
     if (flip && sub == 0 && row) {
@@ -396,10 +411,10 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
     __syncthreads();
     if (flip && sub == 0 && row) { sd[r] = dr; se[r] = er; }
   }
-  if (a.jobz && row)
+  if (!WIN && a.jobz && row)
     for (int j = sub; j < n; j += P) S[r + j * LD] = (r == (flip ? n - 1 - j : j)) ? 1.0 : 0.0;
   __syncthreads();
-  {
+  if constexpr (!WIN) {
     const double eps = 1.1102230246251565e-16;
     double *sc_ = sv, *ss_ = sw;
     int failed = 0;
@@ -507,7 +522,13 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
       return;
     }
   }
-  if (!rank_sort<NC>(n, wex, sd, srank, p.w, info)) return;
+  int nz = n;                                       // columns of Z: n, or the window's m
+  if constexpr (WIN) {
+    if (!bwindow::stage4w<NC, NW>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red, phase, srank, p.w, info, nz))
+      return;
+  } else {
+    if (!rank_sort<NC>(n, wex, sd, srank, p.w, info)) return;
+  }
   if (!a.jobz) {
     if (t == 0) *info = 0;
     return;
@@ -524,7 +545,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
       double nx = 0.0;
       if (k >= 1 && t > k && t < n) nx = A[t + (size_t)(k - 1) * lda];
       const double tau = st[k];
-      if (tau != 0.0 && t < n) {
+      if (tau != 0.0 && t < nz) {
         double *col = S + t * LD;
         double dot = col[k + 1];
         for (int i = k + 2; i < n; ++i) dot += cur[i] * col[i];
@@ -548,7 +569,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
       const double *cur = sl + (s & 1) * NC;
       double nx = 0.0;
       if (i >= 1 && t >= i - 1 && t < n) nx = B[t + (size_t)(i - 1) * ldb];
-      if (t < n) {
+      if (t < nz) {
         double *col = S + t * LD;
         double acc = col[i];
         for (int k = i + 1; k < n; ++k) acc -= cur[k] * col[k];
@@ -560,7 +581,7 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   }
   __syncthreads();
   if (row)
-    for (int j = sub; j < n; j += P) Z[r + (size_t)srank[j] * ldz] = S[r + j * LD];
+    for (int j = sub; j < nz; j += P) Z[r + (size_t)srank[j] * ldz] = S[r + j * LD];
   if (t == 0) *info = 0;
 }
 
@@ -614,6 +635,35 @@ static int ensure_info(size_t batch) {
   return 0;
 }
 
+// ek_hip_eigenpairs_window_batched*: a count per problem, and the LU factors of inverse iteration -- one slot per
+// workgroup of a launch, the batch running in chunks of g_wchunk problems that share the slots (the stream's order
+// separates two users of a slot, as in ek_batched_x.hip).  Grown, never shrunk, released in ek_hip_finalize
+constexpr int kWindowChunk = 1024;
+constexpr size_t kWindowBytes = (size_t)256 << 20;
+static int g_wchunk = kWindowChunk;
+static int *g_dm = nullptr;
+static size_t g_dm_count = 0;
+static double *g_wws = nullptr;
+static size_t g_wws_bytes = 0;
+
+static int ensure_window(size_t batch, size_t bytes) {
+  if (batch > g_dm_count) {
+    if (g_dm) (void)hipFree(g_dm);
+    g_dm = nullptr;
+    g_dm_count = 0;
+    EK_HIP_CHECK(hipMalloc((void **)&g_dm, batch * sizeof(int)));
+    g_dm_count = batch;
+  }
+  if (bytes > g_wws_bytes) {
+    if (g_wws) (void)hipFree(g_wws);
+    g_wws = nullptr;
+    g_wws_bytes = 0;
+    EK_HIP_CHECK(hipMalloc((void **)&g_wws, bytes));
+    g_wws_bytes = bytes;
+  }
+  return 0;
+}
+
 static int ensure_variable(size_t entries, int sides) {
   if (entries > g_dtable_count) {
     if (g_dtable) (void)hipFree(g_dtable);
@@ -640,6 +690,12 @@ void release_batched() {
   if (g_dtable) (void)hipFree(g_dtable);
   g_dtable = nullptr;
   g_dtable_count = 0;
+  if (g_dm) (void)hipFree(g_dm);
+  g_dm = nullptr;
+  g_dm_count = 0;
+  if (g_wws) (void)hipFree(g_wws);
+  g_wws = nullptr;
+  g_wws_bytes = 0;
   std::vector<Desc>().swap(g_htable);
   for (int k = 0; k < kClasses - 1; ++k) {
     if (g_side[k]) (void)hipStreamDestroy(g_side[k]);
@@ -900,6 +956,154 @@ static int batched_host_entry(int problem, int itype, int jobz, int n, int batch
   return 0;
 }
 
+// ---- a window of eigenpairs per problem (ek_hip_eigenpairs_window_batched*)
+
+// The 23 arguments of the prototype in their order; no data pointer is dereferenced
+static int window_check(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                        const void *A, int lda, long long strideA, const void *B, int ldb, long long strideB,
+                        const int *m, const void *w, const void *Z, int ldz, int zcap, long long strideZ,
+                        const int *info, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (jobz != 0 && jobz != 1) return -2;
+  if (range != 0 && range != 1) return -3;
+  if (n < 0 || n > EK_HIP_BATCH_NMAX) return -4;
+  if (batch < 0) return -5;
+  if (n == 0 || batch == 0) { *nothing = true; return 0; }
+  if (range == 1) {
+    if (vl != vl) return -6;
+    if (!(vl < vu)) return -7;                      // vu NaN, or an empty interval
+  } else {
+    if (il < 1 || il > n) return -8;
+    if (iu < il || iu > n) return -9;
+  }
+  if (!A) return -10;
+  if (lda < n) return -11;
+  if (strideA < (long long)lda * n) return -12;
+  if (problem == 1) {
+    if (!B) return -13;
+    if (ldb < n) return -14;
+    if (strideB < (long long)ldb * n) return -15;
+  }
+  if (!m) return -16;
+  if (!w) return -17;
+  if (jobz == 1) {
+    if (!Z) return -18;
+    if (ldz < n) return -19;
+  }
+  if (zcap < 0 || (range == 0 && zcap < iu - il + 1)) return -20;   // with and without vectors
+  if (jobz == 1 && strideZ < (long long)ldz * std::max(1, zcap)) return -21;
+  if (!info) return -22;
+  return 0;
+}
+
+// arguments checked, context up, g_mu held
+static int window_device_locked(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                                double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
+                                double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
+                                double *seconds) {
+  using namespace batched;
+  hipStream_t s = g_ctx.stream;
+  const int wcols = !jobz ? 0 : range == 0 ? iu - il + 1 : std::min(zcap, n);
+  const size_t slot = (size_t)5 * n * wcols * sizeof(double);
+  // wide slots: fewer problems per launch, so that the workspace stays near kWindowBytes -- in whole rounds of 256
+  // workgroups (class 128 runs one per compute unit: a chunk of 409 would be three rounds for 512 problems), two at least
+  const int fit = (int)std::min<size_t>(kWindowBytes / std::max(slot, (size_t)1), (size_t)g_wchunk);
+  const int K = std::min(g_wchunk, std::max(512, fit / 256 * 256));
+  { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
+  { int rc0 = ensure_window((size_t)batch, (size_t)std::min(batch, K) * slot); if (rc0) return rc0; }
+  EK_HIP_CHECK(hipMemsetAsync(g_dm, 0, (size_t)batch * sizeof(int), s));   // a problem that ends before stage 4W: m = 0
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (seconds) {
+    EK_HIP_CHECK(hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e != hipSuccess) { (void)hipEventDestroy(e0); return -1000 - (int)e; }
+    (void)hipEventRecord(e0, s);
+  }
+  int rc = 0;
+  for (int c0 = 0; c0 < batch && !rc; c0 += K) {
+    const int count = std::min(K, batch - c0);
+    WArgs a{{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
+             problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
+             jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, 1},
+            {range, il, iu, zcap, vl, vu, g_dm + c0, g_wws, wcols}};
+    switch (class_of(n)) {
+      case 32: rc = launch_instance<32, 64, WArgs, false>(s, count, a); break;
+      case 64: rc = launch_instance<64, 128, WArgs, false>(s, count, a); break;
+      default: rc = launch_instance<128, 256, WArgs, false>(s, count, a); break;
+    }
+  }
+  if (seconds) (void)hipEventRecord(e1, s);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (!rc && e == hipSuccess) e = hipMemcpyAsync(m, g_dm, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
+  if (seconds) {
+    float ms = 0.f;
+    if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *seconds = (double)ms * 1e-3;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  return rc;
+}
+
+static int window_device_entry(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                               double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
+                               double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
+                               double *seconds) {
+  bool nothing;
+  int rc = window_check(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw, dZ,
+                        ldz, zcap, strideZ, info, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return window_device_locked(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+                              dZ, ldz, zcap, strideZ, info, seconds);
+}
+
+static int window_host_entry(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                             const double *A, int lda, long long strideA, const double *B, int ldb, long long strideB,
+                             int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
+                             double *seconds) {
+  bool nothing;
+  int rc = window_check(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
+                        zcap, strideZ, info, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  // device copies with the caller's own layout; w and Z travel both ways, so that what the kernel leaves alone (the
+  // rest of a row of w, the columns from m[b] on, a failed problem's slots) comes back as the caller had it
+  auto span = [&](int ld, long long stride, int cols) {
+    return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (cols - 1) + n;
+  };
+  const size_t cA = span(lda, strideA, n), cB = problem ? span(ldb, strideB, n) : 0;
+  const size_t cZ = (jobz && zcap > 0) ? span(ldz, strideZ, zcap) : 0, cw = (size_t)batch * n;
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cA * 8);
+  if (!rc) rc = mem.alloc(&uw, cw * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
+  if (!rc && jobz) rc = mem.alloc(&uZ, std::max(cZ, (size_t)1) * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
+  if (cZ) EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
+  rc = window_device_locked(problem, jobz, range, n, batch, vl, vu, il, iu, uA, lda, strideA, uB, ldb, strideB, m, uw, uZ,
+                            ldz, zcap, strideZ, info, seconds);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
+  if (cZ) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
 static int vbatched_device_entry(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
                                  const int *lda, double *const *dB, const int *ldb, double *const *dw,
                                  double *const *dZ, const int *ldz, int *info, double *seconds,
@@ -1111,6 +1315,29 @@ int ek_hip_sygv_xvbatched(int itype, int jobz, int batch, const int *n, const do
                           int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
   return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_eigenpairs_window_batched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
+                                            int il, int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                            long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                            long long strideZ, int *info, double *seconds) {
+  return window_device_entry(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+                             dZ, ldz, zcap, strideZ, info, seconds);
+}
+
+int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                     int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
+                                     long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
+                                     long long strideZ, int *info, double *seconds) {
+  return window_host_entry(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
+                           zcap, strideZ, info, seconds);
+}
+
+int ek_hip_debug_window_batched_chunk(int problems) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int before = batched::g_wchunk;
+  batched::g_wchunk = problems > 0 ? problems : batched::kWindowChunk;
+  return before;
 }
 
 int ek_hip_debug_vbatched_streams(int streams) {

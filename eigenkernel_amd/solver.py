@@ -194,6 +194,13 @@ def load_library(path=None):
         "ek_hip_sygv_xbatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
                                          c_ll, _ip, _dp]),
         "ek_hip_debug_xbatched_chunk": (c_int, [c_int]),
+        "ek_hip_eigenpairs_window_batched_device": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int,
+                                                            vp, c_int, c_ll, vp, c_int, c_ll, _ip, vp, vp, c_int, c_int,
+                                                            c_ll, _ip, _dp]),
+        "ek_hip_eigenpairs_window_batched": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, _dp,
+                                                     c_int, c_ll, _dp, c_int, c_ll, _ip, _dp, _dp, c_int, c_int, c_ll,
+                                                     _ip, _dp]),
+        "ek_hip_debug_window_batched_chunk": (c_int, [c_int]),
         "ek_hip_check_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
                                                  c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
@@ -286,6 +293,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_stage_leaves256", "ek_hip_debug_set_sygst_direct", "ek_hip_debug_sygst_scratch",
     "ek_hip_solve_sparse", "ek_hip_check_sparse_device", "ek_hip_check_sparse", "ek_hip_sparse_to_dense",
     "ek_hip_debug_sparse_check_workspace_bytes", "ek_hip_debug_sparse_csr",
+    "ek_hip_eigenpairs_window_batched_device", "ek_hip_eigenpairs_window_batched", "ek_hip_debug_window_batched_chunk",
 )
 
 
@@ -888,6 +896,58 @@ def eigenpairs_batched(A, B=None, vectors=True, seconds=None):
     are not modified.  seconds: None or a float64 array of one entry that receives the device time.  Raises SolverError
     only when the call itself fails (illegal argument, HIP error), never for a problem's info."""
     return _batched_call("ek_hip_eigenpairs_batched", 0 if B is None else 1, A, B, vectors, seconds)
+
+
+def eigenpairs_window_batched(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, zcap=None, seconds=None):
+    """A window of eigenpairs of every problem of a batch (ek_hip_eigenpairs_window_batched; _batched_call's conventions):
+    A (and B, SPD) of shape (batch, n, n), n <= BATCH_NMAX.  By index: il..iu (1-based; defaults 1 and n).  By value: vl
+    and / or vu given -> the eigenvalues in (vl, vu] (a missing bound is -inf / +inf).  zcap: columns of Z per problem
+    (default: iu - il + 1 by index, n by value).  Returns (w, Z or None, m, info): m[b] the number of pairs of problem b,
+    w[b, :m[b]] its values ascending, Z[b][:, k] the vector of w[b, k] (B-orthonormal with B) for k < m[b]; what lies
+    behind m[b] is zero.  info[b]: 0; k > 0 B[b] not SPD at pivot k; -5 NaN / Inf in A[b]; -20 more than zcap values in
+    the window (m[b] is their number, nothing else of the problem is returned); 100000 + n + 1, 200000 + k: see
+    include/ek_hip.h.  A and B are not modified.  Raises SolverError only when the call itself fails."""
+    lib = load_library()
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("A must have shape (batch, n, n)")
+    batch, n = A.shape[0], A.shape[1]
+    by_value = vl is not None or vu is not None
+    if by_value and (il is not None or iu is not None):
+        raise ValueError("give either il / iu or vl / vu")
+    vl = -np.inf if vl is None else float(vl)
+    vu = np.inf if vu is None else float(vu)
+    il = 1 if il is None else int(il)
+    iu = n if iu is None else int(iu)
+    if zcap is None:
+        zcap = n if by_value else max(iu - il + 1, 0)
+    zcap = int(zcap)
+    At = np.ascontiguousarray(A.transpose(0, 2, 1))
+    Bt = None
+    if B is not None:
+        B = np.asarray(B, dtype=np.float64)
+        if B.shape != A.shape:
+            raise ValueError("B must have the shape of A")
+        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
+    w = np.zeros((batch, n))
+    zc = max(zcap, 1)
+    Zt = np.zeros((batch, zc, max(n, 1))) if vectors else None
+    m = np.zeros(max(batch, 1), dtype=np.int32)
+    info = np.zeros(max(batch, 1), dtype=np.int32)
+    rc = lib.ek_hip_eigenpairs_window_batched(0 if B is None else 1, 1 if vectors else 0, 1 if by_value else 0, n, batch,
+                                              vl, vu, il, iu, _P(At), max(n, 1), max(n * n, 1),
+                                              _P(Bt) if Bt is not None else None, max(n, 1), max(n * n, 1), _I(m), _P(w),
+                                              _P(Zt) if vectors else None, max(n, 1), zcap, zc * max(n, 1), _I(info),
+                                              _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError("ek_hip_eigenpairs_window_batched failed", rc)
+    return w, (Zt.transpose(0, 2, 1)[:, :n, :zcap] if vectors else None), m[:batch], info[:batch]
+
+
+def window_batched_chunk(problems):
+    """Problems per launch of eigenpairs_window_batched (ek_hip_debug_window_batched_chunk): 0 restores the default.
+    Returns the previous value.  No result depends on it."""
+    return int(load_library().ek_hip_debug_window_batched_chunk(int(problems)))
 
 
 XBATCH_NMAX = 256   # EK_HIP_XBATCH_NMAX

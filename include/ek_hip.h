@@ -252,6 +252,65 @@ int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const dou
                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                               long long strideZ, int *info, double *seconds);
 
+/* A WINDOW of eigenpairs of every problem of a batch (RANGE 'I' / 'V', as rocSOLVER's syevdx_strided_batched has it): one
+ * order 0 <= n <= EK_HIP_BATCH_NMAX and one window for the whole batch, a workgroup per problem from first load to last
+ * store.  The reduction is that of ek_hip_eigenpairs_batched*; the implicit QL is replaced by Sturm bisection of the wanted
+ * values and inverse iteration (DSTEIN's scheme) for their vectors, and only the window's columns are back-transformed: no
+ * full spectrum is computed anywhere.  NOT COLLECTIVE; the call synchronises.  23 arguments:
+ *   problem, jobz, dA .. strideB, seconds : exactly as ek_hip_eigenpairs_batched* (a stride of 0 is an argument error; B
+ *                   is not looked at for problem 0; lower triangles only)
+ *   range         : 0 'I': the indices il .. iu, 1-based, 1 <= il <= iu <= n; vl, vu not referenced
+ *                   1 'V': the eigenvalues in the half-open (vl, vu], vl < vu, -Inf / +Inf legal; il, iu not referenced.
+ *                   They are counted on the tridiagonal by Sturm counts, the bounds scaled by the exact power of two by
+ *                   which the kernel scaled the problem (ek_hip_stebz_range's rule)
+ *   m             : out: HOST array of batch ints: the number of pairs problem b returns -- iu - il + 1 for every
+ *                   successful problem under 'I', the count under 'V' (it differs from problem to problem; 0 is
+ *                   success).  A failed problem gets 0, except under info[b] = -20
+ *   dw            : out: batch x n doubles; problem b's m[b] values ascending at dw + b * n, the rest of the row is not
+ *                   written
+ *   dZ, ldz, zcap, strideZ : out (jobz = 1): problem b's vectors are columns 0 .. m[b] - 1 of the n x zcap array at
+ *                   dZ + b * strideZ, ldz >= max(1, n), strideZ >= ldz * max(1, zcap); the columns from m[b] on are
+ *                   not written.  Orthonormal, B-orthonormal for problem 1.  'I' needs zcap >= iu - il + 1.  'V' with
+ *                   m[b] > zcap: info[b] = -20, m[b] is the count, and nothing of that problem's w or Z is written; the
+ *                   other problems are unaffected.  dZ, ldz and strideZ are not referenced when jobz = 0; zcap is
+ *                   checked all the same
+ *   info          : out: HOST array of batch ints: 0, always with finite w; k > 0 the failing pivot of B and -5 NaN / Inf
+ *                   in A's lower triangle, as ek_hip_eigenpairs_batched*; -20 as above; 100000 + n + 1: the reduction
+ *                   left a non-finite tridiagonal, or an eigenvalue lies beyond a double; 200000 + k: inverse iteration
+ *                   did not converge for the eigenvalue of global index k (5 iterations to meet DSTEIN's growth test,
+ *                   then 2 more).  A failed problem writes only its own slots
+ * Return value: 0, or -k for argument k of the prototype, decided before any device work without dereferencing a data
+ * pointer, the first offending argument deciding: -1 problem, -2 jobz, -3 range, -4 n, -5 batch (n = 0 or batch = 0:
+ * success, nothing further looked at); -6 vl NaN, -7 vu NaN or vl >= vu ('V' only); -8 il, -9 iu ('I' only); -10 .. -12 A;
+ * -13 .. -15 B (problem 1 only); -16 m; -17 w; -18 Z, -19 ldz and -21 strideZ (jobz = 1 only); -20 zcap < 0 or 'I' with
+ * zcap < iu - il + 1; -22 info; <= -1000 HIP runtime error.
+ * In place (device form): dA[b] <- DSYTD2's lower layout and dB[b] <- L, bit for bit what
+ * ek_hip_eigenpairs_batched_device leaves for the same pair (the stages in front of QL are the same arithmetic); strictly
+ * upper triangles, rows n .. ld - 1 and the gaps between the problems are neither read nor written.  The host form leaves
+ * A and B untouched, and of w and Z everything the device form does not write.
+ * Same bits: the value of index k depends on (n, A, B, k) alone -- not on il / iu, range, jobz, zcap, the batch, the
+ * position or the form: every index makes the same bisection passes over one grid that the tridiagonal fixes.  A
+ * vector's bits may depend on the window, because its cluster mates inside the window do, and on nothing else.  Values
+ * agree with ek_hip_eigenpairs_batched*'s to the bound, not to the bit (bisection here, QL there).
+ * A batch runs in chunks of at most K problems, launched one after the other on one stream: K = 1024, or as many slots
+ * (below) as fit 256 MiB where that is fewer, in multiples of 256 and at least 512.
+ * Workspace (device memory, grown on demand, kept until ek_hip_finalize): 2 batch ints, and for jobz = 1 the LU factors
+ * of inverse iteration, min(batch, K) slots of 5 n c doubles, c = iu - il + 1 ('I') or min(zcap, n) ('V'): 655 360 bytes
+ * a slot at n = c = 128 (K = 512, 336 MB at most), 81 920 bytes for a window of 16 (K = 1024, 84 MB).  Under 'V' give the
+ * zcap that is needed: c follows it.
+ * Where it is slow: the vectors of a cluster (gaps <= 1e-3 |T|_1) are formed one after the other, a round each.  A fully
+ * clustered problem with all pairs wanted (A = c I at order 128: 128 rounds) costs 16 times the full call of
+ * ek_hip_eigenpairs_batched* (two clusters of 64: 5 times), which is then the call to use. */
+int ek_hip_eigenpairs_window_batched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
+                                            int il, int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                            long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                            long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout */
+int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                     int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
+                                     long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
+                                     long long strideZ, int *info, double *seconds);
+
 /* The same call for orders up to EK_HIP_XBATCH_NMAX ("xbatched").  Argument for argument these are
  * ek_hip_eigenpairs_batched_device / ek_hip_eigenpairs_batched -- 16 arguments, the same argument-error codes decided
  * before any device work and without dereferencing a pointer, the first offending argument deciding -- with one

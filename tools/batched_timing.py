@@ -34,6 +34,11 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  above 128) behind the type's own solve
   python tools/batched_timing.py --once 64g --once-batch 1024 --check
                                                  one solve and one check after a warm-up of each
+  python tools/batched_timing.py --window 0.125,1 [--sizes 64,128] [--batches 512,1024]
+                                                 a window of that fraction of n (ek_hip_eigenpairs_window_batched_device)
+                                                 by index and by value, with and without vectors, against the existing
+                                                 call, the kinds alternated; then a fully clustered standard batch
+                                                 (all_equal, two_clusters of tests/batched_cases.py) both ways
 
 Per (problem, jobz, n, batch): one warm-up of each kind, then three rounds that alternate the kinds, best by wall clock
 (both calls synchronise; both work in place, so the inputs are restored outside the clock).  The loop is timed over
@@ -106,6 +111,23 @@ class Case:
         t = time.perf_counter() - t0
         assert rc == 0 and not self.info.any(), (rc, self.info[self.info != 0][:4])
         return t, sec.value
+
+    def window(self, problem, jobz, il=None, iu=None, vl=None, vu=None):
+        """ek_hip_eigenpairs_window_batched_device by index (il, iu) or by value (vl, vu): wall, device, m."""
+        n, nn = self.n, self.n * self.n
+        self.restore()
+        sec = ctypes.c_double(0.0)
+        m = np.zeros(self.batch, dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        by_value = vl is not None
+        t0 = time.perf_counter()
+        rc = self.lib.ek_hip_eigenpairs_window_batched_device(
+            problem, jobz, 1 if by_value else 0, n, self.batch, vl if by_value else 0.0, vu if by_value else 0.0,
+            il or 0, iu or 0, self.dA, n, nn, self.dB if problem else None, n, nn, m.ctypes.data_as(ip), self.dw,
+            self.dZ if jobz else None, n, n, nn, self.info.ctypes.data_as(ip), ctypes.byref(sec))
+        t = time.perf_counter() - t0
+        assert rc == 0 and not self.info.any(), (rc, self.info[self.info != 0][:4])
+        return t, sec.value, m
 
     def check(self, problem):
         """The batched check on what the last batched(problem, 1) left in dw and dZ: wall time, device time, out."""
@@ -353,6 +375,56 @@ def mixed_check(lib, batch, orders, by_order, groups, offsets, host, device, tab
     print("            all t_var wall ms: %s" % " ".join("%.3f" % (x[0] * 1e3) for x in tv))
 
 
+def window_rows(lib, sizes, batches, fractions):
+    """Device ms, best of 3, the kinds alternated: the existing call, and a window of each fraction of n by index and by
+    value (bounds at the window's ends in the first problem's spectrum, so that the count varies over the batch)."""
+    import scipy.linalg as sl
+    print("# problem     n batch fraction | full jobz=1  jobz=0 | window 'I' jobz=1 (ratio)  'V' jobz=1 (ratio, mean m)  "
+          "'I' jobz=0 (ratio to full jobz=0)")
+    for n in sizes:
+        for batch in batches:
+            c = Case(lib, n, batch)
+            A0 = c.hA[:n * n].reshape(n, n).T
+            B0 = c.hB[:n * n].reshape(n, n).T
+            for problem in (1, 0):
+                w0 = sl.eigh(A0, B0, eigvals_only=True) if problem else sl.eigh(A0, eigvals_only=True)
+                for f in fractions:
+                    m = max(1, int(round(f * n)))
+                    vl, vu = -np.inf, (0.5 * (w0[m - 1] + w0[m]) if m < n else np.inf)
+                    kinds = {"f1": lambda: c.batched(problem, 1)[1], "f0": lambda: c.batched(problem, 0)[1],
+                             "i1": lambda: c.window(problem, 1, il=1, iu=m)[1],
+                             "v1": lambda: c.window(problem, 1, vl=vl, vu=vu)[1],
+                             "i0": lambda: c.window(problem, 0, il=1, iu=m)[1]}
+                    best = {}
+                    for rep in range(4):            # the first round warms up
+                        for k, fn in kinds.items():
+                            t = fn()
+                            if rep:
+                                best[k] = min(best.get(k, np.inf), t)
+                    mv = c.window(problem, 1, vl=vl, vu=vu)[2].mean()
+                    print("  %7d %5d %5d %8.3f | %11.3f %7.3f | %17.3f (%.3f) %11.3f (%.3f, %.1f) %11.3f (%.3f)"
+                          % (problem, n, batch, f, best["f1"] * 1e3, best["f0"] * 1e3, best["i1"] * 1e3,
+                             best["i1"] / best["f1"], best["v1"] * 1e3, best["v1"] / best["f1"], mv, best["i0"] * 1e3,
+                             best["i0"] / best["f0"]), flush=True)
+            c.close()
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import batched_cases as bc
+    print("# fully clustered standard batches, every pair wanted: full jobz=1 ms | window 1..n jobz=1 ms (ratio)")
+    for n in sizes:
+        for name in ("all_equal", "two_clusters"):
+            c = Case(lib, n, batches[0])
+            c.hA = np.ascontiguousarray(np.tile(bc.make(name, n).A.T, (batches[0], 1, 1))).ravel()
+            best = {}
+            for rep in range(4):
+                for k, fn in (("f1", lambda: c.batched(0, 1)[1]), ("i1", lambda: c.window(0, 1, il=1, iu=n)[1])):
+                    t = fn()
+                    if rep:
+                        best[k] = min(best.get(k, np.inf), t)
+            print("  %-14s n=%d batch=%d | %9.3f | %9.3f (%.3f)"
+                  % (name, n, batches[0], best["f1"] * 1e3, best["i1"] * 1e3, best["i1"] / best["f1"]), flush=True)
+            c.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="30,64,128")
@@ -369,9 +441,16 @@ def main():
                     "(an upper order above 128: ek_hip_eigenpairs_xvbatched_device)")
     ap.add_argument("--mixed-batch", type=int, default=2048)
     ap.add_argument("--mixed-orders", default="8,128", help="lo,hi of the uniformly drawn orders")
+    ap.add_argument("--window", default=None, help="fractions of n, e.g. 0.125,1: the window call by index and by value "
+                    "against the existing call, then fully clustered batches")
     args = ap.parse_args()
     lib = solver.load_library()
     assert lib.ek_hip_init(0) == 0
+    if args.window:
+        window_rows(lib, [int(x) for x in args.sizes.split(",")], [int(x) for x in args.batches.split(",")],
+                    [float(x) for x in args.window.split(",")])
+        lib.ek_hip_finalize()
+        return
     if args.mixed:
         lo, hi = (int(x) for x in args.mixed_orders.split(","))
         mixed(lib, args.mixed_batch, lo, hi, check=args.check)
