@@ -253,6 +253,9 @@ size_t sy2sb_work_bytes(int n);
 // s2: second stream, the panel factorisation of the next panel runs on it beside the trailing update.
 void sy2sb_lower(hipStream_t s, hipStream_t s2, int n, double *A, int lda, double *Vall, int ldv, double *tau1,
                  int *d_flag, void *work);
+// the stage tests' override of EK_SY2SB_PAIR_MIN / EK_SY2SB_LOOKAHEAD_MIN on one GPU: each < 0 as the switch says (the
+// default), >= 0 that many rows; 0 is "never" for both
+void sy2sb_set_flow(int pair_min, int lookahead_min);
 
 // Team form (1 x P, 128-wide column strips, strip S on rank S mod P): a member passes its copy of the matrix, of which
 // only the columns of its own strips need to be valid (and only they are kept current); V, tau1 come out complete and

@@ -208,10 +208,13 @@ int ek_hip_profile_symv_get(double *seconds, long long *launches, double *algori
 // ---- two-stage tridiagonalisation, piece by piece on host arrays (tests and tools; declared in
 // include/ek_hip_debug.h).  Stage 1: A (n x n, lower) -> band (in A) + explicit reflectors V (n x n)
 // + tau; *flag = 0, or the reason the CholeskyQR2 panel factorisation gave up.
-int ek_hip_debug_sy2sb(int n, double *A, int lda, double *V, int ldv, double *tau, int *flag) {
-  if (n < 1) return -1;
-  if (!A || lda < n) return -3;
-  if (!V || ldv < n) return -5;
+// (poison: the stage's own workspace holds a NaN with a payload before the stage -- what the stage reads of it before
+// writing it comes out as NaN)
+__global__ void fill_words_kernel(unsigned long long *p, size_t count, unsigned long long word) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) p[i] = word;
+}
+
+static int sy2sb_on_host_arrays(int n, double *A, int lda, double *V, int ldv, double *tau, int poison, int *flag) {
   int rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
   hipStream_t s = g_ctx.stream;
@@ -229,6 +232,8 @@ int ek_hip_debug_sy2sb(int n, double *A, int lda, double *V, int ldv, double *ta
   EK_HIP_CHECK(hipMemsetAsync(dt, 0, (size_t)ld * 8, s));
   EK_HIP_CHECK(hipMemsetAsync(g_ctx.d_info, 0, 4 * sizeof(int), s));
   rc = h2d_matrix(n, n, A, lda, dA, ld, s); if (rc) return rc;
+  if (poison && wb >= 8)
+    hipLaunchKernelGGL(fill_words_kernel, dim3(256), dim3(256), 0, s, (unsigned long long *)work, wb / 8, 0x7FF8DEADBEEF1234ull);
   sy2sb_lower(s, g_ctx.stream2, n, dA, ld, dV, ld, dt, g_ctx.d_info + 2, work);
   EK_HIP_CHECK(hipGetLastError());
   rc = d2h_matrix(n, n, dA, ld, A, lda, s); if (rc) return rc;
@@ -240,6 +245,30 @@ int ek_hip_debug_sy2sb(int n, double *A, int lda, double *V, int ldv, double *ta
   if (flag) *flag = f;
   return 0;
 }
+
+int ek_hip_debug_sy2sb(int n, double *A, int lda, double *V, int ldv, double *tau, int *flag) {
+  if (n < 1) return -1;
+  if (!A || lda < n) return -3;
+  if (!V || ldv < n) return -5;
+  return sy2sb_on_host_arrays(n, A, lda, V, ldv, tau, 0, flag);
+}
+
+// The same stage for its stage tests: poison != 0 fills the stage's workspace (sy2sb_work_bytes(n)) with the NaN
+// 0x7FF8DEADBEEF1234 first.  -k for an illegal k-th argument, before any device work.
+int ek_hip_debug_sy2sb_stage(int n, double *A, int lda, double *V, int ldv, double *tau, int poison, int *flag) {
+  if (n < 1) return -1;
+  if (!A) return -2;
+  if (lda < n) return -3;
+  if (!V) return -4;
+  if (ldv < n) return -5;
+  if (!tau) return -6;
+  if (!flag) return -8;
+  return sy2sb_on_host_arrays(n, A, lda, V, ldv, tau, poison, flag);
+}
+
+// pair_min / lookahead_min of sy2sb_lower on one GPU: each < 0 as its switch says (the default), >= 0 that many rows
+// (0: never).  The team form keeps its own (ek_hip_debug_sy2sb_team_profile).
+int ek_hip_debug_set_sy2sb_flow(int pair_min, int lookahead_min) { sy2sb_set_flow(pair_min, lookahead_min); return 0; }
 
 // Stage 2: the lower band (half bandwidth 64) of A -> d, e; Z (n x ncols, may be null) <- Q2 Z.
 __global__ void band_to_matrix_kernel(int n, const double *__restrict__ AB, double *__restrict__ A, int lda) {

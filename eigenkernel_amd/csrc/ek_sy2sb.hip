@@ -11,14 +11,14 @@
 //
 // Per panel p (columns c0 = 64 p .. c0+63, rows r0 = c0+64 .. n-1, m = n - r0):
 //   1. panel factorisation  P = A(r0:n, c0:c0+64) = Q R  with Q = I - V T V^T:
-//        m > 192 : CholeskyQR2 (two Gram + triangular-solve passes: everything is a tall-skinny
+//        m >= 128: CholeskyQR2 (two Gram + triangular-solve passes: everything is a tall-skinny
 //                  GEMM) followed by Householder reconstruction (Ballard et al. 2014: an LU of the
 //                  top 64x64 block of Q - S without pivoting gives V, T and the signs S), checked on
 //                  the device (Cholesky pivots, ||Q1^T Q1 - I||): a panel CholeskyQR2 cannot handle
 //                  (rank deficient / cond > 1e7) sets THAT PANEL's flag and is factored by Householder
 //                  reflections inside the stage (house_tall_kernel and its companions: the per-panel rescue);
 //                  bits 8.. of *d_flag count the panels that took it, the low byte stays 0;
-//        m <= 192: Householder QR of the panel inside one workgroup's LDS (handles any rank).
+//        m <= 127: Householder QR of the panel inside one workgroup's LDS (handles any rank; SMALL_MAX below).
 //   2. Y = A22 V            (SYMM on the lower triangle, split-K partial sums)
 //   3. W = Y T - 1/2 V (T^T V^T Y T)
 //   4. A22 -= W V^T + V W^T (one GEMM with K = 128 on the image [W | V | W])
@@ -28,6 +28,7 @@
 #include "ek_switch.h"
 
 #include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <vector>
 
@@ -463,7 +464,8 @@ __global__ __launch_bounds__(256, 2) void hr_kernel(HrArgs p) {
 }
 
 // ---------------------------------------------------------------- panel with few rows: Householder
-// QR inside one workgroup (any rank, any m <= 256).  Same outputs as the CholeskyQR2 chain.
+// QR inside one workgroup (any rank, any m <= SMALL_MAX = 127: the LDS image has SMALL_ROWS = 128 rows).  Same outputs as
+// the CholeskyQR2 chain.
 struct SmallArgs {
   int m;
   double *Apanel; int lda; double *Vall; int ldv; double *Vd1, *Vd2; int ldi;
@@ -1417,10 +1419,13 @@ struct DistProf {
 };
 DistProf g_dprof;
 int g_dist_la_min = -1;            // rows from which the team form looks ahead (0: never); -1: environment / default
+// one GPU, ek_hip_debug_set_sy2sb_flow (the stage tests): < 0 as the switches say; pair_min 0: no pairs, la_min 0: no look-ahead
+int g_flow_pair_min = -1, g_flow_la_min = -1;
 
 }  // namespace
 
 size_t sy2sb_work_bytes(int n) { return Layout(n).total; }
+void sy2sb_set_flow(int pair_min, int lookahead_min) { g_flow_pair_min = pair_min; g_flow_la_min = lookahead_min; }
 
 // Two panels per trailing update (round 5).  The rank-128 update of the trailing matrix reads and writes 16 bytes of it per
 // 128 flops and runs at 37 TFLOP/s; with K = 256 the same kernel does 55 (tools/gemm_shapes.py).  So panels go in PAIRS
@@ -1468,11 +1473,12 @@ void sy2sb_lower(hipStream_t s, hipStream_t s2, int n, double *A, int lda, doubl
   // of the look-ahead finds room beside it), above the plain 8-wave GEMM (two per CU, 33 against 27 - 32 TFLOP/s
   // alone; the chain is short against the update there).  N = 16384: 0.2025 -> 0.1949 s, N = 32768: 1.364 -> 1.278 s.
   constexpr int staged_max = 8192;
-  const int la_min = switch_int(kSwLookaheadMin);
+  // (the hook's 0 is "never": m >= 0 would look ahead on every panel)
+  const int la_min = g_flow_la_min < 0 ? switch_int(kSwLookaheadMin) : (g_flow_la_min == 0 ? INT_MAX : g_flow_la_min);
   constexpr int small_max = 4096;  // (N = 4096: stage 14.6 -> 13.9 ms)
   // rows of the first panel's trailing matrix from which panels go in pairs (0: never; read per call: the tests force
   // pairs at small orders)
-  const int pair_min = switch_int(kSwPairMin);
+  const int pair_min = g_flow_pair_min < 0 ? switch_int(kSwPairMin) : g_flow_pair_min;
 
   int *nzrows = (int *)(sm + 13 * 4096);               // one word per panel (room for 8192)
   (void)hipMemsetAsync(nzrows, 0, (size_t)ceil_div(n, SB) * sizeof(int), s);

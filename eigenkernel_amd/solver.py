@@ -116,6 +116,8 @@ def load_library(path=None):
         "ek_hip_debug_reduce_team": (c_int, [c_int, c_int, c_int, _dp]),
         "ek_hip_profile_symv_get": (c_int, [_dp, ctypes.POINTER(ctypes.c_longlong), _dp]),
         "ek_hip_debug_sy2sb": (c_int, [c_int, _dp, c_int, _dp, c_int, _dp, _ip]),
+        "ek_hip_debug_sy2sb_stage": (c_int, [c_int, _dp, c_int, _dp, c_int, _dp, c_int, _ip]),
+        "ek_hip_debug_set_sy2sb_flow": (c_int, [c_int, c_int]),
         "ek_hip_debug_sb2st": (c_int, [c_int, _dp, c_int, _dp, _dp, _dp, c_int, c_int, _ip]),
         "ek_hip_debug_sb2st_stage": (c_int, [c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, c_int, _dp, c_int, _dp, c_int,
                                              c_int, _ip, _ip]),
@@ -265,7 +267,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_potrf_team", "ek_hip_debug_reduce_team", "ek_hip_comm_attach_host",
     "ek_hip_debug_set_sytrd_maxcols", "ek_hip_debug_sytrd_work_bytes", "ek_hip_debug_sytrd_at", "ek_hip_debug_sytrd_split", "ek_hip_debug_gemm_at",
     "ek_hip_debug_gemm_desc", "ek_hip_debug_gemm_plan", "ek_hip_debug_gemm_compact_map",
-    "ek_hip_debug_sy2sb", "ek_hip_debug_sb2st", "ek_hip_debug_sb2st_stage", "ek_hip_debug_two_stage_timing", "ek_hip_debug_set_two_stage",
+    "ek_hip_debug_sy2sb", "ek_hip_debug_sy2sb_stage", "ek_hip_debug_set_sy2sb_flow", "ek_hip_debug_sb2st", "ek_hip_debug_sb2st_stage", "ek_hip_debug_two_stage_timing", "ek_hip_debug_set_two_stage",
     "ek_hip_profile_kernels", "ek_hip_profile_kernels_get", "ek_hip_debug_last_solve_stats",
     "ek_hip_debug_sy2sb_team", "ek_hip_debug_sy2sb_team_timing", "ek_hip_debug_sy2sb_team_profile", "ek_hip_debug_workspace_bytes", "ek_hip_debug_fail_next_chase", "ek_hip_debug_last_pipe_stats",
     "ek_hip_debug_stedc_team", "ek_hip_debug_stedc_team_get", "ek_hip_debug_stedc",
@@ -1284,6 +1286,27 @@ def sy2sb(A):
     if rc:
         raise RuntimeError("ek_hip_debug_sy2sb info=%d" % rc)
     return A, V, tau[:n], flag.value
+
+
+def sy2sb_stage(A, poison=False):
+    """sy2sb through ek_hip_debug_sy2sb_stage; poison: the stage's workspace holds the NaN 0x7FF8DEADBEEF1234 on entry, so
+    anything the stage reads of it before writing it shows in the output.  Returns (A_out, V, tau, flag)."""
+    lib = load_library()
+    A = np.array(_farr(A), order="F", copy=True)
+    n = A.shape[0]
+    V = np.zeros((n, n), order="F"); tau = np.zeros(max(n, 1)); flag = ctypes.c_int(-1)
+    rc = lib.ek_hip_debug_sy2sb_stage(n, _P(A), max(1, n), _P(V), max(1, n), _P(tau), 1 if poison else 0, ctypes.byref(flag))
+    if rc:
+        raise RuntimeError("ek_hip_debug_sy2sb_stage info=%d" % rc)
+    return A, V, tau[:n], flag.value
+
+
+def set_sy2sb_flow(pair_min=-1, lookahead_min=-1):
+    """Rows of a trailing matrix from which sy2sb takes its panels in pairs / factors the next panel beside the update: each
+    < 0 as its switch says (the default), 0 never.  Holds until set back: callers restore (-1, -1) in try / finally."""
+    rc = load_library().ek_hip_debug_set_sy2sb_flow(int(pair_min), int(lookahead_min))
+    if rc:
+        raise RuntimeError("ek_hip_debug_set_sy2sb_flow info=%d" % rc)
 
 
 def sy2sb_team(A, nteam):

@@ -79,6 +79,17 @@ int ek_hip_debug_sy2sb(int n, double *A, int lda, double *V, int ldv, double *ta
 int ek_hip_debug_sb2st(int n, const double *A, int lda, double *d, double *e, double *Z, int ldz, int ncols, int *flag);
 int ek_hip_debug_two_stage_timing(int n, int ncols, int reps, double *seconds, int *flag);
 int ek_hip_debug_set_two_stage(int min_order);
+/*   _sy2sb_stage : _sy2sb for the stage tests.  poison != 0: the stage's own workspace is filled with the NaN
+ *            0x7FF8DEADBEEF1234 before the stage, so that whatever the stage reads of it before writing it shows in the
+ *            output.  All of A, V, tau and flag are required.  Returns 0, -k for an illegal k-th argument (before any
+ *            device work), or <= -1000.
+ *   _set_sy2sb_flow : the rows of a trailing matrix from which the panels of _sy2sb go in pairs (pair_min) and from which
+ *            the next panel is factored on the second stream beside the update (lookahead_min), on one GPU: each < 0 as
+ *            its switch says (EK_SY2SB_PAIR_MIN, EK_SY2SB_LOOKAHEAD_MIN; the default), 0 never, > 0 that many rows.  Holds
+ *            for every later call of the process, whole-path solves included, until it is set back to (-1, -1).
+ *            Returns 0. */
+int ek_hip_debug_sy2sb_stage(int n, double *A, int lda, double *V, int ldv, double *tau, int poison, int *flag);
+int ek_hip_debug_set_sy2sb_flow(int pair_min, int lookahead_min);
 /*   _sb2st_stage : _sb2st with what the stage leaves behind, in either workspace form.  form 0: the layout of _sb2st;
  *            form 1: what a whole-path solve does (the band packed by the caller into the stage's workspace without
  *            records, the records of Q2 lent as a separate array).  chase_mode 0: default, 1: sweeps through memory, 2:

@@ -40,8 +40,8 @@ def _random_band(n, seed):
 
 @pytest.mark.parametrize("n", [3, 64, 65, 66, 130, 200, 257, 258, 321, 449, 700, 1000])
 def test_dense_to_band_is_an_orthogonal_similarity(hip, oracle, n):
-    """Panels with > 192 rows go through CholeskyQR2 + Householder reconstruction, the last ones through
-    the in-LDS Householder QR: both must give A = Q1 Bd Q1^T with Q1 orthogonal to rounding."""
+    """Panels with >= 128 rows go through CholeskyQR2 + Householder reconstruction, the last ones (<= 127 rows)
+    through the in-LDS Householder QR: both must give A = Q1 Bd Q1^T with Q1 orthogonal to rounding."""
     A = oracle.synth_matrix(n, 1)
     Ab, V, tau, flag = hip.sy2sb(A)
     assert flag == 0
