@@ -82,6 +82,15 @@ int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int 
 int xvbatched_prepare(int count);  // its images (min(count, K) slots), to be called before the call's first event
 int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count, const batched::Desc *table,
                      int *dinfo);
+// ek_hip_eigenpairs_window_xbatched* above EK_HIP_BATCH_NMAX: the images of `slots` workgroups (before the call's first
+// event), then one chunk of count <= slots problems on s.  The pointers are the chunk's; dm, dinfo: a word per problem of
+// it; lu: a slot of 5 n wcols doubles per workgroup (jobz = 1).  The host driver (counts, chunks, LU slots) is
+// ek_batched.hip's
+int xwindow_prepare(int slots);
+int xwindow_launch(hipStream_t s, int problem, int jobz, int n, int count, double *dA, int lda, long long strideA,
+                   double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
+                   int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm, double *lu,
+                   int wcols);
 void release_batched_check();     // every batched check's scratch, output words, table and events (ek_batched_check.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);
 

@@ -641,6 +641,12 @@ static int ensure_info(size_t batch) {
 constexpr int kWindowChunk = 1024;
 constexpr size_t kWindowBytes = (size_t)256 << 20;
 static int g_wchunk = kWindowChunk;
+// ek_hip_eigenpairs_window_xbatched* above EK_HIP_BATCH_NMAX: ek_batched_x.hip's class keeps two workgroups on a compute
+// unit, 512 on the device, and a slot of LU is up to 2.6 MB (n = c = 256): 1024 problems a launch, or as many slots as fit
+// 1 GiB where that is fewer, in whole rounds of 512 and never under one round (ek_hip_debug_window_xbatched_chunk)
+constexpr int kXWindowChunk = 1024, kXWindowRound = 512;
+constexpr size_t kXWindowBytes = (size_t)1 << 30;
+static int g_xwchunk = kXWindowChunk;
 static int *g_dm = nullptr;
 static size_t g_dm_count = 0;
 static double *g_wws = nullptr;
@@ -962,12 +968,12 @@ static int batched_host_entry(int problem, int itype, int jobz, int n, int batch
 static int window_check(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
                         const void *A, int lda, long long strideA, const void *B, int ldb, long long strideB,
                         const int *m, const void *w, const void *Z, int ldz, int zcap, long long strideZ,
-                        const int *info, bool *nothing) {
+                        const int *info, bool *nothing, int nmax) {
   *nothing = false;
   if (problem != 0 && problem != 1) return -1;
   if (jobz != 0 && jobz != 1) return -2;
   if (range != 0 && range != 1) return -3;
-  if (n < 0 || n > EK_HIP_BATCH_NMAX) return -4;
+  if (n < 0 || n > nmax) return -4;
   if (batch < 0) return -5;
   if (n == 0 || batch == 0) { *nothing = true; return 0; }
   if (range == 1) {
@@ -1009,9 +1015,13 @@ static int window_device_locked(int problem, int jobz, int range, int n, int bat
   // wide slots: fewer problems per launch, so that the workspace stays near kWindowBytes -- in whole rounds of 256
   // workgroups (class 128 runs one per compute unit: a chunk of 409 would be three rounds for 512 problems), two at least
   const int fit = (int)std::min<size_t>(kWindowBytes / std::max(slot, (size_t)1), (size_t)g_wchunk);
-  const int K = std::min(g_wchunk, std::max(512, fit / 256 * 256));
+  const bool x = n > EK_HIP_BATCH_NMAX;              // ek_batched_x.hip's class: its own chunk rule, and an image per slot
+  const int xfit = (int)std::min<size_t>(kXWindowBytes / std::max(slot, (size_t)1), (size_t)g_xwchunk);
+  const int K = x ? std::min(g_xwchunk, std::max(kXWindowRound, xfit / kXWindowRound * kXWindowRound))
+                  : std::min(g_wchunk, std::max(512, fit / 256 * 256));
   { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
   { int rc0 = ensure_window((size_t)batch, (size_t)std::min(batch, K) * slot); if (rc0) return rc0; }
+  if (x) { int rc0 = xwindow_prepare(std::min(batch, K)); if (rc0) return rc0; }
   EK_HIP_CHECK(hipMemsetAsync(g_dm, 0, (size_t)batch * sizeof(int), s));   // a problem that ends before stage 4W: m = 0
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (seconds) {
@@ -1023,6 +1033,13 @@ static int window_device_locked(int problem, int jobz, int range, int n, int bat
   int rc = 0;
   for (int c0 = 0; c0 < batch && !rc; c0 += K) {
     const int count = std::min(K, batch - c0);
+    if (x) {
+      rc = xwindow_launch(s, problem, jobz, n, count, dA + (long long)c0 * strideA, lda, strideA,
+                          problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
+                          jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, range, il, iu, zcap,
+                          vl, vu, g_dm + c0, g_wws, wcols);
+      continue;
+    }
     WArgs a{{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
              problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
              jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, 1},
@@ -1051,10 +1068,10 @@ static int window_device_locked(int problem, int jobz, int range, int n, int bat
 static int window_device_entry(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
                                double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
                                double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
-                               double *seconds) {
+                               double *seconds, int nmax = EK_HIP_BATCH_NMAX) {
   bool nothing;
   int rc = window_check(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw, dZ,
-                        ldz, zcap, strideZ, info, &nothing);
+                        ldz, zcap, strideZ, info, &nothing, nmax);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -1067,10 +1084,10 @@ static int window_device_entry(int problem, int jobz, int range, int n, int batc
 static int window_host_entry(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
                              const double *A, int lda, long long strideA, const double *B, int ldb, long long strideB,
                              int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
-                             double *seconds) {
+                             double *seconds, int nmax = EK_HIP_BATCH_NMAX) {
   bool nothing;
   int rc = window_check(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
-                        zcap, strideZ, info, &nothing);
+                        zcap, strideZ, info, &nothing, nmax);
   if (rc) return rc;
   if (seconds) *seconds = 0.0;
   if (nothing) return 0;
@@ -1331,6 +1348,30 @@ int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, in
                                      long long strideZ, int *info, double *seconds) {
   return window_host_entry(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
                            zcap, strideZ, info, seconds);
+}
+
+// The same for orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's window instantiation
+int ek_hip_eigenpairs_window_xbatched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
+                                             int il, int iu, double *dA, int lda, long long strideA, double *dB,
+                                             int ldb, long long strideB, int *m, double *dw, double *dZ, int ldz,
+                                             int zcap, long long strideZ, int *info, double *seconds) {
+  return window_device_entry(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+                             dZ, ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_eigenpairs_window_xbatched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                      int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
+                                      long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
+                                      long long strideZ, int *info, double *seconds) {
+  return window_host_entry(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
+                           zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_debug_window_xbatched_chunk(int problems) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int before = batched::g_xwchunk;
+  batched::g_xwchunk = problems > 0 ? problems : batched::kXWindowChunk;
+  return before;
 }
 
 int ek_hip_debug_window_batched_chunk(int problems) {

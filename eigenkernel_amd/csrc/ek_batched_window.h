@@ -1,6 +1,7 @@
-// ek_batched_window.h -- stage 4W of the batched kernel (ek_batched.hip, not installed): a window of
-// eigenpairs of the scaled tridiagonal (d, e) in LDS by Sturm bisection and inverse iteration, in place of the QL of
-// stage 4.  Called by the whole workgroup of ek_hip_eigenpairs_window_batched*'s instantiation and by no other.
+// ek_batched_window.h -- stage 4W of the batched kernels (ek_batched.hip, ek_batched_x.hip; not installed; DESIGN.md 30,
+// 32): a window of eigenpairs of the scaled tridiagonal (d, e) in LDS by Sturm bisection and inverse iteration, in place
+// of the QL of stage 4.  Called by the whole workgroup of the window instantiations (ek_hip_eigenpairs_window_batched*,
+// ek_hip_eigenpairs_window_xbatched*) and by no other.
 //
 //   count    Gershgorin interval, pivmin, tolerance and number of passes by ek_stebz.hip's rules; RANGE 'V' counts at
 //            vl and vu (every thread runs the two chains: the result is uniform without a broadcast)
@@ -21,6 +22,13 @@
 //            Where this is not DSTEIN: T is not split into its blocks, so |T|_1 in ortol and in the scaling of the
 //            right-hand side is the whole matrix's; that scaling uses eps = 2^-53 where DSTEIN has DLAMCH('P'); and a
 //            vector has 5 iterations to meet the growth test and then 2 more (DSTEIN: 5 in all).
+//
+// The image comes in two layouts (the LAY parameter of stage4w):
+//   ColumnsInLds   ek_batched.hip: the image in LDS, wanted vector j is column j, entry i at S[i + j LD]
+//   RowsInMemory   ek_batched_x.hip: the image in device memory, wanted vector j is ROW j, entry i at
+//                  S[j + i LD], so that the lanes of a wave that iterate consecutive vectors touch consecutive addresses
+//                  and stage 5 of that kernel finds Z^T where it wants it.  Its loops over a vector load eight entries
+//                  ahead of their use, and the two Gram-Schmidt passes have a thread map of their own (see there)
 #pragma once
 #include "ek_batched_stages.h"
 
@@ -33,6 +41,11 @@ using namespace bstages;
 constexpr int kLanes = 2, kPts = 4, kParts = kLanes * kPts;   // 3 bits per pass
 constexpr int kRefine = 18;                                   // further passes an eigenvalue small against |T| may take
 constexpr int kMaxIts = 5, kExtra = 2;                        // DSTEIN: 5 iterations to grow, then 2 more
+
+// where the wanted vectors live (see the head of this file)
+struct ColumnsInLds { typedef double elem; static constexpr bool rows = false; };
+struct RowsInMemory { typedef gdouble elem; static constexpr bool rows = true; };
+constexpr int kTree = 16;                           // RowsInMemory: members in front from which an update sums by a tree
 
 // what the window entries add to the batched kernel's arguments
 struct Window {
@@ -75,15 +88,113 @@ __device__ __forceinline__ double start_entry(int k, int i) {
   return (double)(int32_t)h * 0x1p-31;
 }
 
+// RowsInMemory: the vectors of round `round` (pos[j] == round, not finished) against the `round` finished members in
+// front of each, classical Gram-Schmidt twice, by the whole workgroup of 2 NC threads.  Vector j is row j of the image.
+//   dots     thread (r, sub) takes finished vector r and the round's vector of its cluster: the entries sub, sub + 2, ...
+//            in ascending order from 0.0; a product is half 0's sum plus half 1's.  The lanes of a wave are consecutive
+//            vectors: consecutive addresses, and one address for the mate of a cluster
+//   update   round < kTree: thread (r, sub) takes the round's vector r and every other entry of it; an entry's sum runs
+//            over the members in front in ascending order.  The lanes are vectors again: the many small clusters.
+//            round >= kTree: the round's vectors one after the other; a wave takes eight entries at a time, lane l the
+//            members l, l + 64, ... in front (consecutive addresses), in ascending order, and the 64 partial sums are
+//            added by a butterfly: the few large clusters, where one lane per vector would leave the workgroup idle.
+// Either way the order of a sum depends on the position in the cluster (round, member) and on n alone, not on where the
+// cluster lies in the window.  Starts with a barrier; the caller's barrier ends it.
+template <int NC, int NW>
+__device__ __forceinline__ void gram_schmidt_rows(gdouble *S, int n, int m, int round, const int *pos, const int *fin,
+                                                  double *sl) {
+  constexpr int LD = NC + 1;
+  const int t = threadIdx.x, r = t % NC, sub = t / NC;
+  for (int pass = 0; pass < 2; ++pass) {
+    __syncthreads();
+    if (r < m) {
+      const int j = r - pos[r] + round;
+      if (pos[r] < round && j < m && pos[j] == round && !fin[j]) {
+        const gdouble *xp = S + r, *xj = S + j;
+        double acc = 0.0;
+        for (int i0 = sub; i0 < n; i0 += 16) {
+          double pv[8], jv[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int i = min(i0 + 2 * q, n - 1);
+            pv[q] = xp[i * LD];
+            jv[q] = xj[i * LD];
+          }
+#pragma unroll
+          for (int q = 0; q < 8; ++q)
+            if (i0 + 2 * q < n) acc += pv[q] * jv[q];
+        }
+        sl[sub * NC + r] = acc;
+      }
+    }
+    __syncthreads();
+    if (round < kTree) {
+      if (r < m && pos[r] == round && !fin[r]) {
+        const gdouble *xq = S + (r - round);
+        const double *c0 = sl + (r - round), *c1 = c0 + NC;
+        for (int i = sub; i < n; i += 2) {
+          double acc = 0.0;
+          for (int q0 = 0; q0 < round; q0 += 8) {
+            double v8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v8[q] = xq[min(q0 + q, round - 1) + i * LD];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+              if (q0 + q < round) acc += (c0[q0 + q] + c1[q0 + q]) * v8[q];
+          }
+          S[r + i * LD] -= acc;
+        }
+      }
+    } else {
+      const int wv = t >> 6, ln = t & 63;
+      for (int j = 0; j < m; ++j) {
+        if (pos[j] != round || fin[j]) continue;    // uniform
+        const gdouble *xq = S + (j - round);
+        const double *c0 = sl + (j - round), *c1 = c0 + NC;
+        for (int ib = 0; ib < n; ib += 8 * NW) {    // entries ib + wv + NW q
+          double acc[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) acc[q] = 0.0;
+          for (int c = ln; c < round; c += 64) {
+            const double cf = c0[c] + c1[c];
+            double v8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v8[q] = xq[c + min(ib + wv + NW * q, n - 1) * LD];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc[q] += cf * v8[q];
+          }
+#pragma unroll
+          for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc[q] += __shfl_xor(acc[q], off, 64);
+          }
+          if (ln == 0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const int i = ib + wv + NW * q;
+              if (i < n) S[j + i * LD] -= acc[q];
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
 // Stage 4W.  In: sd, se the scaled tridiagonal (|T| in [1/2, 1), or T = 0), w = 2^wex lambda.  Scratch: sv (lambda),
 // sw (e^2), sp (2 NC doubles: positions in the cluster, done flags), sl (2 NC: dot products); st is not touched.
 // True: mout values went to w, and with jobz their vectors stand in columns 0 .. mout - 1 of the image, srank is the
 // identity.  False: the problem has ended (info and m[b] written): an empty window, -20, or a failure.
-template <int NC, int NW>
-__device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int wex, double *S, double *sd, double *se,
+template <int NC, int NW, typename LAY = ColumnsInLds>
+__device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int wex, typename LAY::elem *S, double *sd,
+                                        double *se,
                                         double *sv, double *sw, double *sp, double *sl, double *red, int &phase,
                                         int *srank, gdouble *w, int *info, int &mout) {
   constexpr int LD = NC + 1;
+  constexpr int XS = LAY::rows ? LD : 1;            // from an entry of a vector to the next, from a vector to the next
+  constexpr int VS = LAY::rows ? 1 : LD;
+  constexpr int KB = LAY::rows ? 4 : 8;             // rows DLAGTS loads ahead of their use: registers
+  typedef typename LAY::elem elem;
   const int t = threadIdx.x, r = t % NC, sub = t / NC;
   const bool row = r < n;
   int *mword = a.m + blockIdx.x;
@@ -195,7 +306,10 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
 
   // ---- vectors
   if (zero) {
-    if (row)
+    if constexpr (LAY::rows) {
+      if (r < m)
+        for (int i = sub; i < n; i += 2) S[r + i * LD] = (i == first - 1 + r) ? 1.0 : 0.0;
+    } else if (row)
       for (int j = sub; j < m; j += 2) S[r + j * LD] = (r == first - 1 + j) ? 1.0 : 0.0;
     __syncthreads();
     return true;
@@ -226,7 +340,7 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
   const int wc = a.wcols;
   gdouble *lu = (gdouble *)(a.ws + (size_t)blockIdx.x * 5 * (size_t)n * wc) + t;
   const bool lane = t < m;
-  double *x = S + (lane ? t : 0) * LD;
+  elem *x = S + (lane ? t : 0) * VS;
   const int mypos = lane ? pos[t] : -1;
   const double lamj = lane ? sv[t] : 0.0;
   const double dtpcrt = sqrt(0.1 / n), epsm = DBL_EPSILON * 0.5;
@@ -281,53 +395,53 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
       if (tol == 0.0) tol = epsm;
       for (int i = 0; i < n; ++i) {
         const double v = start_entry(first - 1 + t, i);
-        x[i] = v;
+        x[i * XS] = v;
         if (fabs(v) > xmax) { xmax = fabs(v); jmax = i; }
       }
     }
     for (int it = 0; it < kMaxIts + kExtra; ++it) {
       if (mine && !done) {
         const double scl = n * onenrm * fmax(epsm, fabs(unn)) / xmax;
-        // DLAGTS(-1): forward through the multipliers and interchanges, eight rows' loads ahead of their use
+        // DLAGTS(-1): forward through the multipliers and interchanges, KB rows' loads ahead of their use
         double yp = x[0] * scl;
-        for (int k0 = 1; k0 < n; k0 += 8) {
-          double c8[8], i8[8], y8[8];
+        for (int k0 = 1; k0 < n; k0 += KB) {
+          double c8[KB], i8[KB], y8[KB];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
+          for (int q = 0; q < KB; ++q) {
             const int k = min(k0 + q, n - 1);
             c8[q] = lu[(2 * (size_t)n + k - 1) * wc];
             i8[q] = lu[(4 * (size_t)n + k - 1) * wc];
-            y8[q] = x[k] * scl;
+            y8[q] = x[k * XS] * scl;
           }
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
+          for (int q = 0; q < KB; ++q) {
             const int k = k0 + q;
             if (k < n) {
               if (i8[q] == 0.0) {
-                x[k - 1] = yp;
+                x[(k - 1) * XS] = yp;
                 yp = y8[q] - c8[q] * yp;
               } else {
-                x[k - 1] = y8[q];
+                x[(k - 1) * XS] = y8[q];
                 yp = yp - c8[q] * y8[q];
               }
             }
           }
         }
-        x[n - 1] = yp;
+        x[(n - 1) * XS] = yp;
         // back through U, tiny pivots perturbed
         double y1 = 0.0, y2 = 0.0;
-        for (int k0 = n - 1; k0 >= 0; k0 -= 8) {
-          double a8[8], b8[8], d8[8], y8[8];
+        for (int k0 = n - 1; k0 >= 0; k0 -= KB) {
+          double a8[KB], b8[KB], d8[KB], y8[KB];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
+          for (int q = 0; q < KB; ++q) {
             const int k = max(k0 - q, 0);
             a8[q] = lu[(0 * (size_t)n + k) * wc];
             b8[q] = lu[(1 * (size_t)n + k) * wc];
             d8[q] = lu[(3 * (size_t)n + k) * wc];
-            y8[q] = x[k];
+            y8[q] = x[k * XS];
           }
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
+          for (int q = 0; q < KB; ++q) {
             const int k = k0 - q;
             if (k >= 0) {
               double temp = y8[q] - b8[q] * y1 - d8[q] * y2;
@@ -345,7 +459,7 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
                 break;
               }
               const double y = temp / ak;
-              x[k] = y;
+              x[k * XS] = y;
               y2 = y1; y1 = y;
             }
           }
@@ -353,44 +467,80 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
       }
       if (round > 0) {
         // the round's vectors against the finished members in front of them, by the whole workgroup, twice
-        for (int pass = 0; pass < 2; ++pass) {
-          __syncthreads();
-          if (t < m) {                              // thread t: the dot product with finished vector t
-            const int j = t - pos[t] + round;
-            if (pos[t] < round && j < m && pos[j] == round && !fin[j]) {
-              const double *xp = S + t * LD, *xj = S + j * LD;
-              double acc = 0.0;
-              for (int i = 0; i < n; ++i) acc += xp[i] * xj[i];
-              sl[t] = acc;
-            }
-          }
-          __syncthreads();
-          if (row)                                  // thread (r, sub): row r of every other vector
-            for (int j = sub; j < m; j += 2)
-              if (pos[j] == round && !fin[j]) {
+        if constexpr (LAY::rows) {
+          gram_schmidt_rows<NC, NW>(S, n, m, round, pos, fin, sl);
+        } else {
+          for (int pass = 0; pass < 2; ++pass) {
+            __syncthreads();
+            if (t < m) {                            // thread t: the dot product with finished vector t
+              const int j = t - pos[t] + round;
+              if (pos[t] < round && j < m && pos[j] == round && !fin[j]) {
+                const double *xp = S + t * LD, *xj = S + j * LD;
                 double acc = 0.0;
-                for (int q = j - round; q < j; ++q) acc += sl[q] * S[r + q * LD];
-                S[r + j * LD] -= acc;
+                for (int i = 0; i < n; ++i) acc += xp[i] * xj[i];
+                sl[t] = acc;
               }
+            }
+            __syncthreads();
+            if (row)                                // thread (r, sub): row r of every other vector
+              for (int j = sub; j < m; j += 2)
+                if (pos[j] == round && !fin[j]) {
+                  double acc = 0.0;
+                  for (int q = j - round; q < j; ++q) acc += sl[q] * S[r + q * LD];
+                  S[r + j * LD] -= acc;
+                }
+          }
         }
         __syncthreads();
       }
       if (mine && !done) {
         xmax = 0.0;
-        for (int i = 0; i < n; ++i) {
-          const double v = fabs(x[i]);
-          if (v > xmax) { xmax = v; jmax = i; }
+        if constexpr (LAY::rows) {
+          for (int i0 = 0; i0 < n; i0 += 8) {
+            double v8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v8[q] = fabs(x[min(i0 + q, n - 1) * XS]);   // a repeated last entry is no new maximum
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+              if (v8[q] > xmax) { xmax = v8[q]; jmax = min(i0 + q, n - 1); }
+          }
+        } else {
+          for (int i = 0; i < n; ++i) {
+            const double v = fabs(x[i]);
+            if (v > xmax) { xmax = v; jmax = i; }
+          }
         }
-        if (xmax >= dtpcrt) ++nrmchk;               // DSTEIN's growth test, then kExtra more solves
+        if (xmax >= dtpcrt) ++nrmchk;              // DSTEIN's growth test, then kExtra more solves
         if (nrmchk >= kExtra + 1) done = 1;
         else if (it + 1 >= kMaxIts && nrmchk == 0) { done = 1; failed = 1; }
         else if (!(xmax > 0.0)) { done = 1; failed = 1; }   // a zero or non-finite iterate cannot be scaled
         if (done) {
           double ss = 0.0;
-          for (int i = 0; i < n; ++i) ss += x[i] * x[i];
-          double scl = 1.0 / sqrt(ss);
-          if (x[jmax] < 0.0) scl = -scl;
-          for (int i = 0; i < n; ++i) x[i] *= scl;
+          if constexpr (LAY::rows) {                // the same sums and products, eight entries' loads ahead
+            for (int i0 = 0; i0 < n; i0 += 8) {
+              double v8[8];
+#pragma unroll
+              for (int q = 0; q < 8; ++q) v8[q] = x[min(i0 + q, n - 1) * XS];
+#pragma unroll
+              for (int q = 0; q < 8; ++q)
+                if (i0 + q < n) ss += v8[q] * v8[q];
+            }
+            double scl = 1.0 / sqrt(ss);
+            if (x[jmax * XS] < 0.0) scl = -scl;
+            for (int i0 = 0; i0 < n; i0 += 8) {
+              double v8[8];
+#pragma unroll
+              for (int q = 0; q < 8; ++q) v8[q] = x[min(i0 + q, n - 1) * XS];
+#pragma unroll
+              for (int q = 0; q < 8; ++q)
+                if (i0 + q < n) x[(i0 + q) * XS] = v8[q] * scl;
+            }
+          } else {
+            for (int i = 0; i < n; ++i) ss += x[i] * x[i];
+            double scl = 1.0 / sqrt(ss);
+            if (x[jmax] < 0.0) scl = -scl;
+            for (int i = 0; i < n; ++i) x[i] *= scl;
+          }
           fin[t] = 1;
         }
       }

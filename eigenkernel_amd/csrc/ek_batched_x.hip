@@ -43,12 +43,17 @@
 // A batch runs in chunks of at most K problems (K = 1024; ek_hip_debug_xbatched_chunk), launched one after the other on
 // the context's stream without a host synchronise; problem i of a chunk works in slot i of the workspace.
 //
+// ek_hip_eigenpairs_window_xbatched*: a third argument type, XWArgs, selects stage 4W of ek_batched_window.h in place of
+// stage 4's QL; the wanted vectors are rows of the image from the start, and stage 5 works on those rows.
+//
 // ek_hip_*_xvbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in entry
 // blockIdx.x of its launch's slice of the variable-order table (ek_batched.hip builds it) instead of at blockIdx.x *
 // stride; the image slot is blockIdx.x either way.
 #include "ek_batched_stages.h"
+#include "ek_batched_window.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace ek {
 namespace batchedx {
@@ -80,6 +85,12 @@ struct XVArgs {
   int *info;
   double *ws;
   int itype;
+};
+
+// ek_hip_eigenpairs_window_xbatched*: Args and the window.  The type is what selects stage 4W (ek_batched_window.h, the
+// vectors as rows of the image) in place of stage 4's QL, so the instantiations of Args and XVArgs hold nothing of it
+struct XWArgs : Args {
+  bwindow::Window win;
 };
 
 // What a workgroup works on, whichever way it found it.  The pointers are typed as global (gdouble).  n is the same in
@@ -173,8 +184,10 @@ __device__ __forceinline__ void cong_pass(gdouble *S, const gdouble *B, int ldb,
 // CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
 // CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
 // ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or XVArgs (a table entry).
+// WIN (ARGS = XWArgs): stage 4W for QL, and stage 5 on the window's m rows of the image.
 template <bool CONG, typename ARGS = Args>
 __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
+  constexpr bool WIN = std::is_same<ARGS, XWArgs>::value;
   __shared__ double sd[NC], se[NC], st[NC];         // d, e, tau: alive from stage 3 to the end
   __shared__ double sv[NC], sw[NC];                 // stage 1: the scaled column; 3: v, w; 4: c, s of a sweep
   __shared__ double sp[P * NC];                     // partial sums of a pair
@@ -390,126 +403,134 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
     }
   }
   __syncthreads();
-  const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
-  {
-    double dr = 0.0, er = 0.0;
-    if (flip && sub == 0 && row) {
-      dr = sd[n - 1 - r];
-      er = (r < n - 1) ? se[n - 2 - r] : 0.0;
+  int nz = n;                                       // pairs that stage 5 works on: n, or the window's m
+  if constexpr (WIN) {
+    // ---- 4W: the window's values by bisection, their vectors by inverse iteration as rows 0 .. nz - 1 of the image
+    if (!bwindow::stage4w<NC, NW, bwindow::RowsInMemory>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red, phase,
+                                                         srank, W, info, nz))
+      return;
+  } else {
+    const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
+    {
+      double dr = 0.0, er = 0.0;
+      if (flip && sub == 0 && row) {
+        dr = sd[n - 1 - r];
+        er = (r < n - 1) ? se[n - 2 - r] : 0.0;
+      }
+      __syncthreads();
+      if (flip && sub == 0 && row) { sd[r] = dr; se[r] = er; }
     }
+    if (a.jobz && row)
+      for (int j = sub; j < n; j += P) S[r + j * LD] = (r == (flip ? n - 1 - j : j)) ? 1.0 : 0.0;
     __syncthreads();
-    if (flip && sub == 0 && row) { sd[r] = dr; se[r] = er; }
-  }
-  if (a.jobz && row)
-    for (int j = sub; j < n; j += P) S[r + j * LD] = (r == (flip ? n - 1 - j : j)) ? 1.0 : 0.0;
-  __syncthreads();
-  {
-    const double eps = 1.1102230246251565e-16;
-    double *sc_ = sv, *ss_ = sw;
-    int failed = 0;
-    int iter = 0;
-    for (int l = 0; l < n && !failed; ++l) {
-      while (true) {
-        if (t == 0) {
-          int m = l;
-          for (bool found = false; !found;) {
-            double dv[9], ev[8];
+    {
+      const double eps = 1.1102230246251565e-16;
+      double *sc_ = sv, *ss_ = sw;
+      int failed = 0;
+      int iter = 0;
+      for (int l = 0; l < n && !failed; ++l) {
+        while (true) {
+          if (t == 0) {
+            int m = l;
+            for (bool found = false; !found;) {
+              double dv[9], ev[8];
 #pragma unroll
-            for (int q = 0; q < 9; ++q) dv[q] = sd[min(m + q, n - 1)];
+              for (int q = 0; q < 9; ++q) dv[q] = sd[min(m + q, n - 1)];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) ev[q] = se[min(m + q, n - 1)];
-            int hit = -1;
+              for (int q = 0; q < 8; ++q) ev[q] = se[min(m + q, n - 1)];
+              int hit = -1;
 #pragma unroll
-            for (int q = 7; q >= 0; --q)
-              if (m + q >= n - 1 || fabs(ev[q]) <= eps * (fabs(dv[q]) + fabs(dv[q + 1]))) hit = q;
-            if (hit >= 0) { m = min(m + hit, n - 1); found = true; } else m += 8;
-          }
-          if (m == l) {
-            s_state = 0;
-          } else if (iter++ == 30 * n) {
-            s_state = 2;
-          } else {
-            const double dl = sd[l], el = se[l];
-            double g = (sd[l + 1] - dl) / (2.0 * el);
-            double rr = sqrt(g * g + 1.0);
-            g = sd[m] - dl + el / (g + copysign(rr, g));
-            double s = 1.0, c = 1.0, p = 0.0;
-            int i, lo = l;
-            bool under = false;
-            double ei = se[m - 1], di = sd[m - 1], dup = sd[m];
-            for (i = m - 1; i >= l; --i) {
-              double en = 0.0, dn = 0.0;
-              if (i > l) { en = se[i - 1]; dn = sd[i - 1]; }
-              const double f = s * ei, bb = c * ei;
-              const double h = f * f + g * g;
-              if (!(h >= 1e-280)) {                 // recover from underflow: split here
-                se[i + 1] = 0.0;
-                sd[i + 1] = dup - p;
-                se[m] = 0.0;
-                under = true;
-                lo = i + 1;
-                break;
+              for (int q = 7; q >= 0; --q)
+                if (m + q >= n - 1 || fabs(ev[q]) <= eps * (fabs(dv[q]) + fabs(dv[q + 1]))) hit = q;
+              if (hit >= 0) { m = min(m + hit, n - 1); found = true; } else m += 8;
+            }
+            if (m == l) {
+              s_state = 0;
+            } else if (iter++ == 30 * n) {
+              s_state = 2;
+            } else {
+              const double dl = sd[l], el = se[l];
+              double g = (sd[l + 1] - dl) / (2.0 * el);
+              double rr = sqrt(g * g + 1.0);
+              g = sd[m] - dl + el / (g + copysign(rr, g));
+              double s = 1.0, c = 1.0, p = 0.0;
+              int i, lo = l;
+              bool under = false;
+              double ei = se[m - 1], di = sd[m - 1], dup = sd[m];
+              for (i = m - 1; i >= l; --i) {
+                double en = 0.0, dn = 0.0;
+                if (i > l) { en = se[i - 1]; dn = sd[i - 1]; }
+                const double f = s * ei, bb = c * ei;
+                const double h = f * f + g * g;
+                if (!(h >= 1e-280)) {                 // recover from underflow: split here
+                  se[i + 1] = 0.0;
+                  sd[i + 1] = dup - p;
+                  se[m] = 0.0;
+                  under = true;
+                  lo = i + 1;
+                  break;
+                }
+                double y = __builtin_amdgcn_rsq(h);
+                y = y * (1.5 - 0.5 * h * y * y);
+                y = y * (1.5 - 0.5 * h * y * y);
+                rr = h * y;
+                se[i + 1] = rr;
+                s = f * y;
+                c = g * y;
+                g = dup - p;
+                rr = (di - g) * s + 2.0 * c * bb;
+                p = s * rr;
+                sd[i + 1] = g + p;
+                g = c * rr - bb;
+                sc_[i] = c;
+                ss_[i] = s;
+                dup = di; di = dn; ei = en;
               }
-              double y = __builtin_amdgcn_rsq(h);
-              y = y * (1.5 - 0.5 * h * y * y);
-              y = y * (1.5 - 0.5 * h * y * y);
-              rr = h * y;
-              se[i + 1] = rr;
-              s = f * y;
-              c = g * y;
-              g = dup - p;
-              rr = (di - g) * s + 2.0 * c * bb;
-              p = s * rr;
-              sd[i + 1] = g + p;
-              g = c * rr - bb;
-              sc_[i] = c;
-              ss_[i] = s;
-              dup = di; di = dn; ei = en;
+              if (!under) {
+                sd[l] = dup - p;
+                se[l] = g;
+                se[m] = 0.0;
+              }
+              s_state = 1; s_m = m; s_lo = lo;
             }
-            if (!under) {
-              sd[l] = dup - p;
-              se[l] = g;
-              se[m] = 0.0;
-            }
-            s_state = 1; s_m = m; s_lo = lo;
           }
+          __syncthreads();
+          const int state = s_state, m = s_m, lo = s_lo;
+          if (state == 1 && a.jobz && t < n) {        // the sweep's rotations on row t of Z
+            gdouble *zr = S + t;
+            double f = zr[m * LD];
+            int i = m - 1;
+            for (; i - 7 >= lo; i -= 8) {             // eight rotations' loads before the first store
+              double zv[8], cv[8], sv8[8];
+#pragma unroll
+              for (int q = 0; q < 8; ++q) zv[q] = zr[(i - q) * LD];
+#pragma unroll
+              for (int q = 0; q < 8; ++q) { cv[q] = sc_[i - q]; sv8[q] = ss_[i - q]; }
+#pragma unroll
+              for (int q = 0; q < 8; ++q) {
+                zr[(i + 1 - q) * LD] = sv8[q] * zv[q] + cv[q] * f;
+                f = cv[q] * zv[q] - sv8[q] * f;
+              }
+            }
+            for (; i >= lo; --i) {
+              const double c = sc_[i], s = ss_[i], z0 = zr[i * LD];
+              zr[(i + 1) * LD] = s * z0 + c * f;
+              f = c * z0 - s * f;
+            }
+            zr[lo * LD] = f;
+          }
+          __syncthreads();
+          if (state == 2) failed = l + 1;
+          if (state != 1) break;
         }
-        __syncthreads();
-        const int state = s_state, m = s_m, lo = s_lo;
-        if (state == 1 && a.jobz && t < n) {        // the sweep's rotations on row t of Z
-          gdouble *zr = S + t;
-          double f = zr[m * LD];
-          int i = m - 1;
-          for (; i - 7 >= lo; i -= 8) {             // eight rotations' loads before the first store
-            double zv[8], cv[8], sv8[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) zv[q] = zr[(i - q) * LD];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { cv[q] = sc_[i - q]; sv8[q] = ss_[i - q]; }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              zr[(i + 1 - q) * LD] = sv8[q] * zv[q] + cv[q] * f;
-              f = cv[q] * zv[q] - sv8[q] * f;
-            }
-          }
-          for (; i >= lo; --i) {
-            const double c = sc_[i], s = ss_[i], z0 = zr[i * LD];
-            zr[(i + 1) * LD] = s * z0 + c * f;
-            f = c * z0 - s * f;
-          }
-          zr[lo * LD] = f;
-        }
-        __syncthreads();
-        if (state == 2) failed = l + 1;
-        if (state != 1) break;
+      }
+      if (failed) {
+        if (t == 0) *info = 100000 + failed;
+        return;
       }
     }
-    if (failed) {
-      if (t == 0) *info = 100000 + failed;
-      return;
-    }
+    if (!rank_sort<NC>(n, wex, sd, srank, W, info)) return;
   }
-  if (!rank_sort<NC>(n, wex, sd, srank, W, info)) return;
   if (!a.jobz) {
     if (t == 0) *info = 0;
     return;
@@ -517,8 +538,10 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
   gdouble *Z = vectors(a, p);
   const int ldz = p.ldz;
 
-  // ---- 5: the image becomes Z^T: the pair r owns column r of Z = row r of the image
-  if (row)
+  // ---- 5: the image becomes Z^T: the pair r owns column r of Z = row r of the image (WIN: stage 4W left its nz vectors
+  // as rows already, and only the pairs r < nz work)
+  const bool zrow = WIN ? r < nz : row;
+  if (!WIN && row)
     for (int j = sub; j < r; j += P) {
       const double lo = S[r + j * LD], up = S[j + r * LD];
       S[r + j * LD] = up;
@@ -535,12 +558,12 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
       const double tau = st[k];
       if (tau != 0.0) {                             // uniform
         double c1 = 0.0;
-        if (row) {
+        if (zrow) {
           if (sub == 0) c1 = S[r + (k + 1) * LD];
           sp[sub * NC + r] = img_dot<LD, P>(S + r, cur, k + 2 + sub, n, c1);
         }
         __syncthreads();
-        if (row) {
+        if (zrow) {
           const double dot = (sp[r] + sp[NC + r]) * tau;
           if (sub == 0) S[r + (k + 1) * LD] = c1 - dot;
           img_axpy<LD, P>(S + r, cur, dot, k + 2 + sub, n);
@@ -580,20 +603,20 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
       double nx = 0.0;
       if (i >= 1 && t >= i - 1 && t < n) nx = B[t + (size_t)(i - 1) * ldb];
       double zi = 0.0;
-      if (row) {
+      if (zrow) {
         if (sub == 0) zi = S[r + i * LD];
         sp[sub * NC + r] = img_dot<LD, P>(S + r, cur, i + 1 + sub, n, 0.0);
       }
       __syncthreads();
-      if (sub == 0 && row) S[r + i * LD] = ((zi - sp[r]) - sp[NC + r]) / cur[i];
+      if (sub == 0 && zrow) S[r + i * LD] = ((zi - sp[r]) - sp[NC + r]) / cur[i];
       if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
       __syncthreads();
     }
   }
   __syncthreads();
-  if (row) {                                        // Z[r, j] = image[j, r]
+  if (row) {                                        // Z[r, j] = image[j, r], j < nz
     int j = sub;
-    for (; j + 7 * P < n; j += 8 * P) {
+    for (; j + 7 * P < nz; j += 8 * P) {
       double zv[8];
       int rk[8];
 #pragma unroll
@@ -603,7 +626,7 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) Z[r + (size_t)rk[q] * ldz] = zv[q];
     }
-    for (; j < n; j += P) Z[r + (size_t)srank[j] * ldz] = S[j + r * LD];
+    for (; j < nz; j += P) Z[r + (size_t)srank[j] * ldz] = S[j + r * LD];
   }
   if (t == 0) *info = 0;
 }
@@ -658,6 +681,29 @@ int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int 
 int xvbatched_prepare(int count) {
   using namespace batchedx;
   return ensure_images((size_t)std::min(count, g_chunk));
+}
+
+// ek_hip_eigenpairs_window_xbatched*: the images of a launch of `slots` workgroups, before the call's first event
+int xwindow_prepare(int slots) {
+  using namespace batchedx;
+  return ensure_images((size_t)slots);
+}
+
+// One chunk of `count` <= slots problems of order EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX through the window
+// instantiation (type 1 only): the pointers are the chunk's, dm and dinfo hold a word per problem of it, lu a slot of
+// 5 n wcols doubles per workgroup (jobz = 1).  g_mu held, xwindow_prepare(slots) done
+int xwindow_launch(hipStream_t s, int problem, int jobz, int n, int count, double *dA, int lda, long long strideA,
+                   double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
+                   int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm, double *lu,
+                   int wcols) {
+  using namespace batchedx;
+  if ((size_t)count > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
+  XWArgs a{{problem, jobz, n, dA, lda, strideA, problem ? dB : nullptr, ldb, strideB, dw, jobz ? dZ : nullptr, ldz,
+            strideZ, dinfo, g_ws, 1},
+           {range, il, iu, zcap, vl, vu, dm, lu, wcols}};
+  hipLaunchKernelGGL((xbatched_kernel<false, XWArgs>), dim3(count), dim3(T), 0, s, a);
+  EK_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 // arguments checked, g_mu held, xvbatched_prepare(count) done; `table` (device) holds `count` > 0 entries of orders

@@ -203,6 +203,13 @@ def load_library(path=None):
                                                      c_int, c_ll, _dp, c_int, c_ll, _ip, _dp, _dp, c_int, c_int, c_ll,
                                                      _ip, _dp]),
         "ek_hip_debug_window_batched_chunk": (c_int, [c_int]),
+        "ek_hip_eigenpairs_window_xbatched_device": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int,
+                                                             vp, c_int, c_ll, vp, c_int, c_ll, _ip, vp, vp, c_int, c_int,
+                                                             c_ll, _ip, _dp]),
+        "ek_hip_eigenpairs_window_xbatched": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, _dp,
+                                                      c_int, c_ll, _dp, c_int, c_ll, _ip, _dp, _dp, c_int, c_int, c_ll,
+                                                      _ip, _dp]),
+        "ek_hip_debug_window_xbatched_chunk": (c_int, [c_int]),
         "ek_hip_check_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
                                                  c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
@@ -296,6 +303,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_solve_sparse", "ek_hip_check_sparse_device", "ek_hip_check_sparse", "ek_hip_sparse_to_dense",
     "ek_hip_debug_sparse_check_workspace_bytes", "ek_hip_debug_sparse_csr",
     "ek_hip_eigenpairs_window_batched_device", "ek_hip_eigenpairs_window_batched", "ek_hip_debug_window_batched_chunk",
+    "ek_hip_eigenpairs_window_xbatched_device", "ek_hip_eigenpairs_window_xbatched",
+    "ek_hip_debug_window_xbatched_chunk",
 )
 
 
@@ -909,6 +918,10 @@ def eigenpairs_window_batched(A, B=None, il=None, iu=None, vl=None, vu=None, vec
     behind m[b] is zero.  info[b]: 0; k > 0 B[b] not SPD at pivot k; -5 NaN / Inf in A[b]; -20 more than zcap values in
     the window (m[b] is their number, nothing else of the problem is returned); 100000 + n + 1, 200000 + k: see
     include/ek_hip.h.  A and B are not modified.  Raises SolverError only when the call itself fails."""
+    return _window_batched_call("ek_hip_eigenpairs_window_batched", A, B, il, iu, vl, vu, vectors, zcap, seconds)
+
+
+def _window_batched_call(entry, A, B, il, iu, vl, vu, vectors, zcap, seconds):
     lib = load_library()
     A = np.asarray(A, dtype=np.float64)
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
@@ -936,13 +949,12 @@ def eigenpairs_window_batched(A, B=None, il=None, iu=None, vl=None, vu=None, vec
     Zt = np.zeros((batch, zc, max(n, 1))) if vectors else None
     m = np.zeros(max(batch, 1), dtype=np.int32)
     info = np.zeros(max(batch, 1), dtype=np.int32)
-    rc = lib.ek_hip_eigenpairs_window_batched(0 if B is None else 1, 1 if vectors else 0, 1 if by_value else 0, n, batch,
-                                              vl, vu, il, iu, _P(At), max(n, 1), max(n * n, 1),
-                                              _P(Bt) if Bt is not None else None, max(n, 1), max(n * n, 1), _I(m), _P(w),
-                                              _P(Zt) if vectors else None, max(n, 1), zcap, zc * max(n, 1), _I(info),
-                                              _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, entry)(0 if B is None else 1, 1 if vectors else 0, 1 if by_value else 0, n, batch, vl, vu, il, iu,
+                             _P(At), max(n, 1), max(n * n, 1), _P(Bt) if Bt is not None else None, max(n, 1),
+                             max(n * n, 1), _I(m), _P(w), _P(Zt) if vectors else None, max(n, 1), zcap, zc * max(n, 1),
+                             _I(info), _P(seconds) if seconds is not None else None)
     if rc != 0:
-        raise SolverError("ek_hip_eigenpairs_window_batched failed", rc)
+        raise SolverError(entry + " failed", rc)
     return w, (Zt.transpose(0, 2, 1)[:, :n, :zcap] if vectors else None), m[:batch], info[:batch]
 
 
@@ -966,6 +978,20 @@ def xbatched_chunk(problems):
     """Problems per launch of eigenpairs_xbatched above BATCH_NMAX (ek_hip_debug_xbatched_chunk): 0 restores the default.
     Returns the previous value.  No result depends on it."""
     return int(load_library().ek_hip_debug_xbatched_chunk(int(problems)))
+
+
+def eigenpairs_window_xbatched(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, zcap=None, seconds=None):
+    """eigenpairs_window_batched for orders up to XBATCH_NMAX (ek_hip_eigenpairs_window_xbatched): the same arguments,
+    returns and errors.  Orders up to BATCH_NMAX give eigenpairs_window_batched's bits; above it the kernel class of
+    eigenpairs_xbatched runs the same bisection and inverse iteration.  An order beyond XBATCH_NMAX raises SolverError
+    with info -4."""
+    return _window_batched_call("ek_hip_eigenpairs_window_xbatched", A, B, il, iu, vl, vu, vectors, zcap, seconds)
+
+
+def window_xbatched_chunk(problems):
+    """Problems per launch of eigenpairs_window_xbatched above BATCH_NMAX (ek_hip_debug_window_xbatched_chunk): 0 restores
+    the default.  Returns the previous value.  No result depends on it."""
+    return int(load_library().ek_hip_debug_window_xbatched_chunk(int(problems)))
 
 
 def sygv_batched(A, B, itype=1, vectors=True, seconds=None):

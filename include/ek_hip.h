@@ -311,6 +311,39 @@ int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, in
                                      long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
                                      long long strideZ, int *info, double *seconds);
 
+/* The window call for orders up to EK_HIP_XBATCH_NMAX.  Argument for argument these are
+ * ek_hip_eigenpairs_window_batched_device / ek_hip_eigenpairs_window_batched -- 23 arguments, the same argument-error
+ * codes decided before any device work and without dereferencing a data pointer, the first offending argument deciding --
+ * with one difference: -4 is for n < 0 or n > EK_HIP_XBATCH_NMAX.
+ *   0 <= n <= EK_HIP_BATCH_NMAX : forwarded to the code behind ek_hip_eigenpairs_window_batched*: the same kernel, the
+ *                   same bits in m, w, Z, info and the in-place images
+ *   EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX : the kernel class of ek_hip_eigenpairs_xbatched* (the n x n image in a
+ *                   device workspace) with the same bisection and inverse iteration in place of its QL; the wanted
+ *                   vectors are held as rows of the image
+ * The whole contract above holds at the new orders: m, info (0 / k > 0 / -5 / -20 / 100000 + n + 1 / 200000 + k), what is
+ * written and what is left alone, and the bit contracts -- the value of index k depends on (n, A, B, k) alone; a vector's
+ * bits depend on the window only through its cluster mates inside it; after a device call dA and dB are, bit for bit, what
+ * ek_hip_eigenpairs_xbatched_device leaves for the same pair; values agree with ek_hip_eigenpairs_xbatched*'s to the bound,
+ * not to the bit.
+ * Above EK_HIP_BATCH_NMAX a batch runs in chunks of at most K problems on one stream: K = 1024, or as many LU slots as fit
+ * 1 GiB where that is fewer, in multiples of 512 (the workgroups the device holds at once, two per compute unit) and at
+ * least 512.  Workspace (device memory, grown on demand, kept until ek_hip_finalize): 2 batch ints; min(batch, K) images
+ * of 526 336 bytes (shared with ek_hip_eigenpairs_xbatched*: 539 MB at K = 1024); and for jobz = 1 min(batch, K) LU slots
+ * of 5 n c doubles, c = iu - il + 1 ('I') or min(zcap, n) ('V'): 2 621 440 bytes at n = c = 256, where K = 512 -- 1.34 GB
+ * of LU and 269 MB of images at most; 327 680 bytes for a window of 32 at n = 256 (K = 1024, 336 MB).  Under 'V' give the
+ * zcap that is needed: c follows it.
+ * Where it is slow: as above, a fully clustered problem with all pairs wanted; ek_hip_eigenpairs_xbatched* is then the
+ * call to use. */
+int ek_hip_eigenpairs_window_xbatched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
+                                             int il, int iu, double *dA, int lda, long long strideA, double *dB,
+                                             int ldb, long long strideB, int *m, double *dw, double *dZ, int ldz,
+                                             int zcap, long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout */
+int ek_hip_eigenpairs_window_xbatched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                      int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
+                                      long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
+                                      long long strideZ, int *info, double *seconds);
+
 /* The same call for orders up to EK_HIP_XBATCH_NMAX ("xbatched").  Argument for argument these are
  * ek_hip_eigenpairs_batched_device / ek_hip_eigenpairs_batched -- 16 arguments, the same argument-error codes decided
  * before any device work and without dereferencing a pointer, the first offending argument deciding -- with one

@@ -174,6 +174,10 @@ int ek_hip_debug_xbatched_chunk(int problems);
    slots of the inverse iteration's LU workspace).  0 (or less) restores the default of 1024; returns the previous value.
    A tuning and test hook: no result depends on it. */
 int ek_hip_debug_window_batched_chunk(int problems);
+/* ek_hip_eigenpairs_window_xbatched*, orders above EK_HIP_BATCH_NMAX: problems per launch (a batch runs in chunks of that
+   many, each chunk reusing the same image and LU slots).  0 (or less) restores the default of 1024; returns the previous
+   value.  A tuning and test hook: no result depends on it. */
+int ek_hip_debug_window_xbatched_chunk(int problems);
 /* ek_hip_check_xbatched* and ek_hip_check_sygv_xbatched*, orders above EK_HIP_BATCH_NMAX: checked problems per launch (a batch
    runs in chunks of that many, each chunk reusing the same scratch for S = B Z; types 2 and 3: for the products, L and W).
    0 (or less) restores the default of 1024; returns the previous value.  A tuning and test hook: no result depends on it. */

@@ -35,7 +35,8 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
   python tools/batched_timing.py --once 64g --once-batch 1024 --check
                                                  one solve and one check after a warm-up of each
   python tools/batched_timing.py --window 0.125,1 [--sizes 64,128] [--batches 512,1024]
-                                                 a window of that fraction of n (ek_hip_eigenpairs_window_batched_device)
+                                                 a window of that fraction of n (ek_hip_eigenpairs_window_batched_device; sizes
+                                                 above 128: ek_hip_eigenpairs_window_xbatched_device)
                                                  by index and by value, with and without vectors, against the existing
                                                  call, the kinds alternated; then a fully clustered standard batch
                                                  (all_equal, two_clusters of tests/batched_cases.py) both ways
@@ -113,7 +114,8 @@ class Case:
         return t, sec.value
 
     def window(self, problem, jobz, il=None, iu=None, vl=None, vu=None):
-        """ek_hip_eigenpairs_window_batched_device by index (il, iu) or by value (vl, vu): wall, device, m."""
+        """ek_hip_eigenpairs_window_batched_device (above BATCH_NMAX: ek_hip_eigenpairs_window_xbatched_device) by index
+        (il, iu) or by value (vl, vu): wall, device, m."""
         n, nn = self.n, self.n * self.n
         self.restore()
         sec = ctypes.c_double(0.0)
@@ -121,7 +123,10 @@ class Case:
         ip = ctypes.POINTER(ctypes.c_int)
         by_value = vl is not None
         t0 = time.perf_counter()
-        rc = self.lib.ek_hip_eigenpairs_window_batched_device(
+        fn = self.lib.ek_hip_eigenpairs_window_batched_device
+        if n > solver.BATCH_NMAX:
+            fn = self.lib.ek_hip_eigenpairs_window_xbatched_device
+        rc = fn(
             problem, jobz, 1 if by_value else 0, n, self.batch, vl if by_value else 0.0, vu if by_value else 0.0,
             il or 0, iu or 0, self.dA, n, nn, self.dB if problem else None, n, nn, m.ctypes.data_as(ip), self.dw,
             self.dZ if jobz else None, n, n, nn, self.info.ctypes.data_as(ip), ctypes.byref(sec))

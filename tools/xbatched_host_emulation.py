@@ -3,6 +3,11 @@
 thread, __syncthreads() as a barrier and __shared__ as static storage; one problem per run (tools, not product).
 
   python tools/xbatched_host_emulation.py [--n 129] [--problem 1] [--itype 1|2|3] [--table] [--tsan] [--stop 0|1|2]
+                                          [--window IL,IU | --vl X --vu Y] [--case random|all_equal]
+      --window the window instantiation (ek_hip_eigenpairs_window_xbatched*): the pairs IL .. IU (1-based)
+               by stage 4W -- bisection, inverse iteration on the rows of the image -- and stage 5 on those rows
+      --vl, --vu  the same by value: the pairs in (vl, vu]; a missing bound is infinite
+      --case   all_equal: A = 3 B (problem 0: 3 I), one cluster of n, a round per wanted vector: the Gram-Schmidt maps
       --table  the kernel's table instantiation (ek_hip_*_xvbatched*): the problem as the one entry of a variable-order
                table, image slot 0, the status word at info[entry.index]
       --itype  DSYGV's problem type (problem 1): 2 and 3 run the kernel's CONG instantiation
@@ -29,15 +34,30 @@ ap.add_argument("--itype", type=int, default=1, choices=(1, 2, 3))
 ap.add_argument("--table", action="store_true")
 ap.add_argument("--tsan", action="store_true")
 ap.add_argument("--stop", type=int, default=0)
+ap.add_argument("--window", default=None)
+ap.add_argument("--vl", type=float, default=None)
+ap.add_argument("--vu", type=float, default=None)
+ap.add_argument("--case", default="random", choices=("random", "all_equal"))
 args = ap.parse_args()
+by_value = args.vl is not None or args.vu is not None
+window = args.window is not None or by_value
+assert not (args.window and by_value), "--window or --vl / --vu"
+assert not window or (args.itype == 1 and not args.table and not args.stop), "the window: type 1, uniform form, --stop 0"
 assert args.itype == 1 or (args.problem == 1 and args.stop != 1), "--itype 2|3: problem 1, and --stop 0 or 2"
-src = open(os.path.join(ROOT, "eigenkernel_amd", "csrc", "ek_batched_x.hip")).read()
+CSRC = os.path.join(ROOT, "eigenkernel_amd", "csrc")
+src = open(os.path.join(CSRC, "ek_batched_x.hip")).read()
 def patch(text, old, new):
-    assert text.count(old) == 1, "anchor not found exactly once in ek_batched_x.hip: %r" % old
+    assert text.count(old) == 1, "anchor not found exactly once in ek_batched_x.hip and its headers: %r" % old
     return text.replace(old, new)
 
 
 src = src[:src.index("// the images: grown")]
+# the two headers the kernel shares with ek_batched.hip, in place of their #include lines
+stages = open(os.path.join(CSRC, "ek_batched_stages.h")).read().replace("#pragma once\n", "")
+wind = open(os.path.join(CSRC, "ek_batched_window.h")).read().replace("#pragma once\n", "")
+wind = patch(wind, '#include "ek_batched_stages.h"\n', "")
+src = patch(src, '#include "ek_batched_window.h"\n', wind)
+src = patch(src, '#include "ek_batched_stages.h"\n', stages)
 # the table's entry, shared through ek_api_internal.h: the struct as it stands there
 internal = open(os.path.join(ROOT, "eigenkernel_amd", "csrc", "ek_api_internal.h")).read()
 assert internal.count("struct Desc {") == 1, "struct Desc not found exactly once in ek_api_internal.h"
@@ -52,6 +72,8 @@ hdr = r'''
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <cstdint>
+#include <type_traits>
 #define EK_HIP_XBATCH_NMAX 256
 #define __global__
 #define __device__
@@ -64,14 +86,18 @@ static std::barrier<> *g_bar;
 static double g_xch[512]; static int g_or;
 static inline void __syncthreads() { g_bar->arrive_and_wait(); }
 static inline int __syncthreads_or(int v) { if (threadIdx.x == 0) g_or = 0; g_bar->arrive_and_wait(); if (v) __atomic_store_n(&g_or, 1, __ATOMIC_RELAXED); g_bar->arrive_and_wait(); int r = g_or; g_bar->arrive_and_wait(); return r; }
-static inline double __shfl_xor(double x, int o, int) { g_xch[threadIdx.x] = x; g_bar->arrive_and_wait(); double y = g_xch[threadIdx.x ^ o]; g_bar->arrive_and_wait(); return y; }
+static inline int __syncthreads_and(int v) { return !__syncthreads_or(!v); }
+static std::barrier<> *g_pair[256];                 // stage 4W's bisection exchanges inside a pair of lanes, under a condition
+static inline double __shfl_xor(double x, int o, int w) { if (w == 2) { std::barrier<> *b = g_pair[threadIdx.x >> 1]; g_xch[threadIdx.x] = x; b->arrive_and_wait(); double y = g_xch[threadIdx.x ^ o]; b->arrive_and_wait(); return y; } g_xch[threadIdx.x] = x; g_bar->arrive_and_wait(); double y = g_xch[threadIdx.x ^ o]; g_bar->arrive_and_wait(); return y; }
 static inline double __builtin_amdgcn_rsq(double h) { return 1.0 / std::sqrt(h); }
 using std::min;
+using std::max;
 static int g_stop2 = 0;
 namespace ek { namespace batched { @DESC@ } }
 '''.replace("@DESC@", desc)
 src = patch(src, '#include "ek_api_internal.h"', hdr)
 src = patch(src, "typedef __attribute__((address_space(1))) double gdouble;", "typedef double gdouble;")
+src = patch(src, "typedef const __attribute__((address_space(1))) double cgdouble;", "typedef const double cgdouble;")
 src = patch(src, "  // ---- 3: Householder", "  if (g_stop2) return;\n  // ---- 3: Householder")
 src = patch(src, "    // the lower half of X the right way round", "    if (g_stop2 == 1) return;\n    // the lower half of X the right way round")
 src += r'''
@@ -91,8 +117,47 @@ int main(int argc, char **argv) {
       A[i + (size_t)j * n] = rnd();
       B[i + (size_t)j * n] = (i == j) ? 2.0 + 0.5 * rnd() : rnd() / n;
     }
+  const bool all_equal = argc > 10 && atoi(argv[10]);
+  if (all_equal)                                      // A = 3 B (3 I): every eigenvalue is 3, one cluster of n
+    for (int j = 0; j < n; ++j)
+      for (int i = j; i < n; ++i) A[i + (size_t)j * n] = problem ? 3.0 * B[i + (size_t)j * n] : (i == j ? 3.0 : 0.0);
   std::vector<double> A0 = A, B0 = B;
   const bool table = argc > 4 && atoi(argv[4]);
+  // the window: argv 5 .. 9 = range (-1: none), il, iu, vl, vu
+  const int range = argc > 5 ? atoi(argv[5]) : -1;
+  if (range >= 0) {
+    const int il = atoi(argv[6]), iu = atoi(argv[7]);
+    const double vl = atof(argv[8]), vu = atof(argv[9]);
+    const int zcap = range ? n : iu - il + 1;
+    int m = 777, winfo = 777;
+    std::vector<double> lu((size_t)5 * n * zcap, NAN);
+    XWArgs xw{{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &winfo, ws.data(), 1},
+              {range, il, iu, zcap, vl, vu, &m, lu.data(), zcap}};
+    std::barrier<> wbar(T);
+    g_bar = &wbar;
+    for (int q = 0; q < 256; ++q) g_pair[q] = new std::barrier<>(2);
+    std::vector<std::thread> wth;
+    for (int t = 0; t < T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; xbatched_kernel<false>(xw); });
+    for (auto &x : wth) x.join();
+    auto a0 = [&](int i, int j) { return i >= j ? A0[i + (size_t)j * n] : A0[j + (size_t)i * n]; };
+    auto b0 = [&](int i, int j) { if (!problem) return i == j ? 1.0 : 0.0; return i >= j ? B0[i + (size_t)j * n] : B0[j + (size_t)i * n]; };
+    if (winfo != 0 || m < 0 || m > zcap) { printf("n=%d window: info=%d m=%d\n", n, winfo, m); return 1; }
+    double res = 0, orth = 0, wmax = 0; bool asc = true, rest = true;
+    std::vector<double> BZ((size_t)n * std::max(m, 1));
+    for (int k = 0; k < m; ++k) for (int i = 0; i < n; ++i) { double sacc = 0; for (int j = 0; j < n; ++j) sacc += b0(i, j) * Z[j + (size_t)k * n]; BZ[i + (size_t)k * n] = sacc; }
+    for (int k = 0; k < m; ++k) {
+      wmax = std::max(wmax, std::fabs(w[k])); if (k && w[k] < w[k - 1]) asc = false;
+      if (range && !(w[k] > vl && w[k] <= vu)) asc = false;
+      for (int i = 0; i < n; ++i) { double sacc = 0; for (int j = 0; j < n; ++j) sacc += a0(i, j) * Z[j + (size_t)k * n]; res = std::max(res, std::fabs(sacc - w[k] * BZ[i + (size_t)k * n])); }
+      for (int l = 0; l < m; ++l) { double sacc = 0; for (int i = 0; i < n; ++i) sacc += Z[i + (size_t)k * n] * BZ[i + (size_t)l * n]; orth = std::max(orth, std::fabs(sacc - (k == l ? 1.0 : 0.0))); }
+    }
+    for (int k = m; k < n; ++k) { rest = rest && w[k] == -7.0; for (int i = 0; i < n; ++i) rest = rest && Z[i + (size_t)k * n] == -7.0; }
+    const double eps = 2.220446049250313e-16, c = problem ? 256 : 64;
+    printf("n=%d problem=%d window range=%d info=%d m=%d in order and inside=%d max|w|=%.3f residual %.3e (bound %.3e) orthogonality %.3e (bound %.3e)\n", n, problem, range, winfo, m, (int)asc, wmax, res, c * n * eps, orth, c * n * eps);
+    bool upper = true; for (int j = 0; j < n; ++j) for (int i = 0; i < j; ++i) upper = upper && std::isnan(A[i + (size_t)j * n]) && std::isnan(B[i + (size_t)j * n]);
+    printf("upper triangles untouched: %d; w and Z behind m untouched: %d\n", (int)upper, (int)rest);
+    return (asc && res <= c * n * eps && orth <= c * n * eps && upper && rest && (range || m == iu - il + 1)) ? 0 : 1;
+  }
   int infos[3] = {777, 777, 777};
   int &info = infos[table ? 2 : 0];                   // the table form: the status word of the entry's index
   Args a{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, infos, ws.data(), itype};
@@ -186,4 +251,13 @@ if args.stop:
     env["STOP2"] = str(args.stop)
 if args.tsan:
     env.setdefault("TSAN_OPTIONS", "halt_on_error=1 history_size=4")
-sys.exit(subprocess.call([exe, str(args.n), str(args.problem), str(args.itype), str(int(args.table))], env=env))
+argv = [exe, str(args.n), str(args.problem), str(args.itype), str(int(args.table))]
+if window:
+    il, iu = (int(x) for x in args.window.split(",")) if args.window else (0, 0)
+    assert by_value or 1 <= il <= iu <= args.n, "--window IL,IU with 1 <= IL <= IU <= n"
+    argv += [str(int(by_value)), str(il), str(iu), repr(-float("inf") if args.vl is None else args.vl),
+             repr(float("inf") if args.vu is None else args.vu)]
+else:
+    argv += ["-1", "0", "0", "0", "0"]
+argv.append(str(int(args.case == "all_equal")))
+sys.exit(subprocess.call(argv, env=env))
