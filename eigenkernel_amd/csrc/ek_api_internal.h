@@ -87,10 +87,10 @@ int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count,
 // it; lu: a slot of 5 n wcols doubles per workgroup (jobz = 1).  The host driver (counts, chunks, LU slots) is
 // ek_batched.hip's
 int xwindow_prepare(int slots);
-int xwindow_launch(hipStream_t s, int problem, int jobz, int n, int count, double *dA, int lda, long long strideA,
-                   double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
-                   int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm, double *lu,
-                   int wcols);
+int xwindow_launch(hipStream_t s, int problem, int itype, int jobz, int n, int count, double *dA, int lda,
+                   long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                   long long strideZ, int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm,
+                   double *lu, int wcols);
 void release_batched_check();     // every batched check's scratch, output words, table and events (ek_batched_check.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);
 

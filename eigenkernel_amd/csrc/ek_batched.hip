@@ -33,6 +33,8 @@
 // selects stage 4W of ek_batched_window.h in place of stage 4's QL -- Sturm bisection of the wanted values, inverse
 // iteration for their vectors -- and stage 5 then runs on the window's columns only.  Stages 0 to 3 are
 // the same lines for every argument type, and the instantiations of Args and VArgs hold nothing of the window.
+// ek_hip_sygv_window_batched*: the same with itype.  Types 2 and 3 run WArgs with CONG: stages 0 to 3 are CONG's, stage 4W
+// is the window's, and type 3's Z <- L Z (multiply_window_by_l) works on the window's columns alone.
 //
 // Image layout: column-major with leading dimension NC + 1 (odd), NC the class size 32 / 64 / 128.  A wave that walks
 // down a column (consecutive rows) and a wave that walks along a row (stride NC + 1, odd) both hit 32 different
@@ -187,6 +189,29 @@ __device__ __forceinline__ void multiply_by_l(double *S, double *sl, const gdoub
       double *col = S + t * LD;
       const double zk = col[k];
       lds_axpy<1>(col, cur, -zk, k + 1, n);         // y - x (-zk): the sign change is exact
+      col[k] = zk * cur[k];
+    }
+    if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
+    __syncthreads();
+  }
+}
+
+// The same for the window kernel: the nz wanted vectors are the columns t < nz; the columns behind them hold leftovers of
+// stage 3 and are not touched.  Every t < n stages L as above, and a column sees the same steps in the same order.
+template <int NC>
+__device__ __forceinline__ void multiply_window_by_l(double *S, double *sl, const gdouble *B, int ldb, int n, int nz) {
+  constexpr int LD = NC + 1;
+  const int t = threadIdx.x;
+  if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
+  __syncthreads();
+  for (int k = n - 1, s = 0; k >= 0; --k, ++s) {
+    const double *cur = sl + (s & 1) * NC;
+    double nx = 0.0;
+    if (k >= 1 && t >= k - 1 && t < n) nx = B[t + (size_t)(k - 1) * ldb];
+    if (t < nz) {
+      double *col = S + t * LD;
+      const double zk = col[k];
+      lds_axpy<1>(col, cur, -zk, k + 1, n);
       col[k] = zk * cur[k];
     }
     if (t < n) sl[((s + 1) & 1) * NC + t] = nx;
@@ -524,7 +549,8 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   }
   int nz = n;                                       // columns of Z: n, or the window's m
   if constexpr (WIN) {
-    if (!bwindow::stage4w<NC, NW>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red, phase, srank, p.w, info, nz))
+    if (!bwindow::stage4w<NC, NW, bwindow::ColumnsInLds, CONG>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red,
+                                                               phase, srank, p.w, info, nz))
       return;
   } else {
     if (!rank_sort<NC>(n, wex, sd, srank, p.w, info)) return;
@@ -560,7 +586,8 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   // Z <- L^-T Z (types 1 and 2), Z <- L Z (type 3)
   if (CONG && a.itype == 3) {
     __syncthreads();
-    multiply_by_l<NC>(S, sl, B, ldb, n);
+    if constexpr (WIN) multiply_window_by_l<NC>(S, sl, B, ldb, n, nz);
+    else multiply_by_l<NC>(S, sl, B, ldb, n);
   } else if (a.problem) {
     __syncthreads();
     if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
@@ -962,7 +989,7 @@ static int batched_host_entry(int problem, int itype, int jobz, int n, int batch
   return 0;
 }
 
-// ---- a window of eigenpairs per problem (ek_hip_eigenpairs_window_batched*)
+// ---- a window of eigenpairs per problem (ek_hip_eigenpairs_window_batched*; ek_hip_sygv_window_batched* with itype)
 
 // The 23 arguments of the prototype in their order; no data pointer is dereferenced
 static int window_check(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
@@ -1004,7 +1031,7 @@ static int window_check(int problem, int jobz, int range, int n, int batch, doub
 }
 
 // arguments checked, context up, g_mu held
-static int window_device_locked(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+static int window_device_locked(int problem, int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
                                 double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
                                 double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
                                 double *seconds) {
@@ -1034,7 +1061,7 @@ static int window_device_locked(int problem, int jobz, int range, int n, int bat
   for (int c0 = 0; c0 < batch && !rc; c0 += K) {
     const int count = std::min(K, batch - c0);
     if (x) {
-      rc = xwindow_launch(s, problem, jobz, n, count, dA + (long long)c0 * strideA, lda, strideA,
+      rc = xwindow_launch(s, problem, itype, jobz, n, count, dA + (long long)c0 * strideA, lda, strideA,
                           problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
                           jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, range, il, iu, zcap,
                           vl, vu, g_dm + c0, g_wws, wcols);
@@ -1042,12 +1069,12 @@ static int window_device_locked(int problem, int jobz, int range, int n, int bat
     }
     WArgs a{{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
              problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
-             jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, 1},
+             jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, itype},
             {range, il, iu, zcap, vl, vu, g_dm + c0, g_wws, wcols}};
     switch (class_of(n)) {
-      case 32: rc = launch_instance<32, 64, WArgs, false>(s, count, a); break;
-      case 64: rc = launch_instance<64, 128, WArgs, false>(s, count, a); break;
-      default: rc = launch_instance<128, 256, WArgs, false>(s, count, a); break;
+      case 32: rc = launch_class<32, 64>(s, count, a); break;
+      case 64: rc = launch_class<64, 128>(s, count, a); break;
+      default: rc = launch_class<128, 256>(s, count, a); break;
     }
   }
   if (seconds) (void)hipEventRecord(e1, s);
@@ -1065,7 +1092,7 @@ static int window_device_locked(int problem, int jobz, int range, int n, int bat
   return rc;
 }
 
-static int window_device_entry(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+static int window_device_entry(int problem, int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
                                double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
                                double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
                                double *seconds, int nmax = EK_HIP_BATCH_NMAX) {
@@ -1077,11 +1104,11 @@ static int window_device_entry(int problem, int jobz, int range, int n, int batc
   if (nothing) return 0;
   rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
-  return window_device_locked(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
-                              dZ, ldz, zcap, strideZ, info, seconds);
+  return window_device_locked(problem, itype, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB,
+                              m, dw, dZ, ldz, zcap, strideZ, info, seconds);
 }
 
-static int window_host_entry(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+static int window_host_entry(int problem, int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
                              const double *A, int lda, long long strideA, const double *B, int ldb, long long strideB,
                              int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
                              double *seconds, int nmax = EK_HIP_BATCH_NMAX) {
@@ -1112,8 +1139,8 @@ static int window_host_entry(int problem, int jobz, int range, int n, int batch,
   EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
   if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
   if (cZ) EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  rc = window_device_locked(problem, jobz, range, n, batch, vl, vu, il, iu, uA, lda, strideA, uB, ldb, strideB, m, uw, uZ,
-                            ldz, zcap, strideZ, info, seconds);
+  rc = window_device_locked(problem, itype, jobz, range, n, batch, vl, vu, il, iu, uA, lda, strideA, uB, ldb, strideB, m,
+                            uw, uZ, ldz, zcap, strideZ, info, seconds);
   if (rc) return rc;
   EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
   if (cZ) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
@@ -1334,11 +1361,50 @@ int ek_hip_sygv_xvbatched(int itype, int jobz, int batch, const int *n, const do
   return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds, EK_HIP_XBATCH_NMAX);
 }
 
+// A window of eigenpairs of DSYGV's three problem types: the window entries' problem 1 with itype in its place
+int ek_hip_sygv_window_batched_device(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                      int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                      long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                      long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return window_device_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+                             dZ, ldz, zcap, strideZ, info, seconds);
+}
+
+int ek_hip_sygv_window_batched(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                               const double *A, int lda, long long strideA, const double *B, int ldb, long long strideB,
+                               int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
+                               double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return window_host_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z,
+                           ldz, zcap, strideZ, info, seconds);
+}
+
+// The same for orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's window instantiation, CONG for
+// types 2 and 3
+int ek_hip_sygv_window_xbatched_device(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                       int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                       long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                       long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return window_device_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+                             dZ, ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
+int ek_hip_sygv_window_xbatched(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                                const double *A, int lda, long long strideA, const double *B, int ldb,
+                                long long strideB, int *m, double *w, double *Z, int ldz, int zcap, long long strideZ,
+                                int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return window_host_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z,
+                           ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+}
+
 int ek_hip_eigenpairs_window_batched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
                                             int il, int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
                                             long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
                                             long long strideZ, int *info, double *seconds) {
-  return window_device_entry(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+  return window_device_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
                              dZ, ldz, zcap, strideZ, info, seconds);
 }
 
@@ -1346,7 +1412,7 @@ int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, in
                                      int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
                                      long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
                                      long long strideZ, int *info, double *seconds) {
-  return window_host_entry(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
+  return window_host_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
                            zcap, strideZ, info, seconds);
 }
 
@@ -1355,7 +1421,7 @@ int ek_hip_eigenpairs_window_xbatched_device(int problem, int jobz, int range, i
                                              int il, int iu, double *dA, int lda, long long strideA, double *dB,
                                              int ldb, long long strideB, int *m, double *dw, double *dZ, int ldz,
                                              int zcap, long long strideZ, int *info, double *seconds) {
-  return window_device_entry(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
+  return window_device_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
                              dZ, ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
 }
 
@@ -1363,7 +1429,7 @@ int ek_hip_eigenpairs_window_xbatched(int problem, int jobz, int range, int n, i
                                       int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
                                       long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
                                       long long strideZ, int *info, double *seconds) {
-  return window_host_entry(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
+  return window_host_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
                            zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
 }
 

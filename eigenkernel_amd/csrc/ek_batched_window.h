@@ -185,7 +185,9 @@ __device__ __forceinline__ void gram_schmidt_rows(gdouble *S, int n, int m, int 
 // sw (e^2), sp (2 NC doubles: positions in the cluster, done flags), sl (2 NC: dot products); st is not touched.
 // True: mout values went to w, and with jobz their vectors stand in columns 0 .. mout - 1 of the image, srank is the
 // identity.  False: the problem has ended (info and m[b] written): an empty window, -20, or a failure.
-template <int NC, int NW, typename LAY = ColumnsInLds>
+// OWNER: nothing but a name.  s_rounds below is one LDS variable per instantiation of this function; a kernel passes a
+// value of its own, so that no two kernels share the variable and each keeps it in its own LDS frame.
+template <int NC, int NW, typename LAY = ColumnsInLds, int OWNER = 0>
 __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int wex, typename LAY::elem *S, double *sd,
                                         double *se,
                                         double *sv, double *sw, double *sp, double *sl, double *red, int &phase,

@@ -45,6 +45,8 @@
 //
 // ek_hip_eigenpairs_window_xbatched*: a third argument type, XWArgs, selects stage 4W of ek_batched_window.h in place of
 // stage 4's QL; the wanted vectors are rows of the image from the start, and stage 5 works on those rows.
+// ek_hip_sygv_window_xbatched*: XWArgs with CONG for types 2 and 3; type 3's Z <- L Z works on those rows too
+// (DESIGN.md 33).
 //
 // ek_hip_*_xvbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in entry
 // blockIdx.x of its launch's slice of the variable-order table (ek_batched.hip builds it) instead of at blockIdx.x *
@@ -406,8 +408,8 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
   int nz = n;                                       // pairs that stage 5 works on: n, or the window's m
   if constexpr (WIN) {
     // ---- 4W: the window's values by bisection, their vectors by inverse iteration as rows 0 .. nz - 1 of the image
-    if (!bwindow::stage4w<NC, NW, bwindow::RowsInMemory>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red, phase,
-                                                         srank, W, info, nz))
+    if (!bwindow::stage4w<NC, NW, bwindow::RowsInMemory, CONG>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red,
+                                                               phase, srank, W, info, nz))
       return;
   } else {
     const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
@@ -578,13 +580,13 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
     // thread applies them; z[k] is as stage 4 and the reflectors left it until step k, loaded by both halves a step ahead
     __syncthreads();
     if (t < n) sl[t] = (t == n - 1) ? B[t + (size_t)(n - 1) * ldb] : 0.0;
-    double pv = row ? S[r + (n - 1) * LD] : 0.0;
+    double pv = zrow ? S[r + (n - 1) * LD] : 0.0;
     __syncthreads();
     for (int k = n - 1, s = 0; k >= 0; --k, ++s) {
       const double *cur = sl + (s & 1) * NC;
       double nx = 0.0;
       if (k >= 1 && t >= k - 1 && t < n) nx = B[t + (size_t)(k - 1) * ldb];
-      if (row) {
+      if (zrow) {
         double nv = 0.0;
         if (k >= 1) nv = S[r + (k - 1) * LD];       // no step before its own writes it
         if (sub == 0) S[r + k * LD] = pv * cur[k];
@@ -690,18 +692,19 @@ int xwindow_prepare(int slots) {
 }
 
 // One chunk of `count` <= slots problems of order EK_HIP_BATCH_NMAX + 1 .. EK_HIP_XBATCH_NMAX through the window
-// instantiation (type 1 only): the pointers are the chunk's, dm and dinfo hold a word per problem of it, lu a slot of
-// 5 n wcols doubles per workgroup (jobz = 1).  g_mu held, xwindow_prepare(slots) done
-int xwindow_launch(hipStream_t s, int problem, int jobz, int n, int count, double *dA, int lda, long long strideA,
-                   double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz, long long strideZ,
-                   int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm, double *lu,
-                   int wcols) {
+// instantiation (CONG's for types 2 and 3): the pointers are the chunk's, dm and dinfo hold a word per problem of it, lu
+// a slot of 5 n wcols doubles per workgroup (jobz = 1).  g_mu held, xwindow_prepare(slots) done
+int xwindow_launch(hipStream_t s, int problem, int itype, int jobz, int n, int count, double *dA, int lda,
+                   long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                   long long strideZ, int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm,
+                   double *lu, int wcols) {
   using namespace batchedx;
   if ((size_t)count > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
   XWArgs a{{problem, jobz, n, dA, lda, strideA, problem ? dB : nullptr, ldb, strideB, dw, jobz ? dZ : nullptr, ldz,
-            strideZ, dinfo, g_ws, 1},
+            strideZ, dinfo, g_ws, itype},
            {range, il, iu, zcap, vl, vu, dm, lu, wcols}};
-  hipLaunchKernelGGL((xbatched_kernel<false, XWArgs>), dim3(count), dim3(T), 0, s, a);
+  if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XWArgs>), dim3(count), dim3(T), 0, s, a);
+  else hipLaunchKernelGGL((xbatched_kernel<false, XWArgs>), dim3(count), dim3(T), 0, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }

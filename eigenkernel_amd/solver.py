@@ -210,6 +210,16 @@ def load_library(path=None):
                                                       c_int, c_ll, _dp, c_int, c_ll, _ip, _dp, _dp, c_int, c_int, c_ll,
                                                       _ip, _dp]),
         "ek_hip_debug_window_xbatched_chunk": (c_int, [c_int]),
+        "ek_hip_sygv_window_batched_device": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, vp,
+                                                      c_int, c_ll, vp, c_int, c_ll, _ip, vp, vp, c_int, c_int, c_ll,
+                                                      _ip, _dp]),
+        "ek_hip_sygv_window_batched": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, _dp, c_int,
+                                               c_ll, _dp, c_int, c_ll, _ip, _dp, _dp, c_int, c_int, c_ll, _ip, _dp]),
+        "ek_hip_sygv_window_xbatched_device": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, vp,
+                                                       c_int, c_ll, vp, c_int, c_ll, _ip, vp, vp, c_int, c_int, c_ll,
+                                                       _ip, _dp]),
+        "ek_hip_sygv_window_xbatched": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int, _dp, c_int,
+                                                c_ll, _dp, c_int, c_ll, _ip, _dp, _dp, c_int, c_int, c_ll, _ip, _dp]),
         "ek_hip_check_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
                                                  c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
@@ -305,6 +315,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_eigenpairs_window_batched_device", "ek_hip_eigenpairs_window_batched", "ek_hip_debug_window_batched_chunk",
     "ek_hip_eigenpairs_window_xbatched_device", "ek_hip_eigenpairs_window_xbatched",
     "ek_hip_debug_window_xbatched_chunk",
+    "ek_hip_sygv_window_batched_device", "ek_hip_sygv_window_batched",
+    "ek_hip_sygv_window_xbatched_device", "ek_hip_sygv_window_xbatched",
 )
 
 
@@ -921,7 +933,8 @@ def eigenpairs_window_batched(A, B=None, il=None, iu=None, vl=None, vu=None, vec
     return _window_batched_call("ek_hip_eigenpairs_window_batched", A, B, il, iu, vl, vu, vectors, zcap, seconds)
 
 
-def _window_batched_call(entry, A, B, il, iu, vl, vu, vectors, zcap, seconds):
+def _window_batched_call(entry, A, B, il, iu, vl, vu, vectors, zcap, seconds, itype=None):
+    """itype None: the eigenpairs entries (argument 1 is problem); 1 / 2 / 3: the sygv entries (argument 1 is itype)."""
     lib = load_library()
     A = np.asarray(A, dtype=np.float64)
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
@@ -949,10 +962,11 @@ def _window_batched_call(entry, A, B, il, iu, vl, vu, vectors, zcap, seconds):
     Zt = np.zeros((batch, zc, max(n, 1))) if vectors else None
     m = np.zeros(max(batch, 1), dtype=np.int32)
     info = np.zeros(max(batch, 1), dtype=np.int32)
-    rc = getattr(lib, entry)(0 if B is None else 1, 1 if vectors else 0, 1 if by_value else 0, n, batch, vl, vu, il, iu,
-                             _P(At), max(n, 1), max(n * n, 1), _P(Bt) if Bt is not None else None, max(n, 1),
-                             max(n * n, 1), _I(m), _P(w), _P(Zt) if vectors else None, max(n, 1), zcap, zc * max(n, 1),
-                             _I(info), _P(seconds) if seconds is not None else None)
+    first = (0 if B is None else 1) if itype is None else int(itype)
+    rc = getattr(lib, entry)(first, 1 if vectors else 0, 1 if by_value else 0, n, batch, vl, vu, il, iu, _P(At),
+                             max(n, 1), max(n * n, 1), _P(Bt) if Bt is not None else None, max(n, 1), max(n * n, 1),
+                             _I(m), _P(w), _P(Zt) if vectors else None, max(n, 1), zcap, zc * max(n, 1), _I(info),
+                             _P(seconds) if seconds is not None else None)
     if rc != 0:
         raise SolverError(entry + " failed", rc)
     return w, (Zt.transpose(0, 2, 1)[:, :n, :zcap] if vectors else None), m[:batch], info[:batch]
@@ -992,6 +1006,26 @@ def window_xbatched_chunk(problems):
     """Problems per launch of eigenpairs_window_xbatched above BATCH_NMAX (ek_hip_debug_window_xbatched_chunk): 0 restores
     the default.  Returns the previous value.  No result depends on it."""
     return int(load_library().ek_hip_debug_window_xbatched_chunk(int(problems)))
+
+
+def sygv_window_batched(A, B, itype=1, il=None, iu=None, vl=None, vu=None, vectors=True, zcap=None, seconds=None):
+    """eigenpairs_window_batched for DSYGV's three problem types (ek_hip_sygv_window_batched): itype 1 A x = l B x,
+    2 A B x = l x, 3 B A x = l x, B SPD and always required.  The window, zcap, the returns (w, Z or None, m, info) and
+    the errors are those of eigenpairs_window_batched; Z[b][:, :m[b]] is B-orthonormal for types 1 and 2 and
+    B^-1-orthonormal for type 3.  itype 1 returns eigenpairs_window_batched's bits; types 2 and 3 return the same w and
+    m.  An itype outside 1..3 raises SolverError with info -1."""
+    if B is None:
+        raise ValueError("B is required")
+    return _window_batched_call("ek_hip_sygv_window_batched", A, B, il, iu, vl, vu, vectors, zcap, seconds, itype)
+
+
+def sygv_window_xbatched(A, B, itype=1, il=None, iu=None, vl=None, vu=None, vectors=True, zcap=None, seconds=None):
+    """sygv_window_batched for orders up to XBATCH_NMAX (ek_hip_sygv_window_xbatched): the same arguments, returns and
+    errors.  Orders up to BATCH_NMAX give sygv_window_batched's bits; above it the kernel class of sygv_xbatched runs
+    the same bisection and inverse iteration.  An order beyond XBATCH_NMAX raises SolverError with info -4."""
+    if B is None:
+        raise ValueError("B is required")
+    return _window_batched_call("ek_hip_sygv_window_xbatched", A, B, il, iu, vl, vu, vectors, zcap, seconds, itype)
 
 
 def sygv_batched(A, B, itype=1, vectors=True, seconds=None):

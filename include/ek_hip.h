@@ -526,6 +526,50 @@ int ek_hip_sygv_xbatched(int itype, int jobz, int n, int batch, const double *A,
                          const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                          long long strideZ, int *info, double *seconds);
 
+/* A WINDOW of eigenpairs of DSYGV's three problem types, per problem of a batch -- what itype is to rocSOLVER's
+ * sygvdx_strided_batched, and what ek_hip_sygv_batched* are to ek_hip_eigenpairs_batched*, for
+ * ek_hip_eigenpairs_window_batched* / ek_hip_eigenpairs_window_xbatched*.  The 23 arguments of those entries with problem
+ * = 1 (argument k here is argument k there, itype in the place of problem); B is always required.
+ * Return value: -1 for itype outside 1 .. 3 first, then the window entries' codes -2 .. -22 (B: -13 / -14 / -15 for every
+ * type), decided before any device work and without dereferencing a data pointer; n = 0 or batch = 0: 0, nothing touched.
+ * -4 is for n > EK_HIP_BATCH_NMAX (the batched pair) or n > EK_HIP_XBATCH_NMAX (the xbatched pair, which forwards
+ * n <= EK_HIP_BATCH_NMAX to the code behind the batched pair: the same bits).
+ * itype 1 IS ek_hip_eigenpairs_window_batched* / ek_hip_eigenpairs_window_xbatched* with problem = 1: the same bits in m,
+ * info, w, Z, dA and dB.
+ * Types 2 and 3 run an instantiation of the window kernels with the reduction C = L^T A L in place of type 1's (stages 0
+ * to 3 are those of ek_hip_sygv_batched* / ek_hip_sygv_xbatched*, stage 4W is the window entries'), and recover
+ * x = L^-T y (type 2) or x = L y (type 3) on the window's columns alone:
+ *   values        : the eigenvalue of index k is the same bits in both types and m[b] under 'V' is the same; it depends on
+ *                   (n, A, B, k) alone -- not on the window, range, jobz, zcap, the batch, the position, the chunk or the
+ *                   form.  'V' counts the eigenvalues of C = L^T A L, the bounds scaled by the exact power of two of the
+ *                   kernel's scaling as in the window entries
+ *   images        : after a device call dA and dB are, bit for bit, what ek_hip_sygv_batched_device /
+ *                   ek_hip_sygv_xbatched_device leave for the same pair and type; dB is type 1's L
+ *   vectors       : type 2's are B-orthonormal, type 3's B^-1-orthonormal, and Z3 = B Z2 to rounding, column by column
+ * m, info (0, the failing pivot k, -5, -20, 100000 + n + 1, 200000 + k), the isolation of a failed problem, what is written
+ * (m[b] values of a row of w, m[b] columns of Z; nothing of w or Z under -20) and what is neither read nor written (upper
+ * triangles, rows n .. ld - 1, gaps; A and B in the host forms) are the window entries'.  So are the chunk rule and the
+ * workspace: see ek_hip_eigenpairs_window_batched* and, above EK_HIP_BATCH_NMAX, ek_hip_eigenpairs_window_xbatched*.
+ * ek_hip_eigenpairs_window_*batched* themselves stay type 1 only (problem = 2 is -1 there). */
+int ek_hip_sygv_window_batched_device(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                      int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                      long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                      long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout */
+int ek_hip_sygv_window_batched(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                               const double *A, int lda, long long strideA, const double *B, int ldb, long long strideB,
+                               int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
+                               double *seconds);
+int ek_hip_sygv_window_xbatched_device(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                       int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                       long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                       long long strideZ, int *info, double *seconds);
+/* host arrays A, B, w, Z with the same layout */
+int ek_hip_sygv_window_xbatched(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
+                                const double *A, int lda, long long strideA, const double *B, int ldb,
+                                long long strideB, int *m, double *w, double *Z, int ldz, int zcap, long long strideZ,
+                                int *info, double *seconds);
+
 /* The acceptance checks and the inverse participation ratios of EVERY problem of a batch -- what ek_hip_residual_device,
  * ek_hip_orthogonality_device and ek_hip_ipratios_device are to one problem, with the same normalisations (the
  * reference's: verifier.f90:75-204, :233-330, distribute_matrix.f90:18-78), for the eigenpairs that

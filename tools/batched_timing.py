@@ -40,6 +40,10 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  by index and by value, with and without vectors, against the existing
                                                  call, the kinds alternated; then a fully clustered standard batch
                                                  (all_equal, two_clusters of tests/batched_cases.py) both ways
+  python tools/batched_timing.py --window 0.125,1 --itype 2 [--sizes 64,128,256] [--batches 256]
+                                                 the window call of type 2 / 3 (ek_hip_sygv_window_batched_device; above
+                                                 128: ek_hip_sygv_window_xbatched_device) against the full call of the same
+                                                 type and against the type-1 window call
 
 Per (problem, jobz, n, batch): one warm-up of each kind, then three rounds that alternate the kinds, best by wall clock
 (both calls synchronise; both work in place, so the inputs are restored outside the clock).  The loop is timed over
@@ -113,9 +117,10 @@ class Case:
         assert rc == 0 and not self.info.any(), (rc, self.info[self.info != 0][:4])
         return t, sec.value
 
-    def window(self, problem, jobz, il=None, iu=None, vl=None, vu=None):
+    def window(self, problem, jobz, il=None, iu=None, vl=None, vu=None, itype=1):
         """ek_hip_eigenpairs_window_batched_device (above BATCH_NMAX: ek_hip_eigenpairs_window_xbatched_device) by index
-        (il, iu) or by value (vl, vu): wall, device, m."""
+        (il, iu) or by value (vl, vu): wall, device, m.  itype 2 / 3 (problem 1): ek_hip_sygv_window_batched_device /
+        ek_hip_sygv_window_xbatched_device."""
         n, nn = self.n, self.n * self.n
         self.restore()
         sec = ctypes.c_double(0.0)
@@ -123,11 +128,12 @@ class Case:
         ip = ctypes.POINTER(ctypes.c_int)
         by_value = vl is not None
         t0 = time.perf_counter()
-        fn = self.lib.ek_hip_eigenpairs_window_batched_device
-        if n > solver.BATCH_NMAX:
-            fn = self.lib.ek_hip_eigenpairs_window_xbatched_device
+        x = "xbatched" if n > solver.BATCH_NMAX else "batched"
+        fn, first = getattr(self.lib, "ek_hip_eigenpairs_window_%s_device" % x), problem
+        if problem and itype != 1:
+            fn, first = getattr(self.lib, "ek_hip_sygv_window_%s_device" % x), itype
         rc = fn(
-            problem, jobz, 1 if by_value else 0, n, self.batch, vl if by_value else 0.0, vu if by_value else 0.0,
+            first, jobz, 1 if by_value else 0, n, self.batch, vl if by_value else 0.0, vu if by_value else 0.0,
             il or 0, iu or 0, self.dA, n, nn, self.dB if problem else None, n, nn, m.ctypes.data_as(ip), self.dw,
             self.dZ if jobz else None, n, n, nn, self.info.ctypes.data_as(ip), ctypes.byref(sec))
         t = time.perf_counter() - t0
@@ -430,6 +436,33 @@ def window_rows(lib, sizes, batches, fractions):
             c.close()
 
 
+def sygv_window_rows(lib, sizes, batches, fractions, itype):
+    """Device ms, best of 3, the kinds alternated: the window call of type itype (2 / 3) by index against the full call of
+    the same type (ek_hip_sygv_batched_device / ek_hip_sygv_xbatched_device) and against the type-1 window call."""
+    print("# itype %d     n batch fraction | full jobz=1  jobz=0 | window 'I' jobz=1 (of full, of type 1's window)  "
+          "'I' jobz=0 (of full jobz=0, of type 1's)" % itype)
+    for n in sizes:
+        for batch in batches:
+            c = Case(lib, n, batch, itype=itype)
+            for f in fractions:
+                m = max(1, int(round(f * n)))
+                kinds = {"f1": lambda: c.batched(1, 1)[1], "f0": lambda: c.batched(1, 0)[1],
+                         "i1": lambda: c.window(1, 1, il=1, iu=m, itype=itype)[1],
+                         "i0": lambda: c.window(1, 0, il=1, iu=m, itype=itype)[1],
+                         "t1": lambda: c.window(1, 1, il=1, iu=m)[1], "t0": lambda: c.window(1, 0, il=1, iu=m)[1]}
+                best = {}
+                for rep in range(4):                # the first round warms up
+                    for k, fn in kinds.items():
+                        t = fn()
+                        if rep:
+                            best[k] = min(best.get(k, np.inf), t)
+                print("  %7d %5d %5d %8.3f | %11.3f %7.3f | %17.3f (%.3f, %.3f) %21.3f (%.3f, %.3f)"
+                      % (itype, n, batch, f, best["f1"] * 1e3, best["f0"] * 1e3, best["i1"] * 1e3,
+                         best["i1"] / best["f1"], best["i1"] / best["t1"], best["i0"] * 1e3, best["i0"] / best["f0"],
+                         best["i0"] / best["t0"]), flush=True)
+            c.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="30,64,128")
@@ -451,6 +484,11 @@ def main():
     args = ap.parse_args()
     lib = solver.load_library()
     assert lib.ek_hip_init(0) == 0
+    if args.window and args.itype != 1:
+        sygv_window_rows(lib, [int(x) for x in args.sizes.split(",")], [int(x) for x in args.batches.split(",")],
+                         [float(x) for x in args.window.split(",")], args.itype)
+        lib.ek_hip_finalize()
+        return
     if args.window:
         window_rows(lib, [int(x) for x in args.sizes.split(",")], [int(x) for x in args.batches.split(",")],
                     [float(x) for x in args.window.split(",")])

@@ -10,7 +10,9 @@ thread, __syncthreads() as a barrier and __shared__ as static storage; one probl
       --case   all_equal: A = 3 B (problem 0: 3 I), one cluster of n, a round per wanted vector: the Gram-Schmidt maps
       --table  the kernel's table instantiation (ek_hip_*_xvbatched*): the problem as the one entry of a variable-order
                table, image slot 0, the status word at info[entry.index]
-      --itype  DSYGV's problem type (problem 1): 2 and 3 run the kernel's CONG instantiation
+      --itype  DSYGV's problem type (problem 1): 2 and 3 run the kernel's CONG instantiation; with
+               --window or --vl / --vu the CONG instantiation of the window kernel (ek_hip_sygv_window_xbatched*,
+               DESIGN.md 33), judged with the type's quantities on the window's m columns
       --tsan   build with -fsanitize=thread: a missing barrier shows as a data race with both source lines
       --stop   1: end after X = L^-1 A and compare the image with a forward substitution's X^T (type 1 only); 2: after
                stage 2 (C = L^-1 A L^-T; types 2 and 3: C = L^T A L formed by plain loops in the kernel's summation order)
@@ -42,7 +44,7 @@ args = ap.parse_args()
 by_value = args.vl is not None or args.vu is not None
 window = args.window is not None or by_value
 assert not (args.window and by_value), "--window or --vl / --vu"
-assert not window or (args.itype == 1 and not args.table and not args.stop), "the window: type 1, uniform form, --stop 0"
+assert not window or (not args.table and not args.stop), "the window: uniform form, --stop 0"
 assert args.itype == 1 or (args.problem == 1 and args.stop != 1), "--itype 2|3: problem 1, and --stop 0 or 2"
 CSRC = os.path.join(ROOT, "eigenkernel_amd", "csrc")
 src = open(os.path.join(CSRC, "ek_batched_x.hip")).read()
@@ -131,18 +133,49 @@ int main(int argc, char **argv) {
     const int zcap = range ? n : iu - il + 1;
     int m = 777, winfo = 777;
     std::vector<double> lu((size_t)5 * n * zcap, NAN);
-    XWArgs xw{{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &winfo, ws.data(), 1},
+    XWArgs xw{{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &winfo, ws.data(), itype},
               {range, il, iu, zcap, vl, vu, &m, lu.data(), zcap}};
     std::barrier<> wbar(T);
     g_bar = &wbar;
     for (int q = 0; q < 256; ++q) g_pair[q] = new std::barrier<>(2);
     std::vector<std::thread> wth;
-    for (int t = 0; t < T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; xbatched_kernel<false>(xw); });
+    for (int t = 0; t < T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (cong) xbatched_kernel<true>(xw); else xbatched_kernel<false>(xw); });
     for (auto &x : wth) x.join();
     auto a0 = [&](int i, int j) { return i >= j ? A0[i + (size_t)j * n] : A0[j + (size_t)i * n]; };
     auto b0 = [&](int i, int j) { if (!problem) return i == j ? 1.0 : 0.0; return i >= j ? B0[i + (size_t)j * n] : B0[j + (size_t)i * n]; };
     if (winfo != 0 || m < 0 || m > zcap) { printf("n=%d window: info=%d m=%d\n", n, winfo, m); return 1; }
     double res = 0, orth = 0, wmax = 0; bool asc = true, rest = true;
+    if (cong) {
+      // the quantities of the type on the m columns: |M z - w z|_2 / (max|A| |B|_2 |z|_2) with M = A B (2), B A (3);
+      // max|Z^T B Z - I_m| (2), max|(L^-1 Z)^T (L^-1 Z) - I_m| (3) with the factor left in B
+      std::vector<double> Y((size_t)n * std::max(m, 1)), x(n, 1.0), y(n), u(n), v(n);
+      auto mul = [&](auto mat, const double *in, double *out) { for (int i = 0; i < n; ++i) { double sacc = 0; for (int j = 0; j < n; ++j) sacc += mat(i, j) * in[j]; out[i] = sacc; } };
+      double amax = 0, bnorm = 0;
+      for (int j = 0; j < n; ++j) for (int i = j; i < n; ++i) amax = std::max(amax, std::fabs(A0[i + (size_t)j * n]));
+      for (int it = 0; it < 300; ++it) { mul(b0, x.data(), y.data()); bnorm = 0; for (int i = 0; i < n; ++i) bnorm += y[i] * y[i]; bnorm = std::sqrt(bnorm); for (int i = 0; i < n; ++i) x[i] = y[i] / bnorm; }
+      for (int k = 0; k < m; ++k) {
+        const double *z = &Z[(size_t)k * n];
+        if (itype == 2) { mul(b0, z, u.data()); mul(a0, u.data(), v.data()); } else { mul(a0, z, u.data()); mul(b0, u.data(), v.data()); }
+        double rn = 0, zn = 0;
+        for (int i = 0; i < n; ++i) { const double d = v[i] - w[k] * z[i]; rn += d * d; zn += z[i] * z[i]; }
+        res = std::max(res, std::sqrt(rn) / (amax * bnorm * std::sqrt(zn)));
+        wmax = std::max(wmax, std::fabs(w[k])); if (k && w[k] < w[k - 1]) asc = false;
+        if (range && !(w[k] > vl && w[k] <= vu)) asc = false;
+        if (itype == 2) mul(b0, z, &Y[(size_t)k * n]);
+        else for (int i = 0; i < n; ++i) { double sacc = z[i]; for (int j = 0; j < i; ++j) sacc -= B[i + (size_t)j * n] * Y[j + (size_t)k * n]; Y[i + (size_t)k * n] = sacc / B[i + (size_t)i * n]; }
+      }
+      for (int k = 0; k < m; ++k) for (int l = 0; l < m; ++l) {
+        double sacc = 0;
+        for (int i = 0; i < n; ++i) sacc += (itype == 2 ? Z[i + (size_t)k * n] : Y[i + (size_t)k * n]) * Y[i + (size_t)l * n];
+        orth = std::max(orth, std::fabs(sacc - (k == l ? 1.0 : 0.0)));
+      }
+      for (int k = m; k < n; ++k) { rest = rest && w[k] == -7.0; for (int i = 0; i < n; ++i) rest = rest && Z[i + (size_t)k * n] == -7.0; }
+      const double lim = 256 * n * 2.220446049250313e-16;
+      printf("n=%d itype=%d window range=%d info=%d m=%d in order and inside=%d max|w|=%.3f residual %.3e (bound %.3e) orthogonality %.3e (bound %.3e)\n", n, itype, range, winfo, m, (int)asc, wmax, res, lim, orth, lim);
+      bool upper = true; for (int j = 0; j < n; ++j) for (int i = 0; i < j; ++i) upper = upper && std::isnan(A[i + (size_t)j * n]) && std::isnan(B[i + (size_t)j * n]);
+      printf("upper triangles untouched: %d; w and Z behind m untouched: %d\n", (int)upper, (int)rest);
+      return (asc && res <= lim && orth <= lim && upper && rest && (range || m == iu - il + 1)) ? 0 : 1;
+    }
     std::vector<double> BZ((size_t)n * std::max(m, 1));
     for (int k = 0; k < m; ++k) for (int i = 0; i < n; ++i) { double sacc = 0; for (int j = 0; j < n; ++j) sacc += b0(i, j) * Z[j + (size_t)k * n]; BZ[i + (size_t)k * n] = sacc; }
     for (int k = 0; k < m; ++k) {
