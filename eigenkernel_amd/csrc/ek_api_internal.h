@@ -29,6 +29,15 @@ struct Desc {
   int n, lda, ldb, ldz, index, pad;
 };
 static_assert(sizeof(Desc) == 56, "the table's entry");
+// ek_hip_*_window_xvbatched*: an entry of the second table, beside the Desc of the same index: the problem's window, the
+// vectors its LU slot holds, and where that slot starts in its class's region of the LU workspace (in doubles: the
+// prefix sum of 5 n wcols inside its launch)
+struct WDesc {
+  double vl, vu;
+  int il, iu, zcap, wcols;
+  long long lu;
+};
+static_assert(sizeof(WDesc) == 40, "the window table's entry");
 }  // namespace batched
 
 namespace api {
@@ -91,6 +100,11 @@ int xwindow_launch(hipStream_t s, int problem, int itype, int jobz, int n, int c
                    long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                    long long strideZ, int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm,
                    double *lu, int wcols);
+// ek_hip_*_window_xvbatched*: one launch of count <= slots entries of the variable-order table and of the window table
+// beside it (device), all of order above EK_HIP_BATCH_NMAX; dinfo, dm: a word per problem of the caller's batch; lu: the
+// class's region of the LU workspace.  xwindow_prepare(slots) done
+int xvwindow_launch(hipStream_t s, int problem, int itype, int jobz, int range, int count, const batched::Desc *table,
+                    const batched::WDesc *wtable, int *dinfo, int *dm, double *lu);
 void release_batched_check();     // every batched check's scratch, output words, table and events (ek_batched_check.hip)
 void *choose_sytrd_scratch(int n, int ld, double *wA, void *arena_work, double *vecs, size_t need);
 

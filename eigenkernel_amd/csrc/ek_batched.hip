@@ -46,6 +46,12 @@
 // ek_hip_eigenpairs_vbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in
 // a table instead of at blockIdx.x * stride; every problem runs in the class its own order picks (the uniform call's
 // bits), the classes as one launch each, the problems of a class in descending order.
+//
+// ek_hip_eigenpairs_window_xvbatched*, ek_hip_sygv_window_xvbatched*: a window per problem for problems of different orders.
+// A fourth argument type, VWArgs: the table form, and beside the problem's entry an entry of a second table with its
+// window and the place of its LU slot.  Stages 0 to 3 are the table kernels' lines, stage 4W and stage 5 the window
+// kernels'; the host driver (classes, launches by count and by LU budget, a region of the LU workspace per class) is
+// vwindow_device_locked below, for ek_batched_x.hip's class too.
 #include "ek_batched_stages.h"
 #include "ek_batched_window.h"
 
@@ -81,6 +87,19 @@ struct WArgs : Args {
   bwindow::Window win;
 };
 
+// ek_hip_eigenpairs_window_xvbatched*: VArgs and a window per problem.  Entry blockIdx.x of `wtable` lies beside entry
+// blockIdx.x of `table`; the count goes to m[entry.index] as the status word goes to info[entry.index], and the LU slot
+// starts at ws + wtable[blockIdx.x].lu.  Selects stage 4W like WArgs
+struct VWArgs {
+  int problem, jobz;
+  const Desc *table;
+  const bwindow::WDesc *wtable;
+  int *info;
+  int *m;
+  double *ws;
+  int range, itype;
+};
+
 // What a workgroup works on, whichever way it found it.  The pointers are typed as global (gdouble, ek_batched_stages.h)
 struct Problem {
   int n;
@@ -98,6 +117,15 @@ __device__ __forceinline__ Problem locate(const Args &a) {
 __device__ __forceinline__ Problem locate(const VArgs &a) {
   const Desc &d = a.table[blockIdx.x];
   return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz, a.info + d.index};
+}
+__device__ __forceinline__ Problem locate(const VWArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz, a.info + d.index};
+}
+// the window of stage 4W: the call's, or the workgroup's own
+__device__ __forceinline__ const bwindow::Window &window(const WArgs &a) { return a.win; }
+__device__ __forceinline__ bwindow::OwnWindow window(const VWArgs &a) {
+  return bwindow::own_window(a.range, a.wtable[blockIdx.x], a.m + a.table[blockIdx.x].index, a.ws);
 }
 
 // y[i * SY] -= a * x[i] for i0 <= i < i1, x and y in LDS: four elements' loads go out before the first store, so that
@@ -219,14 +247,16 @@ __device__ __forceinline__ void multiply_window_by_l(double *S, double *sl, cons
   }
 }
 
-// ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or VArgs (a table entry)
+// ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or VArgs (a table entry);
+// WArgs and VWArgs are the two with a window
 // CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
 // CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
-// WIN (ARGS = WArgs): stage 4W for QL, and stage 5 on the window's columns.
+// WIN (ARGS = WArgs or VWArgs): stage 4W for QL, and stage 5 on the window's columns.
 template <int NC, int T, typename ARGS = Args, bool CONG = false>
 __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   constexpr int LD = NC + 1, P = T / NC, NW = T / 64;
-  constexpr bool WIN = std::is_same<ARGS, WArgs>::value;
+  constexpr bool VWIN = std::is_same<ARGS, VWArgs>::value;
+  constexpr bool WIN = VWIN || std::is_same<ARGS, WArgs>::value;
   static_assert(P == 2 && T % 64 == 0, "two threads per row");
   extern __shared__ double smem[];
   double *S = smem;                       // NC x NC image, leading dimension LD
@@ -549,8 +579,9 @@ __global__ __launch_bounds__(T) void batched_kernel(ARGS a) {
   }
   int nz = n;                                       // columns of Z: n, or the window's m
   if constexpr (WIN) {
-    if (!bwindow::stage4w<NC, NW, bwindow::ColumnsInLds, CONG>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red,
-                                                               phase, srank, p.w, info, nz))
+    constexpr int OWNER = VWIN ? 2 + CONG : CONG;   // s_rounds: one variable per kernel
+    if (!bwindow::stage4w<NC, NW, bwindow::ColumnsInLds, OWNER>(window(a), a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red,
+                                                                phase, srank, p.w, info, nz))
       return;
   } else {
     if (!rank_sort<NC>(n, wex, sd, srank, p.w, info)) return;
@@ -679,6 +710,13 @@ static size_t g_dm_count = 0;
 static double *g_wws = nullptr;
 static size_t g_wws_bytes = 0;
 
+// ek_hip_*_window_xvbatched*: the window table beside the problem table, kept like it
+static WDesc *g_dwtable = nullptr;
+static size_t g_dwtable_count = 0;
+static std::vector<WDesc> g_hwtable;
+static long long g_vwbudget = 0;                    // LU bytes a launch may hold (ek_hip_debug_window_xvbatched_budget)
+struct VLaunch { int cls, first, count; };          // a launch: `count` table entries from `first`
+
 static int ensure_window(size_t batch, size_t bytes) {
   if (batch > g_dm_count) {
     if (g_dm) (void)hipFree(g_dm);
@@ -730,6 +768,10 @@ void release_batched() {
   g_wws = nullptr;
   g_wws_bytes = 0;
   std::vector<Desc>().swap(g_htable);
+  if (g_dwtable) (void)hipFree(g_dwtable);
+  g_dwtable = nullptr;
+  g_dwtable_count = 0;
+  std::vector<WDesc>().swap(g_hwtable);
   for (int k = 0; k < kClasses - 1; ++k) {
     if (g_side[k]) (void)hipStreamDestroy(g_side[k]);
     g_side[k] = nullptr;
@@ -1241,7 +1283,341 @@ static int vbatched_host_entry(int problem, int itype, int jobz, int batch, cons
   return 0;
 }
 
+// ---- a window per problem, for problems of different orders (ek_hip_*_window_xvbatched*)
+
+// The 19 checked arguments of the prototype in their order; all arrays are host arrays of `batch` entries, and the pointers
+// in the pointer arrays are not dereferenced.  Per-problem conditions hold for the problems of order > 0
+static int vwindow_check(int problem, int jobz, int range, int batch, const int *n, const double *vl, const double *vu,
+                         const int *il, const int *iu, const void *const *A, const int *lda, const void *const *B,
+                         const int *ldb, const int *m, const void *const *w, const void *const *Z, const int *ldz,
+                         const int *zcap, const int *info, bool *nothing) {
+  *nothing = false;
+  if (problem != 0 && problem != 1) return -1;
+  if (jobz != 0 && jobz != 1) return -2;
+  if (range != 0 && range != 1) return -3;
+  if (batch < 0) return -4;
+  if (batch == 0) { *nothing = true; return 0; }
+  if (!n) return -5;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] < 0 || n[b] > EK_HIP_XBATCH_NMAX) return -5;
+  if (range == 1) {
+    if (!vl) return -6;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && vl[b] != vl[b]) return -6;
+    if (!vu) return -7;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && !(vl[b] < vu[b])) return -7;  // vu NaN, or an empty interval
+  } else {
+    if (!il) return -8;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && (il[b] < 1 || il[b] > n[b])) return -8;
+    if (!iu) return -9;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && (iu[b] < il[b] || iu[b] > n[b])) return -9;
+  }
+  auto entries = [&](const void *const *P) {
+    if (!P) return false;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && !P[b]) return false;
+    return true;
+  };
+  auto leading = [&](const int *ld) {
+    if (!ld) return false;
+    for (int b = 0; b < batch; ++b)
+      if (ld[b] < (n[b] > 1 ? n[b] : 1)) return false;
+    return true;
+  };
+  if (!entries(A)) return -10;
+  if (!leading(lda)) return -11;
+  if (problem == 1) {
+    if (!entries(B)) return -12;
+    if (!leading(ldb)) return -13;
+  }
+  if (!m) return -14;
+  if (!entries(w)) return -15;
+  if (jobz == 1) {
+    if (!Z) return -16;
+    for (int b = 0; b < batch; ++b)                 // no Z is needed where it has no column
+      if (n[b] > 0 && !Z[b] && !(zcap && zcap[b] == 0)) return -16;
+    if (!leading(ldz)) return -17;
+  }
+  if (!zcap) return -18;
+  for (int b = 0; b < batch; ++b)                   // with and without vectors, as the uniform call
+    if (n[b] > 0 && (zcap[b] < 0 || (range == 0 && zcap[b] < iu[b] - il[b] + 1))) return -18;
+  if (!info) return -19;
+  return 0;
+}
+
+// arguments checked, a problem of order > 0 present, context up, g_mu held; the pointers in dA, dB, dw, dZ are device
+// addresses.  The table, the classes and their streams are vbatched_device_locked's.  A class runs in launches of
+// consecutive table entries: a launch ends at K problems or where its LU slots, summed, would pass the class's budget.  The
+// classes run beside each other, so each has a region of its own in the LU workspace: the launches of a class share it in
+// the order of the class's stream
+static int vwindow_device_locked(int problem, int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                 const double *vu, const int *il, const int *iu, double *const *dA, const int *lda,
+                                 double *const *dB, const int *ldb, int *m, double *const *dw, double *const *dZ,
+                                 const int *ldz, const int *zcap, int *info, double *seconds) {
+  using namespace batched;
+  std::vector<int> order;
+  order.reserve((size_t)batch);
+  for (int b = 0; b < batch; ++b)
+    if (n[b] > 0) order.push_back(b);
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
+  g_htable.resize(order.size());
+  g_hwtable.resize(order.size());
+  int count[kClasses] = {0, 0, 0, 0};               // classes of 256, 128, 64, 32
+  for (size_t i = 0; i < order.size(); ++i) {
+    const int b = order[i], c = class_of(n[b]);
+    ++count[n[b] > EK_HIP_BATCH_NMAX ? 0 : c == 128 ? 1 : c == 64 ? 2 : 3];
+    g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], jobz ? dZ[b] : nullptr, n[b], lda[b],
+                       problem ? ldb[b] : 1, jobz ? ldz[b] : 1, b, 0};
+    const int wcols = !jobz ? 0 : range == 0 ? iu[b] - il[b] + 1 : std::min(zcap[b], n[b]);
+    g_hwtable[i] = WDesc{range ? vl[b] : 0.0, range ? vu[b] : 0.0, range ? 0 : il[b], range ? 0 : iu[b], zcap[b], wcols, 0};
+  }
+  // the launches, the slot offsets inside each, and a region per class as wide as its widest launch.  The three classes
+  // of LDS share the uniform calls' kWindowBytes in equal parts, the class of 256 has its kXWindowBytes
+  int small = 0;
+  for (int k = 1; k < kClasses; ++k) small += count[k] ? 1 : 0;
+  std::vector<VLaunch> launches;
+  size_t region[kClasses] = {0, 0, 0, 0}, base[kClasses] = {0, 0, 0, 0};   // doubles
+  int xslots = 0;
+  for (int k = 0, off = 0; k < kClasses; off += count[k], ++k) {
+    if (!count[k]) continue;
+    const int K = k == 0 ? g_xwchunk : g_wchunk;
+    const size_t budget = (g_vwbudget > 0 ? (size_t)g_vwbudget : k == 0 ? kXWindowBytes : kWindowBytes / small) / 8;
+    VLaunch cur{k, off, 0};
+    size_t sum = 0;
+    for (int i = off; i < off + count[k]; ++i) {
+      const size_t slot = (size_t)5 * g_htable[i].n * g_hwtable[i].wcols;
+      if (cur.count > 0 && (cur.count >= K || sum + slot > budget)) {   // a launch always takes one problem
+        launches.push_back(cur);
+        cur = VLaunch{k, i, 0};
+        sum = 0;
+      }
+      g_hwtable[i].lu = (long long)sum;
+      sum += slot;
+      ++cur.count;
+      region[k] = std::max(region[k], sum);
+      if (k == 0) xslots = std::max(xslots, cur.count);
+    }
+    launches.push_back(cur);
+  }
+  for (int k = 1; k < kClasses; ++k) base[k] = base[k - 1] + region[k - 1];
+  const size_t lubytes = (base[kClasses - 1] + region[kClasses - 1]) * sizeof(double);
+  int side[kClasses] = {-1, -1, -1, -1}, sides = 0; // -1: the context's stream
+  if (g_streams == 3)
+    for (int k = 0, used = 0; k < kClasses; ++k)
+      if (count[k] && used++ > 0) side[k] = sides++;
+  { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
+  { int rc0 = ensure_variable(order.size(), std::max(sides, 2)); if (rc0) return rc0; }
+  if (order.size() > g_dwtable_count) {
+    if (g_dwtable) (void)hipFree(g_dwtable);
+    g_dwtable = nullptr;
+    g_dwtable_count = 0;
+    EK_HIP_CHECK(hipMalloc((void **)&g_dwtable, order.size() * sizeof(WDesc)));
+    g_dwtable_count = order.size();
+  }
+  { int rc0 = ensure_window((size_t)batch, lubytes); if (rc0) return rc0; }
+  if (xslots) { int rc0 = xwindow_prepare(xslots); if (rc0) return rc0; }
+  hipStream_t s = g_ctx.stream;
+  EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(g_dwtable, g_hwtable.data(), g_hwtable.size() * sizeof(WDesc), hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemsetAsync(g_dm, 0, (size_t)batch * sizeof(int), s));   // a problem that ends before stage 4W: m = 0
+  hipStream_t cs[kClasses];
+  for (int k = 0; k < kClasses; ++k) cs[k] = side[k] < 0 ? s : g_side[side[k]];
+  EK_HIP_CHECK(hipEventRecord(g_ev[0], s));         // before the first launch
+  int rc = 0;
+  size_t next = 0;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < kClasses && !rc && e == hipSuccess; ++k) {
+    if (!count[k]) continue;
+    if (cs[k] != s) e = hipStreamWaitEvent(cs[k], g_ev[0], 0);
+    if (e != hipSuccess) break;
+    if (seconds) (void)hipEventRecord(g_ev[kClasses + 2 * k], cs[k]);
+    for (; next < launches.size() && launches[next].cls == k && !rc; ++next) {
+      const VLaunch &l = launches[next];
+      if (k == 0) {
+        rc = xvwindow_launch(cs[k], problem, itype, jobz, range, l.count, g_dtable + l.first, g_dwtable + l.first,
+                             g_dinfo, g_dm, g_wws + base[k]);
+        continue;
+      }
+      VWArgs a{problem, jobz, g_dtable + l.first, g_dwtable + l.first, g_dinfo, g_dm, g_wws + base[k], range, itype};
+      rc = k == 1 ? launch_class<128, 256>(cs[k], l.count, a)
+         : k == 2 ? launch_class<64, 128>(cs[k], l.count, a) : launch_class<32, 64>(cs[k], l.count, a);
+    }
+    if (seconds) (void)hipEventRecord(g_ev[kClasses + 1 + 2 * k], cs[k]);
+    if (cs[k] != s) {                               // join
+      e = hipEventRecord(g_ev[k], cs[k]);
+      if (e == hipSuccess) e = hipStreamWaitEvent(s, g_ev[k], 0);
+    }
+  }
+  if (seconds) (void)hipEventRecord(g_ev[kEvents - 1], s);   // after the last launch has ended
+  if (!rc && e == hipSuccess)
+    e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (!rc && e == hipSuccess) e = hipMemcpyAsync(m, g_dm, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  hipError_t es = hipStreamSynchronize(s);
+  if (e != hipSuccess || rc)                        // an error may have left a class outside the join
+    for (int k = 0; k < kClasses - 1; ++k)
+      if (g_side[k]) (void)hipStreamSynchronize(g_side[k]);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
+  if (seconds && !rc) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[kEvents - 1]) == hipSuccess) *seconds = (double)ms * 1e-3;
+    for (int k = 0; k < kClasses; ++k) {
+      g_class_count[k] = count[k];
+      g_class_seconds[k] = 0.0;
+      if (count[k] && hipEventElapsedTime(&ms, g_ev[kClasses + 2 * k], g_ev[kClasses + 1 + 2 * k]) == hipSuccess)
+        g_class_seconds[k] = (double)ms * 1e-3;
+    }
+  }
+  if (!rc)
+    for (int b = 0; b < batch; ++b)
+      if (n[b] == 0) { info[b] = 0; m[b] = 0; }
+  return rc;
+}
+
+static int vwindow_device_entry(int problem, int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                const double *vu, const int *il, const int *iu, double *const *dA, const int *lda,
+                                double *const *dB, const int *ldb, int *m, double *const *dw, double *const *dZ,
+                                const int *ldz, const int *zcap, int *info, double *seconds) {
+  bool nothing;
+  int rc = vwindow_check(problem, jobz, range, batch, n, vl, vu, il, iu, (const void *const *)dA, lda,
+                         (const void *const *)dB, ldb, m, (const void *const *)dw, (const void *const *)dZ, ldz, zcap,
+                         info, &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  bool work = false;
+  for (int b = 0; b < batch && !work; ++b) work = n[b] > 0;
+  if (!work) {
+    for (int b = 0; b < batch; ++b) { info[b] = 0; m[b] = 0; }
+    return 0;
+  }
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  return vwindow_device_locked(problem, itype, jobz, range, batch, n, vl, vu, il, iu, dA, lda, dB, ldb, m, dw, dZ, ldz,
+                               zcap, info, seconds);
+}
+
+static int vwindow_host_entry(int problem, int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                              const double *vu, const int *il, const int *iu, const double *const *A, const int *lda,
+                              const double *const *B, const int *ldb, int *m, double *const *w, double *const *Z,
+                              const int *ldz, const int *zcap, int *info, double *seconds) {
+  bool nothing;
+  int rc = vwindow_check(problem, jobz, range, batch, n, vl, vu, il, iu, (const void *const *)A, lda,
+                         (const void *const *)B, ldb, m, (const void *const *)w, (const void *const *)Z, ldz, zcap, info,
+                         &nothing);
+  if (rc) return rc;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  // compact device layout (ld = n[b]; Z with zcap[b] columns), a problem behind the other: the caller's padding never
+  // travels, and A and B are packed lower triangles on the way in (vbatched_host_entry)
+  std::vector<size_t> offm((size_t)batch + 1, 0), offv((size_t)batch + 1, 0), offz((size_t)batch + 1, 0);
+  for (int b = 0; b < batch; ++b) {
+    offm[b + 1] = offm[b] + (size_t)n[b] * n[b];
+    offv[b + 1] = offv[b] + (size_t)n[b];
+    offz[b + 1] = offz[b] + (jobz && n[b] > 0 ? (size_t)n[b] * zcap[b] : 0);
+  }
+  const size_t cm = offm[batch], cv = offv[batch], cz = offz[batch];
+  if (cm == 0) {
+    for (int b = 0; b < batch; ++b) { info[b] = 0; m[b] = 0; }
+    return 0;
+  }
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = g_ctx.stream;
+  auto pack = [&](const double *const *M, const int *ld, std::vector<double> &h) {
+    h.assign(cm, 0.0);
+    for (int b = 0; b < batch; ++b)
+      for (int j = 0; j < n[b]; ++j)
+        std::memcpy(&h[offm[b] + (size_t)j * n[b] + j], M[b] + (size_t)j * ld[b] + j, (size_t)(n[b] - j) * 8);
+  };
+  std::vector<double> hA, hB, hw, hZ;
+  pack(A, lda, hA);
+  if (problem) pack(B, ldb, hB);
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cm * 8);
+  if (!rc) rc = mem.alloc(&uw, cv * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cm * 8);
+  if (!rc && jobz) rc = mem.alloc(&uZ, std::max(cz, (size_t)1) * 8);
+  if (rc) return rc;
+  std::vector<double *> pA((size_t)batch), pB((size_t)batch), pw((size_t)batch), pZ((size_t)batch);
+  std::vector<int> ldc((size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    pA[b] = uA + offm[b];
+    pB[b] = problem ? uB + offm[b] : nullptr;
+    pw[b] = uw + offv[b];
+    pZ[b] = jobz ? uZ + offz[b] : nullptr;
+    ldc[b] = n[b] > 1 ? n[b] : 1;
+  }
+  EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
+  rc = vwindow_device_locked(problem, itype, jobz, range, batch, n, vl, vu, il, iu, pA.data(), ldc.data(), pB.data(),
+                             ldc.data(), m, pw.data(), pZ.data(), ldc.data(), zcap, info, seconds);
+  if (rc) return rc;
+  hw.resize(cv);
+  EK_HIP_CHECK(hipMemcpyAsync(hw.data(), uw, cv * 8, hipMemcpyDeviceToHost, s));
+  if (jobz && cz) {
+    hZ.resize(cz);
+    EK_HIP_CHECK(hipMemcpyAsync(hZ.data(), uZ, cz * 8, hipMemcpyDeviceToHost, s));
+  }
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  for (int b = 0; b < batch; ++b) {                 // only what the kernel wrote: m[b] values, m[b] columns
+    if (info[b] != 0 || n[b] == 0) continue;
+    std::memcpy(w[b], &hw[offv[b]], (size_t)m[b] * 8);
+    if (jobz)
+      for (int j = 0; j < m[b]; ++j)
+        std::memcpy(Z[b] + (size_t)j * ldz[b], &hZ[offz[b] + (size_t)j * n[b]], (size_t)n[b] * 8);
+  }
+  return 0;
+}
+
 extern "C" {
+
+// A window of eigenpairs per problem, for problems of different orders up to EK_HIP_XBATCH_NMAX
+int ek_hip_eigenpairs_window_xvbatched_device(int problem, int jobz, int range, int batch, const int *n, const double *vl,
+                                              const double *vu, const int *il, const int *iu, double *const *dA,
+                                              const int *lda, double *const *dB, const int *ldb, int *m,
+                                              double *const *dw, double *const *dZ, const int *ldz, const int *zcap,
+                                              int *info, double *seconds) {
+  return vwindow_device_entry(problem, 1, jobz, range, batch, n, vl, vu, il, iu, dA, lda, dB, ldb, m, dw, dZ, ldz, zcap,
+                              info, seconds);
+}
+
+int ek_hip_eigenpairs_window_xvbatched(int problem, int jobz, int range, int batch, const int *n, const double *vl,
+                                       const double *vu, const int *il, const int *iu, const double *const *A,
+                                       const int *lda, const double *const *B, const int *ldb, int *m, double *const *w,
+                                       double *const *Z, const int *ldz, const int *zcap, int *info, double *seconds) {
+  return vwindow_host_entry(problem, 1, jobz, range, batch, n, vl, vu, il, iu, A, lda, B, ldb, m, w, Z, ldz, zcap, info,
+                            seconds);
+}
+
+int ek_hip_sygv_window_xvbatched_device(int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                        const double *vu, const int *il, const int *iu, double *const *dA,
+                                        const int *lda, double *const *dB, const int *ldb, int *m, double *const *dw,
+                                        double *const *dZ, const int *ldz, const int *zcap, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return vwindow_device_entry(1, itype, jobz, range, batch, n, vl, vu, il, iu, dA, lda, dB, ldb, m, dw, dZ, ldz, zcap,
+                              info, seconds);
+}
+
+int ek_hip_sygv_window_xvbatched(int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                 const double *vu, const int *il, const int *iu, const double *const *A, const int *lda,
+                                 const double *const *B, const int *ldb, int *m, double *const *w, double *const *Z,
+                                 const int *ldz, const int *zcap, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return vwindow_host_entry(1, itype, jobz, range, batch, n, vl, vu, il, iu, A, lda, B, ldb, m, w, Z, ldz, zcap, info,
+                            seconds);
+}
+
+long long ek_hip_debug_window_xvbatched_budget(long long bytes) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const long long before = batched::g_vwbudget;
+  batched::g_vwbudget = bytes > 0 ? bytes : 0;
+  return before;
+}
 
 int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                      double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,

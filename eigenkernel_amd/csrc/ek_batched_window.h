@@ -55,6 +55,20 @@ struct Window {
   double *ws;                                       // LU workspace: a slot of 5 n wcols doubles per workgroup
   int wcols;                                        // vectors a slot holds
 };
+// The variable-order form (ek_hip_*_window_xvbatched*): the same fields filled from the workgroup's entry of the window
+// table, m the problem's own word and ws the base of its own LU slot.  The type is what tells stage4w how to find the two
+struct OwnWindow : Window {};
+__device__ __forceinline__ int *m_word(const Window &a) { return a.m + blockIdx.x; }
+__device__ __forceinline__ int *m_word(const OwnWindow &a) { return a.m; }
+__device__ __forceinline__ gdouble *lu_slot(const Window &a, int n, int wc) {
+  return (gdouble *)(a.ws + (size_t)blockIdx.x * 5 * (size_t)n * wc);
+}
+__device__ __forceinline__ gdouble *lu_slot(const OwnWindow &a, int, int) { return (gdouble *)a.ws; }
+
+using batched::WDesc;                              // the window table's entry (ek_api_internal.h)
+__device__ __forceinline__ OwnWindow own_window(int range, const WDesc &e, int *m, double *ws) {
+  return OwnWindow{{range, e.il, e.iu, e.zcap, e.vl, e.vu, m, ws + e.lu, e.wcols}};
+}
 
 // negative pivots of the LDL^T of T - x I at K points (ek_stebz.hip's sturm_counts on LDS operands)
 template <int K>
@@ -187,8 +201,10 @@ __device__ __forceinline__ void gram_schmidt_rows(gdouble *S, int n, int m, int 
 // identity.  False: the problem has ended (info and m[b] written): an empty window, -20, or a failure.
 // OWNER: nothing but a name.  s_rounds below is one LDS variable per instantiation of this function; a kernel passes a
 // value of its own, so that no two kernels share the variable and each keeps it in its own LDS frame.
-template <int NC, int NW, typename LAY = ColumnsInLds, int OWNER = 0>
-__device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int wex, typename LAY::elem *S, double *sd,
+// WINDOW: Window (the uniform calls: the m word and the LU slot at blockIdx.x) or OwnWindow (the variable-order calls: both
+// are the problem's own).
+template <int NC, int NW, typename LAY = ColumnsInLds, int OWNER = 0, typename WINDOW = Window>
+__device__ __forceinline__ bool stage4w(const WINDOW &a, int jobz, int n, int wex, typename LAY::elem *S, double *sd,
                                         double *se,
                                         double *sv, double *sw, double *sp, double *sl, double *red, int &phase,
                                         int *srank, gdouble *w, int *info, int &mout) {
@@ -199,7 +215,7 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
   typedef typename LAY::elem elem;
   const int t = threadIdx.x, r = t % NC, sub = t / NC;
   const bool row = r < n;
-  int *mword = a.m + blockIdx.x;
+  int *mword = m_word(a);
   __shared__ int s_rounds;
   mout = 0;
 
@@ -340,7 +356,7 @@ __device__ __forceinline__ bool stage4w(const Window &a, int jobz, int n, int we
 
   // lane t < m: vector t.  LU of T - lambda I in the slot, element (array q, row i) of vector t at ((q n + i) wcols + t)
   const int wc = a.wcols;
-  gdouble *lu = (gdouble *)(a.ws + (size_t)blockIdx.x * 5 * (size_t)n * wc) + t;
+  gdouble *lu = lu_slot(a, n, wc) + t;
   const bool lane = t < m;
   elem *x = S + (lane ? t : 0) * VS;
   const int mypos = lane ? pos[t] : -1;

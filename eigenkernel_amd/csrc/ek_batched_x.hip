@@ -48,6 +48,8 @@
 // ek_hip_sygv_window_xbatched*: XWArgs with CONG for types 2 and 3; type 3's Z <- L Z works on those rows too
 // (DESIGN.md 33).
 //
+// ek_hip_*_window_xvbatched*: a fourth argument type, XVWArgs: the table form with a window per problem.
+//
 // ek_hip_*_xvbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in entry
 // blockIdx.x of its launch's slice of the variable-order table (ek_batched.hip builds it) instead of at blockIdx.x *
 // stride; the image slot is blockIdx.x either way.
@@ -95,6 +97,19 @@ struct XWArgs : Args {
   bwindow::Window win;
 };
 
+// ek_hip_eigenpairs_window_xvbatched*: XVArgs and a window per problem -- entry blockIdx.x of `wtable` beside entry
+// blockIdx.x of `table`, the count to m[entry.index], the LU slot at lu + wtable[blockIdx.x].lu
+struct XVWArgs {
+  int problem, jobz;
+  const Desc *table;
+  const bwindow::WDesc *wtable;
+  int *info;
+  int *m;
+  double *ws;
+  double *lu;
+  int range, itype;
+};
+
 // What a workgroup works on, whichever way it found it.  The pointers are typed as global (gdouble).  n is the same in
 // every lane either way (a kernel argument or a load at an address that depends on blockIdx.x alone): every barrier and
 // every loop bound depends on it.
@@ -118,12 +133,23 @@ __device__ __forceinline__ Problem locate(const XVArgs &a) {
   return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz,
           (gdouble *)(a.ws + (size_t)blockIdx.x * kSlot), a.info + d.index};
 }
+__device__ __forceinline__ Problem locate(const XVWArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz,
+          (gdouble *)(a.ws + (size_t)blockIdx.x * kSlot), a.info + d.index};
+}
+// the window of stage 4W: the call's, or the workgroup's own
+__device__ __forceinline__ const bwindow::Window &window(const XWArgs &a) { return a.win; }
+__device__ __forceinline__ bwindow::OwnWindow window(const XVWArgs &a) {
+  return bwindow::own_window(a.range, a.wtable[blockIdx.x], a.m + a.table[blockIdx.x].index, a.lu);
+}
 // Z where the kernel first needs it, behind the exit of jobz = 0 (whose callers pass no Z): the uniform form does its
 // address arithmetic only there, as it always did; the table form loaded the pointer with the rest of its entry
 __device__ __forceinline__ gdouble *vectors(const Args &a, const Problem &) {
   return (gdouble *)(a.Z + (long long)blockIdx.x * a.sZ);
 }
 __device__ __forceinline__ gdouble *vectors(const XVArgs &, const Problem &p) { return p.Z; }
+__device__ __forceinline__ gdouble *vectors(const XVWArgs &, const Problem &p) { return p.Z; }
 
 // y[i * SY] -= x[i] * a for i = i0, i0 + STEP, ... < i1; y in the image, x in LDS: eight loads before the first store
 template <int SY, int STEP>
@@ -185,11 +211,17 @@ __device__ __forceinline__ void cong_pass(gdouble *S, const gdouble *B, int ldb,
 
 // CONG: the instantiation for types 2 and 3 (C = L^T A L; the host picks it when problem == 1 and itype != 1).  With
 // CONG = false nothing of those types is compiled in: the standard problem and type 1 run the code they always ran.
-// ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or XVArgs (a table entry).
-// WIN (ARGS = XWArgs): stage 4W for QL, and stage 5 on the window's m rows of the image.
+// ARGS: how the workgroup finds its problem -- Args (one order, strided: blockIdx.x * stride) or XVArgs (a table entry);
+// XWArgs and XVWArgs are the two with a window.
+// WIN (ARGS = XWArgs or XVWArgs): stage 4W for QL, and stage 5 on the window's m rows of the image.
+// The table-and-window instantiations are held to four waves a SIMD, that is 128 vector registers and two workgroups on a
+// compute unit like the other three argument types: left alone, one of the two came out at 129.  The attribute's value for
+// the other types, 2, is what 512 threads imply anyway, and their code is unchanged by it
 template <bool CONG, typename ARGS = Args>
-__global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
-  constexpr bool WIN = std::is_same<ARGS, XWArgs>::value;
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(std::is_same<ARGS, XVWArgs>::value ? 4 : 2)))
+void xbatched_kernel(ARGS a) {
+  constexpr bool VWIN = std::is_same<ARGS, XVWArgs>::value;
+  constexpr bool WIN = VWIN || std::is_same<ARGS, XWArgs>::value;
   __shared__ double sd[NC], se[NC], st[NC];         // d, e, tau: alive from stage 3 to the end
   __shared__ double sv[NC], sw[NC];                 // stage 1: the scaled column; 3: v, w; 4: c, s of a sweep
   __shared__ double sp[P * NC];                     // partial sums of a pair
@@ -408,8 +440,9 @@ __global__ __launch_bounds__(T) void xbatched_kernel(ARGS a) {
   int nz = n;                                       // pairs that stage 5 works on: n, or the window's m
   if constexpr (WIN) {
     // ---- 4W: the window's values by bisection, their vectors by inverse iteration as rows 0 .. nz - 1 of the image
-    if (!bwindow::stage4w<NC, NW, bwindow::RowsInMemory, CONG>(a.win, a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red,
-                                                               phase, srank, W, info, nz))
+    constexpr int OWNER = VWIN ? 2 + CONG : CONG;   // s_rounds: one variable per kernel
+    if (!bwindow::stage4w<NC, NW, bwindow::RowsInMemory, OWNER>(window(a), a.jobz, n, wex, S, sd, se, sv, sw, sp, sl, red,
+                                                                phase, srank, W, info, nz))
       return;
   } else {
     const bool flip = fabs(sd[0]) > fabs(sd[n - 1]);
@@ -705,6 +738,21 @@ int xwindow_launch(hipStream_t s, int problem, int itype, int jobz, int n, int c
            {range, il, iu, zcap, vl, vu, dm, lu, wcols}};
   if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XWArgs>), dim3(count), dim3(T), 0, s, a);
   else hipLaunchKernelGGL((xbatched_kernel<false, XWArgs>), dim3(count), dim3(T), 0, s, a);
+  EK_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ek_hip_*_window_xvbatched*: one launch of `count` <= slots entries of the two tables (device; orders above
+// EK_HIP_BATCH_NMAX) through the table-and-window instantiation; dinfo and dm hold a word per problem of the caller's
+// batch; lu is the base of the class's region of the LU workspace, the entries' offsets counted from it.  g_mu held,
+// xwindow_prepare(slots) done
+int xvwindow_launch(hipStream_t s, int problem, int itype, int jobz, int range, int count, const batched::Desc *table,
+                    const batched::WDesc *wtable, int *dinfo, int *dm, double *lu) {
+  using namespace batchedx;
+  if ((size_t)count > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
+  XVWArgs a{problem, jobz, table, wtable, dinfo, dm, g_ws, lu, range, itype};
+  if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XVWArgs>), dim3(count), dim3(T), 0, s, a);
+  else hipLaunchKernelGGL((xbatched_kernel<false, XVWArgs>), dim3(count), dim3(T), 0, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -237,6 +237,15 @@ def load_library(path=None):
         "ek_hip_sygv_xvbatched_device": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_sygv_xvbatched": (c_int, [c_int, c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp]),
         "ek_hip_debug_xvbatched_last": (c_int, [_dp, _ip]),
+        "ek_hip_eigenpairs_window_xvbatched_device": (c_int, [c_int, c_int, c_int, c_int, _ip, _dp, _dp, _ip, _ip, vp, _ip,
+                                                              vp, _ip, _ip, vp, vp, _ip, _ip, _ip, _dp]),
+        "ek_hip_eigenpairs_window_xvbatched": (c_int, [c_int, c_int, c_int, c_int, _ip, _dp, _dp, _ip, _ip, vp, _ip, vp,
+                                                       _ip, _ip, vp, vp, _ip, _ip, _ip, _dp]),
+        "ek_hip_sygv_window_xvbatched_device": (c_int, [c_int, c_int, c_int, c_int, _ip, _dp, _dp, _ip, _ip, vp, _ip, vp,
+                                                        _ip, _ip, vp, vp, _ip, _ip, _ip, _dp]),
+        "ek_hip_sygv_window_xvbatched": (c_int, [c_int, c_int, c_int, c_int, _ip, _dp, _dp, _ip, _ip, vp, _ip, vp, _ip,
+                                                 _ip, vp, vp, _ip, _ip, _ip, _dp]),
+        "ek_hip_debug_window_xvbatched_budget": (ctypes.c_longlong, [ctypes.c_longlong]),
         "ek_hip_check_xvbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
         "ek_hip_check_xvbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
         "ek_hip_check_sygv_xvbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp,
@@ -307,6 +316,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_sygv_xbatched_device", "ek_hip_check_sygv_xbatched",
     "ek_hip_eigenpairs_xvbatched_device", "ek_hip_eigenpairs_xvbatched", "ek_hip_sygv_xvbatched_device",
     "ek_hip_sygv_xvbatched", "ek_hip_debug_xvbatched_last",
+    "ek_hip_eigenpairs_window_xvbatched_device", "ek_hip_eigenpairs_window_xvbatched",
+    "ek_hip_sygv_window_xvbatched_device", "ek_hip_sygv_window_xvbatched", "ek_hip_debug_window_xvbatched_budget",
     "ek_hip_check_xvbatched_device", "ek_hip_check_xvbatched", "ek_hip_check_sygv_xvbatched_device",
     "ek_hip_check_sygv_xvbatched", "ek_hip_debug_check_xvbatched_last",
     "ek_hip_debug_stage_leaves256", "ek_hip_debug_set_sygst_direct", "ek_hip_debug_sygst_scratch",
@@ -1124,6 +1135,93 @@ def sygv_xvbatched(As, Bs, itype=1, vectors=True, seconds=None):
     if Bs is None:
         raise ValueError("Bs is required")
     return _vbatched_call("ek_hip_sygv_xvbatched", int(itype), As, Bs, vectors, seconds)
+
+
+def _window_vbatched_call(entry, first, As, Bs, il, iu, vl, vu, vectors, zcap, seconds):
+    """ek_hip_eigenpairs_window_xvbatched / ek_hip_sygv_window_xvbatched on sequences of square arrays; `first` is the
+    first argument (problem or itype); il, iu, vl, vu, zcap: None, a scalar for every problem, or a value per problem."""
+    lib = load_library()
+    Af = []
+    for M in As:
+        M = np.asarray(M, dtype=np.float64)
+        if M.ndim != 2 or M.shape[0] != M.shape[1]:
+            raise ValueError("every A must be a square 2-D array")
+        Af.append(np.asfortranarray(M))
+    batch = len(Af)
+    Bf = None
+    if Bs is not None:
+        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
+        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
+            raise ValueError("Bs must hold one array of A's shape per problem")
+    by_value = vl is not None or vu is not None
+    if by_value and (il is not None or iu is not None):
+        raise ValueError("give either il / iu or vl / vu")
+    if batch == 0:
+        return [], ([] if vectors else None), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
+
+    def per_problem(x, default, dtype):
+        if x is None:
+            x = default
+        x = np.asarray(x, dtype=dtype)
+        if x.ndim == 0:
+            x = np.full(batch, x, dtype=dtype)
+        if x.shape != (batch,):
+            raise ValueError("a window argument must be a scalar or hold one value per problem")
+        return np.ascontiguousarray(x)
+
+    vl = per_problem(vl, -np.inf, np.float64)
+    vu = per_problem(vu, np.inf, np.float64)
+    il = per_problem(il, 1, np.int32)
+    iu = per_problem(iu, n, np.int32)
+    zcap = per_problem(zcap, n if by_value else np.maximum(iu - il + 1, 0), np.int32)
+    ld = np.maximum(n, 1).astype(np.int32)
+    w = [np.zeros(k) for k in n]
+    Z = [np.zeros((n[b], max(int(zcap[b]), 0)), order="F") for b in range(batch)] if vectors else None
+    m = np.zeros(batch, dtype=np.int32)
+    info = np.zeros(batch, dtype=np.int32)
+
+    def table(arrays):
+        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
+
+    rc = getattr(lib, entry)(first, 1 if vectors else 0, 1 if by_value else 0, batch, _I(n), _P(vl), _P(vu), _I(il),
+                             _I(iu), table(Af), _I(ld), table(Bf) if Bf is not None else None, _I(ld), _I(m), table(w),
+                             table(Z) if vectors else None, _I(ld), _I(zcap), _I(info),
+                             _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError(entry + " failed", rc)
+    keep = [int(m[b]) if info[b] == 0 else 0 for b in range(batch)]
+    return ([w[b][:keep[b]] for b in range(batch)],
+            [Z[b][:, :keep[b]] for b in range(batch)] if vectors else None, m, info)
+
+
+def eigenpairs_window_xvbatched(As, Bs=None, il=None, iu=None, vl=None, vu=None, vectors=True, zcap=None, seconds=None):
+    """A window of eigenpairs PER PROBLEM for problems of different orders up to XBATCH_NMAX in one call
+    (ek_hip_eigenpairs_window_xvbatched): As (and Bs, SPD) sequences of square 2-D arrays as in eigenpairs_xvbatched.  By
+    index: il, iu (1-based; a scalar for every problem or one value per problem; defaults 1 and the order).  By value: vl
+    and / or vu likewise -> the eigenvalues in (vl[b], vu[b]].  zcap: columns of Z per problem (default: iu - il + 1 by
+    index, the order by value).  Returns (list of w, list of Z or None, m, info): w[b] the m[b] values of problem b
+    ascending, Z[b] its n[b] x m[b] vectors; both empty where info[b] != 0.  info[b] as in eigenpairs_window_batched
+    (-20: m[b] is the count).  Each problem's bits are those of eigenpairs_window_xbatched on that pair and window alone.
+    As and Bs are not modified.  Raises ValueError for bad shapes, SolverError only when the call itself fails."""
+    return _window_vbatched_call("ek_hip_eigenpairs_window_xvbatched", 0 if Bs is None else 1, As, Bs, il, iu, vl, vu,
+                                 vectors, zcap, seconds)
+
+
+def sygv_window_xvbatched(As, Bs, itype=1, il=None, iu=None, vl=None, vu=None, vectors=True, zcap=None, seconds=None):
+    """eigenpairs_window_xvbatched for DSYGV's three problem types (ek_hip_sygv_window_xvbatched), itype one value for the
+    whole call; each problem's bits are those of sygv_window_xbatched on that pair and window alone.  An itype outside
+    1 .. 3 raises SolverError with info -1."""
+    if Bs is None:
+        raise ValueError("Bs is required")
+    return _window_vbatched_call("ek_hip_sygv_window_xvbatched", int(itype), As, Bs, il, iu, vl, vu, vectors, zcap,
+                                 seconds)
+
+
+def window_xvbatched_budget(nbytes):
+    """Bytes of LU workspace a launch of eigenpairs_window_xvbatched may hold (ek_hip_debug_window_xvbatched_budget): 0
+    restores the defaults.  Returns the previous value.  No result depends on it."""
+    return int(load_library().ek_hip_debug_window_xvbatched_budget(int(nbytes)))
 
 
 CHECK_NOUT = 4   # EK_HIP_CHECK_NOUT: a_norm, res_ave, res_max, orthogonality

@@ -570,6 +570,64 @@ int ek_hip_sygv_window_xbatched(int itype, int jobz, int range, int n, int batch
                                 long long strideB, int *m, double *w, double *Z, int ldz, int zcap, long long strideZ,
                                 int *info, double *seconds);
 
+/* A WINDOW of eigenpairs PER PROBLEM for problems of DIFFERENT orders up to EK_HIP_XBATCH_NMAX in one call -- what
+ * ek_hip_*_xvbatched* are to ek_hip_*_xbatched*, for ek_hip_eigenpairs_window_xbatched* and ek_hip_sygv_window_xbatched*.
+ * Twenty arguments.  problem (itype), jobz (0 / 1) and range (0 = 'I', 1 = 'V') are one value for the call; everything else
+ * is per problem.  n, vl, vu, il, iu, lda, ldb, m, ldz, zcap, info and the four pointer arrays are HOST arrays of `batch`
+ * entries in both forms; the pointers inside dA, dB, dw, dZ are device addresses in the device form and host addresses in
+ * the host form.  Problem b: order n[b], the window il[b] .. iu[b] ('I'; vl, vu not looked at, may be NULL) or
+ * (vl[b], vu[b]] ('V'; il, iu not looked at, may be NULL), dw[b] with room for n[b] doubles of which m[b] are written,
+ * dZ[b] n[b] x zcap[b] with ldz[b] >= max(1, n[b]) of which the columns 0 .. m[b]-1 are written.
+ * Return value: 0, or -k for argument k, decided before any device work and without dereferencing a pointer of the pointer
+ * arrays, the first offending argument deciding; per-problem conditions hold for the problems of order > 0:
+ *   -1 problem (itype outside 1 .. 3, first)   -2 jobz   -3 range   -4 batch < 0 (batch = 0: 0, nothing looked at)
+ *   -5 n NULL or an order outside 0 .. EK_HIP_XBATCH_NMAX
+ *   -6 vl NULL or a NaN, -7 vu NULL, a NaN or vl[b] >= vu[b] ('V' only)
+ *   -8 il NULL or il[b] outside 1 .. n[b], -9 iu NULL or iu[b] outside il[b] .. n[b] ('I' only)
+ *   -10 / -11 A / lda   -12 / -13 B / ldb (problem 1; always for the sygv forms)   -14 m   -15 dw
+ *   -16 / -17 Z / ldz (jobz = 1 only; dZ[b] may be NULL where zcap[b] = 0)
+ *   -18 zcap NULL, zcap[b] < 0, or 'I' with zcap[b] < iu[b] - il[b] + 1 (with and without vectors)   -19 info
+ *   <= -1000 a HIP runtime error
+ * n[b] = 0 references nothing and gets info[b] = 0, m[b] = 0; a batch of nothing but empty problems is filled on the host.
+ * THE SAME BITS AS THE UNIFORM CALL: problem b's m, info, w[0 .. m), Z[:, 0 .. m) and the in-place images of dA[b] and dB[b]
+ * are bit for bit what ek_hip_eigenpairs_window_xbatched_device (ek_hip_sygv_window_xbatched_device) returns for
+ * (n[b], A, B, window b, zcap[b]) alone -- wherever the problem sits, whatever surrounds it, in whichever launch, under
+ * either setting of ek_hip_debug_vbatched_streams, in the host and the device form.  So the value of index k depends on
+ * (n, A, B, k) alone, itype = 1 is the eigenpairs entry with problem = 1, and types 2 and 3 share w and m.
+ * info[b] and m[b] are the uniform window call's: 0 (always with finite w), the failing pivot of B, -5, -20 ('V' with
+ * m[b] > zcap[b] under jobz = 1: m[b] is the count, nothing of that problem's w or Z is written), 100000 + n[b] + 1,
+ * 200000 + k.  A failed problem touches only its own slots.  Strictly upper triangles, rows n[b] .. ld-1, the rest of w[b],
+ * the columns of Z[b] from m[b] on and whatever lies between problems are neither read nor written.  The problems must not
+ * overlap in memory (not checked); NOT COLLECTIVE; the call synchronises; *seconds (may be NULL) is the device time from
+ * before the first launch to after the last.
+ * Problem b runs in the class its order picks (256 / 128 / 64 / 32), the classes largest first beside each other on streams
+ * of their own, a class's problems in descending order.  A class runs in launches of consecutive problems: a launch ends at
+ * 1024 problems (ek_hip_debug_window_batched_chunk, ek_hip_debug_window_xbatched_chunk) or where the LU slots of inverse
+ * iteration (5 n[b] wcols[b] doubles, wcols[b] = iu[b]-il[b]+1 or min(zcap[b], n[b]); jobz = 1) would pass the class's
+ * budget: 1 GiB above EK_HIP_BATCH_NMAX, 256 MiB shared in equal parts by the classes present below it.  Workspace: the
+ * widest launch of every class in LU slots, an image per problem of the widest launch above EK_HIP_BATCH_NMAX, two tables
+ * and two words per problem; kept until ek_hip_finalize. */
+int ek_hip_eigenpairs_window_xvbatched_device(int problem, int jobz, int range, int batch, const int *n, const double *vl,
+                                              const double *vu, const int *il, const int *iu, double *const *dA,
+                                              const int *lda, double *const *dB, const int *ldb, int *m,
+                                              double *const *dw, double *const *dZ, const int *ldz, const int *zcap,
+                                              int *info, double *seconds);
+/* host addresses in A, B, w, Z: A and B are left untouched, their lower triangles travel packed (ld = n[b]) in one copy per
+ * matrix kind, and only what the kernel wrote comes back: m[b] values of w[b], m[b] columns of Z[b], of the problems with
+ * info[b] = 0 */
+int ek_hip_eigenpairs_window_xvbatched(int problem, int jobz, int range, int batch, const int *n, const double *vl,
+                                       const double *vu, const int *il, const int *iu, const double *const *A,
+                                       const int *lda, const double *const *B, const int *ldb, int *m, double *const *w,
+                                       double *const *Z, const int *ldz, const int *zcap, int *info, double *seconds);
+int ek_hip_sygv_window_xvbatched_device(int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                        const double *vu, const int *il, const int *iu, double *const *dA,
+                                        const int *lda, double *const *dB, const int *ldb, int *m, double *const *dw,
+                                        double *const *dZ, const int *ldz, const int *zcap, int *info, double *seconds);
+int ek_hip_sygv_window_xvbatched(int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                 const double *vu, const int *il, const int *iu, const double *const *A, const int *lda,
+                                 const double *const *B, const int *ldb, int *m, double *const *w, double *const *Z,
+                                 const int *ldz, const int *zcap, int *info, double *seconds);
+
 /* The acceptance checks and the inverse participation ratios of EVERY problem of a batch -- what ek_hip_residual_device,
  * ek_hip_orthogonality_device and ek_hip_ipratios_device are to one problem, with the same normalisations (the
  * reference's: verifier.f90:75-204, :233-330, distribute_matrix.f90:18-78), for the eigenpairs that

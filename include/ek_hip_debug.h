@@ -178,6 +178,10 @@ int ek_hip_debug_window_batched_chunk(int problems);
    many, each chunk reusing the same image and LU slots).  0 (or less) restores the default of 1024; returns the previous
    value.  A tuning and test hook: no result depends on it. */
 int ek_hip_debug_window_xbatched_chunk(int problems);
+/* ek_hip_*_window_xvbatched*: bytes of LU workspace the slots of one launch may sum to, for every class (a launch still
+   takes at least one problem).  0 (or less) restores the defaults (1 GiB above EK_HIP_BATCH_NMAX, 256 MiB shared by the
+   classes present below it); returns the previous value.  A tuning and test hook: no result depends on it. */
+long long ek_hip_debug_window_xvbatched_budget(long long bytes);
 /* ek_hip_check_xbatched* and ek_hip_check_sygv_xbatched*, orders above EK_HIP_BATCH_NMAX: checked problems per launch (a batch
    runs in chunks of that many, each chunk reusing the same scratch for S = B Z; types 2 and 3: for the products, L and W).
    0 (or less) restores the default of 1024; returns the previous value.  A tuning and test hook: no result depends on it. */

@@ -45,6 +45,15 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  128: ek_hip_sygv_window_xbatched_device) against the full call of the same
                                                  type and against the type-1 window call
 
+  python tools/batched_timing.py --mixed --window 0.125 [--mixed-batch 512] [--mixed-orders 8,256] [--itype 1]
+                                                 the variable-order window call (ek_hip_eigenpairs_window_xvbatched_device;
+                                                 --itype 2 / 3: ek_hip_sygv_window_xvbatched_device), the lowest
+                                                 max(1, fraction n[b]) pairs of every problem with vectors, against a
+                                                 uniform window call per distinct order, the full variable call
+                                                 (ek_hip_*_xvbatched_device) and one uniform window call with every
+                                                 problem padded to the largest order; device times, a stream per class
+                                                 and one stream, the classes' times and counts
+
 Per (problem, jobz, n, batch): one warm-up of each kind, then three rounds that alternate the kinds, best by wall clock
 (both calls synchronise; both work in place, so the inputs are restored outside the clock).  The loop is timed over
 min(batch, --loop-max) pairs and scaled to the batch.  "device" is the launch's own time (events around it)."""
@@ -463,6 +472,117 @@ def sygv_window_rows(lib, sizes, batches, fractions, itype):
             c.close()
 
 
+def mixed_window(lib, batch, lo, hi, fraction, itype):
+    """The variable-order window call against its three alternatives (module docstring): generalized problems of orders
+    drawn uniformly from lo .. hi, the lowest max(1, fraction n) pairs with vectors.  One warm-up of each kind, then three
+    rounds that alternate the kinds, best device time; the inputs are restored outside the clock."""
+    I = ctypes.POINTER(ctypes.c_int)
+    D = ctypes.POINTER(ctypes.c_double)
+    rng = np.random.default_rng(2024)
+    orders = np.sort(rng.integers(lo, hi + 1, size=batch))         # the problems of an order stand behind each other
+    distinct = np.unique(orders)
+    N = int(orders.max())
+    seeds = {int(n): pairs(500 + int(n), 1, int(n)) for n in distinct}
+    offm = np.concatenate([[0], np.cumsum(orders.astype(np.int64) ** 2)])
+    offw = np.concatenate([[0], np.cumsum(orders.astype(np.int64))])
+    hA, hB = np.empty(offm[-1]), np.empty(offm[-1])
+    PA, PB = np.zeros((batch, N, N)), np.zeros((batch, N, N))
+    PA[:, np.arange(N), np.arange(N)] = 1e6                         # the padding's eigenvalues lie above every window
+    PB[:, np.arange(N), np.arange(N)] = 1.0
+    for b, n in enumerate(orders):
+        A, B = seeds[int(n)]
+        hA[offm[b]:offm[b + 1]], hB[offm[b]:offm[b + 1]] = A[0].ravel(), B[0].ravel()
+        PA[b, :n, :n], PB[b, :n, :n] = A[0], B[0]
+    PA, PB = PA.ravel(), PB.ravel()
+    keep = []
+
+    def alloc(nbytes):
+        p = ctypes.c_void_p()
+        assert lib.ek_hip_malloc(ctypes.byref(p), int(max(nbytes, 8))) == 0
+        keep.append(p)
+        return p
+
+    def put(p, a):
+        assert lib.ek_hip_memcpy_h2d(p, a.ctypes.data, a.nbytes) == 0
+
+    dA, dB, dZ, dw = alloc(hA.nbytes), alloc(hB.nbytes), alloc(hA.nbytes), alloc(offw[-1] * 8)
+    dPA, dPB, dPZ, dPw = alloc(PA.nbytes), alloc(PB.nbytes), alloc(PA.nbytes), alloc(batch * N * 8)
+    perm = rng.permutation(batch)
+
+    def table(base, off):
+        return (ctypes.c_void_p * batch)(*[base.value + int(off[b]) * 8 for b in perm])
+
+    def at(p, off):
+        return ctypes.c_void_p(p.value + int(off) * 8)
+
+    tA, tB, tw, tZ = table(dA, offm), table(dB, offm), table(dw, offw), table(dZ, offm)
+    n32 = orders[perm].astype(np.int32)
+    il = np.ones(batch, dtype=np.int32)
+    iu = np.maximum(1, (fraction * n32).astype(np.int32)).astype(np.int32)
+    m, info = np.zeros(batch, dtype=np.int32), np.zeros(batch, dtype=np.int32)
+    sec = np.zeros(1)
+    ip = lambda a: a.ctypes.data_as(I)              # noqa: E731
+    first = itype if itype != 1 else 1
+    wentry = lib.ek_hip_sygv_window_xvbatched_device if itype != 1 else lib.ek_hip_eigenpairs_window_xvbatched_device
+    fentry = lib.ek_hip_sygv_xvbatched_device if itype != 1 else lib.ek_hip_eigenpairs_xvbatched_device
+    uentry = lib.ek_hip_sygv_window_xbatched_device if itype != 1 else lib.ek_hip_eigenpairs_window_xbatched_device
+
+    def variable():
+        put(dA, hA); put(dB, hB)
+        rc = wentry(first, 1, 0, batch, ip(n32), None, None, ip(il), ip(iu), tA, ip(n32), tB, ip(n32), ip(m), tw, tZ,
+                    ip(n32), ip(iu), ip(info), sec.ctypes.data_as(D))
+        assert rc == 0 and not info.any() and (m == iu).all(), (rc, info[info != 0][:4])
+        return float(sec[0])
+
+    def full():
+        put(dA, hA); put(dB, hB)
+        rc = fentry(first, 1, batch, ip(n32), tA, ip(n32), tB, ip(n32), tw, tZ, ip(n32), ip(info), sec.ctypes.data_as(D))
+        assert rc == 0 and not info.any()
+        return float(sec[0])
+
+    def per_order():
+        put(dA, hA); put(dB, hB)
+        t = 0.0
+        for n in distinct:
+            n = int(n)
+            f, c, k = int(np.searchsorted(orders, n)), int((orders == n).sum()), max(1, int(fraction * n))
+            rc = uentry(first, 1, 0, n, c, 0.0, 0.0, 1, k, at(dA, offm[f]), n, n * n, at(dB, offm[f]), n, n * n, ip(m),
+                        at(dw, offw[f]), at(dZ, offm[f]), n, k, n * n, ip(info), sec.ctypes.data_as(D))
+            assert rc == 0 and not info[:c].any()
+            t += float(sec[0])
+        return t
+
+    kmax = max(1, int(fraction * N))
+
+    def padded():
+        put(dPA, PA); put(dPB, PB)
+        rc = uentry(first, 1, 0, N, batch, 0.0, 0.0, 1, kmax, dPA, N, N * N, dPB, N, N * N, ip(m), dPw, dPZ, N, kmax,
+                    N * N, ip(info), sec.ctypes.data_as(D))
+        assert rc == 0 and not info.any()
+        return float(sec[0])
+
+    print("# %d generalized problems (itype %d) of orders %d..%d (%d distinct), the lowest max(1, %g n) pairs with vectors"
+          % (batch, itype, lo, hi, len(distinct), fraction))
+    for streams in (3, 1):
+        lib.ek_hip_debug_vbatched_streams(streams)
+        tv, tf, tg, tp = [], [], [], []
+        variable(); full(); per_order(); padded()      # warm-up
+        for _ in range(3):
+            tv.append(variable()); tf.append(full()); tg.append(per_order()); tp.append(padded())
+        variable()
+        csec, ccnt = np.zeros(4), np.zeros(4, dtype=np.int32)
+        lib.ek_hip_debug_xvbatched_last(csec.ctypes.data_as(D), ip(ccnt))
+        print("  streams %d: variable window %.3f ms | full variable call %.3f ms (window / full %.3f) | window call per "
+              "order %.3f ms (%.1f x) | padded to %d: %.3f ms (%.2f x)"
+              % (streams, min(tv) * 1e3, min(tf) * 1e3, min(tv) / min(tf), min(tg) * 1e3, min(tg) / min(tv), N,
+                 min(tp) * 1e3, min(tp) / min(tv)))
+        print("             classes 256 / 128 / 64 / 32: %s ms, %s problems"
+              % (" / ".join("%.3f" % (x * 1e3) for x in csec), " / ".join(str(x) for x in ccnt)), flush=True)
+    lib.ek_hip_debug_vbatched_streams(3)
+    for p in keep:
+        lib.ek_hip_free(p)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="30,64,128")
@@ -484,6 +604,12 @@ def main():
     args = ap.parse_args()
     lib = solver.load_library()
     assert lib.ek_hip_init(0) == 0
+    if args.mixed and args.window:
+        lo, hi = (int(x) for x in args.mixed_orders.split(","))
+        for fraction in (float(x) for x in args.window.split(",")):
+            mixed_window(lib, args.mixed_batch, lo, hi, fraction, args.itype)
+        lib.ek_hip_finalize()
+        return
     if args.window and args.itype != 1:
         sygv_window_rows(lib, [int(x) for x in args.sizes.split(",")], [int(x) for x in args.batches.split(",")],
                          [float(x) for x in args.window.split(",")], args.itype)

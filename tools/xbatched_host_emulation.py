@@ -9,7 +9,9 @@ thread, __syncthreads() as a barrier and __shared__ as static storage; one probl
       --vl, --vu  the same by value: the pairs in (vl, vu]; a missing bound is infinite
       --case   all_equal: A = 3 B (problem 0: 3 I), one cluster of n, a round per wanted vector: the Gram-Schmidt maps
       --table  the kernel's table instantiation (ek_hip_*_xvbatched*): the problem as the one entry of a variable-order
-               table, image slot 0, the status word at info[entry.index]
+               table, image slot 0, the status word at info[entry.index]; with --window or --vl / --vu the
+               table-and-window instantiation (ek_hip_*_window_xvbatched*): the window in the entry of a second
+               table, the count at m[entry.index], the LU slot at the entry's offset into a workspace of NaNs
       --itype  DSYGV's problem type (problem 1): 2 and 3 run the kernel's CONG instantiation; with
                --window or --vl / --vu the CONG instantiation of the window kernel (ek_hip_sygv_window_xbatched*,
                DESIGN.md 33), judged with the type's quantities on the window's m columns
@@ -44,7 +46,7 @@ args = ap.parse_args()
 by_value = args.vl is not None or args.vu is not None
 window = args.window is not None or by_value
 assert not (args.window and by_value), "--window or --vl / --vu"
-assert not window or (not args.table and not args.stop), "the window: uniform form, --stop 0"
+assert not window or not args.stop, "the window: --stop 0"
 assert args.itype == 1 or (args.problem == 1 and args.stop != 1), "--itype 2|3: problem 1, and --stop 0 or 2"
 CSRC = os.path.join(ROOT, "eigenkernel_amd", "csrc")
 src = open(os.path.join(CSRC, "ek_batched_x.hip")).read()
@@ -65,6 +67,9 @@ internal = open(os.path.join(ROOT, "eigenkernel_amd", "csrc", "ek_api_internal.h
 assert internal.count("struct Desc {") == 1, "struct Desc not found exactly once in ek_api_internal.h"
 desc = internal[internal.index("struct Desc {"):]
 desc = desc[:desc.index("};") + 2]
+assert internal.count("struct WDesc {") == 1, "struct WDesc not found exactly once in ek_api_internal.h"
+wdesc = internal[internal.index("struct WDesc {"):]
+desc += "\n" + wdesc[:wdesc.index("};") + 2]
 hdr = r'''
 #include <barrier>
 #include <thread>
@@ -81,6 +86,7 @@ hdr = r'''
 #define __device__
 #define __forceinline__ inline
 #define __launch_bounds__(x)
+#define __attribute__(x)                            // the occupancy attribute of the kernel: nothing for the host
 #define __shared__ static
 struct Idx { int x; };
 static thread_local Idx threadIdx, blockIdx;
@@ -132,15 +138,26 @@ int main(int argc, char **argv) {
     const double vl = atof(argv[8]), vu = atof(argv[9]);
     const int zcap = range ? n : iu - il + 1;
     int m = 777, winfo = 777;
-    std::vector<double> lu((size_t)5 * n * zcap, NAN);
+    const size_t luoff = table ? 1000 : 0;             // the table form: a slot that does not start at the workspace's base
+    std::vector<double> lu(luoff + (size_t)5 * n * zcap, NAN);
+    int ms[3] = {777, 777, 777}, winfos[3] = {777, 777, 777};
+    Desc wd{A.data(), problem ? B.data() : nullptr, w.data(), Z.data(), n, n, n, n, 2, 0};
+    ek::batched::WDesc ww{vl, vu, il, iu, zcap, zcap, (long long)luoff};
+    XVWArgs xvw{problem, 1, &wd, &ww, winfos, ms, ws.data(), lu.data(), range, itype};
     XWArgs xw{{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &winfo, ws.data(), itype},
               {range, il, iu, zcap, vl, vu, &m, lu.data(), zcap}};
     std::barrier<> wbar(T);
     g_bar = &wbar;
     for (int q = 0; q < 256; ++q) g_pair[q] = new std::barrier<>(2);
     std::vector<std::thread> wth;
-    for (int t = 0; t < T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (cong) xbatched_kernel<true>(xw); else xbatched_kernel<false>(xw); });
+    for (int t = 0; t < T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (table) { if (cong) xbatched_kernel<true>(xvw); else xbatched_kernel<false>(xvw); } else if (cong) xbatched_kernel<true>(xw); else xbatched_kernel<false>(xw); });
     for (auto &x : wth) x.join();
+    if (table) {
+      m = ms[2]; winfo = winfos[2];
+      bool own = ms[0] == 777 && ms[1] == 777 && winfos[0] == 777 && winfos[1] == 777;
+      for (size_t q = 0; q < luoff; ++q) own = own && std::isnan(lu[q]);
+      if (!own) { printf("a word outside the entry's index, or the workspace in front of the entry's LU slot, was written\n"); return 1; }
+    }
     auto a0 = [&](int i, int j) { return i >= j ? A0[i + (size_t)j * n] : A0[j + (size_t)i * n]; };
     auto b0 = [&](int i, int j) { if (!problem) return i == j ? 1.0 : 0.0; return i >= j ? B0[i + (size_t)j * n] : B0[j + (size_t)i * n]; };
     if (winfo != 0 || m < 0 || m > zcap) { printf("n=%d window: info=%d m=%d\n", n, winfo, m); return 1; }
