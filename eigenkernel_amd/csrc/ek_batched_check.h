@@ -8,6 +8,8 @@
 //   ek_batched_check_x.hip, ek_batched_check_sygv_x.hip  the kernels above EK_HIP_BATCH_NMAX and their uniform entries
 //                              (ek_batched_check_x.h), which hand the host driver a launch function, and the launches of
 //                              their table form for the variable driver (launch_x, launch_sygv_x)
+//   ek_batched_check_window.hip  the kernel of the window check (m[b] columns per problem, every order up to
+//                              EK_HIP_XBATCH_NMAX) and its entries, which hand the window driver a launch function
 // The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
 #pragma once
 #include "ek_batched_stages.h"
@@ -152,6 +154,23 @@ int uniform_arguments(const Uniform &u, int nmax, bool *nothing);
 // launches, the fetch and the scatter.  scratch: doubles per problem (chunked = false: one launch, indexed by problem
 // number) or per workgroup of a launch (chunked = true: ek_hip_debug_check_xbatched_chunk problems a launch)
 int uniform_entry(const Uniform &u, bool nothing, bool host, size_t scratch, bool chunked, UniformLaunch launch);
+
+// ---- the same driver for the window check (ek_batched_check_window.hip): problem b has m[b] values and the
+// columns 0 .. m[b]-1 of an n x zcap array; u.itype is 0, m is a host array
+struct Window {
+  Uniform u;
+  const int *m;
+  int zcap;
+};
+// One launch for the entries first .. first + count - 1 of the map, whose entry e is the pair (problem, m[problem]) in
+// map[2 e], map[2 e + 1]; S: sS doubles per workgroup of the launch (problem 1: n x the largest checked m)
+typedef int (*WindowLaunch)(hipStream_t s, const Window &w, const int *map, int first, int count, long long sS, double *S,
+                            double *dout, double *dipr);
+// -1 .. -15, -17 as include/ek_hip.h lists them; *nothing: n == 0 or batch == 0
+int window_arguments(const Window &w, int nmax, bool *nothing);
+// the rest of the entry: a batch without a problem to check is filled here without the device; otherwise the map by
+// descending m, the pool, g_chunk problems a launch, the fetch, and a scatter of m[b] IPRs per row
+int window_entry(const Window &w, bool nothing, bool host, WindowLaunch launch);
 
 }  // namespace bcheck
 }  // namespace ek

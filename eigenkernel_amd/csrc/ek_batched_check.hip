@@ -30,6 +30,8 @@
 // pool with one release function, one run function and one stager of host arrays, declared in ek_batched_check.h.
 // ek_batched_check_x.hip and ek_batched_check_sygv_x.hip (orders above EK_HIP_BATCH_NMAX) keep their kernel, its launch
 // and thin entries, and hand this driver a launch function.  All entries serialise on g_mu, so one pool serves them all.
+// ek_batched_check_window.hip (ek_hip_check_window_xbatched*) does the same with the window driver beside it
+// (window_arguments, window_entry): the same pool, events, chunk size and fetch, a count m[b] per problem.
 //
 // The variable-order entries for orders up to EK_HIP_XBATCH_NMAX (ek_hip_check_xvbatched*, ek_hip_check_sygv_xvbatched*,
 // DESIGN.md 24) are this unit's too: the variable driver with a fourth class in front, whose launches are those two units'
@@ -386,6 +388,117 @@ int ek::bcheck::uniform_entry(const Uniform &u, bool nothing, bool host, size_t 
   Uniform d = u;
   d.A = uA; d.B = uB; d.w = uw; d.Z = uZ;
   return uniform_run(d, scratch, chunked, launch);
+}
+
+// ---- the window check (ek_hip_check_window_xbatched*): the driver above with a count m[b] per problem
+static bool window_skipped(const bcheck::Window &w, int b) { return w.u.info && w.u.info[b] != 0; }
+
+// The argument errors in the order of the prototype (17 arguments before ipr and seconds: 10 is m, 14 zcap, 16 info).  m and
+// info are host arrays and are read; no data pointer is dereferenced
+int ek::bcheck::window_arguments(const Window &w, int nmax, bool *nothing) {
+  const Uniform &u = w.u;
+  const int n = u.n;
+  *nothing = false;
+  if (u.problem != 0 && u.problem != 1) return -1;
+  if (n < 0 || n > nmax) return -2;
+  if (u.batch < 0) return -3;
+  if (n == 0 || u.batch == 0) { *nothing = true; return 0; }
+  if (!u.A) return -4;
+  if (u.lda < n) return -5;
+  if (u.sA < (long long)u.lda * n) return -6;
+  if (u.problem == 1) {
+    if (!u.B) return -7;
+    if (u.ldb < n) return -8;
+    if (u.sB < (long long)u.ldb * n) return -9;
+  }
+  if (!w.m) return -10;
+  for (int b = 0; b < u.batch; ++b)
+    if (!window_skipped(w, b) && (w.m[b] < 0 || w.m[b] > n)) return -10;
+  if (!u.w) return -11;
+  if (!u.Z) return -12;
+  if (u.ldz < n) return -13;
+  if (w.zcap < 0) return -14;
+  for (int b = 0; b < u.batch; ++b)
+    if (!window_skipped(w, b) && w.m[b] > w.zcap) return -14;
+  if (u.sZ < (long long)u.ldz * std::max(1, w.zcap)) return -15;
+  if (!u.out) return -17;                           // 16 is info: NULL means every problem
+  return 0;
+}
+
+// arguments checked, at least one problem to check, context up, g_mu held; u.A, u.B, u.w, u.Z device.  g_hmap holds the
+// pairs (problem, m) by descending m -- the widest windows first, so that a launch ends on its cheapest problems; the bit
+// contract makes the order invisible
+static int window_run(const bcheck::Window &w, bcheck::WindowLaunch launch) {
+  using namespace bcheck;
+  const Uniform &u = w.u;
+  const int n = u.n, batch = u.batch, count = (int)(g_hmap.size() / 2), cmax = g_hmap[1];
+  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (u.ipr ? (size_t)batch * n : 0);
+  const int K = g_chunk;
+  const long long sS = u.problem ? (long long)n * cmax : 0;
+  int rc = ensure((size_t)std::min(count, K) * (size_t)sS, words, g_hmap.size() * sizeof(int));
+  if (rc) return rc;
+  rc = run_and_fetch(words, u.seconds, [&](hipStream_t s) -> int {
+    EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_hmap.data(), g_hmap.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    for (int c0 = 0; c0 < count; c0 += K) {
+      const int rcl = launch(s, w, (const int *)g_dtable, c0, std::min(K, count - c0), sS, g_scratch, g_dout,
+                             u.ipr ? g_dout + nout : nullptr);
+      if (rcl) return rcl;
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  const double *h = g_hout.data();
+  for (int b = 0; b < batch; ++b) {
+    double *o = u.out + (size_t)b * EK_HIP_CHECK_NOUT;
+    if (window_skipped(w, b) || w.m[b] == 0) {
+      o[0] = o[1] = o[2] = o[3] = kNaN;
+    } else {
+      std::memcpy(o, h + (size_t)b * EK_HIP_CHECK_NOUT, EK_HIP_CHECK_NOUT * sizeof(double));
+      if (u.ipr) std::memcpy(u.ipr + (size_t)b * n, h + nout + (size_t)b * n, (size_t)w.m[b] * sizeof(double));
+    }
+  }
+  return 0;
+}
+
+int ek::bcheck::window_entry(const Window &w, bool nothing, bool host, WindowLaunch launch) {
+  const Uniform &u = w.u;
+  if (u.seconds) *u.seconds = 0.0;
+  if (nothing) return 0;
+  const int n = u.n, batch = u.batch, problem = u.problem;
+  std::vector<int> order;
+  for (int b = 0; b < batch; ++b)
+    if (!window_skipped(w, b) && w.m[b] > 0) order.push_back(b);
+  if (order.empty()) {                              // nothing to check: no context, no device
+    for (size_t k = 0; k < (size_t)batch * EK_HIP_CHECK_NOUT; ++k) u.out[k] = kNaN;
+    return 0;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return w.m[x] > w.m[y]; });
+  int rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  g_hmap.clear();
+  for (int b : order) { g_hmap.push_back(b); g_hmap.push_back(w.m[b]); }
+  if (!host) return window_run(w, launch);
+  // device copies with the caller's own layout; zcap >= 1 here, since some m[b] is
+  hipStream_t s = g_ctx.stream;
+  auto span = [&](int ld, long long stride, int cols) {
+    return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (cols - 1) + n;
+  };
+  const size_t cA = span(u.lda, u.sA, n), cB = problem ? span(u.ldb, u.sB, n) : 0, cZ = span(u.ldz, u.sZ, w.zcap);
+  const size_t cw = (size_t)batch * n;
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cA * 8);
+  if (!rc) rc = mem.alloc(&uw, cw * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
+  if (!rc) rc = mem.alloc(&uZ, cZ * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(uA, u.A, cA * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, u.B, cB * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, u.w, cw * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uZ, u.Z, cZ * 8, hipMemcpyHostToDevice, s));
+  Window d = w;
+  d.u.A = uA; d.u.B = uB; d.u.w = uw; d.u.Z = uZ;
+  return window_run(d, launch);
 }
 
 // this unit's part of a call: the class kernels (orders up to EK_HIP_BATCH_NMAX) index everything by problem number

@@ -225,6 +225,10 @@ def load_library(path=None):
         "ek_hip_check_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int, c_ll,
                                           _ip, _dp, _dp, _dp]),
         "ek_hip_debug_check_xbatched_chunk": (c_int, [c_int]),
+        "ek_hip_check_window_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, _ip, vp, vp,
+                                                        c_int, c_int, c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_window_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _ip, _dp, _dp,
+                                                 c_int, c_int, c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_sygv_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
                                                       c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_sygv_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
@@ -328,6 +332,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_debug_window_xbatched_chunk",
     "ek_hip_sygv_window_batched_device", "ek_hip_sygv_window_batched",
     "ek_hip_sygv_window_xbatched_device", "ek_hip_sygv_window_xbatched",
+    "ek_hip_check_window_xbatched_device", "ek_hip_check_window_xbatched",
 )
 
 
@@ -1291,6 +1296,56 @@ def check_xbatched(A, B, w, Z, info=None, ipr=True, seconds=None):
     and returns.  Orders up to BATCH_NMAX run the kernel of check_batched (the same bits); above it a kernel class of its
     own forms A Z, B Z and Z^T B Z on the matrix cores.  An order beyond XBATCH_NMAX raises SolverError with info -2."""
     return _check_batched_call("ek_hip_check_xbatched", 0 if B is None else 1, A, B, w, Z, info, ipr, seconds)
+
+
+def check_window_xbatched(A, B, m, w, Z, info=None, ipr=True, zcap=None, seconds=None):
+    """check_xbatched for a window of eigenpairs per problem (ek_hip_check_window_xbatched), behind
+    eigenpairs_window_xbatched, whose m, w, Z and info can be handed over unchanged: A (and B, or None) of shape
+    (batch, n, n) -- the ORIGINAL matrices --, m (batch,) ints, w (batch, n) of which w[b, :m[b]] counts, Z (batch, n, zc)
+    of which Z[b][:, :m[b]] counts (zcap: None for zc, or a smaller capacity).  Returns (out, ipr) like check_xbatched,
+    with the averages over m[b] columns; ipr[b, j] is NaN for j >= m[b].  A problem with info[b] != 0 or m[b] == 0 gets a
+    NaN row in both.  Raises ValueError for bad shapes, SolverError when the call itself fails (-10: an m[b] outside
+    0 .. n, -14: an m[b] above zcap, of a problem that info does not skip)."""
+    lib = load_library()
+    name = "ek_hip_check_window_xbatched"
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("A must have shape (batch, n, n)")
+    batch, n = A.shape[0], A.shape[1]
+    Z = np.asarray(Z, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    if Z.ndim != 3 or Z.shape[:2] != (batch, n):
+        raise ValueError("Z must have shape (batch, n, columns)")
+    if w.shape != (batch, n):
+        raise ValueError("w must have shape (batch, n)")
+    m = np.ascontiguousarray(np.asarray(m), dtype=np.int32)
+    if m.shape != (batch,):
+        raise ValueError("m must hold one int per problem")
+    zc = Z.shape[2]
+    zcap = zc if zcap is None else int(zcap)
+    if zcap > zc:
+        raise ValueError("zcap exceeds the columns of Z")
+    Bt = None
+    if B is not None:
+        B = np.asarray(B, dtype=np.float64)
+        if B.shape != A.shape:
+            raise ValueError("B must have the shape of A")
+        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
+    info = _check_info(info, batch)
+    At = np.ascontiguousarray(A.transpose(0, 2, 1))
+    Zt = np.ascontiguousarray(Z.transpose(0, 2, 1))
+    wc = np.ascontiguousarray(w)
+    out = np.full((batch, CHECK_NOUT), np.nan)
+    q = np.full((batch, n), np.nan) if ipr else None
+    if n == 0 or batch == 0:                        # the library references nothing, `out` included
+        return out, q
+    rc = getattr(lib, name)(0 if B is None else 1, n, batch, _P(At), n, n * n, _P(Bt) if Bt is not None else None, n,
+                            n * n, _I(m), _P(wc), _P(Zt), n, zcap, max(zc, 1) * n,
+                            _I(info) if info is not None else None, _P(out), _P(q) if ipr else None,
+                            _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError(name + " failed", rc)
+    return out, q
 
 
 def check_xbatched_chunk(problems):

@@ -706,6 +706,60 @@ int ek_hip_check_xbatched_device(int problem, int n, int batch, const double *dA
 int ek_hip_check_xbatched(int problem, int n, int batch, const double *A, int lda, long long strideA, const double *B,
                           int ldb, long long strideB, const double *w, const double *Z, int ldz, long long strideZ,
                           const int *info, double *out, double *ipr, double *seconds);
+/* The same checks for a WINDOW of eigenpairs per problem, behind ek_hip_eigenpairs_window_xbatched* (RANGE 'I' / 'V'), every
+ * order 0 .. EK_HIP_XBATCH_NMAX: problem b holds c = m[b] pairs, and the c columns are what is checked.  Nineteen arguments;
+ * the layouts are exactly what ek_hip_eigenpairs_window_xbatched* returns, so that its m, dw, dZ and info can be handed over
+ * unchanged:
+ *   m, info       : HOST arrays of batch ints (info may be NULL: no problem is skipped)
+ *   dw            : problem b's values are dw[b * n .. b * n + m[b])
+ *   dZ            : problem b's vectors are the columns 0 .. m[b]-1 of the n x zcap array at dZ + b * strideZ
+ *   dA, dB        : the ORIGINAL matrices, lower triangles only; dB, ldb, strideB are not looked at for problem 0
+ *   out           : HOST, batch * EK_HIP_CHECK_NOUT doubles
+ *   ipr           : HOST or NULL, batch x n with problem b at ipr + b * n: m[b] entries are written, the rest of the row is
+ *                   left as it was
+ * Per checked problem, with c = m[b], the quantities of ek_hip_check_sygvx_device(1, n, n_cols = c) and of the reference's
+ * verifier with n_check = c:
+ *   out[4 b + 0]  ||A||_F
+ *   out[4 b + 1]  sum_{j < c} ||r_j||_2 / a_norm / c,  r_j = A z_j - w_j B z_j  (B = I for problem 0)
+ *   out[4 b + 2]  max_{j < c} ||r_j||_2 / a_norm; the maximum keeps a NaN
+ *   out[4 b + 3]  || D^-1/2 G D^-1/2 with zero diagonal ||_F, G = Z^T B Z of order c, scaled by the computed G_jj
+ *   ipr_j         sum_i z_ij^4 / G_jj^2 for j < c
+ * Divisions are plain IEEE, as in the entries above.
+ * SKIPPED PROBLEMS: with info != NULL and info[b] != 0 the four slots get NaN, the ipr row is left alone, and nothing of the
+ * problem's m, w, Z is looked at -- -20 included, where m[b] is a count larger than zcap.  EMPTY WINDOWS: m[b] == 0 (an empty
+ * 'V' window) is handled the same way: four NaN, the ipr row left alone, nothing read.  A batch in which every problem is
+ * skipped or empty is filled on the host without touching the device.
+ * NEVER READ: w from m[b] on, the columns of Z from m[b] on, strictly upper triangles, rows n .. ld-1 and the gaps between
+ * problems of the device form (a NaN there shows nowhere).  NEVER WRITTEN: A, B, w, Z are const and come back bit for bit.
+ * Return value: 0, or -k for argument k of the prototype, the first offender deciding, before any device work and without
+ * dereferencing a data pointer (m and info are host arrays and are read):
+ *   -1 problem   -2 n outside 0 .. EK_HIP_XBATCH_NMAX   -3 batch < 0 (n = 0 or batch = 0: 0, nothing referenced or written)
+ *   -4 / -5 / -6 A NULL, lda < n, strideA < lda n   -7 / -8 / -9 the same for B (problem 1 only)
+ *   -10 m NULL, or m[b] outside 0 .. n for a problem that info does not skip   -11 w NULL   -12 Z NULL   -13 ldz < n
+ *   -14 zcap < 0, or zcap < m[b] of a problem that info does not skip   -15 strideZ < ldz max(1, zcap)   -17 out NULL
+ *   info, ipr, seconds may be NULL;   <= -1000 a HIP runtime error
+ * THE SAME BITS WHEREVER A PROBLEM SITS: a problem's outputs depend on (problem, n, A, B, m[b], w[0 .. m), Z[:, 0 .. m))
+ * alone -- not on zcap, ldz, the strides, the other problems' m, the batch, the position, the chunk or the form: loop
+ * bounds from (n, m[b]), fixed summation orders, no atomics.  With m[b] = n the outputs agree with ek_hip_check_xbatched* to
+ * rounding, not to the bit (at orders up to EK_HIP_BATCH_NMAX that entry sums in another order).
+ * One kernel class serves every order: a workgroup of 512 threads per problem from first load to last store, A Z, S = B Z
+ * (over the c columns) and G = Z^T S (c x c) on the fp64 matrix cores over LDS-staged tiles.  The problems run by descending
+ * m[b], in chunks of at most 1024 checked problems (ek_hip_debug_check_xbatched_chunk governs it) launched one after the
+ * other on one stream.  NOT COLLECTIVE; the call synchronises; *seconds is the device time from before the first launch to
+ * after the last.
+ * Workspace (device memory of the pool of all ek_hip_check_*batched* entries, kept until ek_hip_finalize): n x max m[b]
+ * doubles for each of the min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z), 4 + n doubles
+ * per problem for the outputs, 8 bytes per checked problem, two events.
+ * Not offered: the window check of DSYGV's types 2 and 3, and a variable-order form behind ek_hip_*_window_xvbatched*. */
+int ek_hip_check_window_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
+                                        const double *dB, int ldb, long long strideB, const int *m, const double *dw,
+                                        const double *dZ, int ldz, int zcap, long long strideZ, const int *info,
+                                        double *out, double *ipr, double *seconds);
+/* host arrays A, B, w, Z with the same layout (the call works on device copies; the caller's arrays are untouched) */
+int ek_hip_check_window_xbatched(int problem, int n, int batch, const double *A, int lda, long long strideA,
+                                 const double *B, int ldb, long long strideB, const int *m, const double *w,
+                                 const double *Z, int ldz, int zcap, long long strideZ, const int *info, double *out,
+                                 double *ipr, double *seconds);
 /* The same for problems of DIFFERENT orders, with the conventions of ek_hip_eigenpairs_vbatched*: n, lda, ldb, ldz, info,
  * out and the pointer arrays dA, dB, dw, dZ, ipr are HOST arrays of `batch` entries; the pointers IN dA, dB, dw, dZ are
  * device addresses (device form) or host addresses (host form), those in ipr always host addresses.
