@@ -10,6 +10,7 @@
 //                              their table form for the variable driver (launch_x, launch_sygv_x)
 //   ek_batched_check_window.hip  the kernel of the window check (m[b] columns per problem, every order up to
 //                              EK_HIP_XBATCH_NMAX) and its entries, which hand the window driver a launch function
+//   ek_batched_check_sygv_window.hip  the same for DSYGV's types 2 and 3
 // The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
 #pragma once
 #include "ek_batched_stages.h"
@@ -156,14 +157,18 @@ int uniform_arguments(const Uniform &u, int nmax, bool *nothing);
 int uniform_entry(const Uniform &u, bool nothing, bool host, size_t scratch, bool chunked, UniformLaunch launch);
 
 // ---- the same driver for the window check (ek_batched_check_window.hip): problem b has m[b] values and the
-// columns 0 .. m[b]-1 of an n x zcap array; u.itype is 0, m is a host array
+// columns 0 .. m[b]-1 of an n x zcap array; m is a host array.  sygv = false: ek_hip_check_window_xbatched*, u.itype is 0
+// and u.problem the caller's; sygv = true: ek_hip_check_sygv_window_xbatched* (ek_batched_check_sygv_window.hip, DESIGN.md
+// 36), u.itype is the caller's (1 .. 3, anything else is -1) and u.problem is 1, so that B is required and staged
 struct Window {
   Uniform u;
   const int *m;
   int zcap;
+  bool sygv;
 };
 // One launch for the entries first .. first + count - 1 of the map, whose entry e is the pair (problem, m[problem]) in
-// map[2 e], map[2 e + 1]; S: sS doubles per workgroup of the launch (problem 1: n x the largest checked m)
+// map[2 e], map[2 e + 1]; S: sS doubles per workgroup of the launch (problem 1 and type 2: n x the largest checked m;
+// type 3: n^2 more for the factor)
 typedef int (*WindowLaunch)(hipStream_t s, const Window &w, const int *map, int first, int count, long long sS, double *S,
                             double *dout, double *dipr);
 // -1 .. -15, -17 as include/ek_hip.h lists them; *nothing: n == 0 or batch == 0

@@ -32,6 +32,7 @@
 // and thin entries, and hand this driver a launch function.  All entries serialise on g_mu, so one pool serves them all.
 // ek_batched_check_window.hip (ek_hip_check_window_xbatched*) does the same with the window driver beside it
 // (window_arguments, window_entry): the same pool, events, chunk size and fetch, a count m[b] per problem.
+// ek_batched_check_sygv_window.hip (ek_hip_check_sygv_window_xbatched*) is that driver's second user.
 //
 // The variable-order entries for orders up to EK_HIP_XBATCH_NMAX (ek_hip_check_xvbatched*, ek_hip_check_sygv_xvbatched*,
 // DESIGN.md 24) are this unit's too: the variable driver with a fourth class in front, whose launches are those two units'
@@ -399,7 +400,8 @@ int ek::bcheck::window_arguments(const Window &w, int nmax, bool *nothing) {
   const Uniform &u = w.u;
   const int n = u.n;
   *nothing = false;
-  if (u.problem != 0 && u.problem != 1) return -1;
+  // the sygv form carries the caller's itype and problem = 1: B is required for every type
+  if (w.sygv ? (u.itype < 1 || u.itype > 3) : (u.problem != 0 && u.problem != 1)) return -1;
   if (n < 0 || n > nmax) return -2;
   if (u.batch < 0) return -3;
   if (n == 0 || u.batch == 0) { *nothing = true; return 0; }
@@ -434,7 +436,8 @@ static int window_run(const bcheck::Window &w, bcheck::WindowLaunch launch) {
   const int n = u.n, batch = u.batch, count = (int)(g_hmap.size() / 2), cmax = g_hmap[1];
   const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT, words = nout + (u.ipr ? (size_t)batch * n : 0);
   const int K = g_chunk;
-  const long long sS = u.problem ? (long long)n * cmax : 0;
+  // S = B Z (problem 1, type 2) or U = A Z, then W^T (type 3): n x the widest window; type 3: the factor in front of it
+  const long long sS = u.problem ? (long long)n * cmax + (u.itype == 3 ? (long long)n * n : 0) : 0;
   int rc = ensure((size_t)std::min(count, K) * (size_t)sS, words, g_hmap.size() * sizeof(int));
   if (rc) return rc;
   rc = run_and_fetch(words, u.seconds, [&](hipStream_t s) -> int {

@@ -229,6 +229,10 @@ def load_library(path=None):
                                                         c_int, c_int, c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_window_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _ip, _dp, _dp,
                                                  c_int, c_int, c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_sygv_window_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, _ip, vp,
+                                                             vp, c_int, c_int, c_ll, _ip, _dp, _dp, _dp]),
+        "ek_hip_check_sygv_window_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _ip, _dp,
+                                                      _dp, c_int, c_int, c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_sygv_xbatched_device": (c_int, [c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, c_int,
                                                       c_ll, _ip, _dp, _dp, _dp]),
         "ek_hip_check_sygv_xbatched": (c_int, [c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
@@ -333,6 +337,7 @@ EXPORTED_SYMBOLS = (
     "ek_hip_sygv_window_batched_device", "ek_hip_sygv_window_batched",
     "ek_hip_sygv_window_xbatched_device", "ek_hip_sygv_window_xbatched",
     "ek_hip_check_window_xbatched_device", "ek_hip_check_window_xbatched",
+    "ek_hip_check_sygv_window_xbatched_device", "ek_hip_check_sygv_window_xbatched",
 )
 
 
@@ -1306,8 +1311,12 @@ def check_window_xbatched(A, B, m, w, Z, info=None, ipr=True, zcap=None, seconds
     with the averages over m[b] columns; ipr[b, j] is NaN for j >= m[b].  A problem with info[b] != 0 or m[b] == 0 gets a
     NaN row in both.  Raises ValueError for bad shapes, SolverError when the call itself fails (-10: an m[b] outside
     0 .. n, -14: an m[b] above zcap, of a problem that info does not skip)."""
+    return _check_window_call("ek_hip_check_window_xbatched", 0 if B is None else 1, A, B, m, w, Z, info, ipr, zcap, seconds)
+
+
+def _check_window_call(name, first, A, B, m, w, Z, info, ipr, zcap, seconds):
+    """The call behind check_window_xbatched and check_sygv_window_xbatched: `first` is the entry's first argument."""
     lib = load_library()
-    name = "ek_hip_check_window_xbatched"
     A = np.asarray(A, dtype=np.float64)
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
         raise ValueError("A must have shape (batch, n, n)")
@@ -1339,13 +1348,27 @@ def check_window_xbatched(A, B, m, w, Z, info=None, ipr=True, zcap=None, seconds
     q = np.full((batch, n), np.nan) if ipr else None
     if n == 0 or batch == 0:                        # the library references nothing, `out` included
         return out, q
-    rc = getattr(lib, name)(0 if B is None else 1, n, batch, _P(At), n, n * n, _P(Bt) if Bt is not None else None, n,
+    rc = getattr(lib, name)(first, n, batch, _P(At), n, n * n, _P(Bt) if Bt is not None else None, n,
                             n * n, _I(m), _P(wc), _P(Zt), n, zcap, max(zc, 1) * n,
                             _I(info) if info is not None else None, _P(out), _P(q) if ipr else None,
                             _P(seconds) if seconds is not None else None)
     if rc != 0:
         raise SolverError(name + " failed", rc)
     return out, q
+
+
+def check_sygv_window_xbatched(A, B, m, w, Z, itype=1, info=None, ipr=True, zcap=None, seconds=None):
+    """check_window_xbatched for DSYGV's three problem types (ek_hip_check_sygv_window_xbatched), behind
+    sygv_window_xbatched and sygv_window_batched, whose m, w, Z and info can be handed over unchanged: the shapes and the
+    returns of check_window_xbatched.  itype 1 is check_window_xbatched(A, B, ...) to the bit; for types 2 and 3 out[b] =
+    (||A||_F ||B||_F, res_ave, res_max, orthogonality) and ipr with the quantities of eigenkernel_amd.verifier's *_sygv
+    functions on Z[b][:, :m[b]] (a B[b] that is not SPD gives NaN in orthogonality and ipr of type 3).  A missing B or an
+    itype outside 1 .. 3 raises ValueError before the library is called."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if B is None:
+        raise ValueError("B is required")
+    return _check_window_call("ek_hip_check_sygv_window_xbatched", int(itype), A, B, m, w, Z, info, ipr, zcap, seconds)
 
 
 def check_xbatched_chunk(problems):

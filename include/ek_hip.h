@@ -750,7 +750,8 @@ int ek_hip_check_xbatched(int problem, int n, int batch, const double *A, int ld
  * Workspace (device memory of the pool of all ek_hip_check_*batched* entries, kept until ek_hip_finalize): n x max m[b]
  * doubles for each of the min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z), 4 + n doubles
  * per problem for the outputs, 8 bytes per checked problem, two events.
- * Not offered: the window check of DSYGV's types 2 and 3, and a variable-order form behind ek_hip_*_window_xvbatched*. */
+ * Not offered: a variable-order form behind ek_hip_*_window_xvbatched*.  DSYGV's types 2 and 3 are
+ * ek_hip_check_sygv_window_xbatched* below. */
 int ek_hip_check_window_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                         const double *dB, int ldb, long long strideB, const int *m, const double *dw,
                                         const double *dZ, int ldz, int zcap, long long strideZ, const int *info,
@@ -760,6 +761,49 @@ int ek_hip_check_window_xbatched(int problem, int n, int batch, const double *A,
                                  const double *B, int ldb, long long strideB, const int *m, const double *w,
                                  const double *Z, int ldz, int zcap, long long strideZ, const int *info, double *out,
                                  double *ipr, double *seconds);
+/* The window check for DSYGV's three types, behind ek_hip_sygv_window_xbatched* and ek_hip_sygv_window_batched*, every order
+ * 0 .. EK_HIP_XBATCH_NMAX: the nineteen arguments of ek_hip_check_window_xbatched* with itype (1: A x = l B x, 2: A B x = l x,
+ * 3: B A x = l x) in the place of problem, the same layouts, so that the solvers' m, dw, dZ and info are handed over
+ * unchanged.  dA and dB are the ORIGINAL matrices, lower triangles only (the solvers overwrite theirs: keep copies); dB is
+ * required for every type.
+ * itype = 1 IS ek_hip_check_window_xbatched*(problem = 1): the same kernel, the same bits.  For types 2 and 3, per checked
+ * problem with c = m[b] and B = L L^T, the quantities of ek_hip_check_sygv_xbatched* on c columns:
+ *   out[4 b + 0]  ||A||_F ||B||_F
+ *   out[4 b + 1]  sum_{j < c} rho_j / c,  rho_j = ||r_j||_2 / (||A||_F ||B||_F ||z_j||_2),
+ *                 r_j = A (B z_j) - w_j z_j (type 2), B (A z_j) - w_j z_j (type 3)
+ *   out[4 b + 2]  max_{j < c} rho_j; the maximum keeps a NaN
+ *   out[4 b + 3]  || D^-1/2 G D^-1/2 with zero diagonal ||_F, G of order c, scaled by the computed G_jj:
+ *                 G = Z^T B Z (type 2), (L^-1 Z)^T (L^-1 Z) (type 3)
+ *   ipr_j         sum_i z_ij^4 / G_jj^2 for j < c; the rest of the row is left as it was
+ * Divisions are plain IEEE.
+ * TYPE 3'S FACTOR: the kernel factors the caller's original B itself.  A pivot that is not positive and finite gives NaN in
+ * slot 3 and in the m[b] IPR slots of that problem; its residual slots stay valid and the return value stays 0.
+ * SKIPPED PROBLEMS (info[b] != 0, -20 with m[b] > zcap included) and EMPTY WINDOWS (m[b] == 0): four NaN, the ipr row left
+ * alone, nothing of the problem read; a batch of nothing else is filled on the host without touching the device.
+ * NEVER READ: w and the columns of Z from m[b] on, strictly upper triangles, rows n .. ld-1, the gaps between problems.
+ * NEVER WRITTEN: A, B, w, Z.
+ * Return value: -1 itype outside 1 .. 3 (before everything else); then the codes of ek_hip_check_window_xbatched* with
+ * problem = 1: -2 n, -3 batch (n = 0 or batch = 0: 0, nothing referenced or written), -4 / -5 / -6 A, -7 / -8 / -9 B (every
+ * type), -10 m, -11 w, -12 Z, -13 ldz, -14 zcap, -15 strideZ, -17 out; the first offender decides, before any device work
+ * and without dereferencing a data pointer (m and info are host arrays and are read); <= -1000 a HIP runtime error.
+ * THE SAME BITS WHEREVER A PROBLEM SITS: a problem's outputs depend on (itype, n, A, B, m[b], w[0 .. m), Z[:, 0 .. m)) alone,
+ * not on zcap, ldz, the strides, the other problems, the batch, the position, the chunk or the form.  For the same
+ * (B, Z, m[b]) slot 3 and the IPRs of type 2 are the bits of the type-1 call.  With m[b] = n the outputs agree with
+ * ek_hip_check_sygv_xbatched* to rounding, not to the bit.
+ * One kernel class per type serves every order: a workgroup of 512 threads per problem, the products (n^2 c each) on the
+ * fp64 matrix cores over LDS-staged tiles; type 3's factor costs n^3 / 3 whatever c is, its forward solve runs over the c
+ * columns with 512 / (the power of two >= max(c, 16)) threads per column.  Chunks and *seconds as above.
+ * Workspace (the same pool): per problem of a chunk n x max m[b] doubles (type 2), n^2 + n x max m[b] (type 3).
+ * Not offered: a variable-order form. */
+int ek_hip_check_sygv_window_xbatched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
+                                             const double *dB, int ldb, long long strideB, const int *m, const double *dw,
+                                             const double *dZ, int ldz, int zcap, long long strideZ, const int *info,
+                                             double *out, double *ipr, double *seconds);
+/* host arrays A, B, w, Z with the same layout (the call works on device copies; the caller's arrays are untouched) */
+int ek_hip_check_sygv_window_xbatched(int itype, int n, int batch, const double *A, int lda, long long strideA,
+                                      const double *B, int ldb, long long strideB, const int *m, const double *w,
+                                      const double *Z, int ldz, int zcap, long long strideZ, const int *info, double *out,
+                                      double *ipr, double *seconds);
 /* The same for problems of DIFFERENT orders, with the conventions of ek_hip_eigenpairs_vbatched*: n, lda, ldb, ldz, info,
  * out and the pointer arrays dA, dB, dw, dZ, ipr are HOST arrays of `batch` entries; the pointers IN dA, dB, dw, dZ are
  * device addresses (device form) or host addresses (host form), those in ipr always host addresses.

@@ -44,11 +44,13 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  the window call of type 2 / 3 (ek_hip_sygv_window_batched_device; above
                                                  128: ek_hip_sygv_window_xbatched_device) against the full call of the same
                                                  type and against the type-1 window call
-  python tools/batched_timing.py --window 0.125 --check [--sizes 128,129,256] [--batches 256]
+  python tools/batched_timing.py --window 0.125 --check [--sizes 128,129,256] [--batches 256] [--itype 2]
                                                  the window check (ek_hip_check_window_xbatched_device) on the m, w and Z
                                                  of the window solve, against the full check of the same batch
                                                  (ek_hip_check_xbatched_device on all n columns of a full solve) and
-                                                 against a host loop over ek_hip_check_sygvx_device, the kinds alternated
+                                                 against a host loop over ek_hip_check_sygvx_device, the kinds alternated;
+                                                 --itype 2 / 3: ek_hip_check_sygv_window_xbatched_device behind the type's
+                                                 window solve, against the type's full check and the type's host loop
 
   python tools/batched_timing.py --mixed --window 0.125 [--mixed-batch 512] [--mixed-orders 8,256] [--itype 1]
                                                  the variable-order window call (ek_hip_eigenpairs_window_xvbatched_device;
@@ -588,18 +590,20 @@ def mixed_window(lib, batch, lo, hi, fraction, itype):
         lib.ek_hip_free(p)
 
 
-def window_check_rows(lib, sizes, batches, fractions, loop_max):
+def window_check_rows(lib, sizes, batches, fractions, loop_max, itype=1):
     """The window of max(1, fraction n) pairs from index n / 4 + 1, with vectors.  Per (problem, n, batch, fraction): a
     warm-up, then three rounds of window solve, window check, full check (on a full solve's w and Z, made once) and the
     host loop over ek_hip_check_sygvx_device (min(batch, loop_max) problems, scaled; the standard problem gets B = I);
-    device times, wall for the loop and beside the window check."""
+    device times, wall for the loop and beside the window check.  itype 2 / 3: the generalized rows alone, with
+    ek_hip_check_sygv_window_xbatched_device behind the type's window solve, the type's full check and the type's loop."""
     ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
-    print("# problem     n batch     m | window solve ms | window check wall ms  device ms | full check ms | loop ms (scaled) | "
-          "window / full  window / solve  loop / window | worst res_max  orthogonality")
+    print("# %s     n batch     m | window solve ms | window check wall ms  device ms | full check ms | loop ms (scaled) | "
+          "window / full  window / solve  loop / window | worst res_max  orthogonality"
+          % ("problem" if itype == 1 else "  itype"))
     for n in sizes:
         nn = n * n
         for batch in batches:
-            c = Case(lib, n, batch)
+            c = Case(lib, n, batch, itype=itype)
             win = (c.dw, c.dZ)
             full = (c.alloc(batch * n * 8), c.alloc(batch * nn * 8))
             dI = c.alloc(nn * 8)
@@ -609,7 +613,10 @@ def window_check_rows(lib, sizes, batches, fractions, loop_max):
             one, q1 = np.zeros(4), np.zeros(n)
             count = min(batch, loop_max)
             at = lambda p, b, per: ctypes.c_void_p(p.value + b * per * 8)  # noqa: E731
-            for problem in (1, 0):
+            wcheck, first = lib.ek_hip_check_window_xbatched_device, None
+            if itype != 1:
+                wcheck, first = lib.ek_hip_check_sygv_window_xbatched_device, itype
+            for problem in ((1, 0) if itype == 1 else (1,)):
                 c.dw, c.dZ = full
                 c.batched(problem, 1)
                 c.check(problem)                    # makes the kept originals dA0, dB0
@@ -620,12 +627,12 @@ def window_check_rows(lib, sizes, batches, fractions, loop_max):
                     iu = il + mcols - 1
                     ts, tw, tf, tl, worst = [], [], [], [], np.zeros(2)
                     for rep in range(4):            # the first round warms up
-                        _, d, m = c.window(problem, 1, il=il, iu=iu)
+                        _, d, m = c.window(problem, 1, il=il, iu=iu, itype=itype)
                         ts.append(d)
                         sec = ctypes.c_double(0.0)
                         t0 = time.perf_counter()
-                        rc = lib.ek_hip_check_window_xbatched_device(
-                            problem, n, batch, c.dA0, n, nn, c.dB0 if problem else None, n, nn, m.ctypes.data_as(ip), c.dw,
+                        rc = wcheck(
+                            problem if first is None else first, n, batch, c.dA0, n, nn, c.dB0 if problem else None, n, nn, m.ctypes.data_as(ip), c.dw,
                             c.dZ, n, n, nn, c.info.ctypes.data_as(ip), out.ctypes.data_as(dp), ipr.ctypes.data_as(dp),
                             ctypes.byref(sec))
                         tw.append((sec.value, time.perf_counter() - t0))
@@ -636,7 +643,7 @@ def window_check_rows(lib, sizes, batches, fractions, loop_max):
                         c.dw, c.dZ = win
                         t0 = time.perf_counter()
                         for b in range(count):
-                            rc = lib.ek_hip_check_sygvx_device(1, n, mcols, at(c.dA0, b, nn), n,
+                            rc = lib.ek_hip_check_sygvx_device(itype, n, mcols, at(c.dA0, b, nn), n,
                                                                at(c.dB0, b, nn) if problem else dI, n, at(c.dw, b, n),
                                                                at(c.dZ, b, nn), n, one.ctypes.data_as(dp),
                                                                q1.ctypes.data_as(dp))
@@ -645,7 +652,7 @@ def window_check_rows(lib, sizes, batches, fractions, loop_max):
                     d, t = min(tw[1:])
                     s, fc, lo = min(ts[1:]), min(tf[1:]), min(tl[1:])
                     print("  %7d %5d %5d %5d | %15.3f | %20.3f %10.3f | %13.3f | %16.2f | %13.3f %15.3f %14.1f | %13.2e %14.2e"
-                          % (problem, n, batch, mcols, s * 1e3, t * 1e3, d * 1e3, fc * 1e3, lo * 1e3, d / fc, d / s, lo / t,
+                          % (problem if itype == 1 else itype, n, batch, mcols, s * 1e3, t * 1e3, d * 1e3, fc * 1e3, lo * 1e3, d / fc, d / s, lo / t,
                              worst[0], worst[1]), flush=True)
             c.close()
 
@@ -677,14 +684,14 @@ def main():
             mixed_window(lib, args.mixed_batch, lo, hi, fraction, args.itype)
         lib.ek_hip_finalize()
         return
-    if args.window and args.itype != 1:
+    if args.window and args.itype != 1 and not args.check:
         sygv_window_rows(lib, [int(x) for x in args.sizes.split(",")], [int(x) for x in args.batches.split(",")],
                          [float(x) for x in args.window.split(",")], args.itype)
         lib.ek_hip_finalize()
         return
     if args.window and args.check:
         window_check_rows(lib, [int(x) for x in args.sizes.split(",")], [int(x) for x in args.batches.split(",")],
-                          [float(x) for x in args.window.split(",")], args.loop_max)
+                          [float(x) for x in args.window.split(",")], args.loop_max, args.itype)
         lib.ek_hip_finalize()
         return
     if args.window:
