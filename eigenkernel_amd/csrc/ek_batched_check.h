@@ -11,6 +11,9 @@
 //   ek_batched_check_window.hip  the kernel of the window check (m[b] columns per problem, every order up to
 //                              EK_HIP_XBATCH_NMAX) and its entries, which hand the window driver a launch function
 //   ek_batched_check_sygv_window.hip  the same for DSYGV's types 2 and 3
+//                              Both window units also hold the table instantiation of their kernel (launch_window_v,
+//                              launch_sygv_window_v) for ek_hip_check_*window_xvbatched* (DESIGN.md 37), whose driver and
+//                              entries are ek_batched_check.hip's
 // The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
 #pragma once
 #include "ek_batched_stages.h"
@@ -34,11 +37,12 @@ struct Args {
 
 // the variable form's table: one entry per problem to check, a class after the other, descending order inside a class.
 // S: the entry's own scratch -- n^2 doubles per problem in the classes up to 128; in the class of 256 a slot of the
-// entry's chunk (n^2 doubles, 2 n^2 for type 3), reused by the next chunk
+// entry's chunk (n^2 doubles, 2 n^2 for type 3), reused by the next chunk.  m: the columns to check in the variable window
+// form, whose S is a slot of n m doubles (type 3: n^2 more) of the entry's chunk; 0 and unread elsewhere
 struct Desc {
   const double *A, *B, *w, *Z;
   double *S, *ipr;
-  int n, lda, ldb, ldz, index, pad;
+  int n, lda, ldb, ldz, index, m;
 };
 struct VArgs {
   int problem;
@@ -67,6 +71,23 @@ __device__ __forceinline__ Problem locate(const Args &a) {
 __device__ __forceinline__ Problem locate(const VArgs &a) {
   const Desc &d = a.table[blockIdx.x];
   return {d.n, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
+          (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};
+}
+
+// What a workgroup of the window kernels (ek_batched_check_window.hip, ek_batched_check_sygv_window.hip) works on: c = m[b]
+// columns of problem b.  Both argument forms of those kernels resolve to this in their first lines
+struct WProblem {
+  int n, c;
+  cgdouble *A; int lda;
+  cgdouble *B; int ldb;
+  cgdouble *w;
+  cgdouble *Z; int ldz;
+  gdouble *S, *out, *ipr;
+};
+// the table form: entry blockIdx.x of the launch's slice of the table
+__device__ __forceinline__ WProblem locate_window(const VArgs &a) {
+  const Desc &d = a.table[blockIdx.x];
+  return {d.n, d.m, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
           (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};
 }
 
@@ -132,6 +153,10 @@ int launch_sygv(hipStream_t s, int itype, int nc, int count, const VArgs &a);
 // ek_batched_check_x.hip's (the standard problem and type 1, a.problem says which), ek_batched_check_sygv_x.hip's (itype 2, 3)
 int launch_x(hipStream_t s, int count, const VArgs &a);
 int launch_sygv_x(hipStream_t s, int itype, int count, const VArgs &a);
+// one launch of the window kernels' table form for `count` entries of the table, each with 1 <= m <= n:
+// ek_batched_check_window.hip's (a.problem says which), ek_batched_check_sygv_window.hip's (itype 2, 3)
+int launch_window_v(hipStream_t s, int count, const VArgs &a);
+int launch_sygv_window_v(hipStream_t s, int itype, int count, const VArgs &a);
 
 // ---- the host driver of the uniform-order entries (ek_batched_check.hip)
 // One call.  itype: 0 the standard problem and type 1 (`problem` says which), 2 or 3 those types (problem = 1).  A, B, w

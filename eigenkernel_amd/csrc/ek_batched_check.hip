@@ -37,6 +37,10 @@
 // The variable-order entries for orders up to EK_HIP_XBATCH_NMAX (ek_hip_check_xvbatched*, ek_hip_check_sygv_xvbatched*,
 // DESIGN.md 24) are this unit's too: the variable driver with a fourth class in front, whose launches are those two units'
 // table instantiations (bcheck::launch_x, bcheck::launch_sygv_x).
+//
+// The variable-order window checks (ek_hip_check_window_xvbatched*, ek_hip_check_sygv_window_xvbatched*) are
+// this unit's as well: the window driver's count m[b] per problem on the variable driver's table, one class for every
+// order (vwindow_check, vwindow_entry), launching the table instantiations of the two window units' kernels.
 #include "ek_batched_check.h"
 
 #include <algorithm>
@@ -735,6 +739,206 @@ static int variable_host_entry(int itype, int problem, int batch, const int *n, 
                                 pZ.data(), ldc.data(), info, out, ipr, seconds);
 }
 
+// ---- the variable window check (ek_hip_check_window_xvbatched*, ek_hip_check_sygv_window_xvbatched*): the
+// window driver's count m[b] per problem on the variable driver's table.  One kernel class serves every order, so there are
+// no classes here: one table by descending work, g_chunk entries a launch
+static bool vwindow_skipped(const int *info, int b) { return info && info[b] != 0; }
+
+// The argument errors in the order of the prototype (8 is m, 12 zcap, 13 info, 14 out).  sygv: `first` is itype (1 .. 3) and
+// B is required for every type; otherwise it is problem (0, 1).  All arrays are host arrays of `batch` entries; m and info
+// are read, the pointers in the pointer arrays are not dereferenced
+static int vwindow_check(bool sygv, int first, int batch, const int *n, const void *const *A, const int *lda,
+                         const void *const *B, const int *ldb, const int *m, const void *const *w, const void *const *Z,
+                         const int *ldz, const int *zcap, const int *info, const double *out, bool *nothing) {
+  *nothing = false;
+  if (sygv ? (first < 1 || first > 3) : (first != 0 && first != 1)) return -1;
+  if (batch < 0) return -2;
+  if (batch == 0) { *nothing = true; return 0; }
+  if (!n) return -3;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] < 0 || n[b] > EK_HIP_XBATCH_NMAX) return -3;
+  auto entries = [&](const void *const *P) {
+    if (!P) return false;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && !P[b]) return false;
+    return true;
+  };
+  auto leading = [&](const int *ld) {
+    if (!ld) return false;
+    for (int b = 0; b < batch; ++b)
+      if (ld[b] < (n[b] > 1 ? n[b] : 1)) return false;
+    return true;
+  };
+  if (!entries(A)) return -4;
+  if (!leading(lda)) return -5;
+  if (sygv || first == 1) {
+    if (!entries(B)) return -6;
+    if (!leading(ldb)) return -7;
+  }
+  if (!m) return -8;
+  for (int b = 0; b < batch; ++b)
+    if (!vwindow_skipped(info, b) && (m[b] < 0 || m[b] > n[b])) return -8;
+  if (!entries(w)) return -9;
+  if (!Z) return -10;
+  if (zcap)                                         // the solver allows a NULL entry where zcap[b] = 0; a NULL zcap is -12
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && zcap[b] > 0 && !Z[b]) return -10;
+  if (!leading(ldz)) return -11;
+  if (!zcap) return -12;
+  for (int b = 0; b < batch; ++b)
+    if (zcap[b] < 0 || (!vwindow_skipped(info, b) && zcap[b] < m[b])) return -12;
+  if (!out) return -14;                             // 13 is info: NULL means every problem
+  return 0;
+}
+
+// the problems to check (not skipped, m[b] > 0) in the order of execution: by descending estimated work -- n^2 m per
+// product, n^3 / 3 for type 3's factor -- so that a launch ends on its cheapest problems; the bit contract makes the order
+// invisible
+static std::vector<int> vwindow_order(int itype, int batch, const int *n, const int *m, const int *info) {
+  std::vector<int> order;
+  for (int b = 0; b < batch; ++b)
+    if (!vwindow_skipped(info, b) && m[b] > 0) order.push_back(b);
+  auto work = [&](int b) {
+    const long long nn = n[b];
+    return nn * nn * m[b] + (itype == 3 ? nn * nn * nn / 3 : 0);
+  };
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return work(x) > work(y); });
+  return order;
+}
+
+// arguments checked, `order` not empty, context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses; itype: 0
+// (`problem` says which), 2 or 3.  Entry e of the table belongs to chunk e / g_chunk and names its own slot of that chunk's
+// scratch (prefix sums inside the chunk; the next chunk starts at the buffer's beginning): n m doubles for problem 1 and
+// type 2, n^2 more for type 3 -- the layouts of the uniform kernels, which depend on (n, m) alone.  The launches follow one
+// another on the context's stream, so they may share the buffer
+static int vwindow_device_locked(int itype, int problem, int batch, const std::vector<int> &order, const int *n,
+                                 const double *const *dA, const int *lda, const double *const *dB, const int *ldb,
+                                 const int *m, const double *const *dw, const double *const *dZ, const int *ldz,
+                                 const int *info, double *out, double *const *ipr, double *seconds) {
+  using namespace bcheck;
+  const size_t nout = (size_t)batch * EK_HIP_CHECK_NOUT;
+  const int K = g_chunk, count = (int)order.size();
+  auto slot = [&](int b) {
+    const size_t nn = (size_t)n[b];
+    return problem ? nn * (size_t)m[b] + (itype == 3 ? nn * nn : 0) : (size_t)0;
+  };
+  std::vector<size_t> off((size_t)batch, 0), offs((size_t)batch, 0);
+  size_t words = nout, scratch = 0, chunk = 0;
+  for (int e = 0; e < count; ++e) {
+    const int b = order[e];
+    if (ipr && ipr[b]) { off[b] = words; words += (size_t)m[b]; }
+    if (e % K == 0) chunk = 0;                      // a chunk's first entry
+    offs[b] = chunk;
+    chunk += slot(b);
+    scratch = std::max(scratch, chunk);
+  }
+  int rc = ensure(scratch, words, (size_t)count * sizeof(Desc));
+  if (rc) return rc;
+  g_htable.resize((size_t)count);
+  for (int e = 0; e < count; ++e) {
+    const int b = order[e];
+    g_htable[e] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], dZ[b], problem ? g_scratch + offs[b] : nullptr,
+                       (ipr && ipr[b]) ? g_dout + off[b] : nullptr, n[b], lda[b], problem ? ldb[b] : 1, ldz[b], b, m[b]};
+  }
+  rc = run_and_fetch(words, seconds, [&](hipStream_t s) -> int {
+    EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+    for (int c0 = 0; c0 < count; c0 += K) {
+      VArgs a{problem, (const Desc *)g_dtable + c0, g_dout};
+      const int cnt = std::min(K, count - c0);
+      const int rcl = itype ? launch_sygv_window_v(s, itype, cnt, a) : launch_window_v(s, cnt, a);
+      if (rcl) return rcl;
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  const double *h = g_hout.data();
+  for (int b = 0; b < batch; ++b) {
+    double *o = out + (size_t)b * EK_HIP_CHECK_NOUT;
+    if (vwindow_skipped(info, b) || m[b] == 0) {
+      o[0] = o[1] = o[2] = o[3] = kNaN;
+    } else {
+      std::memcpy(o, h + (size_t)b * EK_HIP_CHECK_NOUT, EK_HIP_CHECK_NOUT * sizeof(double));
+      if (ipr && ipr[b]) std::memcpy(ipr[b], h + off[b], (size_t)m[b] * sizeof(double));
+    }
+  }
+  return 0;
+}
+
+// The four entries.  sygv: `first` is itype, and type 1 is the other family's problem 1 after this one's argument check.
+// host: the pointers in A, B, w, Z are host addresses; the lower triangles of A and B, m[b] values of w and m[b] columns of
+// Z of every problem to check go to a compact device image (ld = n[b]), one copy per matrix kind, as in
+// variable_host_entry; nothing of a skipped or empty problem is staged
+static int vwindow_entry(bool sygv, int first, int batch, const int *n, const double *const *A, const int *lda,
+                         const double *const *B, const int *ldb, const int *m, const double *const *w,
+                         const double *const *Z, const int *ldz, const int *zcap, const int *info, double *out,
+                         double *const *ipr, double *seconds, bool host) {
+  bool nothing;
+  int rc = vwindow_check(sygv, first, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb, m,
+                         (const void *const *)w, (const void *const *)Z, ldz, zcap, info, out, &nothing);
+  if (rc) return rc;
+  if (sygv && first == 1)
+    return host ? ek_hip_check_window_xvbatched(1, batch, n, A, lda, B, ldb, m, w, Z, ldz, zcap, info, out, ipr, seconds)
+                : ek_hip_check_window_xvbatched_device(1, batch, n, A, lda, B, ldb, m, w, Z, ldz, zcap, info, out, ipr,
+                                                       seconds);
+  const int itype = sygv ? first : 0, problem = sygv ? 1 : first;
+  if (seconds) *seconds = 0.0;
+  if (nothing) return 0;
+  const std::vector<int> order = vwindow_order(itype, batch, n, m, info);
+  if (order.empty()) {                              // nothing to check: no context, no device
+    for (size_t k = 0; k < (size_t)batch * EK_HIP_CHECK_NOUT; ++k) out[k] = kNaN;
+    return 0;
+  }
+  rc = ensure_init(); if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!host)
+    return vwindow_device_locked(itype, problem, batch, order, n, A, lda, B, ldb, m, w, Z, ldz, info, out, ipr, seconds);
+  hipStream_t s = g_ctx.stream;
+  std::vector<size_t> offm((size_t)batch, 0), offz((size_t)batch, 0), offv((size_t)batch, 0);
+  size_t cm = 0, cz = 0, cv = 0;
+  for (int b : order) {
+    offm[b] = cm; offz[b] = cz; offv[b] = cv;
+    cm += (size_t)n[b] * n[b];
+    cz += (size_t)n[b] * m[b];
+    cv += (size_t)m[b];
+  }
+  auto pack = [&](const double *const *M, const int *ld, std::vector<double> &h) {   // the lower triangles
+    h.assign(cm, 0.0);
+    for (int b : order)
+      for (int j = 0; j < n[b]; ++j)
+        std::memcpy(&h[offm[b] + (size_t)j * n[b] + j], M[b] + (size_t)j * ld[b] + j, (size_t)(n[b] - j) * 8);
+  };
+  std::vector<double> hA, hB, hZ(cz), hw(cv);
+  pack(A, lda, hA);
+  if (problem) pack(B, ldb, hB);
+  for (int b : order) {
+    for (int j = 0; j < m[b]; ++j)
+      std::memcpy(&hZ[offz[b] + (size_t)j * n[b]], Z[b] + (size_t)j * ldz[b], (size_t)n[b] * 8);
+    std::memcpy(&hw[offv[b]], w[b], (size_t)m[b] * 8);
+  }
+  DevMem mem;
+  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
+  rc = mem.alloc(&uA, cm * 8);
+  if (!rc) rc = mem.alloc(&uw, cv * 8);
+  if (!rc && problem) rc = mem.alloc(&uB, cm * 8);
+  if (!rc) rc = mem.alloc(&uZ, cz * 8);
+  if (rc) return rc;
+  std::vector<const double *> pA((size_t)batch), pB((size_t)batch), pw((size_t)batch), pZ((size_t)batch);
+  std::vector<int> ldc((size_t)batch);
+  for (int b = 0; b < batch; ++b) ldc[b] = n[b] > 1 ? n[b] : 1;
+  for (int b : order) {
+    pA[b] = uA + offm[b];
+    pB[b] = problem ? uB + offm[b] : nullptr;
+    pw[b] = uw + offv[b];
+    pZ[b] = uZ + offz[b];
+  }
+  EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
+  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uw, hw.data(), cv * 8, hipMemcpyHostToDevice, s));
+  EK_HIP_CHECK(hipMemcpyAsync(uZ, hZ.data(), cz * 8, hipMemcpyHostToDevice, s));
+  return vwindow_device_locked(itype, problem, batch, order, n, pA.data(), ldc.data(), pB.data(), ldc.data(), m, pw.data(),
+                               pZ.data(), ldc.data(), info, out, ipr, seconds);
+}
+
 extern "C" {
 
 int ek_hip_check_batched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
@@ -832,6 +1036,37 @@ int ek_hip_check_sygv_xvbatched(int itype, int batch, const int *n, const double
   if (itype < 1 || itype > 3) return -1;
   return variable_host_entry(itype == 1 ? 0 : itype, 1, batch, n, A, lda, B, ldb, w, Z, ldz, info, out, ipr, seconds,
                              EK_HIP_XBATCH_NMAX);
+}
+
+// The variable window checks: what ek_hip_eigenpairs_window_xvbatched* and ek_hip_sygv_window_xvbatched*
+// return, m[b] columns of an n[b] x zcap[b] array per problem, in one call
+int ek_hip_check_window_xvbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                         const double *const *dB, const int *ldb, const int *m, const double *const *dw,
+                                         const double *const *dZ, const int *ldz, const int *zcap, const int *info,
+                                         double *out, double *const *ipr, double *seconds) {
+  return vwindow_entry(false, problem, batch, n, dA, lda, dB, ldb, m, dw, dZ, ldz, zcap, info, out, ipr, seconds, false);
+}
+
+int ek_hip_check_window_xvbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                                  const double *const *B, const int *ldb, const int *m, const double *const *w,
+                                  const double *const *Z, const int *ldz, const int *zcap, const int *info, double *out,
+                                  double *const *ipr, double *seconds) {
+  return vwindow_entry(false, problem, batch, n, A, lda, B, ldb, m, w, Z, ldz, zcap, info, out, ipr, seconds, true);
+}
+
+int ek_hip_check_sygv_window_xvbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
+                                              const double *const *dB, const int *ldb, const int *m,
+                                              const double *const *dw, const double *const *dZ, const int *ldz,
+                                              const int *zcap, const int *info, double *out, double *const *ipr,
+                                              double *seconds) {
+  return vwindow_entry(true, itype, batch, n, dA, lda, dB, ldb, m, dw, dZ, ldz, zcap, info, out, ipr, seconds, false);
+}
+
+int ek_hip_check_sygv_window_xvbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
+                                       const double *const *B, const int *ldb, const int *m, const double *const *w,
+                                       const double *const *Z, const int *ldz, const int *zcap, const int *info,
+                                       double *out, double *const *ipr, double *seconds) {
+  return vwindow_entry(true, itype, batch, n, A, lda, B, ldb, m, w, Z, ldz, zcap, info, out, ipr, seconds, true);
 }
 
 // the classes of the last variable-order check that was given `seconds` (include/ek_hip_debug.h)

@@ -33,6 +33,9 @@
 // every summation order depend on (n, c) alone; no atomics; the same kernel behind the host and the device form.  A, B, w
 // and Z are read only; nothing of w or Z from m[b] on, strictly above a diagonal, at or beyond row n or between the problems
 // is read.
+//
+// Each type's kernel has a second instantiation that finds order, c and addresses in the variable form's table
+// (bcheck::launch_sygv_window_v, behind ek_hip_check_sygv_window_xvbatched*: DESIGN.md 37); the passes exist once.
 #include "ek_batched_check_x.h"
 
 namespace ek {
@@ -265,8 +268,22 @@ __device__ __forceinline__ void img_axpy(gdouble *y, int sy, const double *x, do
   for (; i < i1; i += st) y[(size_t)i * sy] = fma(-x[i], a, y[(size_t)i * sy]);
 }
 
-template <int ITYPE>
-__global__ __launch_bounds__(T) void wcheck_sygv_kernel(Args a) {
+// the uniform launch's problem: entry first + workgroup of the map, the scratch by workgroup
+__device__ __forceinline__ bcheck::WProblem locate_w(const Args &a) {
+  const int n = a.n;
+  const int e = a.first + (int)blockIdx.x;
+  const long long pb = a.map[2 * e];
+  const int c = a.map[2 * e + 1];                   // 1 <= c <= n
+  return {n, c, (cgdouble *)(a.A + pb * a.sA), a.lda, (cgdouble *)(a.B + pb * a.sB), a.ldb, (cgdouble *)(a.w + pb * n),
+          (cgdouble *)(a.Z + pb * a.sZ), a.ldz, (gdouble *)(a.S + (long long)blockIdx.x * a.sS),
+          (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT), a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr};
+}
+__device__ __forceinline__ bcheck::WProblem locate_w(const bcheck::VArgs &a) { return bcheck::locate_window(a); }
+
+// ARGS: how the workgroup finds its problem -- Args (one order, strided; the scratch by workgroup) or bcheck::VArgs (entry
+// blockIdx.x of the launch's slice of the table, which names the entry's order, its m and its own scratch: DESIGN.md 37)
+template <int ITYPE, typename ARGS>
+__global__ __launch_bounds__(T) void wcheck_sygv_kernel(ARGS a) {
   static_assert(ITYPE == 2 || ITYPE == 3, "type 1 is ek_batched_check_window.hip's");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double *buf = smem;                               // [2][kBuf]
@@ -279,18 +296,16 @@ __global__ __launch_bounds__(T) void wcheck_sygv_kernel(Args a) {
 
   const int t = threadIdx.x, lane = t & 63, l15 = lane & 15, l4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // scalar: a skipped strip is a branch, not a mask
-  const int n = a.n;
-  const int e = a.first + (int)blockIdx.x;
-  const long long pb = a.map[2 * e];
-  const int c = a.map[2 * e + 1];                   // 1 <= c <= n
-  cgdouble *A = (cgdouble *)(a.A + pb * a.sA);
-  cgdouble *B = (cgdouble *)(a.B + pb * a.sB);
-  cgdouble *w = (cgdouble *)(a.w + pb * n);
-  cgdouble *Z = (cgdouble *)(a.Z + pb * a.sZ);
-  gdouble *S = (gdouble *)(a.S + (long long)blockIdx.x * a.sS);
-  gdouble *out = (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT);
-  gdouble *ipr = a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr;
-  const int lda = a.lda, ldb = a.ldb, ldz = a.ldz;
+  const bcheck::WProblem p = locate_w(a);
+  const int n = p.n, c = p.c;
+  cgdouble *A = p.A;
+  cgdouble *B = p.B;
+  cgdouble *w = p.w;
+  cgdouble *Z = p.Z;
+  gdouble *S = p.S;
+  gdouble *out = p.out;
+  gdouble *ipr = p.ipr;
+  const int lda = p.lda, ldb = p.ldb, ldz = p.ldz;
   cgdouble *M1 = ITYPE == 2 ? B : A, *M2 = ITYPE == 2 ? A : B;   // the first product's matrix, the second's
   const int ld1 = ITYPE == 2 ? ldb : lda, ld2 = ITYPE == 2 ? lda : ldb;
 
@@ -459,16 +474,16 @@ __global__ __launch_bounds__(T) void wcheck_sygv_kernel(Args a) {
   }
 }
 
-template <int ITYPE>
-static int launch(hipStream_t s, int count, const Args &a) {
+template <int ITYPE, typename ARGS>
+static int launch(hipStream_t s, int count, const ARGS &a) {
   constexpr size_t lds = (size_t)kLdsDoubles * sizeof(double);
   static bool raised = false;                       // one per instantiation
   if (!raised) {
-    EK_HIP_CHECK(hipFuncSetAttribute((const void *)wcheck_sygv_kernel<ITYPE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)wcheck_sygv_kernel<ITYPE, ARGS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds));
     raised = true;
   }
-  hipLaunchKernelGGL((wcheck_sygv_kernel<ITYPE>), dim3(count), dim3(T), lds, s, a);
+  hipLaunchKernelGGL((wcheck_sygv_kernel<ITYPE, ARGS>), dim3(count), dim3(T), lds, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -499,6 +514,12 @@ static int entry(int itype, int n, int batch, const double *A, int lda, long lon
 }
 
 }  // namespace wcheck_sygv
+
+// the variable form's launch (ek_batched_check.h): `count` entries of the table, itype 2 or 3
+int bcheck::launch_sygv_window_v(hipStream_t s, int itype, int count, const VArgs &a) {
+  return itype == 2 ? wcheck_sygv::launch<2>(s, count, a) : wcheck_sygv::launch<3>(s, count, a);
+}
+
 }  // namespace ek
 
 using namespace ek;

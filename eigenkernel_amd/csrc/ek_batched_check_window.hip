@@ -21,6 +21,9 @@
 //
 // Same bits wherever a problem sits: every loop bound, every skipped strip and every summation order depends on (n, c)
 // alone; no atomics; the same kernel behind the host and the device form.  A, B, w and Z are read only.
+//
+// The kernel has a second instantiation per problem kind that finds order, c and addresses in the variable form's table
+// (bcheck::launch_window_v, behind ek_hip_check_window_xvbatched*: DESIGN.md 37); the passes exist once.
 #include "ek_batched_check_x.h"
 
 namespace ek {
@@ -78,8 +81,25 @@ __device__ __forceinline__ void step_strip(const double *sp, const double *sp2, 
   }
 }
 
+// the uniform launch's problem: entry first + workgroup of the map, the scratch by workgroup
 template <bool GEN>
-__global__ __launch_bounds__(T) void wcheck_kernel(Args a) {
+__device__ __forceinline__ bcheck::WProblem locate_w(const Args &a) {
+  const int n = a.n;
+  const int e = a.first + (int)blockIdx.x;
+  const long long pb = a.map[2 * e];
+  const int c = a.map[2 * e + 1];                   // 1 <= c <= n
+  return {n, c, (cgdouble *)(a.A + pb * a.sA), a.lda, GEN ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (cgdouble *)(a.w + pb * n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
+          GEN ? (gdouble *)(a.S + (long long)blockIdx.x * a.sS) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
+          a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr};
+}
+template <bool GEN>
+__device__ __forceinline__ bcheck::WProblem locate_w(const bcheck::VArgs &a) { return bcheck::locate_window(a); }
+
+// ARGS: how the workgroup finds its problem -- Args (one order, strided; the scratch by workgroup) or bcheck::VArgs (entry
+// blockIdx.x of the launch's slice of the table, which names the entry's order, its m and its own scratch: DESIGN.md 37)
+template <bool GEN, typename ARGS>
+__global__ __launch_bounds__(T) void wcheck_kernel(ARGS a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int kB = kBuf, kQ = 2 * kTileP;         // a buffer; where its tile of Z (or S) starts
   double *buf = smem;                               // [2][kB]
@@ -89,18 +109,16 @@ __global__ __launch_bounds__(T) void wcheck_kernel(Args a) {
 
   const int t = threadIdx.x, lane = t & 63, l15 = lane & 15, l4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // scalar: a skipped strip is a branch, not a mask
-  const int n = a.n;
-  const int e = a.first + (int)blockIdx.x;
-  const long long pb = a.map[2 * e];
-  const int c = a.map[2 * e + 1];                   // 1 <= c <= n
-  cgdouble *A = (cgdouble *)(a.A + pb * a.sA);
-  cgdouble *B = GEN ? (cgdouble *)(a.B + pb * a.sB) : nullptr;
-  cgdouble *w = (cgdouble *)(a.w + pb * n);
-  cgdouble *Z = (cgdouble *)(a.Z + pb * a.sZ);
-  gdouble *S = GEN ? (gdouble *)(a.S + (long long)blockIdx.x * a.sS) : nullptr;
-  gdouble *out = (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT);
-  gdouble *ipr = a.ipr ? (gdouble *)(a.ipr + pb * n) : nullptr;
-  const int lda = a.lda, ldb = a.ldb, ldz = a.ldz;
+  const bcheck::WProblem p = locate_w<GEN>(a);
+  const int n = p.n, c = p.c;
+  cgdouble *A = p.A;
+  cgdouble *B = GEN ? p.B : nullptr;
+  cgdouble *w = p.w;
+  cgdouble *Z = p.Z;
+  gdouble *S = GEN ? p.S : nullptr;
+  gdouble *out = p.out;
+  gdouble *ipr = p.ipr;
+  const int lda = p.lda, ldb = p.ldb, ldz = p.ldz;
   const int nk = (n + KT - 1) / KT;
 
   // ---- 1: A Z, S = B Z, per column ||r_j||^2, G_jj, sum z^4; ||A||_F^2
@@ -259,16 +277,16 @@ __global__ __launch_bounds__(T) void wcheck_kernel(Args a) {
   }
 }
 
-template <bool GEN>
-static int launch(hipStream_t s, int count, const Args &a) {
+template <bool GEN, typename ARGS>
+static int launch(hipStream_t s, int count, const ARGS &a) {
   constexpr size_t lds = (size_t)kLdsDoubles * sizeof(double);
   static bool raised = false;                       // one per instantiation
   if (!raised) {
-    EK_HIP_CHECK(hipFuncSetAttribute((const void *)wcheck_kernel<GEN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    EK_HIP_CHECK(hipFuncSetAttribute((const void *)wcheck_kernel<GEN, ARGS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds));
     raised = true;
   }
-  hipLaunchKernelGGL((wcheck_kernel<GEN>), dim3(count), dim3(T), lds, s, a);
+  hipLaunchKernelGGL((wcheck_kernel<GEN, ARGS>), dim3(count), dim3(T), lds, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -293,6 +311,12 @@ static int entry(int problem, int n, int batch, const double *A, int lda, long l
 }
 
 }  // namespace wcheck
+
+// the variable form's launch (ek_batched_check.h): `count` entries of the table, a.problem says which instantiation
+int bcheck::launch_window_v(hipStream_t s, int count, const VArgs &a) {
+  return a.problem ? wcheck::launch<true>(s, count, a) : wcheck::launch<false>(s, count, a);
+}
+
 }  // namespace ek
 
 using namespace ek;

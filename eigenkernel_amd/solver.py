@@ -260,6 +260,14 @@ def load_library(path=None):
                                                        _dp]),
         "ek_hip_check_sygv_xvbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, vp, vp, _ip, _ip, _dp, vp, _dp]),
         "ek_hip_debug_check_xvbatched_last": (c_int, [_dp, _ip]),
+        "ek_hip_check_window_xvbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, _ip, vp, vp, _ip, _ip,
+                                                          _ip, _dp, vp, _dp]),
+        "ek_hip_check_window_xvbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, _ip, vp, vp, _ip, _ip,
+                                                   _ip, _dp, vp, _dp]),
+        "ek_hip_check_sygv_window_xvbatched_device": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, _ip, vp, vp, _ip, _ip,
+                                                               _ip, _dp, vp, _dp]),
+        "ek_hip_check_sygv_window_xvbatched": (c_int, [c_int, c_int, _ip, vp, _ip, vp, _ip, _ip, vp, vp, _ip, _ip,
+                                                        _ip, _dp, vp, _dp]),
         "ek_hip_debug_stage_leaves256": (c_int, [c_int]),
         "ek_hip_debug_set_sygst_direct": (c_int, [c_int]),
         "ek_hip_debug_sygst_scratch": (c_ull, [c_int, ctypes.POINTER(c_ull)]),
@@ -338,6 +346,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_sygv_window_xbatched_device", "ek_hip_sygv_window_xbatched",
     "ek_hip_check_window_xbatched_device", "ek_hip_check_window_xbatched",
     "ek_hip_check_sygv_window_xbatched_device", "ek_hip_check_sygv_window_xbatched",
+    "ek_hip_check_window_xvbatched_device", "ek_hip_check_window_xvbatched",
+    "ek_hip_check_sygv_window_xvbatched_device", "ek_hip_check_sygv_window_xvbatched",
 )
 
 
@@ -1476,6 +1486,94 @@ def check_sygv_xvbatched(As, Bs, ws, Zs, itype=1, info=None, ipr=True, seconds=N
     if Bs is None:
         raise ValueError("Bs is required")
     return _check_vbatched_call("ek_hip_check_sygv_xvbatched", int(itype), As, Bs, ws, Zs, info, ipr, seconds)
+
+
+def _check_window_vbatched_call(name, first, As, Bs, m, ws, Zs, info, ipr, zcap, seconds):
+    """ek_hip_check_window_xvbatched / ek_hip_check_sygv_window_xvbatched on sequences of arrays; `first` is the first
+    argument.  ws[b] and Zs[b] may be shorter than the order: what eigenpairs_window_xvbatched returns."""
+    lib = load_library()
+    Af = []
+    for M in As:
+        M = np.asarray(M, dtype=np.float64)
+        if M.ndim != 2 or M.shape[0] != M.shape[1]:
+            raise ValueError("every A must be a square 2-D array")
+        Af.append(np.asfortranarray(M))
+    batch = len(Af)
+    Bf = None
+    if Bs is not None:
+        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
+        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
+            raise ValueError("Bs must hold one array of A's shape per problem")
+    Zf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Zs]
+    if len(Zf) != batch or any(Zf[b].ndim != 2 or Zf[b].shape[0] != Af[b].shape[0] for b in range(batch)):
+        raise ValueError("Zs must hold one array with A's rows per problem")
+    wf = [np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for v in ws]
+    if len(wf) != batch or any(v.ndim != 1 for v in wf):
+        raise ValueError("ws must hold one vector per problem")
+    m = np.ascontiguousarray(np.asarray(m), dtype=np.int32)
+    if m.shape != (batch,):
+        raise ValueError("m must hold one int per problem")
+    info = _check_info(info, batch)
+    cols = np.array([M.shape[1] for M in Zf], dtype=np.int32)
+    if zcap is None:
+        zcap = cols
+    else:
+        zcap = np.asarray(zcap, dtype=np.int32)
+        zcap = np.full(batch, zcap, dtype=np.int32) if zcap.ndim == 0 else np.ascontiguousarray(zcap)
+        if zcap.shape != (batch,):
+            raise ValueError("zcap must be a scalar or hold one value per problem")
+        if (zcap > cols).any():
+            raise ValueError("zcap exceeds the columns of Z")
+    live = [(info is None or info[b] == 0) for b in range(batch)]
+    if any(live[b] and 0 <= m[b] <= zcap[b] and wf[b].shape[0] < m[b] for b in range(batch)):
+        raise ValueError("ws[b] must hold at least m[b] values")
+    out = np.full((batch, CHECK_NOUT), np.nan)
+    q = [np.full(M.shape[0], np.nan) for M in Af] if ipr else None
+    if batch == 0:
+        return out, q
+    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
+    ld = np.maximum(n, 1).astype(np.int32)
+    # a problem that is checked hands over what it has; an array without an entry still needs an address where the
+    # library asks for one (an order > 0): a skipped or empty problem's is never read
+    spare = np.zeros(1)
+
+    def table(arrays, need):
+        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else (spare.ctypes.data if need[b] else None)
+                                           for b, a in enumerate(arrays)])
+
+    rc = getattr(lib, name)(first, batch, _I(n), table(Af, n > 0), _I(ld),
+                            table(Bf, n > 0) if Bf is not None else None, _I(ld), _I(m), table(wf, n > 0),
+                            table(Zf, (n > 0) & (zcap > 0)), _I(ld), _I(zcap), _I(info) if info is not None else None,
+                            _P(out), table(q, n < 0) if ipr else None, _P(seconds) if seconds is not None else None)
+    if rc != 0:
+        raise SolverError(name + " failed", rc)
+    return out, q
+
+
+def check_window_xvbatched(As, Bs, m, ws, Zs, info=None, ipr=True, zcap=None, seconds=None):
+    """check_window_xbatched for problems of DIFFERENT orders up to XBATCH_NMAX (ek_hip_check_window_xvbatched), behind
+    eigenpairs_window_xvbatched: As, Bs (or None) the ORIGINAL matrices, and m, ws, Zs, info as that function returns
+    them -- ws[b] holds at least m[b] values, Zs[b] has n[b] rows and at least m[b] columns (zcap: None for the columns of
+    every Zs[b], a scalar or one capacity per problem).  Returns (out, list of ipr arrays or None): out[b] = (a_norm,
+    res_ave, res_max, orthogonality) over m[b] columns; ipr[b] has n[b] entries with NaN from m[b] on.  A problem with
+    info[b] != 0, m[b] == 0 or order 0 gets a NaN row in both.  Each problem's bits are those of check_window_xbatched on it
+    alone.  Raises ValueError for bad shapes, SolverError when the call itself fails (-8: an m[b] outside 0 .. n[b], -12:
+    an m[b] above zcap[b], of a problem that info does not skip)."""
+    return _check_window_vbatched_call("ek_hip_check_window_xvbatched", 0 if Bs is None else 1, As, Bs, m, ws, Zs, info,
+                                       ipr, zcap, seconds)
+
+
+def check_sygv_window_xvbatched(As, Bs, m, ws, Zs, itype=1, info=None, ipr=True, zcap=None, seconds=None):
+    """check_window_xvbatched for DSYGV's three problem types (ek_hip_check_sygv_window_xvbatched), behind
+    sygv_window_xvbatched: the same arguments and returns, each problem's bits those of check_sygv_window_xbatched on it
+    alone (itype 1 is check_window_xvbatched(As, Bs, ...) to the bit).  A missing Bs or an itype outside 1 .. 3 raises
+    ValueError before the library is called."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if Bs is None:
+        raise ValueError("Bs is required")
+    return _check_window_vbatched_call("ek_hip_check_sygv_window_xvbatched", int(itype), As, Bs, m, ws, Zs, info, ipr,
+                                       zcap, seconds)
 
 
 def check_xvbatched_last():

@@ -750,8 +750,8 @@ int ek_hip_check_xbatched(int problem, int n, int batch, const double *A, int ld
  * Workspace (device memory of the pool of all ek_hip_check_*batched* entries, kept until ek_hip_finalize): n x max m[b]
  * doubles for each of the min(checked problems, 1024) problems of a chunk of a generalized batch (S = B Z), 4 + n doubles
  * per problem for the outputs, 8 bytes per checked problem, two events.
- * Not offered: a variable-order form behind ek_hip_*_window_xvbatched*.  DSYGV's types 2 and 3 are
- * ek_hip_check_sygv_window_xbatched* below. */
+ * The variable-order form behind ek_hip_*_window_xvbatched* is ek_hip_check_window_xvbatched* below.  DSYGV's types 2 and 3
+ * are ek_hip_check_sygv_window_xbatched* below. */
 int ek_hip_check_window_xbatched_device(int problem, int n, int batch, const double *dA, int lda, long long strideA,
                                         const double *dB, int ldb, long long strideB, const int *m, const double *dw,
                                         const double *dZ, int ldz, int zcap, long long strideZ, const int *info,
@@ -794,7 +794,8 @@ int ek_hip_check_window_xbatched(int problem, int n, int batch, const double *A,
  * fp64 matrix cores over LDS-staged tiles; type 3's factor costs n^3 / 3 whatever c is, its forward solve runs over the c
  * columns with 512 / (the power of two >= max(c, 16)) threads per column.  Chunks and *seconds as above.
  * Workspace (the same pool): per problem of a chunk n x max m[b] doubles (type 2), n^2 + n x max m[b] (type 3).
- * Not offered: a variable-order form. */
+ * Not offered: a variable-order form of this strided prototype.  Problems of different orders (what
+ * ek_hip_sygv_window_xvbatched* returns) are checked in one call by ek_hip_check_sygv_window_xvbatched* below. */
 int ek_hip_check_sygv_window_xbatched_device(int itype, int n, int batch, const double *dA, int lda, long long strideA,
                                              const double *dB, int ldb, long long strideB, const int *m, const double *dw,
                                              const double *dZ, int ldz, int zcap, long long strideZ, const int *info,
@@ -947,6 +948,63 @@ int ek_hip_check_sygv_xvbatched_device(int itype, int batch, const int *n, const
 int ek_hip_check_sygv_xvbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
                                 const double *const *B, const int *ldb, const double *const *w, const double *const *Z,
                                 const int *ldz, const int *info, double *out, double *const *ipr, double *seconds);
+/* The window checks for problems of DIFFERENT orders, behind ek_hip_eigenpairs_window_xvbatched* and
+ * ek_hip_sygv_window_xvbatched*: problem b has the c = m[b] values dw[b][0 .. c) and the columns 0 .. c-1 of the
+ * n[b] x zcap[b] array dZ[b].  The 14 arguments of ek_hip_check_xvbatched* with m in front of dw and zcap behind ldz, so
+ * that the solvers' n, m, dw, dZ, ldz, zcap and info are handed over unchanged.  n, lda, ldb, m, ldz, zcap, info, out and
+ * the pointer arrays are HOST arrays of `batch` entries; the pointers IN dA, dB, dw, dZ are device addresses (device form)
+ * or host addresses (host form), those in ipr always host addresses (ipr == NULL or a NULL entry: not wanted; ipr[b] holds
+ * at least m[b] doubles, m[b] are written).  dA, dB: the ORIGINAL matrices, lower triangles only.
+ * Per checked problem, with c = m[b]: exactly the four words and c IPRs that ek_hip_check_window_xbatched* (problem 0 / 1)
+ * or ek_hip_check_sygv_window_xbatched* (itype 1 .. 3) define on c columns, type 3's own factor of the caller's B included
+ * (a B that is not positive definite: NaN in slot 3 and in the c IPRs only, return value 0).
+ * SKIPPED PROBLEMS: info != NULL and info[b] != 0 gives four NaN, leaves the ipr row alone and looks at nothing of that
+ * problem's m, w or Z -- -20 included, where m[b] is a count above zcap[b].  EMPTY WINDOWS: m[b] == 0 is handled the same
+ * way.  n[b] == 0 forces m[b] == 0, so an order-0 problem is an empty window and gets FOUR NaN -- not the a_norm = 0 of
+ * ek_hip_check_xvbatched*.  A batch with nothing to check is filled on the host without the context or a device;
+ * batch == 0 returns 0 with nothing referenced or written.
+ * Return value: 0, or -k for argument k of the prototype, the first offender deciding, before any device work and without
+ * dereferencing any pointer of the pointer arrays (m and info are read):
+ *   -1 problem outside 0 / 1 (sygv forms: itype outside 1 .. 3), before everything, batch = 0 included   -2 batch < 0
+ *   -3 n NULL or an order outside 0 .. EK_HIP_XBATCH_NMAX
+ *   -4 / -5 dA NULL or a NULL entry for an order > 0; lda NULL or below max(1, n[b])
+ *   -6 / -7 the same for dB, ldb (problem 1 only; always in the sygv forms, itype = 1 included)
+ *   -8 m NULL, or m[b] outside 0 .. n[b] for a problem that info does not skip
+ *   -9 dw NULL or a NULL entry for an order > 0
+ *   -10 dZ NULL or a NULL entry for an order > 0 with zcap[b] > 0 (NULL is allowed where zcap[b] = 0, as in the solver)
+ *   -11 ldz NULL or below max(1, n[b])
+ *   -12 zcap NULL, zcap[b] < 0, or zcap[b] < m[b] for a problem that info does not skip
+ *   -14 out NULL;   info, ipr, seconds may be NULL;   <= -1000 a HIP runtime error
+ * THE SAME BITS AS THE UNIFORM CALL: problem b's four words and m[b] IPRs are bit for bit those of
+ * ek_hip_check_window_xbatched_device (ek_hip_check_sygv_window_xbatched_device) on (n[b], A, B, m[b], w, Z) alone --
+ * wherever it sits, whatever surrounds it, in whichever launch, in the host and the device form.  So itype = 1 IS
+ * ek_hip_check_window_xvbatched*(problem = 1), and type 2's slot 3 and IPRs are type 1's bits.  NEVER READ: w and Z from
+ * m[b] on, strictly upper triangles, rows n[b] .. ld-1, the gaps between problems.  NEVER WRITTEN: A, B, w, Z.
+ * The window kernels serve every order in one class, so there are no classes here: one stable sort by descending estimated
+ * work (n^2 m, plus n^3 / 3 for type 3), one table upload, launches of at most 1024 entries
+ * (ek_hip_debug_check_xbatched_chunk governs it) one after the other on one stream, one fetch, one synchronise; *seconds is
+ * the device time from before the first launch to after the last.  NOT COLLECTIVE.
+ * Workspace (the pool of all ek_hip_check_*batched* entries): the largest chunk's sum of n[b] m[b] doubles (problem 1,
+ * type 2) or n[b]^2 + n[b] m[b] (type 3), nothing for problem 0; 4 doubles per problem and m[b] per wanted IPR row; 64
+ * bytes per checked problem.  Host form: the lower triangles travel packed (ld = n[b]), one copy per matrix kind, m[b]
+ * values of w and m[b] columns of Z per problem; nothing of a skipped or empty problem is staged. */
+int ek_hip_check_window_xvbatched_device(int problem, int batch, const int *n, const double *const *dA, const int *lda,
+                                         const double *const *dB, const int *ldb, const int *m, const double *const *dw,
+                                         const double *const *dZ, const int *ldz, const int *zcap, const int *info,
+                                         double *out, double *const *ipr, double *seconds);
+int ek_hip_check_window_xvbatched(int problem, int batch, const int *n, const double *const *A, const int *lda,
+                                  const double *const *B, const int *ldb, const int *m, const double *const *w,
+                                  const double *const *Z, const int *ldz, const int *zcap, const int *info, double *out,
+                                  double *const *ipr, double *seconds);
+int ek_hip_check_sygv_window_xvbatched_device(int itype, int batch, const int *n, const double *const *dA, const int *lda,
+                                              const double *const *dB, const int *ldb, const int *m,
+                                              const double *const *dw, const double *const *dZ, const int *ldz,
+                                              const int *zcap, const int *info, double *out, double *const *ipr,
+                                              double *seconds);
+int ek_hip_check_sygv_window_xvbatched(int itype, int batch, const int *n, const double *const *A, const int *lda,
+                                       const double *const *B, const int *ldb, const int *m, const double *const *w,
+                                       const double *const *Z, const int *ldz, const int *zcap, const int *info,
+                                       double *out, double *const *ipr, double *seconds);
 /* One problem of ANY order: the quantities above for the first n_cols columns of Z (what a window of ek_hip_sygvx*
  * returns; sum_j rho_j / n_cols, G of order n_cols), out[0 .. 3] and ipr_host[0 .. n_cols-1] (host; ipr_host may be NULL).
  * dA, dB: the ORIGINAL column-major matrices (lda, ldb >= max(1, n); lower triangles referenced), dw: n_cols eigenvalues,

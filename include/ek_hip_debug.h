@@ -188,7 +188,9 @@ long long ek_hip_debug_window_xvbatched_budget(long long bytes);
 int ek_hip_debug_check_xbatched_chunk(int problems);
 /* the last ek_hip_check_*vbatched* or ek_hip_check_*xvbatched* call that was given `seconds`: device time of the classes of
    256 (orders above EK_HIP_BATCH_NMAX, all chunks), 128, 64 and 32 (events between them on the one stream) and the problems
-   each took; either pointer may be NULL.  The shape of ek_hip_debug_xvbatched_last. */
+   each took; either pointer may be NULL.  The shape of ek_hip_debug_xvbatched_last.  NOT fed by
+   ek_hip_check_window_xvbatched* and ek_hip_check_sygv_window_xvbatched*: they have one kernel class for every order, whose
+   time is their `seconds`; the chunk size above governs their launches too. */
 int ek_hip_debug_check_xvbatched_last(double class_seconds[4], int class_count[4]);
 
 /* Test hooks of the stage entries of the generalized path (ek_hip_sygst, ek_hip_sygst_ibtype, ek_hip_trtrs; ek_chol.hip).

@@ -60,6 +60,12 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  (ek_hip_*_xvbatched_device) and one uniform window call with every
                                                  problem padded to the largest order; device times, a stream per class
                                                  and one stream, the classes' times and counts
+  python tools/batched_timing.py --mixed --window 0.125 --check [--mixed-batch 512] [--mixed-orders 8,256] [--itype 1]
+                                                 the variable window check (ek_hip_check_window_xvbatched_device;
+                                                 --itype 2 / 3: ek_hip_check_sygv_window_xvbatched_device) on that
+                                                 workload's m, w and Z: against a uniform window-check call per distinct
+                                                 order, against the variable window solve that produced the pairs and
+                                                 against the full variable check on the full solve of the same batch
 
 Per (problem, jobz, n, batch): one warm-up of each kind, then three rounds that alternate the kinds, best by wall clock
 (both calls synchronise; both work in place, so the inputs are restored outside the clock).  The loop is timed over
@@ -590,6 +596,122 @@ def mixed_window(lib, batch, lo, hi, fraction, itype):
         lib.ek_hip_free(p)
 
 
+def mixed_window_check(lib, batch, lo, hi, fraction, itype):
+    """The variable window check (ek_hip_check_window_xvbatched_device; --itype 2 / 3:
+    ek_hip_check_sygv_window_xvbatched_device) on the workload of mixed_window: against a uniform window-check call per
+    distinct order, against the variable window solve that produced the pairs, and against the full variable check on
+    the full solve of the same batch.  One warm-up of each kind, then three rounds that alternate the kinds; device
+    seconds (the checks do not touch their inputs), and the wall clock of the two ways to check the windows."""
+    I = ctypes.POINTER(ctypes.c_int)
+    D = ctypes.POINTER(ctypes.c_double)
+    rng = np.random.default_rng(2024)
+    orders = np.sort(rng.integers(lo, hi + 1, size=batch)).astype(np.int64)
+    distinct = np.unique(orders)
+    cols = np.maximum(1, (fraction * orders).astype(np.int64))
+    seeds = {int(n): pairs(500 + int(n), 1, int(n)) for n in distinct}
+    offm = np.concatenate([[0], np.cumsum(orders ** 2)])
+    offw = np.concatenate([[0], np.cumsum(orders)])
+    offz = np.concatenate([[0], np.cumsum(orders * cols)])
+    hA, hB = np.empty(offm[-1]), np.empty(offm[-1])
+    for b, n in enumerate(orders):
+        A, B = seeds[int(n)]
+        hA[offm[b]:offm[b + 1]], hB[offm[b]:offm[b + 1]] = A[0].ravel(), B[0].ravel()
+    keep = []
+
+    def alloc(nbytes):
+        p = ctypes.c_void_p()
+        assert lib.ek_hip_malloc(ctypes.byref(p), int(max(nbytes, 8))) == 0
+        keep.append(p)
+        return p
+
+    def put(p, a):
+        assert lib.ek_hip_memcpy_h2d(p, a.ctypes.data, a.nbytes) == 0
+
+    dA0, dB0, dA, dB = (alloc(hA.nbytes) for _ in range(4))
+    dw, dZ, dwf, dZf = alloc(offw[-1] * 8), alloc(offz[-1] * 8), alloc(offw[-1] * 8), alloc(hA.nbytes)
+    put(dA0, hA); put(dB0, hB)
+    perm = rng.permutation(batch)
+
+    def table(base, off):
+        return (ctypes.c_void_p * batch)(*[base.value + int(off[b]) * 8 for b in perm])
+
+    def at(p, off):
+        return ctypes.c_void_p(p.value + int(off) * 8)
+
+    tA0, tB0, tA, tB = table(dA0, offm), table(dB0, offm), table(dA, offm), table(dB, offm)
+    tw, tZ, twf, tZf = table(dw, offw), table(dZ, offz), table(dwf, offw), table(dZf, offm)
+    n32 = orders[perm].astype(np.int32)
+    il = np.ones(batch, dtype=np.int32)
+    iu = cols[perm].astype(np.int32)
+    m, info = np.zeros(batch, dtype=np.int32), np.zeros(batch, dtype=np.int32)
+    mu = np.zeros(batch, dtype=np.int32)
+    out = np.zeros((batch, 4))
+    sec = np.zeros(1)
+    ip = lambda a: a.ctypes.data_as(I)              # noqa: E731
+    dp = lambda a: a.ctypes.data_as(D)              # noqa: E731
+    if itype != 1:
+        wsolve, fsolve = lib.ek_hip_sygv_window_xvbatched_device, lib.ek_hip_sygv_xvbatched_device
+        vcheck, ucheck = lib.ek_hip_check_sygv_window_xvbatched_device, lib.ek_hip_check_sygv_window_xbatched_device
+        fcheck = lib.ek_hip_check_sygv_xvbatched_device
+    else:
+        wsolve, fsolve = lib.ek_hip_eigenpairs_window_xvbatched_device, lib.ek_hip_eigenpairs_xvbatched_device
+        vcheck, ucheck = lib.ek_hip_check_window_xvbatched_device, lib.ek_hip_check_window_xbatched_device
+        fcheck = lib.ek_hip_check_xvbatched_device
+
+    def solve():
+        put(dA, hA); put(dB, hB)
+        rc = wsolve(itype, 1, 0, batch, ip(n32), None, None, ip(il), ip(iu), tA, ip(n32), tB, ip(n32), ip(m), tw, tZ,
+                    ip(n32), ip(iu), ip(info), dp(sec))
+        assert rc == 0 and not info.any() and (m == iu).all(), (rc, info[info != 0][:4])
+        return float(sec[0])
+
+    def variable():
+        t0 = time.perf_counter()
+        rc = vcheck(itype, batch, ip(n32), tA0, ip(n32), tB0, ip(n32), ip(m), tw, tZ, ip(n32), ip(iu), ip(info), dp(out),
+                    None, dp(sec))
+        assert rc == 0
+        return float(sec[0]), time.perf_counter() - t0
+
+    def per_order():
+        t, t0 = 0.0, time.perf_counter()
+        for n in distinct:
+            n = int(n)
+            f, c, k = int(np.searchsorted(orders, n)), int((orders == n).sum()), max(1, int(fraction * n))
+            mu[:c] = k
+            rc = ucheck(itype, n, c, at(dA0, offm[f]), n, n * n, at(dB0, offm[f]), n, n * n, ip(mu), at(dw, offw[f]),
+                        at(dZ, offz[f]), n, k, n * k, None, dp(out), None, dp(sec))
+            assert rc == 0
+            t += float(sec[0])
+        return t, time.perf_counter() - t0
+
+    def full():
+        rc = fcheck(itype, batch, ip(n32), tA0, ip(n32), tB0, ip(n32), twf, tZf, ip(n32), ip(info), dp(out), None, dp(sec))
+        assert rc == 0
+        return float(sec[0])
+
+    put(dA, hA); put(dB, hB)
+    rc = fsolve(itype, 1, batch, ip(n32), tA, ip(n32), tB, ip(n32), twf, tZf, ip(n32), ip(info), None)
+    assert rc == 0 and not info.any()
+    solve()                                         # warm-up of each kind
+    ts = [solve() for _ in range(3)]
+    variable(); per_order(); full()
+    tv, tvw, tu, tuw, tf = [], [], [], [], []
+    for _ in range(3):
+        a, b = variable()
+        worst = (float(out[:, 2].max()), float(out[:, 3].max()))
+        c, d = per_order()
+        tv.append(a); tvw.append(b); tu.append(c); tuw.append(d); tf.append(full())
+    print("# check of %d generalized problems (itype %d) of orders %d..%d (%d distinct), the lowest max(1, %g n) pairs"
+          % (batch, itype, lo, hi, len(distinct), fraction))
+    print("  variable window check %.3f ms (wall %.3f ms) | uniform window check per order %.3f ms (%.1f x; wall %.3f ms, "
+          "%.1f x) | variable window solve %.3f ms (check / solve %.4f) | full variable check of the full solve %.3f ms "
+          "(window / full %.3f) | worst res_max %.2e, orthogonality %.2e"
+          % (min(tv) * 1e3, min(tvw) * 1e3, min(tu) * 1e3, min(tu) / min(tv), min(tuw) * 1e3, min(tuw) / min(tvw),
+             min(ts) * 1e3, min(tv) / min(ts), min(tf) * 1e3, min(tv) / min(tf), worst[0], worst[1]), flush=True)
+    for p in keep:
+        lib.ek_hip_free(p)
+
+
 def window_check_rows(lib, sizes, batches, fractions, loop_max, itype=1):
     """The window of max(1, fraction n) pairs from index n / 4 + 1, with vectors.  Per (problem, n, batch, fraction): a
     warm-up, then three rounds of window solve, window check, full check (on a full solve's w and Z, made once) and the
@@ -681,7 +803,7 @@ def main():
     if args.mixed and args.window:
         lo, hi = (int(x) for x in args.mixed_orders.split(","))
         for fraction in (float(x) for x in args.window.split(",")):
-            mixed_window(lib, args.mixed_batch, lo, hi, fraction, args.itype)
+            (mixed_window_check if args.check else mixed_window)(lib, args.mixed_batch, lo, hi, fraction, args.itype)
         lib.ek_hip_finalize()
         return
     if args.window and args.itype != 1 and not args.check:
