@@ -5,16 +5,17 @@
 //                              driver of every variable-order entry, ek_hip_check_*xvbatched* included:
 //                              four classes (256, 128, 64, 32) from one table, the class of 256 in chunks
 //   ek_batched_check_sygv.hip  the kernel of DSYGV's types 2 and 3
-//   ek_batched_check_x.hip, ek_batched_check_sygv_x.hip  the kernels above EK_HIP_BATCH_NMAX and their uniform entries
-//                              (ek_batched_check_x.h), which hand the host driver a launch function, and the launches of
+//   ek_batched_check_x.h       the checks on the matrix cores: loaders, step, products, passes and the two kernel bodies
+//                              (DESIGN.md 38), instantiated by four units that each hold their uniform Args, their
+//                              launches and their entries and hand the host driver a launch function:
+//     ek_batched_check_x.hip, ek_batched_check_sygv_x.hip  the full checks above EK_HIP_BATCH_NMAX, and the launches of
 //                              their table form for the variable driver (launch_x, launch_sygv_x)
-//   ek_batched_check_window.hip  the kernel of the window check (m[b] columns per problem, every order up to
-//                              EK_HIP_XBATCH_NMAX) and its entries, which hand the window driver a launch function
-//   ek_batched_check_sygv_window.hip  the same for DSYGV's types 2 and 3
-//                              Both window units also hold the table instantiation of their kernel (launch_window_v,
-//                              launch_sygv_window_v) for ek_hip_check_*window_xvbatched* (DESIGN.md 37), whose driver and
-//                              entries are ek_batched_check.hip's
-// The kernels live in units of their own so that adding one leaves the code generated for the others as it was.
+//     ek_batched_check_window.hip, ek_batched_check_sygv_window.hip  the window checks (m[b] columns per problem, every
+//                              order up to EK_HIP_XBATCH_NMAX), and the launches of their table form
+//                              (launch_window_v, launch_sygv_window_v) for ek_hip_check_*window_xvbatched* (DESIGN.md
+//                              37), whose driver and entries are ek_batched_check.hip's
+// The kernels are instantiated in units of their own so that a unit's code generation does not depend on what else is
+// compiled beside it.
 #pragma once
 #include "ek_batched_stages.h"
 
@@ -53,30 +54,9 @@ struct VArgs {
 // global address space, the solver's own types: a pointer loaded from the table would otherwise cost flat accesses
 using bstages::gdouble;
 using bstages::cgdouble;
+// What a workgroup works on.  c: the columns of Z to check -- n in the kernels up to EK_HIP_BATCH_NMAX; the window kernels
+// take it (the table's m), the full kernels above EK_HIP_BATCH_NMAX take n and leave it unread (ek_batched_check_x.h)
 struct Problem {
-  int n;
-  cgdouble *A; int lda;
-  cgdouble *B; int ldb;
-  cgdouble *w;
-  cgdouble *Z; int ldz;
-  gdouble *S, *out, *ipr;
-};
-__device__ __forceinline__ Problem locate(const Args &a) {
-  const long long pb = a.map ? a.map[blockIdx.x] : (int)blockIdx.x;
-  return {a.n, (cgdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
-          (cgdouble *)(a.w + pb * a.n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
-          a.problem ? (gdouble *)(a.S + pb * a.n * a.n) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
-          a.ipr ? (gdouble *)(a.ipr + pb * a.n) : nullptr};
-}
-__device__ __forceinline__ Problem locate(const VArgs &a) {
-  const Desc &d = a.table[blockIdx.x];
-  return {d.n, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
-          (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};
-}
-
-// What a workgroup of the window kernels (ek_batched_check_window.hip, ek_batched_check_sygv_window.hip) works on: c = m[b]
-// columns of problem b.  Both argument forms of those kernels resolve to this in their first lines
-struct WProblem {
   int n, c;
   cgdouble *A; int lda;
   cgdouble *B; int ldb;
@@ -84,8 +64,17 @@ struct WProblem {
   cgdouble *Z; int ldz;
   gdouble *S, *out, *ipr;
 };
+// One locate per argument form.  The kernels of ek_batched_check_x.h call locate(a, kind) with the problem or the type: the
+// uniform Args of their units, each with a locate of its own beside it, size the scratch by it; the table does not need it
+__device__ __forceinline__ Problem locate(const Args &a) {
+  const long long pb = a.map ? a.map[blockIdx.x] : (int)blockIdx.x;
+  return {a.n, a.n, (cgdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (cgdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
+          (cgdouble *)(a.w + pb * a.n), (cgdouble *)(a.Z + pb * a.sZ), a.ldz,
+          a.problem ? (gdouble *)(a.S + pb * a.n * a.n) : nullptr, (gdouble *)(a.out + pb * EK_HIP_CHECK_NOUT),
+          a.ipr ? (gdouble *)(a.ipr + pb * a.n) : nullptr};
+}
 // the table form: entry blockIdx.x of the launch's slice of the table
-__device__ __forceinline__ WProblem locate_window(const VArgs &a) {
+__device__ __forceinline__ Problem locate(const VArgs &a, int /* kind */ = 0) {
   const Desc &d = a.table[blockIdx.x];
   return {d.n, d.m, (cgdouble *)d.A, d.lda, (cgdouble *)d.B, d.ldb, (cgdouble *)d.w, (cgdouble *)d.Z, d.ldz,
           (gdouble *)d.S, (gdouble *)(a.out + (long long)d.index * EK_HIP_CHECK_NOUT), (gdouble *)d.ipr};

@@ -4,7 +4,10 @@ function bodies between a kernel's label and its .end_amdhsa_kernel / .Lfunc_end
 in block labels masked.  Prints one line per kernel of the first file (identical / DIFFERENT / absent), then the kernels
 only the second file has with their registers, LDS and scratch.
 
-    tools/compare_kernel_asm.py parent.s new.s
+    tools/compare_kernel_asm.py [--in-order] parent.s new.s
+
+--in-order: the k-th kernel of the first file is compared with the k-th of the second, whatever their names (templates
+that were renamed or took a parameter; both files must hold the same number of kernels), and both names are printed.
 """
 import re
 import sys
@@ -40,8 +43,15 @@ def kernels(path):
 
 
 def main():
-    a, _ = kernels(sys.argv[1])
-    b, meta = kernels(sys.argv[2])
+    args = [x for x in sys.argv[1:] if x != "--in-order"]
+    a, _ = kernels(args[0])  # noqa
+    b, meta = kernels(args[1])
+    if "--in-order" in sys.argv:
+        ka, kb = [k for k in a if k in _], [k for k in b if k in meta]
+        assert len(ka) == len(kb), (len(ka), len(kb))
+        for old, new in zip(ka, kb):
+            print("paired     ", old, "->", new, meta[new], "was", _[old])
+        a = {new: [line.replace(old, new) for line in a[old]] for old, new in zip(ka, kb)}
     same = diff = 0
     for k in sorted(a):
         if k not in meta and k not in b:
