@@ -50,8 +50,11 @@
 // ek_hip_eigenpairs_window_xvbatched*, ek_hip_sygv_window_xvbatched*: a window per problem for problems of different orders.
 // A fourth argument type, VWArgs: the table form, and beside the problem's entry an entry of a second table with its
 // window and the place of its LU slot.  Stages 0 to 3 are the table kernels' lines, stage 4W and stage 5 the window
-// kernels'; the host driver (classes, launches by count and by LU budget, a region of the LU workspace per class) is
-// vwindow_device_locked below, for ek_batched_x.hip's class too.
+// kernels'; the host side (classes, launches by count and by LU budget, a region of the LU workspace per class) is
+// run_variable_window below, for ek_batched_x.hip's class too.
+//
+// The host side of all these entries is one driver: an entry fills a UniformCall or a VariableCall, entry()
+// checks it and takes the lock, stage() makes device copies for the host-pointer forms, run() issues the launches.
 #include "ek_batched_stages.h"
 #include "ek_batched_window.h"
 
@@ -666,36 +669,49 @@ static int launch_class(hipStream_t s, int batch, const ARGS &a) {
 // LDS bytes (dynamic part) and threads of the class that takes order n: host arithmetic for tools and DESIGN.md 12
 static int class_of(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
 
-// per-problem status words: grown, never shrunk, released in ek_hip_finalize
-static int *g_dinfo = nullptr;
-static size_t g_dinfo_count = 0;
-
-// the variable form's problem table, the streams of the classes behind the largest one present (that one runs on the
-// context's stream) and the events that tie them to it: kept like the status words
-static Desc *g_dtable = nullptr;
-static size_t g_dtable_count = 0;
-static std::vector<Desc> g_htable;                 // its host image
-constexpr int kClasses = 4;                         // 256 (ek_batched_x.hip's kernel; ek_hip_*_xvbatched* only), 128, 64, 32
-static hipStream_t g_side[kClasses - 1] = {};
-constexpr int kEvents = 3 * kClasses + 1;           // fork, joins, start / end of each class, end of the call
-static hipEvent_t g_ev[kEvents] = {};
-static int g_streams = 3;                           // 3: a stream per class; 1: one stream (ek_hip_debug_vbatched_streams)
-static double g_class_seconds[kClasses] = {};       // the last timed variable call's kernels, by class
-static int g_class_count[kClasses] = {};
-
-static int ensure_info(size_t batch) {
-  if (batch <= g_dinfo_count) return 0;
-  if (g_dinfo) (void)hipFree(g_dinfo);
-  g_dinfo = nullptr;
-  g_dinfo_count = 0;
-  EK_HIP_CHECK(hipMalloc((void **)&g_dinfo, batch * sizeof(int)));
-  g_dinfo_count = batch;
-  return 0;
+// the one switch over the three classes of LDS: `count` workgroups of the class that takes order n
+template <typename ARGS>
+static int launch_order(int n, hipStream_t s, int count, const ARGS &a) {
+  switch (class_of(n)) {
+    case 32: return launch_class<32, 64>(s, count, a);
+    case 64: return launch_class<64, 128>(s, count, a);
+    default: return launch_class<128, 256>(s, count, a);
+  }
 }
 
-// ek_hip_eigenpairs_window_batched*: a count per problem, and the LU factors of inverse iteration -- one slot per
-// workgroup of a launch, the batch running in chunks of g_wchunk problems that share the slots (the stream's order
-// separates two users of a slot, as in ek_batched_x.hip).  Grown, never shrunk, released in ek_hip_finalize
+// ---- the host driver of every entry family
+
+// a device array that is grown, never shrunk, and released in ek_hip_finalize
+template <typename T>
+struct Pool {
+  T *p = nullptr;
+  size_t count = 0;
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    count = 0;
+  }
+  int grow(size_t need) {
+    if (need <= count) return 0;
+    release();
+    EK_HIP_CHECK(hipMalloc((void **)&p, need * sizeof(T)));
+    count = need;
+    return 0;
+  }
+};
+static Pool<int> g_dinfo;                           // per-problem status words
+// the window entries: a count per problem, and the LU factors of inverse iteration -- one slot per workgroup of a
+// launch, the batch running in chunks of g_wchunk problems that share the slots (the stream's order separates two users
+// of a slot, as in ek_batched_x.hip)
+static Pool<int> g_dm;
+static Pool<double> g_wws;
+// the variable forms' problem table and, for ek_hip_*_window_xvbatched*, the window table beside it; their host images are
+// static because the asynchronous upload may still read them when an error returns
+static Pool<Desc> g_dtable;
+static Pool<WDesc> g_dwtable;
+static std::vector<Desc> g_htable;
+static std::vector<WDesc> g_hwtable;
+
 constexpr int kWindowChunk = 1024;
 constexpr size_t kWindowBytes = (size_t)256 << 20;
 static int g_wchunk = kWindowChunk;
@@ -705,48 +721,21 @@ static int g_wchunk = kWindowChunk;
 constexpr int kXWindowChunk = 1024, kXWindowRound = 512;
 constexpr size_t kXWindowBytes = (size_t)1 << 30;
 static int g_xwchunk = kXWindowChunk;
-static int *g_dm = nullptr;
-static size_t g_dm_count = 0;
-static double *g_wws = nullptr;
-static size_t g_wws_bytes = 0;
-
-// ek_hip_*_window_xvbatched*: the window table beside the problem table, kept like it
-static WDesc *g_dwtable = nullptr;
-static size_t g_dwtable_count = 0;
-static std::vector<WDesc> g_hwtable;
 static long long g_vwbudget = 0;                    // LU bytes a launch may hold (ek_hip_debug_window_xvbatched_budget)
-struct VLaunch { int cls, first, count; };          // a launch: `count` table entries from `first`
 
-static int ensure_window(size_t batch, size_t bytes) {
-  if (batch > g_dm_count) {
-    if (g_dm) (void)hipFree(g_dm);
-    g_dm = nullptr;
-    g_dm_count = 0;
-    EK_HIP_CHECK(hipMalloc((void **)&g_dm, batch * sizeof(int)));
-    g_dm_count = batch;
-  }
-  if (bytes > g_wws_bytes) {
-    if (g_wws) (void)hipFree(g_wws);
-    g_wws = nullptr;
-    g_wws_bytes = 0;
-    EK_HIP_CHECK(hipMalloc((void **)&g_wws, bytes));
-    g_wws_bytes = bytes;
-  }
-  return 0;
-}
+// the variable forms: the streams of the classes behind the largest one present (that one runs on the context's stream)
+// and the events that tie them to it, kept like the pools
+constexpr int kClasses = 4;                         // 256 (ek_batched_x.hip's kernel; ek_hip_*_xvbatched* only), 128, 64, 32
+constexpr int kClassOrder[kClasses] = {EK_HIP_XBATCH_NMAX, 128, 64, 32};
+static hipStream_t g_side[kClasses - 1] = {};
+constexpr int kEvents = 3 * kClasses + 1;           // fork, joins, start / end of each class, end of the call
+static hipEvent_t g_ev[kEvents] = {};
+static int g_streams = 3;                           // 3: a stream per class; 1: one stream (ek_hip_debug_vbatched_streams)
+static double g_class_seconds[kClasses] = {};       // the last timed variable call's kernels, by class
+static int g_class_count[kClasses] = {};
 
-static int ensure_variable(size_t entries, int sides) {
-  if (entries > g_dtable_count) {
-    if (g_dtable) (void)hipFree(g_dtable);
-    g_dtable = nullptr;
-    g_dtable_count = 0;
-    EK_HIP_CHECK(hipMalloc((void **)&g_dtable, entries * sizeof(Desc)));
-    g_dtable_count = entries;
-  }
-  for (int k = 0; k < sides; ++k)
-    if (!g_side[k]) EK_HIP_CHECK(hipStreamCreateWithFlags(&g_side[k], hipStreamNonBlocking));
-  for (int k = 0; k < kEvents; ++k)
-    if (!g_ev[k]) EK_HIP_CHECK(hipEventCreate(&g_ev[k]));
+static int create_event(hipEvent_t *e) {
+  EK_HIP_CHECK(hipEventCreate(e));
   return 0;
 }
 
@@ -755,22 +744,12 @@ static int ensure_variable(size_t entries, int sides) {
 namespace api {
 void release_batched() {
   using namespace batched;
-  if (g_dinfo) (void)hipFree(g_dinfo);
-  g_dinfo = nullptr;
-  g_dinfo_count = 0;
-  if (g_dtable) (void)hipFree(g_dtable);
-  g_dtable = nullptr;
-  g_dtable_count = 0;
-  if (g_dm) (void)hipFree(g_dm);
-  g_dm = nullptr;
-  g_dm_count = 0;
-  if (g_wws) (void)hipFree(g_wws);
-  g_wws = nullptr;
-  g_wws_bytes = 0;
+  g_dinfo.release();
+  g_dtable.release();
+  g_dm.release();
+  g_wws.release();
+  g_dwtable.release();
   std::vector<Desc>().swap(g_htable);
-  if (g_dwtable) (void)hipFree(g_dwtable);
-  g_dwtable = nullptr;
-  g_dwtable_count = 0;
   std::vector<WDesc>().swap(g_hwtable);
   for (int k = 0; k < kClasses - 1; ++k) {
     if (g_side[k]) (void)hipStreamDestroy(g_side[k]);
@@ -786,148 +765,382 @@ void release_batched() {
 
 using namespace ek;
 using namespace ek::api;
+using namespace ek::batched;
 
-static int batched_check(int problem, int jobz, int n, int batch, const void *A, int lda, long long strideA,
-                         const void *B, int ldb, long long strideB, const void *w, const void *Z, int ldz,
-                         long long strideZ, const int *info, bool *nothing, int nmax) {
-  *nothing = false;
-  if (problem != 0 && problem != 1) return -1;
-  if (jobz != 0 && jobz != 1) return -2;
-  if (n < 0 || n > nmax) return -3;
-  if (batch < 0) return -4;
-  if (n == 0 || batch == 0) { *nothing = true; return 0; }
-  if (!A) return -5;
-  if (lda < n) return -6;
-  if (strideA < (long long)lda * n) return -7;
-  if (problem == 1) {
-    if (!B) return -8;
-    if (ldb < n) return -9;
-    if (strideB < (long long)ldb * n) return -10;
-  }
-  if (!w) return -11;
-  if (jobz == 1) {
-    if (!Z) return -12;
-    if (ldz < n) return -13;
-    if (strideZ < (long long)ldz * n) return -14;
-  }
-  if (!info) return -15;
+// One call, as its extern "C" entry fills it: ek_hip_eigenpairs_* pass itype 1, ek_hip_sygv_* problem 1 (argument k of
+// the one is argument k of the other).  A, B, w, Z are host or device arrays as the entry says and device arrays from
+// run() on; everything else is the host's.  win: the window of the ek_hip_*_window_* entries, nullptr in the others
+struct UniformWindow {
+  int range;
+  double vl, vu;
+  int il, iu, zcap;
+  int *m;
+};
+struct UniformCall {
+  int problem, itype, jobz, n, batch;
+  double *A; int lda; long long sA;
+  double *B; int ldb; long long sB;
+  double *w;
+  double *Z; int ldz; long long sZ;
+  int *info;
+  double *seconds;
+  const UniformWindow *win;
+};
+// the variable-order forms: host arrays of `batch` entries
+struct VariableWindow {
+  int range;
+  const double *vl, *vu;
+  const int *il, *iu, *zcap;
+  int *m;
+};
+struct VariableCall {
+  int problem, itype, jobz, batch;
+  const int *n;
+  double *const *A; const int *lda;
+  double *const *B; const int *ldb;
+  double *const *w;
+  double *const *Z; const int *ldz;
+  int *info;
+  double *seconds;
+  const VariableWindow *win;
+};
+
+// ---- argument checks: the arguments of the prototype in their order, every error the number include/ek_hip.h gives it;
+// no data pointer is dereferenced, and the pointers in a pointer array are not either
+
+// 0, or which of a matrix argument's three is wrong: 1 the pointer, 2 the leading dimension, 3 the stride
+static int matrix_fault(const void *M, int ld, long long stride, int n) {
+  if (!M) return 1;
+  if (ld < n) return 2;
+  if (stride < (long long)ld * n) return 3;
   return 0;
 }
 
-// arguments checked, context up, g_mu held
-static int batched_device_locked(int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
-                                 long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ,
-                                 int ldz, long long strideZ, int *info, double *seconds) {
+// the 22 checked arguments of a window entry
+static int check_window(const UniformCall &u, int nmax, bool *nothing) {
+  const UniformWindow &v = *u.win;
+  if (u.problem != 0 && u.problem != 1) return -1;
+  if (u.jobz != 0 && u.jobz != 1) return -2;
+  if (v.range != 0 && v.range != 1) return -3;
+  if (u.n < 0 || u.n > nmax) return -4;
+  if (u.batch < 0) return -5;
+  if (u.n == 0 || u.batch == 0) { *nothing = true; return 0; }
+  if (v.range == 1) {
+    if (v.vl != v.vl) return -6;
+    if (!(v.vl < v.vu)) return -7;                  // vu NaN, or an empty interval
+  } else {
+    if (v.il < 1 || v.il > u.n) return -8;
+    if (v.iu < v.il || v.iu > u.n) return -9;
+  }
+  if (int f = matrix_fault(u.A, u.lda, u.sA, u.n)) return -9 - f;
+  if (u.problem == 1)
+    if (int f = matrix_fault(u.B, u.ldb, u.sB, u.n)) return -12 - f;
+  if (!v.m) return -16;
+  if (!u.w) return -17;
+  if (u.jobz == 1) {
+    if (!u.Z) return -18;
+    if (u.ldz < u.n) return -19;
+  }
+  if (v.zcap < 0 || (v.range == 0 && v.zcap < v.iu - v.il + 1)) return -20;   // with and without vectors
+  if (u.jobz == 1 && u.sZ < (long long)u.ldz * std::max(1, v.zcap)) return -21;
+  if (!u.info) return -22;
+  return 0;
+}
+
+// nmax is the largest order the entry takes: EK_HIP_XBATCH_NMAX for the xbatched entries, which are the batched entries up
+// to EK_HIP_BATCH_NMAX and ek_batched_x.hip's kernel above it
+static int check(const UniformCall &u, int nmax, bool *nothing) {
+  *nothing = false;
+  if (u.win) return check_window(u, nmax, nothing);
+  if (u.problem != 0 && u.problem != 1) return -1;
+  if (u.jobz != 0 && u.jobz != 1) return -2;
+  if (u.n < 0 || u.n > nmax) return -3;
+  if (u.batch < 0) return -4;
+  if (u.n == 0 || u.batch == 0) { *nothing = true; return 0; }
+  if (int f = matrix_fault(u.A, u.lda, u.sA, u.n)) return -4 - f;
+  if (u.problem == 1)
+    if (int f = matrix_fault(u.B, u.ldb, u.sB, u.n)) return -7 - f;
+  if (!u.w) return -11;
+  if (u.jobz == 1)
+    if (int f = matrix_fault(u.Z, u.ldz, u.sZ, u.n)) return -11 - f;
+  if (!u.info) return -15;
+  return 0;
+}
+
+// a pointer array with an entry for every problem of order > 0; a leading dimension for every problem
+static bool entries(const VariableCall &v, double *const *P) {
+  if (!P) return false;
+  for (int b = 0; b < v.batch; ++b)
+    if (v.n[b] > 0 && !P[b]) return false;
+  return true;
+}
+static bool leading(const VariableCall &v, const int *ld) {
+  if (!ld) return false;
+  for (int b = 0; b < v.batch; ++b)
+    if (ld[b] < (v.n[b] > 1 ? v.n[b] : 1)) return false;
+  return true;
+}
+
+// the 19 checked arguments of a variable window entry; per-problem conditions hold for the problems of order > 0
+static int check_window(const VariableCall &v, int nmax, bool *nothing) {
+  const VariableWindow &x = *v.win;
+  const int batch = v.batch, *n = v.n;
+  if (v.problem != 0 && v.problem != 1) return -1;
+  if (v.jobz != 0 && v.jobz != 1) return -2;
+  if (x.range != 0 && x.range != 1) return -3;
+  if (batch < 0) return -4;
+  if (batch == 0) { *nothing = true; return 0; }
+  if (!n) return -5;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] < 0 || n[b] > nmax) return -5;
+  if (x.range == 1) {
+    if (!x.vl) return -6;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && x.vl[b] != x.vl[b]) return -6;
+    if (!x.vu) return -7;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && !(x.vl[b] < x.vu[b])) return -7;   // vu NaN, or an empty interval
+  } else {
+    if (!x.il) return -8;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && (x.il[b] < 1 || x.il[b] > n[b])) return -8;
+    if (!x.iu) return -9;
+    for (int b = 0; b < batch; ++b)
+      if (n[b] > 0 && (x.iu[b] < x.il[b] || x.iu[b] > n[b])) return -9;
+  }
+  if (!entries(v, v.A)) return -10;
+  if (!leading(v, v.lda)) return -11;
+  if (v.problem == 1) {
+    if (!entries(v, v.B)) return -12;
+    if (!leading(v, v.ldb)) return -13;
+  }
+  if (!x.m) return -14;
+  if (!entries(v, v.w)) return -15;
+  if (v.jobz == 1) {
+    if (!v.Z) return -16;
+    for (int b = 0; b < batch; ++b)                 // no Z is needed where it has no column
+      if (n[b] > 0 && !v.Z[b] && !(x.zcap && x.zcap[b] == 0)) return -16;
+    if (!leading(v, v.ldz)) return -17;
+  }
+  if (!x.zcap) return -18;
+  for (int b = 0; b < batch; ++b)                   // with and without vectors, as the uniform call
+    if (n[b] > 0 && (x.zcap[b] < 0 || (x.range == 0 && x.zcap[b] < x.iu[b] - x.il[b] + 1))) return -18;
+  if (!v.info) return -19;
+  return 0;
+}
+
+static int check(const VariableCall &v, int nmax, bool *nothing) {
+  *nothing = false;
+  if (v.win) return check_window(v, nmax, nothing);
+  if (v.problem != 0 && v.problem != 1) return -1;
+  if (v.jobz != 0 && v.jobz != 1) return -2;
+  if (v.batch < 0) return -3;
+  if (v.batch == 0) { *nothing = true; return 0; }
+  if (!v.n) return -4;
+  for (int b = 0; b < v.batch; ++b)
+    if (v.n[b] < 0 || v.n[b] > nmax) return -4;
+  if (!entries(v, v.A)) return -5;
+  if (!leading(v, v.lda)) return -6;
+  if (v.problem == 1) {
+    if (!entries(v, v.B)) return -7;
+    if (!leading(v, v.ldb)) return -8;
+  }
+  if (!entries(v, v.w)) return -9;
+  if (v.jobz == 1) {
+    if (!entries(v, v.Z)) return -10;
+    if (!leading(v, v.ldz)) return -11;
+  }
+  if (!v.info) return -12;
+  return 0;
+}
+
+// ---- uniform orders.  From here on: arguments checked, context up, g_mu held, device arrays
+
+// The launches of a uniform call between two timing events (where the caller wants seconds), then info (and a window's m)
+// back and the call's one synchronise.  launches(s) issues them on the context's stream and returns the first error
+template <typename Launches>
+static int run_uniform(const UniformCall &u, Launches launches) {
   hipStream_t s = g_ctx.stream;
-  { int rc0 = batched::ensure_info((size_t)batch); if (rc0) return rc0; }
-  batched::Args a{problem, jobz, n, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, batched::g_dinfo, itype};
+  const size_t words = (size_t)u.batch * sizeof(int);
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (seconds) {
-    EK_HIP_CHECK(hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e != hipSuccess) { (void)hipEventDestroy(e0); return -1000 - (int)e; }
+  if (u.seconds) {
+    int rc0 = create_event(&e0);
+    if (rc0) return rc0;
+    rc0 = create_event(&e1);
+    if (rc0) { (void)hipEventDestroy(e0); return rc0; }
     (void)hipEventRecord(e0, s);
   }
-  int rc;
-  if (n > EK_HIP_BATCH_NMAX) {                      // ek_hip_eigenpairs_xbatched*: the image in device memory
-    rc = xbatched_launch(s, problem, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
-                         batched::g_dinfo);
-  } else switch (batched::class_of(n)) {
-    case 32: rc = batched::launch_class<32, 64>(s, batch, a); break;
-    case 64: rc = batched::launch_class<64, 128>(s, batch, a); break;
-    default: rc = batched::launch_class<128, 256>(s, batch, a); break;
-  }
-  if (seconds) (void)hipEventRecord(e1, s);
+  int rc = launches(s);
+  if (u.seconds) (void)hipEventRecord(e1, s);
   hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(info, batched::g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (!rc) e = hipMemcpyAsync(u.info, g_dinfo.p, words, hipMemcpyDeviceToHost, s);
+  if (!rc && e == hipSuccess && u.win) e = hipMemcpyAsync(u.win->m, g_dm.p, words, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess && !rc) rc = -1000 - (int)e;
-  if (seconds) {
+  if (u.seconds) {
     float ms = 0.f;
-    if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *seconds = (double)ms * 1e-3;
+    if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *u.seconds = (double)ms * 1e-3;
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
   }
   return rc;
 }
 
-// ---- problems of different orders (ek_hip_eigenpairs_vbatched*)
-
-// All arrays are host arrays of `batch` entries; the pointers in the pointer arrays are not dereferenced.
-static int vbatched_check(int problem, int jobz, int batch, const int *n, const void *const *A, const int *lda,
-                          const void *const *B, const int *ldb, const void *const *w, const void *const *Z,
-                          const int *ldz, const int *info, bool *nothing, int nmax) {
-  *nothing = false;
-  if (problem != 0 && problem != 1) return -1;
-  if (jobz != 0 && jobz != 1) return -2;
-  if (batch < 0) return -3;
-  if (batch == 0) { *nothing = true; return 0; }
-  if (!n) return -4;
-  for (int b = 0; b < batch; ++b)
-    if (n[b] < 0 || n[b] > nmax) return -4;
-  auto entries = [&](const void *const *P) {
-    if (!P) return false;
-    for (int b = 0; b < batch; ++b)
-      if (n[b] > 0 && !P[b]) return false;
-    return true;
-  };
-  auto leading = [&](const int *ld) {
-    if (!ld) return false;
-    for (int b = 0; b < batch; ++b)
-      if (ld[b] < (n[b] > 1 ? n[b] : 1)) return false;
-    return true;
-  };
-  if (!entries(A)) return -5;
-  if (!leading(lda)) return -6;
-  if (problem == 1) {
-    if (!entries(B)) return -7;
-    if (!leading(ldb)) return -8;
-  }
-  if (!entries(w)) return -9;
-  if (jobz == 1) {
-    if (!entries(Z)) return -10;
-    if (!leading(ldz)) return -11;
-  }
-  if (!info) return -12;
-  return 0;
+// a window of eigenpairs per problem (ek_hip_eigenpairs_window_*batched*; ek_hip_sygv_window_*batched* with itype)
+static int run_window(const UniformCall &u) {
+  const UniformWindow &v = *u.win;
+  const int n = u.n, batch = u.batch;
+  const int wcols = !u.jobz ? 0 : v.range == 0 ? v.iu - v.il + 1 : std::min(v.zcap, n);
+  const size_t slot = (size_t)5 * n * wcols * sizeof(double);
+  // wide slots: fewer problems per launch, so that the workspace stays near kWindowBytes -- in whole rounds of 256
+  // workgroups (class 128 runs one per compute unit: a chunk of 409 would be three rounds for 512 problems), two at least
+  const int fit = (int)std::min<size_t>(kWindowBytes / std::max(slot, (size_t)1), (size_t)g_wchunk);
+  const bool x = n > EK_HIP_BATCH_NMAX;              // ek_batched_x.hip's class: its own chunk rule, and an image per slot
+  const int xfit = (int)std::min<size_t>(kXWindowBytes / std::max(slot, (size_t)1), (size_t)g_xwchunk);
+  const int K = x ? std::min(g_xwchunk, std::max(kXWindowRound, xfit / kXWindowRound * kXWindowRound))
+                  : std::min(g_wchunk, std::max(512, fit / 256 * 256));
+  int rc0 = g_dinfo.grow((size_t)batch);
+  if (!rc0) rc0 = g_dm.grow((size_t)batch);
+  if (!rc0) rc0 = g_wws.grow((size_t)std::min(batch, K) * slot / sizeof(double));
+  if (!rc0 && x) rc0 = xwindow_prepare(std::min(batch, K));
+  if (rc0) return rc0;
+  // a problem that ends before stage 4W: m = 0
+  EK_HIP_CHECK(hipMemsetAsync(g_dm.p, 0, (size_t)batch * sizeof(int), g_ctx.stream));
+  return run_uniform(u, [&](hipStream_t s) {
+    int rc = 0;
+    for (int c0 = 0; c0 < batch && !rc; c0 += K) {
+      const int count = std::min(K, batch - c0);
+      double *A = u.A + (long long)c0 * u.sA, *B = u.problem ? u.B + (long long)c0 * u.sB : nullptr;
+      double *w = u.w + (long long)c0 * n, *Z = u.jobz ? u.Z + (long long)c0 * u.sZ : nullptr;
+      if (x)
+        rc = xwindow_launch(s, u.problem, u.itype, u.jobz, n, count, A, u.lda, u.sA, B, u.ldb, u.sB, w, Z, u.ldz, u.sZ,
+                            g_dinfo.p + c0, v.range, v.il, v.iu, v.zcap, v.vl, v.vu, g_dm.p + c0, g_wws.p, wcols);
+      else
+        rc = launch_order(n, s, count,
+                          WArgs{{u.problem, u.jobz, n, A, u.lda, u.sA, B, u.ldb, u.sB, w, Z, u.ldz, u.sZ, g_dinfo.p + c0,
+                                 u.itype},
+                                {v.range, v.il, v.iu, v.zcap, v.vl, v.vu, g_dm.p + c0, g_wws.p, wcols}});
+    }
+    return rc;
+  });
 }
 
-// arguments checked, context up, g_mu held; the pointers in dA, dB, dw, dZ are device addresses.  Orders above
-// EK_HIP_BATCH_NMAX (ek_hip_*_xvbatched* only) make a class of their own in front of the three, which runs
-// ek_batched_x.hip's kernel in chunks (xvbatched_launch)
-static int vbatched_device_locked(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
-                                  const int *lda, double *const *dB, const int *ldb, double *const *dw,
-                                  double *const *dZ, const int *ldz, int *info, double *seconds) {
-  using namespace batched;
-  // a class after the other, the largest first; inside a class descending order: the dispatcher hands out workgroups
-  // in index order and a workgroup's time grows like n^2 .. n^3, so this is longest-first list scheduling
+// above EK_HIP_BATCH_NMAX (the xbatched entries only) the image in device memory: ek_batched_x.hip's kernel
+static int run(const UniformCall &u) {
+  if (u.win) return run_window(u);
+  { int rc0 = g_dinfo.grow((size_t)u.batch); if (rc0) return rc0; }
+  return run_uniform(u, [&](hipStream_t s) {
+    if (u.n > EK_HIP_BATCH_NMAX)
+      return xbatched_launch(s, u.problem, u.itype, u.jobz, u.n, u.batch, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z,
+                             u.ldz, u.sZ, g_dinfo.p);
+    return launch_order(u.n, s, u.batch, Args{u.problem, u.jobz, u.n, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z, u.ldz,
+                                              u.sZ, g_dinfo.p, u.itype});
+  });
+}
+
+// The host-pointer form: the caller's arrays are left as they are, the kernel works on device copies with the caller's own
+// layout (what lies between the columns and between the problems travels with them, and comes back as it was).  Z has n
+// columns a problem, or a window's zcap; a window's w and Z travel both ways, so that what the kernel leaves alone (the
+// rest of a row of w, the columns from m[b] on, a failed problem's slots) comes back as the caller had it
+static int stage(const UniformCall &u) {
+  hipStream_t s = g_ctx.stream;
+  const int n = u.n, zcols = u.win ? u.win->zcap : n;
+  auto span = [&](int ld, long long stride, int cols) {
+    return (size_t)(u.batch - 1) * (size_t)stride + (size_t)ld * (cols - 1) + n;
+  };
+  const size_t cA = span(u.lda, u.sA, n), cB = u.problem ? span(u.ldb, u.sB, n) : 0, cw = (size_t)u.batch * n;
+  const size_t cZ = (u.jobz && zcols > 0) ? span(u.ldz, u.sZ, zcols) : 0;
+  const bool zin = u.win ? cZ > 0 : u.jobz && (u.ldz != n || u.sZ != (long long)n * n);
+  DevMem mem;
+  UniformCall d = u;
+  d.B = d.Z = nullptr;
+  int rc = mem.alloc(&d.A, cA * 8);
+  if (!rc) rc = mem.alloc(&d.w, cw * 8);
+  if (!rc && u.problem) rc = mem.alloc(&d.B, cB * 8);
+  if (!rc && u.jobz) rc = mem.alloc(&d.Z, std::max(cZ, (size_t)1) * 8);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(d.A, u.A, cA * 8, hipMemcpyHostToDevice, s));
+  if (u.win) EK_HIP_CHECK(hipMemcpyAsync(d.w, u.w, cw * 8, hipMemcpyHostToDevice, s));
+  if (u.problem) EK_HIP_CHECK(hipMemcpyAsync(d.B, u.B, cB * 8, hipMemcpyHostToDevice, s));
+  if (zin) EK_HIP_CHECK(hipMemcpyAsync(d.Z, u.Z, cZ * 8, hipMemcpyHostToDevice, s));
+  rc = run(d);
+  if (rc) return rc;
+  EK_HIP_CHECK(hipMemcpyAsync(u.w, d.w, cw * 8, hipMemcpyDeviceToHost, s));
+  if (cZ) EK_HIP_CHECK(hipMemcpyAsync(u.Z, d.Z, cZ * 8, hipMemcpyDeviceToHost, s));
+  EK_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+static bool all_empty(const UniformCall &) { return false; }
+
+// ---- problems of different orders (ek_hip_*_vbatched*, ek_hip_*_xvbatched*, ek_hip_*_window_xvbatched*; DESIGN.md 13, 21,
+// 34).  The pointers in A, B, w, Z are device addresses.  Orders above EK_HIP_BATCH_NMAX make a class of their own in front
+// of the three, which runs ek_batched_x.hip's kernel
+
+// The host images of the problem table (and of a window's table beside it) and the problems of each class.  A class
+// after the other, the largest first; inside a class descending order: the dispatcher hands out workgroups in index order
+// and a workgroup's time grows like n^2 .. n^3, so this is longest-first list scheduling
+static void classify(const VariableCall &v, int *count) {
+  const int *n = v.n;
   std::vector<int> order;
-  order.reserve((size_t)batch);
-  for (int b = 0; b < batch; ++b)
+  order.reserve((size_t)v.batch);
+  for (int b = 0; b < v.batch; ++b)
     if (n[b] > 0) order.push_back(b);
-  if (order.empty()) {
-    for (int b = 0; b < batch; ++b) info[b] = 0;
-    return 0;
-  }
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
-  g_htable.resize(order.size());                    // static: the upload below may still read it when an error returns
-  int count[kClasses] = {0, 0, 0, 0};               // classes of 256, 128, 64, 32
+  g_htable.resize(order.size());
+  if (v.win) g_hwtable.resize(order.size());
+  std::fill(count, count + kClasses, 0);
   for (size_t i = 0; i < order.size(); ++i) {
     const int b = order[i], c = class_of(n[b]);
     ++count[n[b] > EK_HIP_BATCH_NMAX ? 0 : c == 128 ? 1 : c == 64 ? 2 : 3];
-    g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], jobz ? dZ[b] : nullptr, n[b], lda[b],
-                       problem ? ldb[b] : 1, jobz ? ldz[b] : 1, b, 0};
+    g_htable[i] = Desc{v.A[b], v.problem ? v.B[b] : nullptr, v.w[b], v.jobz ? v.Z[b] : nullptr, n[b], v.lda[b],
+                       v.problem ? v.ldb[b] : 1, v.jobz ? v.ldz[b] : 1, b, 0};
+    if (const VariableWindow *x = v.win) {
+      const int range = x->range;
+      const int wcols = !v.jobz ? 0 : range == 0 ? x->iu[b] - x->il[b] + 1 : std::min(x->zcap[b], n[b]);
+      g_hwtable[i] = WDesc{range ? x->vl[b] : 0.0, range ? x->vu[b] : 0.0, range ? 0 : x->il[b], range ? 0 : x->iu[b],
+                           x->zcap[b], wcols, 0};
+    }
   }
-  // the largest class present runs on the context's stream, the others on a stream of their own behind the fork event
-  int side[kClasses] = {-1, -1, -1, -1}, sides = 0; // -1: the context's stream
-  if (g_streams == 3)
-    for (int k = 0, used = 0; k < kClasses; ++k)
-      if (count[k] && used++ > 0) side[k] = sides++;
-  { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
-  { int rc0 = ensure_variable(order.size(), std::max(sides, 2)); if (rc0) return rc0; }   // the third: with four classes
-  if (count[0]) { int rc0 = xvbatched_prepare(count[0]); if (rc0) return rc0; }
+}
+
+// the largest class present runs on the context's stream (-1), every other one on a side stream of its own behind the
+// fork event; returns the side streams used
+static int assign_sides(const int *count, int *side) {
+  int sides = 0;
+  for (int k = 0, used = 0; k < kClasses; ++k)
+    side[k] = (g_streams == 3 && count[k] && used++ > 0) ? sides++ : -1;
+  return sides;
+}
+
+// the status words and the table of a classified call, its side streams and the events
+static int ensure_variable(const VariableCall &v, const int *count) {
+  int side[kClasses];
+  const int sides = std::max(assign_sides(count, side), 2);   // the third: with four classes
+  int rc = g_dinfo.grow((size_t)v.batch);
+  if (!rc) rc = g_dtable.grow(g_htable.size());
+  if (rc) return rc;
+  for (int k = 0; k < sides; ++k)
+    if (!g_side[k]) EK_HIP_CHECK(hipStreamCreateWithFlags(&g_side[k], hipStreamNonBlocking));
+  for (int k = 0; k < kEvents && !rc; ++k)
+    if (!g_ev[k]) rc = create_event(&g_ev[k]);
+  return rc;
+}
+
+// A classified call whose pools stand: the tables go up, the classes present run beside each other from the fork event
+// to their joins, info (and a window's m) come back, and the context's stream is synchronised once; the side streams
+// only when an error may have left a class outside the join.  per_class(k, stream, off) issues the launches of class k,
+// whose entries start at `off` in the table, and returns the first error
+template <typename PerClass>
+static int run_classes(const VariableCall &v, const int *count, PerClass per_class) {
   hipStream_t s = g_ctx.stream;
-  EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+  const size_t words = (size_t)v.batch * sizeof(int);
+  EK_HIP_CHECK(hipMemcpyAsync(g_dtable.p, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+  if (v.win) {
+    EK_HIP_CHECK(hipMemcpyAsync(g_dwtable.p, g_hwtable.data(), g_hwtable.size() * sizeof(WDesc), hipMemcpyHostToDevice, s));
+    EK_HIP_CHECK(hipMemsetAsync(g_dm.p, 0, words, s));   // a problem that ends before stage 4W: m = 0
+  }
+  int side[kClasses];
+  assign_sides(count, side);
   hipStream_t cs[kClasses];
   for (int k = 0; k < kClasses; ++k) cs[k] = side[k] < 0 ? s : g_side[side[k]];
   EK_HIP_CHECK(hipEventRecord(g_ev[0], s));         // before the first launch
@@ -937,30 +1150,27 @@ static int vbatched_device_locked(int problem, int itype, int jobz, int batch, c
     if (!count[k]) continue;
     if (cs[k] != s) e = hipStreamWaitEvent(cs[k], g_ev[0], 0);
     if (e != hipSuccess) break;
-    VArgs a{problem, jobz, g_dtable + off, g_dinfo, itype};
-    if (seconds) (void)hipEventRecord(g_ev[kClasses + 2 * k], cs[k]);
-    rc = k == 0 ? xvbatched_launch(cs[k], problem, itype, jobz, count[k], g_dtable + off, g_dinfo)
-       : k == 1 ? launch_class<128, 256>(cs[k], count[k], a)
-       : k == 2 ? launch_class<64, 128>(cs[k], count[k], a) : launch_class<32, 64>(cs[k], count[k], a);
-    if (seconds) (void)hipEventRecord(g_ev[kClasses + 1 + 2 * k], cs[k]);
+    if (v.seconds) (void)hipEventRecord(g_ev[kClasses + 2 * k], cs[k]);
+    rc = per_class(k, cs[k], off);
+    if (v.seconds) (void)hipEventRecord(g_ev[kClasses + 1 + 2 * k], cs[k]);
     if (cs[k] != s) {                               // join
       e = hipEventRecord(g_ev[k], cs[k]);
       if (e == hipSuccess) e = hipStreamWaitEvent(s, g_ev[k], 0);
     }
     off += count[k];
   }
-  if (seconds) (void)hipEventRecord(g_ev[kEvents - 1], s);   // after the last launch has ended
-  if (!rc && e == hipSuccess)
-    e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (v.seconds) (void)hipEventRecord(g_ev[kEvents - 1], s);   // after the last launch has ended
+  if (!rc && e == hipSuccess) e = hipMemcpyAsync(v.info, g_dinfo.p, words, hipMemcpyDeviceToHost, s);
+  if (!rc && e == hipSuccess && v.win) e = hipMemcpyAsync(v.win->m, g_dm.p, words, hipMemcpyDeviceToHost, s);
   hipError_t es = hipStreamSynchronize(s);
   if (e != hipSuccess || rc)                        // an error may have left a class outside the join
     for (int k = 0; k < kClasses - 1; ++k)
       if (g_side[k]) (void)hipStreamSynchronize(g_side[k]);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess && !rc) rc = -1000 - (int)e;
-  if (seconds && !rc) {
+  if (v.seconds && !rc) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[kEvents - 1]) == hipSuccess) *seconds = (double)ms * 1e-3;
+    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[kEvents - 1]) == hipSuccess) *v.seconds = (double)ms * 1e-3;
     for (int k = 0; k < kClasses; ++k) {
       g_class_count[k] = count[k];
       g_class_seconds[k] = 0.0;
@@ -969,418 +1179,31 @@ static int vbatched_device_locked(int problem, int itype, int jobz, int batch, c
     }
   }
   if (!rc)
-    for (int b = 0; b < batch; ++b)
-      if (n[b] == 0) info[b] = 0;
+    for (int b = 0; b < v.batch; ++b)
+      if (v.n[b] == 0) {
+        v.info[b] = 0;
+        if (v.win) v.win->m[b] = 0;
+      }
   return rc;
 }
 
-// The bodies of the entries: ek_hip_eigenpairs_* pass itype 1, ek_hip_sygv_* problem 1 (argument k of the one is
-// argument k of the other).  nmax is the largest order the entry takes: EK_HIP_XBATCH_NMAX for ek_hip_eigenpairs_xbatched*,
-// which are the batched entries up to EK_HIP_BATCH_NMAX and ek_batched_x.hip's kernel above it.
-static int batched_device_entry(int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
-                                long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ,
-                                int ldz, long long strideZ, int *info, double *seconds,
-                                int nmax = EK_HIP_BATCH_NMAX) {
-  bool nothing;
-  int rc = batched_check(problem, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                         &nothing, nmax);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return batched_device_locked(problem, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ,
-                               info, seconds);
-}
-
-static int batched_host_entry(int problem, int itype, int jobz, int n, int batch, const double *A, int lda,
-                              long long strideA, const double *B, int ldb, long long strideB, double *w, double *Z,
-                              int ldz, long long strideZ, int *info, double *seconds,
-                              int nmax = EK_HIP_BATCH_NMAX) {
-  bool nothing;
-  int rc = batched_check(problem, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
-                         &nothing, nmax);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  // the caller's arrays are left as they are: the kernel works on device copies with the caller's own layout (what
-  // lies between the columns and between the problems travels with them, and comes back as it was)
-  auto span = [&](int ld, long long stride) { return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (n - 1) + n; };
-  const size_t cA = span(lda, strideA), cB = problem ? span(ldb, strideB) : 0, cZ = jobz ? span(ldz, strideZ) : 0;
-  const size_t cw = (size_t)batch * n;
-  const bool zpad = jobz && (ldz != n || strideZ != (long long)n * n);
-  DevMem mem;
-  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cA * 8);
-  if (!rc) rc = mem.alloc(&uw, cw * 8);
-  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
-  if (!rc && jobz) rc = mem.alloc(&uZ, cZ * 8);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
-  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
-  if (zpad) EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  rc = batched_device_locked(problem, itype, jobz, n, batch, uA, lda, strideA, uB, ldb, strideB, uw, uZ, ldz, strideZ,
-                             info, seconds);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
-  if (jobz) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
-  EK_HIP_CHECK(hipStreamSynchronize(s));
-  return 0;
-}
-
-// ---- a window of eigenpairs per problem (ek_hip_eigenpairs_window_batched*; ek_hip_sygv_window_batched* with itype)
-
-// The 23 arguments of the prototype in their order; no data pointer is dereferenced
-static int window_check(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
-                        const void *A, int lda, long long strideA, const void *B, int ldb, long long strideB,
-                        const int *m, const void *w, const void *Z, int ldz, int zcap, long long strideZ,
-                        const int *info, bool *nothing, int nmax) {
-  *nothing = false;
-  if (problem != 0 && problem != 1) return -1;
-  if (jobz != 0 && jobz != 1) return -2;
-  if (range != 0 && range != 1) return -3;
-  if (n < 0 || n > nmax) return -4;
-  if (batch < 0) return -5;
-  if (n == 0 || batch == 0) { *nothing = true; return 0; }
-  if (range == 1) {
-    if (vl != vl) return -6;
-    if (!(vl < vu)) return -7;                      // vu NaN, or an empty interval
-  } else {
-    if (il < 1 || il > n) return -8;
-    if (iu < il || iu > n) return -9;
-  }
-  if (!A) return -10;
-  if (lda < n) return -11;
-  if (strideA < (long long)lda * n) return -12;
-  if (problem == 1) {
-    if (!B) return -13;
-    if (ldb < n) return -14;
-    if (strideB < (long long)ldb * n) return -15;
-  }
-  if (!m) return -16;
-  if (!w) return -17;
-  if (jobz == 1) {
-    if (!Z) return -18;
-    if (ldz < n) return -19;
-  }
-  if (zcap < 0 || (range == 0 && zcap < iu - il + 1)) return -20;   // with and without vectors
-  if (jobz == 1 && strideZ < (long long)ldz * std::max(1, zcap)) return -21;
-  if (!info) return -22;
-  return 0;
-}
-
-// arguments checked, context up, g_mu held
-static int window_device_locked(int problem, int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
-                                double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
-                                double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
-                                double *seconds) {
-  using namespace batched;
-  hipStream_t s = g_ctx.stream;
-  const int wcols = !jobz ? 0 : range == 0 ? iu - il + 1 : std::min(zcap, n);
-  const size_t slot = (size_t)5 * n * wcols * sizeof(double);
-  // wide slots: fewer problems per launch, so that the workspace stays near kWindowBytes -- in whole rounds of 256
-  // workgroups (class 128 runs one per compute unit: a chunk of 409 would be three rounds for 512 problems), two at least
-  const int fit = (int)std::min<size_t>(kWindowBytes / std::max(slot, (size_t)1), (size_t)g_wchunk);
-  const bool x = n > EK_HIP_BATCH_NMAX;              // ek_batched_x.hip's class: its own chunk rule, and an image per slot
-  const int xfit = (int)std::min<size_t>(kXWindowBytes / std::max(slot, (size_t)1), (size_t)g_xwchunk);
-  const int K = x ? std::min(g_xwchunk, std::max(kXWindowRound, xfit / kXWindowRound * kXWindowRound))
-                  : std::min(g_wchunk, std::max(512, fit / 256 * 256));
-  { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
-  { int rc0 = ensure_window((size_t)batch, (size_t)std::min(batch, K) * slot); if (rc0) return rc0; }
-  if (x) { int rc0 = xwindow_prepare(std::min(batch, K)); if (rc0) return rc0; }
-  EK_HIP_CHECK(hipMemsetAsync(g_dm, 0, (size_t)batch * sizeof(int), s));   // a problem that ends before stage 4W: m = 0
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (seconds) {
-    EK_HIP_CHECK(hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e != hipSuccess) { (void)hipEventDestroy(e0); return -1000 - (int)e; }
-    (void)hipEventRecord(e0, s);
-  }
-  int rc = 0;
-  for (int c0 = 0; c0 < batch && !rc; c0 += K) {
-    const int count = std::min(K, batch - c0);
-    if (x) {
-      rc = xwindow_launch(s, problem, itype, jobz, n, count, dA + (long long)c0 * strideA, lda, strideA,
-                          problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
-                          jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, range, il, iu, zcap,
-                          vl, vu, g_dm + c0, g_wws, wcols);
-      continue;
-    }
-    WArgs a{{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
-             problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
-             jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, g_dinfo + c0, itype},
-            {range, il, iu, zcap, vl, vu, g_dm + c0, g_wws, wcols}};
-    switch (class_of(n)) {
-      case 32: rc = launch_class<32, 64>(s, count, a); break;
-      case 64: rc = launch_class<64, 128>(s, count, a); break;
-      default: rc = launch_class<128, 256>(s, count, a); break;
-    }
-  }
-  if (seconds) (void)hipEventRecord(e1, s);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (!rc && e == hipSuccess) e = hipMemcpyAsync(m, g_dm, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
-  if (seconds) {
-    float ms = 0.f;
-    if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *seconds = (double)ms * 1e-3;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  return rc;
-}
-
-static int window_device_entry(int problem, int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
-                               double *dA, int lda, long long strideA, double *dB, int ldb, long long strideB, int *m,
-                               double *dw, double *dZ, int ldz, int zcap, long long strideZ, int *info,
-                               double *seconds, int nmax = EK_HIP_BATCH_NMAX) {
-  bool nothing;
-  int rc = window_check(problem, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw, dZ,
-                        ldz, zcap, strideZ, info, &nothing, nmax);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return window_device_locked(problem, itype, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB,
-                              m, dw, dZ, ldz, zcap, strideZ, info, seconds);
-}
-
-static int window_host_entry(int problem, int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
-                             const double *A, int lda, long long strideA, const double *B, int ldb, long long strideB,
-                             int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
-                             double *seconds, int nmax = EK_HIP_BATCH_NMAX) {
-  bool nothing;
-  int rc = window_check(problem, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
-                        zcap, strideZ, info, &nothing, nmax);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  // device copies with the caller's own layout; w and Z travel both ways, so that what the kernel leaves alone (the
-  // rest of a row of w, the columns from m[b] on, a failed problem's slots) comes back as the caller had it
-  auto span = [&](int ld, long long stride, int cols) {
-    return (size_t)(batch - 1) * (size_t)stride + (size_t)ld * (cols - 1) + n;
-  };
-  const size_t cA = span(lda, strideA, n), cB = problem ? span(ldb, strideB, n) : 0;
-  const size_t cZ = (jobz && zcap > 0) ? span(ldz, strideZ, zcap) : 0, cw = (size_t)batch * n;
-  DevMem mem;
-  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cA * 8);
-  if (!rc) rc = mem.alloc(&uw, cw * 8);
-  if (!rc && problem) rc = mem.alloc(&uB, cB * 8);
-  if (!rc && jobz) rc = mem.alloc(&uZ, std::max(cZ, (size_t)1) * 8);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(uA, A, cA * 8, hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(uw, w, cw * 8, hipMemcpyHostToDevice, s));
-  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, B, cB * 8, hipMemcpyHostToDevice, s));
-  if (cZ) EK_HIP_CHECK(hipMemcpyAsync(uZ, Z, cZ * 8, hipMemcpyHostToDevice, s));
-  rc = window_device_locked(problem, itype, jobz, range, n, batch, vl, vu, il, iu, uA, lda, strideA, uB, ldb, strideB, m,
-                            uw, uZ, ldz, zcap, strideZ, info, seconds);
-  if (rc) return rc;
-  EK_HIP_CHECK(hipMemcpyAsync(w, uw, cw * 8, hipMemcpyDeviceToHost, s));
-  if (cZ) EK_HIP_CHECK(hipMemcpyAsync(Z, uZ, cZ * 8, hipMemcpyDeviceToHost, s));
-  EK_HIP_CHECK(hipStreamSynchronize(s));
-  return 0;
-}
-
-static int vbatched_device_entry(int problem, int itype, int jobz, int batch, const int *n, double *const *dA,
-                                 const int *lda, double *const *dB, const int *ldb, double *const *dw,
-                                 double *const *dZ, const int *ldz, int *info, double *seconds,
-                                 int nmax = EK_HIP_BATCH_NMAX) {
-  bool nothing;
-  int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)dA, lda, (const void *const *)dB, ldb,
-                          (const void *const *)dw, (const void *const *)dZ, ldz, info, &nothing, nmax);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  bool work = false;
-  for (int b = 0; b < batch && !work; ++b) work = n[b] > 0;
-  if (!work) {
-    for (int b = 0; b < batch; ++b) info[b] = 0;
-    return 0;
-  }
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return vbatched_device_locked(problem, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
-}
-
-static int vbatched_host_entry(int problem, int itype, int jobz, int batch, const int *n, const double *const *A,
-                               const int *lda, const double *const *B, const int *ldb, double *const *w,
-                               double *const *Z, const int *ldz, int *info, double *seconds,
-                               int nmax = EK_HIP_BATCH_NMAX) {
-  bool nothing;
-  int rc = vbatched_check(problem, jobz, batch, n, (const void *const *)A, lda, (const void *const *)B, ldb,
-                          (const void *const *)w, (const void *const *)Z, ldz, info, &nothing, nmax);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  // compact device layout (ld = n[b]), a problem behind the other: the caller's padding never travels
-  std::vector<size_t> offm((size_t)batch + 1, 0), offv((size_t)batch + 1, 0);
-  for (int b = 0; b < batch; ++b) {
-    offm[b + 1] = offm[b] + (size_t)n[b] * n[b];
-    offv[b + 1] = offv[b] + (size_t)n[b];
-  }
-  const size_t cm = offm[batch], cv = offv[batch];
-  if (cm == 0) {
-    for (int b = 0; b < batch; ++b) info[b] = 0;
-    return 0;
-  }
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  // one staging buffer per matrix kind: the lower triangles, column by column (what lies above them is never read)
-  auto pack = [&](const double *const *M, const int *ld, std::vector<double> &h) {
-    h.assign(cm, 0.0);
-    for (int b = 0; b < batch; ++b)
-      for (int j = 0; j < n[b]; ++j)
-        std::memcpy(&h[offm[b] + (size_t)j * n[b] + j], M[b] + (size_t)j * ld[b] + j, (size_t)(n[b] - j) * 8);
-  };
-  std::vector<double> hA, hB, hw, hZ;
-  pack(A, lda, hA);
-  if (problem) pack(B, ldb, hB);
-  DevMem mem;
-  double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cm * 8);
-  if (!rc) rc = mem.alloc(&uw, cv * 8);
-  if (!rc && problem) rc = mem.alloc(&uB, cm * 8);
-  if (!rc && jobz) rc = mem.alloc(&uZ, cm * 8);
-  if (rc) return rc;
-  std::vector<double *> pA((size_t)batch), pB((size_t)batch), pw((size_t)batch), pZ((size_t)batch);
-  std::vector<int> ldc((size_t)batch);
-  for (int b = 0; b < batch; ++b) {
-    pA[b] = uA + offm[b];
-    pB[b] = problem ? uB + offm[b] : nullptr;
-    pw[b] = uw + offv[b];
-    pZ[b] = jobz ? uZ + offm[b] : nullptr;
-    ldc[b] = n[b] > 1 ? n[b] : 1;
-  }
-  EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
-  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
-  rc = vbatched_device_locked(problem, itype, jobz, batch, n, pA.data(), ldc.data(), pB.data(), ldc.data(), pw.data(),
-                              pZ.data(), ldc.data(), info, seconds);
-  if (rc) return rc;
-  hw.resize(cv);
-  EK_HIP_CHECK(hipMemcpyAsync(hw.data(), uw, cv * 8, hipMemcpyDeviceToHost, s));
-  if (jobz) {
-    hZ.resize(cm);
-    EK_HIP_CHECK(hipMemcpyAsync(hZ.data(), uZ, cm * 8, hipMemcpyDeviceToHost, s));
-  }
-  EK_HIP_CHECK(hipStreamSynchronize(s));
-  for (int b = 0; b < batch; ++b) {                 // like the device form, a failed problem leaves its slots alone
-    if (info[b] != 0 || n[b] == 0) continue;
-    std::memcpy(w[b], &hw[offv[b]], (size_t)n[b] * 8);
-    if (jobz)
-      for (int j = 0; j < n[b]; ++j)
-        std::memcpy(Z[b] + (size_t)j * ldz[b], &hZ[offm[b] + (size_t)j * n[b]], (size_t)n[b] * 8);
-  }
-  return 0;
-}
-
-// ---- a window per problem, for problems of different orders (ek_hip_*_window_xvbatched*)
-
-// The 19 checked arguments of the prototype in their order; all arrays are host arrays of `batch` entries, and the pointers
-// in the pointer arrays are not dereferenced.  Per-problem conditions hold for the problems of order > 0
-static int vwindow_check(int problem, int jobz, int range, int batch, const int *n, const double *vl, const double *vu,
-                         const int *il, const int *iu, const void *const *A, const int *lda, const void *const *B,
-                         const int *ldb, const int *m, const void *const *w, const void *const *Z, const int *ldz,
-                         const int *zcap, const int *info, bool *nothing) {
-  *nothing = false;
-  if (problem != 0 && problem != 1) return -1;
-  if (jobz != 0 && jobz != 1) return -2;
-  if (range != 0 && range != 1) return -3;
-  if (batch < 0) return -4;
-  if (batch == 0) { *nothing = true; return 0; }
-  if (!n) return -5;
-  for (int b = 0; b < batch; ++b)
-    if (n[b] < 0 || n[b] > EK_HIP_XBATCH_NMAX) return -5;
-  if (range == 1) {
-    if (!vl) return -6;
-    for (int b = 0; b < batch; ++b)
-      if (n[b] > 0 && vl[b] != vl[b]) return -6;
-    if (!vu) return -7;
-    for (int b = 0; b < batch; ++b)
-      if (n[b] > 0 && !(vl[b] < vu[b])) return -7;  // vu NaN, or an empty interval
-  } else {
-    if (!il) return -8;
-    for (int b = 0; b < batch; ++b)
-      if (n[b] > 0 && (il[b] < 1 || il[b] > n[b])) return -8;
-    if (!iu) return -9;
-    for (int b = 0; b < batch; ++b)
-      if (n[b] > 0 && (iu[b] < il[b] || iu[b] > n[b])) return -9;
-  }
-  auto entries = [&](const void *const *P) {
-    if (!P) return false;
-    for (int b = 0; b < batch; ++b)
-      if (n[b] > 0 && !P[b]) return false;
-    return true;
-  };
-  auto leading = [&](const int *ld) {
-    if (!ld) return false;
-    for (int b = 0; b < batch; ++b)
-      if (ld[b] < (n[b] > 1 ? n[b] : 1)) return false;
-    return true;
-  };
-  if (!entries(A)) return -10;
-  if (!leading(lda)) return -11;
-  if (problem == 1) {
-    if (!entries(B)) return -12;
-    if (!leading(ldb)) return -13;
-  }
-  if (!m) return -14;
-  if (!entries(w)) return -15;
-  if (jobz == 1) {
-    if (!Z) return -16;
-    for (int b = 0; b < batch; ++b)                 // no Z is needed where it has no column
-      if (n[b] > 0 && !Z[b] && !(zcap && zcap[b] == 0)) return -16;
-    if (!leading(ldz)) return -17;
-  }
-  if (!zcap) return -18;
-  for (int b = 0; b < batch; ++b)                   // with and without vectors, as the uniform call
-    if (n[b] > 0 && (zcap[b] < 0 || (range == 0 && zcap[b] < iu[b] - il[b] + 1))) return -18;
-  if (!info) return -19;
-  return 0;
-}
-
-// arguments checked, a problem of order > 0 present, context up, g_mu held; the pointers in dA, dB, dw, dZ are device
-// addresses.  The table, the classes and their streams are vbatched_device_locked's.  A class runs in launches of
-// consecutive table entries: a launch ends at K problems or where its LU slots, summed, would pass the class's budget.  The
-// classes run beside each other, so each has a region of its own in the LU workspace: the launches of a class share it in
-// the order of the class's stream
-static int vwindow_device_locked(int problem, int itype, int jobz, int range, int batch, const int *n, const double *vl,
-                                 const double *vu, const int *il, const int *iu, double *const *dA, const int *lda,
-                                 double *const *dB, const int *ldb, int *m, double *const *dw, double *const *dZ,
-                                 const int *ldz, const int *zcap, int *info, double *seconds) {
-  using namespace batched;
-  std::vector<int> order;
-  order.reserve((size_t)batch);
-  for (int b = 0; b < batch; ++b)
-    if (n[b] > 0) order.push_back(b);
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return n[x] > n[y]; });
-  g_htable.resize(order.size());
-  g_hwtable.resize(order.size());
-  int count[kClasses] = {0, 0, 0, 0};               // classes of 256, 128, 64, 32
-  for (size_t i = 0; i < order.size(); ++i) {
-    const int b = order[i], c = class_of(n[b]);
-    ++count[n[b] > EK_HIP_BATCH_NMAX ? 0 : c == 128 ? 1 : c == 64 ? 2 : 3];
-    g_htable[i] = Desc{dA[b], problem ? dB[b] : nullptr, dw[b], jobz ? dZ[b] : nullptr, n[b], lda[b],
-                       problem ? ldb[b] : 1, jobz ? ldz[b] : 1, b, 0};
-    const int wcols = !jobz ? 0 : range == 0 ? iu[b] - il[b] + 1 : std::min(zcap[b], n[b]);
-    g_hwtable[i] = WDesc{range ? vl[b] : 0.0, range ? vu[b] : 0.0, range ? 0 : il[b], range ? 0 : iu[b], zcap[b], wcols, 0};
-  }
-  // the launches, the slot offsets inside each, and a region per class as wide as its widest launch.  The three classes
-  // of LDS share the uniform calls' kWindowBytes in equal parts, the class of 256 has its kXWindowBytes
+// The launches of a variable window call, the slot offsets inside each (into the window table's lu), and a region of the LU
+// workspace per class as wide as its widest launch: the classes run beside each other, the launches of a class share its
+// region in the order of the class's stream.  A class runs in launches of consecutive table entries: a launch ends at K
+// problems or where its LU slots, summed, would pass the class's budget.  The three classes of LDS share the uniform
+// calls' kWindowBytes in equal parts, the class of 256 has its kXWindowBytes
+struct VLaunch { int cls, first, count; };          // a launch: `count` table entries from `first`
+struct WindowPlan {
+  std::vector<VLaunch> launches;
+  size_t base[kClasses];                            // where a class's region starts, in doubles
+  size_t doubles;                                   // all regions
+  int xslots;                                       // the widest launch of the class of 256
+};
+static WindowPlan plan_window_launches(const int *count) {
+  WindowPlan p{{}, {0, 0, 0, 0}, 0, 0};
   int small = 0;
   for (int k = 1; k < kClasses; ++k) small += count[k] ? 1 : 0;
-  std::vector<VLaunch> launches;
-  size_t region[kClasses] = {0, 0, 0, 0}, base[kClasses] = {0, 0, 0, 0};   // doubles
-  int xslots = 0;
+  size_t region[kClasses] = {0, 0, 0, 0};
   for (int k = 0, off = 0; k < kClasses; off += count[k], ++k) {
     if (!count[k]) continue;
     const int K = k == 0 ? g_xwchunk : g_wchunk;
@@ -1390,7 +1213,7 @@ static int vwindow_device_locked(int problem, int itype, int jobz, int range, in
     for (int i = off; i < off + count[k]; ++i) {
       const size_t slot = (size_t)5 * g_htable[i].n * g_hwtable[i].wcols;
       if (cur.count > 0 && (cur.count >= K || sum + slot > budget)) {   // a launch always takes one problem
-        launches.push_back(cur);
+        p.launches.push_back(cur);
         cur = VLaunch{k, i, 0};
         sum = 0;
       }
@@ -1398,353 +1221,317 @@ static int vwindow_device_locked(int problem, int itype, int jobz, int range, in
       sum += slot;
       ++cur.count;
       region[k] = std::max(region[k], sum);
-      if (k == 0) xslots = std::max(xslots, cur.count);
+      if (k == 0) p.xslots = std::max(p.xslots, cur.count);
     }
-    launches.push_back(cur);
+    p.launches.push_back(cur);
   }
-  for (int k = 1; k < kClasses; ++k) base[k] = base[k - 1] + region[k - 1];
-  const size_t lubytes = (base[kClasses - 1] + region[kClasses - 1]) * sizeof(double);
-  int side[kClasses] = {-1, -1, -1, -1}, sides = 0; // -1: the context's stream
-  if (g_streams == 3)
-    for (int k = 0, used = 0; k < kClasses; ++k)
-      if (count[k] && used++ > 0) side[k] = sides++;
-  { int rc0 = ensure_info((size_t)batch); if (rc0) return rc0; }
-  { int rc0 = ensure_variable(order.size(), std::max(sides, 2)); if (rc0) return rc0; }
-  if (order.size() > g_dwtable_count) {
-    if (g_dwtable) (void)hipFree(g_dwtable);
-    g_dwtable = nullptr;
-    g_dwtable_count = 0;
-    EK_HIP_CHECK(hipMalloc((void **)&g_dwtable, order.size() * sizeof(WDesc)));
-    g_dwtable_count = order.size();
+  for (int k = 1; k < kClasses; ++k) p.base[k] = p.base[k - 1] + region[k - 1];
+  p.doubles = p.base[kClasses - 1] + region[kClasses - 1];
+  return p;
+}
+
+static int run_variable_window(const VariableCall &v) {
+  int count[kClasses];
+  classify(v, count);
+  const WindowPlan plan = plan_window_launches(count);
+  int rc0 = ensure_variable(v, count);
+  if (!rc0) rc0 = g_dwtable.grow(g_htable.size());
+  if (!rc0) rc0 = g_dm.grow((size_t)v.batch);
+  if (!rc0) rc0 = g_wws.grow(plan.doubles);
+  if (!rc0 && plan.xslots) rc0 = xwindow_prepare(plan.xslots);
+  if (rc0) return rc0;
+  size_t next = 0;                                  // the launches stand in the order of their classes
+  return run_classes(v, count, [&](int k, hipStream_t cs, int) {
+    int rc = 0;
+    for (; next < plan.launches.size() && plan.launches[next].cls == k && !rc; ++next) {
+      const VLaunch &l = plan.launches[next];
+      const Desc *table = g_dtable.p + l.first;
+      const WDesc *wtable = g_dwtable.p + l.first;
+      double *lu = g_wws.p + plan.base[k];
+      rc = k == 0 ? xvwindow_launch(cs, v.problem, v.itype, v.jobz, v.win->range, l.count, table, wtable, g_dinfo.p,
+                                    g_dm.p, lu)
+                  : launch_order(kClassOrder[k], cs, l.count, VWArgs{v.problem, v.jobz, table, wtable, g_dinfo.p, g_dm.p, lu,
+                                                                     v.win->range, v.itype});
+    }
+    return rc;
+  });
+}
+
+// a launch per class; the class of 256 in chunks of its own (xvbatched_launch)
+static int run(const VariableCall &v) {
+  if (v.win) return run_variable_window(v);
+  int count[kClasses];
+  classify(v, count);
+  int rc0 = ensure_variable(v, count);
+  if (!rc0 && count[0]) rc0 = xvbatched_prepare(count[0]);
+  if (rc0) return rc0;
+  return run_classes(v, count, [&](int k, hipStream_t cs, int off) {
+    return k == 0 ? xvbatched_launch(cs, v.problem, v.itype, v.jobz, count[k], g_dtable.p + off, g_dinfo.p)
+                  : launch_order(kClassOrder[k], cs, count[k], VArgs{v.problem, v.jobz, g_dtable.p + off, g_dinfo.p, v.itype});
+  });
+}
+
+// a batch without a problem of order > 0 is answered without the device
+static bool all_empty(const VariableCall &v) {
+  for (int b = 0; b < v.batch; ++b)
+    if (v.n[b] > 0) return false;
+  for (int b = 0; b < v.batch; ++b) {
+    v.info[b] = 0;
+    if (v.win) v.win->m[b] = 0;
   }
-  { int rc0 = ensure_window((size_t)batch, lubytes); if (rc0) return rc0; }
-  if (xslots) { int rc0 = xwindow_prepare(xslots); if (rc0) return rc0; }
+  return true;
+}
+
+// The host-pointer form.  Compact device layout (ld = n[b]; Z with n[b] columns, or a window's zcap[b]), a problem behind
+// the other: the caller's padding never travels.  One staging buffer per matrix kind: A and B go in as lower triangles,
+// column by column (what lies above them is never read).  Only what the kernel wrote comes back -- n[b] values and
+// columns, or a window's m[b] -- and, like the device form, a failed problem leaves its slots alone
+static int stage(const VariableCall &v) {
   hipStream_t s = g_ctx.stream;
-  EK_HIP_CHECK(hipMemcpyAsync(g_dtable, g_htable.data(), g_htable.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemcpyAsync(g_dwtable, g_hwtable.data(), g_hwtable.size() * sizeof(WDesc), hipMemcpyHostToDevice, s));
-  EK_HIP_CHECK(hipMemsetAsync(g_dm, 0, (size_t)batch * sizeof(int), s));   // a problem that ends before stage 4W: m = 0
-  hipStream_t cs[kClasses];
-  for (int k = 0; k < kClasses; ++k) cs[k] = side[k] < 0 ? s : g_side[side[k]];
-  EK_HIP_CHECK(hipEventRecord(g_ev[0], s));         // before the first launch
-  int rc = 0;
-  size_t next = 0;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < kClasses && !rc && e == hipSuccess; ++k) {
-    if (!count[k]) continue;
-    if (cs[k] != s) e = hipStreamWaitEvent(cs[k], g_ev[0], 0);
-    if (e != hipSuccess) break;
-    if (seconds) (void)hipEventRecord(g_ev[kClasses + 2 * k], cs[k]);
-    for (; next < launches.size() && launches[next].cls == k && !rc; ++next) {
-      const VLaunch &l = launches[next];
-      if (k == 0) {
-        rc = xvwindow_launch(cs[k], problem, itype, jobz, range, l.count, g_dtable + l.first, g_dwtable + l.first,
-                             g_dinfo, g_dm, g_wws + base[k]);
-        continue;
-      }
-      VWArgs a{problem, jobz, g_dtable + l.first, g_dwtable + l.first, g_dinfo, g_dm, g_wws + base[k], range, itype};
-      rc = k == 1 ? launch_class<128, 256>(cs[k], l.count, a)
-         : k == 2 ? launch_class<64, 128>(cs[k], l.count, a) : launch_class<32, 64>(cs[k], l.count, a);
-    }
-    if (seconds) (void)hipEventRecord(g_ev[kClasses + 1 + 2 * k], cs[k]);
-    if (cs[k] != s) {                               // join
-      e = hipEventRecord(g_ev[k], cs[k]);
-      if (e == hipSuccess) e = hipStreamWaitEvent(s, g_ev[k], 0);
-    }
-  }
-  if (seconds) (void)hipEventRecord(g_ev[kEvents - 1], s);   // after the last launch has ended
-  if (!rc && e == hipSuccess)
-    e = hipMemcpyAsync(info, g_dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (!rc && e == hipSuccess) e = hipMemcpyAsync(m, g_dm, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s);
-  hipError_t es = hipStreamSynchronize(s);
-  if (e != hipSuccess || rc)                        // an error may have left a class outside the join
-    for (int k = 0; k < kClasses - 1; ++k)
-      if (g_side[k]) (void)hipStreamSynchronize(g_side[k]);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess && !rc) rc = -1000 - (int)e;
-  if (seconds && !rc) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_ev[0], g_ev[kEvents - 1]) == hipSuccess) *seconds = (double)ms * 1e-3;
-    for (int k = 0; k < kClasses; ++k) {
-      g_class_count[k] = count[k];
-      g_class_seconds[k] = 0.0;
-      if (count[k] && hipEventElapsedTime(&ms, g_ev[kClasses + 2 * k], g_ev[kClasses + 1 + 2 * k]) == hipSuccess)
-        g_class_seconds[k] = (double)ms * 1e-3;
-    }
-  }
-  if (!rc)
-    for (int b = 0; b < batch; ++b)
-      if (n[b] == 0) { info[b] = 0; m[b] = 0; }
-  return rc;
-}
-
-static int vwindow_device_entry(int problem, int itype, int jobz, int range, int batch, const int *n, const double *vl,
-                                const double *vu, const int *il, const int *iu, double *const *dA, const int *lda,
-                                double *const *dB, const int *ldb, int *m, double *const *dw, double *const *dZ,
-                                const int *ldz, const int *zcap, int *info, double *seconds) {
-  bool nothing;
-  int rc = vwindow_check(problem, jobz, range, batch, n, vl, vu, il, iu, (const void *const *)dA, lda,
-                         (const void *const *)dB, ldb, m, (const void *const *)dw, (const void *const *)dZ, ldz, zcap,
-                         info, &nothing);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  bool work = false;
-  for (int b = 0; b < batch && !work; ++b) work = n[b] > 0;
-  if (!work) {
-    for (int b = 0; b < batch; ++b) { info[b] = 0; m[b] = 0; }
-    return 0;
-  }
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  return vwindow_device_locked(problem, itype, jobz, range, batch, n, vl, vu, il, iu, dA, lda, dB, ldb, m, dw, dZ, ldz,
-                               zcap, info, seconds);
-}
-
-static int vwindow_host_entry(int problem, int itype, int jobz, int range, int batch, const int *n, const double *vl,
-                              const double *vu, const int *il, const int *iu, const double *const *A, const int *lda,
-                              const double *const *B, const int *ldb, int *m, double *const *w, double *const *Z,
-                              const int *ldz, const int *zcap, int *info, double *seconds) {
-  bool nothing;
-  int rc = vwindow_check(problem, jobz, range, batch, n, vl, vu, il, iu, (const void *const *)A, lda,
-                         (const void *const *)B, ldb, m, (const void *const *)w, (const void *const *)Z, ldz, zcap, info,
-                         &nothing);
-  if (rc) return rc;
-  if (seconds) *seconds = 0.0;
-  if (nothing) return 0;
-  // compact device layout (ld = n[b]; Z with zcap[b] columns), a problem behind the other: the caller's padding never
-  // travels, and A and B are packed lower triangles on the way in (vbatched_host_entry)
+  const int batch = v.batch, *n = v.n;
   std::vector<size_t> offm((size_t)batch + 1, 0), offv((size_t)batch + 1, 0), offz((size_t)batch + 1, 0);
   for (int b = 0; b < batch; ++b) {
     offm[b + 1] = offm[b] + (size_t)n[b] * n[b];
     offv[b + 1] = offv[b] + (size_t)n[b];
-    offz[b + 1] = offz[b] + (jobz && n[b] > 0 ? (size_t)n[b] * zcap[b] : 0);
+    offz[b + 1] = offz[b] + (v.jobz && n[b] > 0 ? (size_t)n[b] * (v.win ? v.win->zcap[b] : n[b]) : 0);
   }
   const size_t cm = offm[batch], cv = offv[batch], cz = offz[batch];
-  if (cm == 0) {
-    for (int b = 0; b < batch; ++b) { info[b] = 0; m[b] = 0; }
-    return 0;
-  }
-  rc = ensure_init(); if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = g_ctx.stream;
-  auto pack = [&](const double *const *M, const int *ld, std::vector<double> &h) {
+  auto pack = [&](double *const *M, const int *ld, std::vector<double> &h) {
     h.assign(cm, 0.0);
     for (int b = 0; b < batch; ++b)
       for (int j = 0; j < n[b]; ++j)
         std::memcpy(&h[offm[b] + (size_t)j * n[b] + j], M[b] + (size_t)j * ld[b] + j, (size_t)(n[b] - j) * 8);
   };
   std::vector<double> hA, hB, hw, hZ;
-  pack(A, lda, hA);
-  if (problem) pack(B, ldb, hB);
+  pack(v.A, v.lda, hA);
+  if (v.problem) pack(v.B, v.ldb, hB);
   DevMem mem;
   double *uA = nullptr, *uB = nullptr, *uw = nullptr, *uZ = nullptr;
-  rc = mem.alloc(&uA, cm * 8);
+  int rc = mem.alloc(&uA, cm * 8);
   if (!rc) rc = mem.alloc(&uw, cv * 8);
-  if (!rc && problem) rc = mem.alloc(&uB, cm * 8);
-  if (!rc && jobz) rc = mem.alloc(&uZ, std::max(cz, (size_t)1) * 8);
+  if (!rc && v.problem) rc = mem.alloc(&uB, cm * 8);
+  if (!rc && v.jobz) rc = mem.alloc(&uZ, std::max(cz, (size_t)1) * 8);
   if (rc) return rc;
   std::vector<double *> pA((size_t)batch), pB((size_t)batch), pw((size_t)batch), pZ((size_t)batch);
   std::vector<int> ldc((size_t)batch);
   for (int b = 0; b < batch; ++b) {
     pA[b] = uA + offm[b];
-    pB[b] = problem ? uB + offm[b] : nullptr;
+    pB[b] = v.problem ? uB + offm[b] : nullptr;
     pw[b] = uw + offv[b];
-    pZ[b] = jobz ? uZ + offz[b] : nullptr;
+    pZ[b] = v.jobz ? uZ + offz[b] : nullptr;
     ldc[b] = n[b] > 1 ? n[b] : 1;
   }
   EK_HIP_CHECK(hipMemcpyAsync(uA, hA.data(), cm * 8, hipMemcpyHostToDevice, s));
-  if (problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
-  rc = vwindow_device_locked(problem, itype, jobz, range, batch, n, vl, vu, il, iu, pA.data(), ldc.data(), pB.data(),
-                             ldc.data(), m, pw.data(), pZ.data(), ldc.data(), zcap, info, seconds);
+  if (v.problem) EK_HIP_CHECK(hipMemcpyAsync(uB, hB.data(), cm * 8, hipMemcpyHostToDevice, s));
+  VariableCall d = v;
+  d.A = pA.data(); d.B = pB.data(); d.w = pw.data(); d.Z = pZ.data();
+  d.lda = d.ldb = d.ldz = ldc.data();
+  rc = run(d);
   if (rc) return rc;
   hw.resize(cv);
   EK_HIP_CHECK(hipMemcpyAsync(hw.data(), uw, cv * 8, hipMemcpyDeviceToHost, s));
-  if (jobz && cz) {
+  if (v.jobz && cz) {
     hZ.resize(cz);
     EK_HIP_CHECK(hipMemcpyAsync(hZ.data(), uZ, cz * 8, hipMemcpyDeviceToHost, s));
   }
   EK_HIP_CHECK(hipStreamSynchronize(s));
-  for (int b = 0; b < batch; ++b) {                 // only what the kernel wrote: m[b] values, m[b] columns
-    if (info[b] != 0 || n[b] == 0) continue;
-    std::memcpy(w[b], &hw[offv[b]], (size_t)m[b] * 8);
-    if (jobz)
-      for (int j = 0; j < m[b]; ++j)
-        std::memcpy(Z[b] + (size_t)j * ldz[b], &hZ[offz[b] + (size_t)j * n[b]], (size_t)n[b] * 8);
+  for (int b = 0; b < batch; ++b) {
+    if (v.info[b] != 0 || n[b] == 0) continue;
+    const int cols = v.win ? v.win->m[b] : n[b];
+    std::memcpy(v.w[b], &hw[offv[b]], (size_t)cols * 8);
+    if (v.jobz)
+      for (int j = 0; j < cols; ++j)
+        std::memcpy(v.Z[b] + (size_t)j * v.ldz[b], &hZ[offz[b] + (size_t)j * n[b]], (size_t)n[b] * 8);
   }
   return 0;
 }
 
-extern "C" {
-
-// A window of eigenpairs per problem, for problems of different orders up to EK_HIP_XBATCH_NMAX
-int ek_hip_eigenpairs_window_xvbatched_device(int problem, int jobz, int range, int batch, const int *n, const double *vl,
-                                              const double *vu, const int *il, const int *iu, double *const *dA,
-                                              const int *lda, double *const *dB, const int *ldb, int *m,
-                                              double *const *dw, double *const *dZ, const int *ldz, const int *zcap,
-                                              int *info, double *seconds) {
-  return vwindow_device_entry(problem, 1, jobz, range, batch, n, vl, vu, il, iu, dA, lda, dB, ldb, m, dw, dZ, ldz, zcap,
-                              info, seconds);
-}
-
-int ek_hip_eigenpairs_window_xvbatched(int problem, int jobz, int range, int batch, const int *n, const double *vl,
-                                       const double *vu, const int *il, const int *iu, const double *const *A,
-                                       const int *lda, const double *const *B, const int *ldb, int *m, double *const *w,
-                                       double *const *Z, const int *ldz, const int *zcap, int *info, double *seconds) {
-  return vwindow_host_entry(problem, 1, jobz, range, batch, n, vl, vu, il, iu, A, lda, B, ldb, m, w, Z, ldz, zcap, info,
-                            seconds);
-}
-
-int ek_hip_sygv_window_xvbatched_device(int itype, int jobz, int range, int batch, const int *n, const double *vl,
-                                        const double *vu, const int *il, const int *iu, double *const *dA,
-                                        const int *lda, double *const *dB, const int *ldb, int *m, double *const *dw,
-                                        double *const *dZ, const int *ldz, const int *zcap, int *info, double *seconds) {
-  if (itype < 1 || itype > 3) return -1;
-  return vwindow_device_entry(1, itype, jobz, range, batch, n, vl, vu, il, iu, dA, lda, dB, ldb, m, dw, dZ, ldz, zcap,
-                              info, seconds);
-}
-
-int ek_hip_sygv_window_xvbatched(int itype, int jobz, int range, int batch, const int *n, const double *vl,
-                                 const double *vu, const int *il, const int *iu, const double *const *A, const int *lda,
-                                 const double *const *B, const int *ldb, int *m, double *const *w, double *const *Z,
-                                 const int *ldz, const int *zcap, int *info, double *seconds) {
-  if (itype < 1 || itype > 3) return -1;
-  return vwindow_host_entry(1, itype, jobz, range, batch, n, vl, vu, il, iu, A, lda, B, ldb, m, w, Z, ldz, zcap, info,
-                            seconds);
-}
-
-long long ek_hip_debug_window_xvbatched_budget(long long bytes) {
+// The body of every entry: check, *seconds = 0, nothing to do (or nothing but empty problems: filled here), the context,
+// g_mu, and the call in its host-pointer or device-pointer form
+template <typename Call>
+static int entry(const Call &c, int nmax, bool host) {
+  bool nothing;
+  int rc = check(c, nmax, &nothing);
+  if (rc) return rc;
+  if (c.seconds) *c.seconds = 0.0;
+  if (nothing || all_empty(c)) return 0;
+  rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
-  const long long before = batched::g_vwbudget;
-  batched::g_vwbudget = bytes > 0 ? bytes : 0;
-  return before;
+  return host ? stage(c) : run(c);
 }
+
+// The entries fill their call: the eigenpairs entries with itype 1; the sygv entries, DSYGV's three problem types, with
+// problem 1 and itype in its place, so that every other argument keeps its number.  The host-pointer forms do not write
+// through A and B.  The x entries take orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's kernel
+// (CONG for types 2 and 3), every other problem the kernel the entries without x give it
+extern "C" {
 
 int ek_hip_eigenpairs_batched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                      double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                      long long strideZ, int *info, double *seconds) {
-  return batched_device_entry(problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                              seconds);
+  return entry(UniformCall{problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, nullptr}, EK_HIP_BATCH_NMAX, false);
 }
 
 int ek_hip_eigenpairs_batched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                               long long strideZ, int *info, double *seconds) {
-  return batched_host_entry(problem, 1, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
-                            seconds);
+  return entry(UniformCall{problem, 1, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, nullptr}, EK_HIP_BATCH_NMAX, true);
 }
 
 int ek_hip_eigenpairs_xbatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                       double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                       long long strideZ, int *info, double *seconds) {
-  return batched_device_entry(problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                              seconds, EK_HIP_XBATCH_NMAX);
+  return entry(UniformCall{problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, nullptr}, EK_HIP_XBATCH_NMAX, false);
 }
 
 int ek_hip_eigenpairs_xbatched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
                                const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                                long long strideZ, int *info, double *seconds) {
-  return batched_host_entry(problem, 1, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
-                            seconds, EK_HIP_XBATCH_NMAX);
+  return entry(UniformCall{problem, 1, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, nullptr}, EK_HIP_XBATCH_NMAX, true);
 }
 
-int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
-                                      double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
-                                      const int *ldz, int *info, double *seconds) {
-  return vbatched_device_entry(problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
-}
-
-int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
-                               const double *const *B, const int *ldb, double *const *w, double *const *Z,
-                               const int *ldz, int *info, double *seconds) {
-  return vbatched_host_entry(problem, 1, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds);
-}
-
-// DSYGV's three problem types: problem 1 with itype in its place, so that every other argument keeps its number
 int ek_hip_sygv_batched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                long long strideZ, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return batched_device_entry(1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                              seconds);
+  return entry(UniformCall{1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, nullptr}, EK_HIP_BATCH_NMAX, false);
 }
 
 int ek_hip_sygv_batched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
                         const double *B, int ldb, long long strideB, double *w, double *Z, int ldz, long long strideZ,
                         int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return batched_host_entry(1, itype, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
-                            seconds);
+  return entry(UniformCall{1, itype, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, nullptr}, EK_HIP_BATCH_NMAX, true);
 }
 
-// The same for orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's kernel, CONG for types 2 and 3
 int ek_hip_sygv_xbatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
                                 double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                                 long long strideZ, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return batched_device_entry(1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
-                              seconds, EK_HIP_XBATCH_NMAX);
+  return entry(UniformCall{1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, nullptr}, EK_HIP_XBATCH_NMAX, false);
 }
 
 int ek_hip_sygv_xbatched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
                          const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                          long long strideZ, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return batched_host_entry(1, itype, jobz, n, batch, A, lda, strideA, B, ldb, strideB, w, Z, ldz, strideZ, info,
-                            seconds, EK_HIP_XBATCH_NMAX);
+  return entry(UniformCall{1, itype, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, nullptr}, EK_HIP_XBATCH_NMAX, true);
+}
+
+// problems of different orders
+int ek_hip_eigenpairs_vbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA, const int *lda,
+                                      double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
+                                      const int *ldz, int *info, double *seconds) {
+  return entry(VariableCall{problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds, nullptr},
+               EK_HIP_BATCH_NMAX, false);
+}
+
+int ek_hip_eigenpairs_vbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
+                               const double *const *B, const int *ldb, double *const *w, double *const *Z,
+                               const int *ldz, int *info, double *seconds) {
+  return entry(VariableCall{problem, 1, jobz, batch, n, (double *const *)A, lda, (double *const *)B, ldb, w, Z, ldz, info,
+                            seconds, nullptr}, EK_HIP_BATCH_NMAX, true);
 }
 
 int ek_hip_sygv_vbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,
                                 double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
                                 const int *ldz, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return vbatched_device_entry(1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds);
+  return entry(VariableCall{1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds, nullptr},
+               EK_HIP_BATCH_NMAX, false);
 }
 
 int ek_hip_sygv_vbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
                          const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
                          int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds);
+  return entry(VariableCall{1, itype, jobz, batch, n, (double *const *)A, lda, (double *const *)B, ldb, w, Z, ldz, info,
+                            seconds, nullptr}, EK_HIP_BATCH_NMAX, true);
 }
 
-// The variable-order entries for orders up to EK_HIP_XBATCH_NMAX: a problem above EK_HIP_BATCH_NMAX runs
-// ek_batched_x.hip's kernel, every other one the kernel ek_hip_*_vbatched* give it
 int ek_hip_eigenpairs_xvbatched_device(int problem, int jobz, int batch, const int *n, double *const *dA,
                                        const int *lda, double *const *dB, const int *ldb, double *const *dw,
                                        double *const *dZ, const int *ldz, int *info, double *seconds) {
-  return vbatched_device_entry(problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds,
-                               EK_HIP_XBATCH_NMAX);
+  return entry(VariableCall{problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds, nullptr},
+               EK_HIP_XBATCH_NMAX, false);
 }
 
 int ek_hip_eigenpairs_xvbatched(int problem, int jobz, int batch, const int *n, const double *const *A, const int *lda,
                                 const double *const *B, const int *ldb, double *const *w, double *const *Z,
                                 const int *ldz, int *info, double *seconds) {
-  return vbatched_host_entry(problem, 1, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds, EK_HIP_XBATCH_NMAX);
+  return entry(VariableCall{problem, 1, jobz, batch, n, (double *const *)A, lda, (double *const *)B, ldb, w, Z, ldz, info,
+                            seconds, nullptr}, EK_HIP_XBATCH_NMAX, true);
 }
 
 int ek_hip_sygv_xvbatched_device(int itype, int jobz, int batch, const int *n, double *const *dA, const int *lda,
                                  double *const *dB, const int *ldb, double *const *dw, double *const *dZ,
                                  const int *ldz, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return vbatched_device_entry(1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds,
-                               EK_HIP_XBATCH_NMAX);
+  return entry(VariableCall{1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds, nullptr},
+               EK_HIP_XBATCH_NMAX, false);
 }
 
 int ek_hip_sygv_xvbatched(int itype, int jobz, int batch, const int *n, const double *const *A, const int *lda,
                           const double *const *B, const int *ldb, double *const *w, double *const *Z, const int *ldz,
                           int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return vbatched_host_entry(1, itype, jobz, batch, n, A, lda, B, ldb, w, Z, ldz, info, seconds, EK_HIP_XBATCH_NMAX);
+  return entry(VariableCall{1, itype, jobz, batch, n, (double *const *)A, lda, (double *const *)B, ldb, w, Z, ldz, info,
+                            seconds, nullptr}, EK_HIP_XBATCH_NMAX, true);
 }
 
-// A window of eigenpairs of DSYGV's three problem types: the window entries' problem 1 with itype in its place
+// a window of eigenpairs per problem
+int ek_hip_eigenpairs_window_batched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
+                                            int il, int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
+                                            long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
+                                            long long strideZ, int *info, double *seconds) {
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, &win}, EK_HIP_BATCH_NMAX, false);
+}
+
+int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                     int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
+                                     long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
+                                     long long strideZ, int *info, double *seconds) {
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{problem, 1, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, &win}, EK_HIP_BATCH_NMAX, true);
+}
+
+int ek_hip_eigenpairs_window_xbatched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
+                                             int il, int iu, double *dA, int lda, long long strideA, double *dB,
+                                             int ldb, long long strideB, int *m, double *dw, double *dZ, int ldz,
+                                             int zcap, long long strideZ, int *info, double *seconds) {
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, &win}, EK_HIP_XBATCH_NMAX, false);
+}
+
+int ek_hip_eigenpairs_window_xbatched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
+                                      int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
+                                      long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
+                                      long long strideZ, int *info, double *seconds) {
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{problem, 1, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, &win}, EK_HIP_XBATCH_NMAX, true);
+}
+
 int ek_hip_sygv_window_batched_device(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il,
                                       int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
                                       long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
                                       long long strideZ, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return window_device_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
-                             dZ, ldz, zcap, strideZ, info, seconds);
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, &win}, EK_HIP_BATCH_NMAX, false);
 }
 
 int ek_hip_sygv_window_batched(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
@@ -1752,19 +1539,19 @@ int ek_hip_sygv_window_batched(int itype, int jobz, int range, int n, int batch,
                                int *m, double *w, double *Z, int ldz, int zcap, long long strideZ, int *info,
                                double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return window_host_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z,
-                           ldz, zcap, strideZ, info, seconds);
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{1, itype, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, &win}, EK_HIP_BATCH_NMAX, true);
 }
 
-// The same for orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's window instantiation, CONG for
-// types 2 and 3
 int ek_hip_sygv_window_xbatched_device(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il,
                                        int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
                                        long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
                                        long long strideZ, int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return window_device_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
-                             dZ, ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, &win}, EK_HIP_XBATCH_NMAX, false);
 }
 
 int ek_hip_sygv_window_xbatched(int itype, int jobz, int range, int n, int batch, double vl, double vu, int il, int iu,
@@ -1772,78 +1559,93 @@ int ek_hip_sygv_window_xbatched(int itype, int jobz, int range, int n, int batch
                                 long long strideB, int *m, double *w, double *Z, int ldz, int zcap, long long strideZ,
                                 int *info, double *seconds) {
   if (itype < 1 || itype > 3) return -1;
-  return window_host_entry(1, itype, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z,
-                           ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+  const UniformWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(UniformCall{1, itype, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, &win}, EK_HIP_XBATCH_NMAX, true);
 }
 
-int ek_hip_eigenpairs_window_batched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
-                                            int il, int iu, double *dA, int lda, long long strideA, double *dB, int ldb,
-                                            long long strideB, int *m, double *dw, double *dZ, int ldz, int zcap,
-                                            long long strideZ, int *info, double *seconds) {
-  return window_device_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
-                             dZ, ldz, zcap, strideZ, info, seconds);
+// a window per problem, for problems of different orders up to EK_HIP_XBATCH_NMAX
+int ek_hip_eigenpairs_window_xvbatched_device(int problem, int jobz, int range, int batch, const int *n, const double *vl,
+                                              const double *vu, const int *il, const int *iu, double *const *dA,
+                                              const int *lda, double *const *dB, const int *ldb, int *m,
+                                              double *const *dw, double *const *dZ, const int *ldz, const int *zcap,
+                                              int *info, double *seconds) {
+  const VariableWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(VariableCall{problem, 1, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds, &win},
+               EK_HIP_XBATCH_NMAX, false);
 }
 
-int ek_hip_eigenpairs_window_batched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
-                                     int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
-                                     long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
-                                     long long strideZ, int *info, double *seconds) {
-  return window_host_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
-                           zcap, strideZ, info, seconds);
+int ek_hip_eigenpairs_window_xvbatched(int problem, int jobz, int range, int batch, const int *n, const double *vl,
+                                       const double *vu, const int *il, const int *iu, const double *const *A,
+                                       const int *lda, const double *const *B, const int *ldb, int *m, double *const *w,
+                                       double *const *Z, const int *ldz, const int *zcap, int *info, double *seconds) {
+  const VariableWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(VariableCall{problem, 1, jobz, batch, n, (double *const *)A, lda, (double *const *)B, ldb, w, Z, ldz, info,
+                            seconds, &win}, EK_HIP_XBATCH_NMAX, true);
 }
 
-// The same for orders up to EK_HIP_XBATCH_NMAX: above EK_HIP_BATCH_NMAX ek_batched_x.hip's window instantiation
-int ek_hip_eigenpairs_window_xbatched_device(int problem, int jobz, int range, int n, int batch, double vl, double vu,
-                                             int il, int iu, double *dA, int lda, long long strideA, double *dB,
-                                             int ldb, long long strideB, int *m, double *dw, double *dZ, int ldz,
-                                             int zcap, long long strideZ, int *info, double *seconds) {
-  return window_device_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, dA, lda, strideA, dB, ldb, strideB, m, dw,
-                             dZ, ldz, zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+int ek_hip_sygv_window_xvbatched_device(int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                        const double *vu, const int *il, const int *iu, double *const *dA,
+                                        const int *lda, double *const *dB, const int *ldb, int *m, double *const *dw,
+                                        double *const *dZ, const int *ldz, const int *zcap, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  const VariableWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(VariableCall{1, itype, jobz, batch, n, dA, lda, dB, ldb, dw, dZ, ldz, info, seconds, &win},
+               EK_HIP_XBATCH_NMAX, false);
 }
 
-int ek_hip_eigenpairs_window_xbatched(int problem, int jobz, int range, int n, int batch, double vl, double vu, int il,
-                                      int iu, const double *A, int lda, long long strideA, const double *B, int ldb,
-                                      long long strideB, int *m, double *w, double *Z, int ldz, int zcap,
-                                      long long strideZ, int *info, double *seconds) {
-  return window_host_entry(problem, 1, jobz, range, n, batch, vl, vu, il, iu, A, lda, strideA, B, ldb, strideB, m, w, Z, ldz,
-                           zcap, strideZ, info, seconds, EK_HIP_XBATCH_NMAX);
+int ek_hip_sygv_window_xvbatched(int itype, int jobz, int range, int batch, const int *n, const double *vl,
+                                 const double *vu, const int *il, const int *iu, const double *const *A, const int *lda,
+                                 const double *const *B, const int *ldb, int *m, double *const *w, double *const *Z,
+                                 const int *ldz, const int *zcap, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  const VariableWindow win{range, vl, vu, il, iu, zcap, m};
+  return entry(VariableCall{1, itype, jobz, batch, n, (double *const *)A, lda, (double *const *)B, ldb, w, Z, ldz, info,
+                            seconds, &win}, EK_HIP_XBATCH_NMAX, true);
+}
+
+long long ek_hip_debug_window_xvbatched_budget(long long bytes) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const long long before = g_vwbudget;
+  g_vwbudget = bytes > 0 ? bytes : 0;
+  return before;
 }
 
 int ek_hip_debug_window_xbatched_chunk(int problems) {
   std::lock_guard<std::mutex> lk(g_mu);
-  const int before = batched::g_xwchunk;
-  batched::g_xwchunk = problems > 0 ? problems : batched::kXWindowChunk;
+  const int before = g_xwchunk;
+  g_xwchunk = problems > 0 ? problems : kXWindowChunk;
   return before;
 }
 
 int ek_hip_debug_window_batched_chunk(int problems) {
   std::lock_guard<std::mutex> lk(g_mu);
-  const int before = batched::g_wchunk;
-  batched::g_wchunk = problems > 0 ? problems : batched::kWindowChunk;
+  const int before = g_wchunk;
+  g_wchunk = problems > 0 ? problems : kWindowChunk;
   return before;
 }
 
 int ek_hip_debug_vbatched_streams(int streams) {
   if (streams != 1 && streams != 3) streams = 3;
   std::lock_guard<std::mutex> lk(g_mu);
-  batched::g_streams = streams;
+  g_streams = streams;
   return 0;
 }
 
 int ek_hip_debug_vbatched_last(double *class_seconds, int *class_count) {
   std::lock_guard<std::mutex> lk(g_mu);
   for (int k = 0; k < 3; ++k) {                     // classes of 128, 64, 32
-    if (class_seconds) class_seconds[k] = batched::g_class_seconds[k + 1];
-    if (class_count) class_count[k] = batched::g_class_count[k + 1];
+    if (class_seconds) class_seconds[k] = g_class_seconds[k + 1];
+    if (class_count) class_count[k] = g_class_count[k + 1];
   }
   return 0;
 }
 
 int ek_hip_debug_xvbatched_last(double *class_seconds, int *class_count) {
   std::lock_guard<std::mutex> lk(g_mu);
-  for (int k = 0; k < batched::kClasses; ++k) {     // classes of 256, 128, 64, 32
-    if (class_seconds) class_seconds[k] = batched::g_class_seconds[k];
-    if (class_count) class_count[k] = batched::g_class_count[k];
+  for (int k = 0; k < kClasses; ++k) {              // classes of 256, 128, 64, 32
+    if (class_seconds) class_seconds[k] = g_class_seconds[k];
+    if (class_count) class_count[k] = g_class_count[k];
   }
   return 0;
 }

@@ -914,22 +914,55 @@ def eigenpairs(A, B=None, il=None, iu=None, vl=None, vu=None, vectors=True, stag
 BATCH_NMAX = 128   # EK_HIP_BATCH_NMAX
 
 
-def _batched_call(name, first, A, B, vectors, seconds):
-    """ek_hip_eigenpairs_batched / ek_hip_sygv_batched on (batch, n, n) arrays; `first` is the first argument (problem
-    or itype)."""
-    lib = load_library()
+def _uniform_mats(A, B):
+    """(batch, n, At, Bt) of A (and B, or None) of shape (batch, n, n): float64 copies that are column-major per problem
+    (the transpose of each C-ordered slice); Bt is None without B."""
     A = np.asarray(A, dtype=np.float64)
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
         raise ValueError("A must have shape (batch, n, n)")
-    batch, n = A.shape[0], A.shape[1]
-    # column-major per problem: the transpose of each C-ordered slice
-    At = np.ascontiguousarray(A.transpose(0, 2, 1))
     Bt = None
     if B is not None:
         B = np.asarray(B, dtype=np.float64)
         if B.shape != A.shape:
             raise ValueError("B must have the shape of A")
         Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
+    return A.shape[0], A.shape[1], np.ascontiguousarray(A.transpose(0, 2, 1)), Bt
+
+
+def _square_list(As, Bs):
+    """(Af, Bf, n, ld) of sequences of square 2-D arrays, a problem per entry: Fortran-ordered float64 copies (Bf is None
+    without Bs), the orders and the leading dimensions max(n, 1) as int32."""
+    Af = []
+    for M in As:
+        M = np.asarray(M, dtype=np.float64)
+        if M.ndim != 2 or M.shape[0] != M.shape[1]:
+            raise ValueError("every A must be a square 2-D array")
+        Af.append(np.asfortranarray(M))
+    Bf = None
+    if Bs is not None:
+        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
+        if len(Bf) != len(Af) or any(Bf[b].shape != Af[b].shape for b in range(len(Af))):
+            raise ValueError("Bs must hold one array of A's shape per problem")
+    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
+    return Af, Bf, n, np.maximum(n, 1).astype(np.int32)
+
+
+_SPARE = np.zeros(1)
+
+
+def _table(arrays, need=None):
+    """The addresses of a problem's array per entry, None for an empty array -- or, where need[b] says that the library
+    asks for an address all the same, that of a spare word (never read: such a problem is skipped or empty)."""
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data if a.size else
+                                             (_SPARE.ctypes.data if need is not None and need[b] else None)
+                                             for b, a in enumerate(arrays)])
+
+
+def _batched_call(name, first, A, B, vectors, seconds):
+    """ek_hip_eigenpairs_batched / ek_hip_sygv_batched on (batch, n, n) arrays; `first` is the first argument (problem
+    or itype)."""
+    lib = load_library()
+    batch, n, At, Bt = _uniform_mats(A, B)
     w = np.zeros((batch, n))
     Zt = np.zeros((batch, n, n)) if vectors else None
     info = np.zeros(max(batch, 1), dtype=np.int32)
@@ -967,10 +1000,7 @@ def eigenpairs_window_batched(A, B=None, il=None, iu=None, vl=None, vu=None, vec
 def _window_batched_call(entry, A, B, il, iu, vl, vu, vectors, zcap, seconds, itype=None):
     """itype None: the eigenpairs entries (argument 1 is problem); 1 / 2 / 3: the sygv entries (argument 1 is itype)."""
     lib = load_library()
-    A = np.asarray(A, dtype=np.float64)
-    if A.ndim != 3 or A.shape[1] != A.shape[2]:
-        raise ValueError("A must have shape (batch, n, n)")
-    batch, n = A.shape[0], A.shape[1]
+    batch, n, At, Bt = _uniform_mats(A, B)
     by_value = vl is not None or vu is not None
     if by_value and (il is not None or iu is not None):
         raise ValueError("give either il / iu or vl / vu")
@@ -981,13 +1011,6 @@ def _window_batched_call(entry, A, B, il, iu, vl, vu, vectors, zcap, seconds, it
     if zcap is None:
         zcap = n if by_value else max(iu - il + 1, 0)
     zcap = int(zcap)
-    At = np.ascontiguousarray(A.transpose(0, 2, 1))
-    Bt = None
-    if B is not None:
-        B = np.asarray(B, dtype=np.float64)
-        if B.shape != A.shape:
-            raise ValueError("B must have the shape of A")
-        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
     w = np.zeros((batch, n))
     zc = max(zcap, 1)
     Zt = np.zeros((batch, zc, max(n, 1))) if vectors else None
@@ -1087,32 +1110,16 @@ def _vbatched_call(name, first, As, Bs, vectors, seconds):
     """ek_hip_eigenpairs_vbatched / ek_hip_sygv_vbatched on sequences of square arrays; `first` is the first argument
     (problem or itype)."""
     lib = load_library()
-    Af = []
-    for M in As:
-        M = np.asarray(M, dtype=np.float64)
-        if M.ndim != 2 or M.shape[0] != M.shape[1]:
-            raise ValueError("every A must be a square 2-D array")
-        Af.append(np.asfortranarray(M))
+    Af, Bf, n, ld = _square_list(As, Bs)
     batch = len(Af)
-    Bf = None
-    if Bs is not None:
-        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
-        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
-            raise ValueError("Bs must hold one array of A's shape per problem")
     if batch == 0:
         return [], ([] if vectors else None), np.zeros(0, dtype=np.int32)
-    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
-    ld = np.maximum(n, 1).astype(np.int32)
     w = [np.zeros(k) for k in n]
     Z = [np.zeros((k, k), order="F") for k in n] if vectors else None
     info = np.zeros(batch, dtype=np.int32)
-
-    def table(arrays):
-        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
-
-    rc = getattr(lib, name)(first, 1 if vectors else 0, batch, _I(n), table(Af), _I(ld),
-                            table(Bf) if Bf is not None else None, _I(ld), table(w),
-                            table(Z) if vectors else None, _I(ld), _I(info),
+    rc = getattr(lib, name)(first, 1 if vectors else 0, batch, _I(n), _table(Af), _I(ld),
+                            _table(Bf) if Bf is not None else None, _I(ld), _table(w),
+                            _table(Z) if vectors else None, _I(ld), _I(info),
                             _P(seconds) if seconds is not None else None)
     if rc != 0:
         raise SolverError(name + " failed", rc)
@@ -1161,24 +1168,13 @@ def _window_vbatched_call(entry, first, As, Bs, il, iu, vl, vu, vectors, zcap, s
     """ek_hip_eigenpairs_window_xvbatched / ek_hip_sygv_window_xvbatched on sequences of square arrays; `first` is the
     first argument (problem or itype); il, iu, vl, vu, zcap: None, a scalar for every problem, or a value per problem."""
     lib = load_library()
-    Af = []
-    for M in As:
-        M = np.asarray(M, dtype=np.float64)
-        if M.ndim != 2 or M.shape[0] != M.shape[1]:
-            raise ValueError("every A must be a square 2-D array")
-        Af.append(np.asfortranarray(M))
+    Af, Bf, n, ld = _square_list(As, Bs)
     batch = len(Af)
-    Bf = None
-    if Bs is not None:
-        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
-        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
-            raise ValueError("Bs must hold one array of A's shape per problem")
     by_value = vl is not None or vu is not None
     if by_value and (il is not None or iu is not None):
         raise ValueError("give either il / iu or vl / vu")
     if batch == 0:
         return [], ([] if vectors else None), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
-    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
 
     def per_problem(x, default, dtype):
         if x is None:
@@ -1195,18 +1191,13 @@ def _window_vbatched_call(entry, first, As, Bs, il, iu, vl, vu, vectors, zcap, s
     il = per_problem(il, 1, np.int32)
     iu = per_problem(iu, n, np.int32)
     zcap = per_problem(zcap, n if by_value else np.maximum(iu - il + 1, 0), np.int32)
-    ld = np.maximum(n, 1).astype(np.int32)
     w = [np.zeros(k) for k in n]
     Z = [np.zeros((n[b], max(int(zcap[b]), 0)), order="F") for b in range(batch)] if vectors else None
     m = np.zeros(batch, dtype=np.int32)
     info = np.zeros(batch, dtype=np.int32)
-
-    def table(arrays):
-        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
-
     rc = getattr(lib, entry)(first, 1 if vectors else 0, 1 if by_value else 0, batch, _I(n), _P(vl), _P(vu), _I(il),
-                             _I(iu), table(Af), _I(ld), table(Bf) if Bf is not None else None, _I(ld), _I(m), table(w),
-                             table(Z) if vectors else None, _I(ld), _I(zcap), _I(info),
+                             _I(iu), _table(Af), _I(ld), _table(Bf) if Bf is not None else None, _I(ld), _I(m), _table(w),
+                             _table(Z) if vectors else None, _I(ld), _I(zcap), _I(info),
                              _P(seconds) if seconds is not None else None)
     if rc != 0:
         raise SolverError(entry + " failed", rc)
@@ -1260,24 +1251,14 @@ def _check_batched_call(name, first, A, B, w, Z, info, ipr, seconds):
     """ek_hip_check_batched / ek_hip_check_sygv_batched on (batch, n, n) arrays; `first` is the first argument (problem or
     itype)."""
     lib = load_library()
-    A = np.asarray(A, dtype=np.float64)
-    if A.ndim != 3 or A.shape[1] != A.shape[2]:
-        raise ValueError("A must have shape (batch, n, n)")
-    batch, n = A.shape[0], A.shape[1]
+    batch, n, At, Bt = _uniform_mats(A, B)
     Z = np.asarray(Z, dtype=np.float64)
     w = np.asarray(w, dtype=np.float64)
-    if Z.shape != A.shape:
+    if Z.shape != At.shape:
         raise ValueError("Z must have the shape of A")
     if w.shape != (batch, n):
         raise ValueError("w must have shape (batch, n)")
-    Bt = None
-    if B is not None:
-        B = np.asarray(B, dtype=np.float64)
-        if B.shape != A.shape:
-            raise ValueError("B must have the shape of A")
-        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
     info = _check_info(info, batch)
-    At = np.ascontiguousarray(A.transpose(0, 2, 1))
     Zt = np.ascontiguousarray(Z.transpose(0, 2, 1))
     wc = np.ascontiguousarray(w)
     out = np.full((batch, CHECK_NOUT), np.nan)
@@ -1327,10 +1308,7 @@ def check_window_xbatched(A, B, m, w, Z, info=None, ipr=True, zcap=None, seconds
 def _check_window_call(name, first, A, B, m, w, Z, info, ipr, zcap, seconds):
     """The call behind check_window_xbatched and check_sygv_window_xbatched: `first` is the entry's first argument."""
     lib = load_library()
-    A = np.asarray(A, dtype=np.float64)
-    if A.ndim != 3 or A.shape[1] != A.shape[2]:
-        raise ValueError("A must have shape (batch, n, n)")
-    batch, n = A.shape[0], A.shape[1]
+    batch, n, At, Bt = _uniform_mats(A, B)
     Z = np.asarray(Z, dtype=np.float64)
     w = np.asarray(w, dtype=np.float64)
     if Z.ndim != 3 or Z.shape[:2] != (batch, n):
@@ -1344,14 +1322,7 @@ def _check_window_call(name, first, A, B, m, w, Z, info, ipr, zcap, seconds):
     zcap = zc if zcap is None else int(zcap)
     if zcap > zc:
         raise ValueError("zcap exceeds the columns of Z")
-    Bt = None
-    if B is not None:
-        B = np.asarray(B, dtype=np.float64)
-        if B.shape != A.shape:
-            raise ValueError("B must have the shape of A")
-        Bt = np.ascontiguousarray(B.transpose(0, 2, 1))
     info = _check_info(info, batch)
-    At = np.ascontiguousarray(A.transpose(0, 2, 1))
     Zt = np.ascontiguousarray(Z.transpose(0, 2, 1))
     wc = np.ascontiguousarray(w)
     out = np.full((batch, CHECK_NOUT), np.nan)
@@ -1416,18 +1387,8 @@ def check_sygv_xbatched(A, B, w, Z, itype=1, info=None, ipr=True, seconds=None):
 def _check_vbatched_call(name, first, As, Bs, ws, Zs, info, ipr, seconds):
     """ek_hip_check_vbatched / ek_hip_check_sygv_vbatched on sequences of arrays; `first` is the first argument."""
     lib = load_library()
-    Af = []
-    for M in As:
-        M = np.asarray(M, dtype=np.float64)
-        if M.ndim != 2 or M.shape[0] != M.shape[1]:
-            raise ValueError("every A must be a square 2-D array")
-        Af.append(np.asfortranarray(M))
+    Af, Bf, n, ld = _square_list(As, Bs)
     batch = len(Af)
-    Bf = None
-    if Bs is not None:
-        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
-        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
-            raise ValueError("Bs must hold one array of A's shape per problem")
     Zf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Zs]
     if len(Zf) != batch or any(Zf[b].shape != Af[b].shape for b in range(batch)):
         raise ValueError("Zs must hold one array of A's shape per problem")
@@ -1439,15 +1400,9 @@ def _check_vbatched_call(name, first, As, Bs, ws, Zs, info, ipr, seconds):
     q = [np.full(M.shape[0], np.nan) for M in Af] if ipr else None
     if batch == 0:
         return out, q
-    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
-    ld = np.maximum(n, 1).astype(np.int32)
-
-    def table(arrays):
-        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else None for a in arrays])
-
-    rc = getattr(lib, name)(first, batch, _I(n), table(Af), _I(ld), table(Bf) if Bf is not None else None, _I(ld),
-                            table(wf), table(Zf), _I(ld), _I(info) if info is not None else None, _P(out),
-                            table(q) if ipr else None, _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, name)(first, batch, _I(n), _table(Af), _I(ld), _table(Bf) if Bf is not None else None, _I(ld),
+                            _table(wf), _table(Zf), _I(ld), _I(info) if info is not None else None, _P(out),
+                            _table(q) if ipr else None, _P(seconds) if seconds is not None else None)
     if rc != 0:
         raise SolverError(name + " failed", rc)
     return out, q
@@ -1492,18 +1447,8 @@ def _check_window_vbatched_call(name, first, As, Bs, m, ws, Zs, info, ipr, zcap,
     """ek_hip_check_window_xvbatched / ek_hip_check_sygv_window_xvbatched on sequences of arrays; `first` is the first
     argument.  ws[b] and Zs[b] may be shorter than the order: what eigenpairs_window_xvbatched returns."""
     lib = load_library()
-    Af = []
-    for M in As:
-        M = np.asarray(M, dtype=np.float64)
-        if M.ndim != 2 or M.shape[0] != M.shape[1]:
-            raise ValueError("every A must be a square 2-D array")
-        Af.append(np.asfortranarray(M))
+    Af, Bf, n, ld = _square_list(As, Bs)
     batch = len(Af)
-    Bf = None
-    if Bs is not None:
-        Bf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Bs]
-        if len(Bf) != batch or any(Bf[b].shape != Af[b].shape for b in range(batch)):
-            raise ValueError("Bs must hold one array of A's shape per problem")
     Zf = [np.asfortranarray(np.asarray(M, dtype=np.float64)) for M in Zs]
     if len(Zf) != batch or any(Zf[b].ndim != 2 or Zf[b].shape[0] != Af[b].shape[0] for b in range(batch)):
         raise ValueError("Zs must hold one array with A's rows per problem")
@@ -1531,20 +1476,12 @@ def _check_window_vbatched_call(name, first, As, Bs, m, ws, Zs, info, ipr, zcap,
     q = [np.full(M.shape[0], np.nan) for M in Af] if ipr else None
     if batch == 0:
         return out, q
-    n = np.array([M.shape[0] for M in Af], dtype=np.int32)
-    ld = np.maximum(n, 1).astype(np.int32)
     # a problem that is checked hands over what it has; an array without an entry still needs an address where the
     # library asks for one (an order > 0): a skipped or empty problem's is never read
-    spare = np.zeros(1)
-
-    def table(arrays, need):
-        return (ctypes.c_void_p * batch)(*[a.ctypes.data if a.size else (spare.ctypes.data if need[b] else None)
-                                           for b, a in enumerate(arrays)])
-
-    rc = getattr(lib, name)(first, batch, _I(n), table(Af, n > 0), _I(ld),
-                            table(Bf, n > 0) if Bf is not None else None, _I(ld), _I(m), table(wf, n > 0),
-                            table(Zf, (n > 0) & (zcap > 0)), _I(ld), _I(zcap), _I(info) if info is not None else None,
-                            _P(out), table(q, n < 0) if ipr else None, _P(seconds) if seconds is not None else None)
+    rc = getattr(lib, name)(first, batch, _I(n), _table(Af, n > 0), _I(ld),
+                            _table(Bf, n > 0) if Bf is not None else None, _I(ld), _I(m), _table(wf, n > 0),
+                            _table(Zf, (n > 0) & (zcap > 0)), _I(ld), _I(zcap), _I(info) if info is not None else None,
+                            _P(out), _table(q) if ipr else None, _P(seconds) if seconds is not None else None)
     if rc != 0:
         raise SolverError(name + " failed", rc)
     return out, q
