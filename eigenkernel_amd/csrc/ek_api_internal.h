@@ -86,6 +86,10 @@ void release_xbatched();           // the images of ek_hip_eigenpairs_xbatched* 
 int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
                     long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
                     long long strideZ, int *dinfo);
+// ek_hip_*_ybatched*, orders above EK_HIP_XBATCH_NMAX: the same arguments, the class of 512 rows and its chunks of 256
+int ybatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
+                    long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                    long long strideZ, int *dinfo);
 // the same for `count` entries of the variable-order table (device), all of order above EK_HIP_BATCH_NMAX: chunk c
 // takes the entries [c K, c K + K) and the image slots 0 .. K-1; the status word of an entry goes to dinfo[index]
 int xvbatched_prepare(int count);  // its images (min(count, K) slots), to be called before the call's first event

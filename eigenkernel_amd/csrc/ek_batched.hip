@@ -1025,11 +1025,15 @@ static int run_window(const UniformCall &u) {
   });
 }
 
-// above EK_HIP_BATCH_NMAX (the xbatched entries only) the image in device memory: ek_batched_x.hip's kernel
+// above EK_HIP_BATCH_NMAX (the xbatched and ybatched entries only) the image in device memory: ek_batched_x.hip's kernel,
+// its class of 256 rows up to EK_HIP_XBATCH_NMAX and its class of 512 rows above (the ybatched entries only)
 static int run(const UniformCall &u) {
   if (u.win) return run_window(u);
   { int rc0 = g_dinfo.grow((size_t)u.batch); if (rc0) return rc0; }
   return run_uniform(u, [&](hipStream_t s) {
+    if (u.n > EK_HIP_XBATCH_NMAX)                    // the ybatched entries only: the class of 512 rows
+      return ybatched_launch(s, u.problem, u.itype, u.jobz, u.n, u.batch, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z,
+                             u.ldz, u.sZ, g_dinfo.p);
     if (u.n > EK_HIP_BATCH_NMAX)
       return xbatched_launch(s, u.problem, u.itype, u.jobz, u.n, u.batch, u.A, u.lda, u.sA, u.B, u.ldb, u.sB, u.w, u.Z,
                              u.ldz, u.sZ, g_dinfo.p);
@@ -1424,6 +1428,38 @@ int ek_hip_sygv_xbatched(int itype, int jobz, int n, int batch, const double *A,
   if (itype < 1 || itype > 3) return -1;
   return entry(UniformCall{1, itype, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
                            strideZ, info, seconds, nullptr}, EK_HIP_XBATCH_NMAX, true);
+}
+
+// the y entries take orders up to EK_HIP_YBATCH_NMAX: above EK_HIP_XBATCH_NMAX ek_batched_x.hip's class of 512 rows, every
+// other problem what the x entries give it
+int ek_hip_eigenpairs_ybatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                      double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                      long long strideZ, int *info, double *seconds) {
+  return entry(UniformCall{problem, 1, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, nullptr}, EK_HIP_YBATCH_NMAX, false);
+}
+
+int ek_hip_eigenpairs_ybatched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                               long long strideZ, int *info, double *seconds) {
+  return entry(UniformCall{problem, 1, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, nullptr}, EK_HIP_YBATCH_NMAX, true);
+}
+
+int ek_hip_sygv_ybatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return entry(UniformCall{1, itype, jobz, n, batch, dA, lda, strideA, dB, ldb, strideB, dw, dZ, ldz, strideZ, info,
+                           seconds, nullptr}, EK_HIP_YBATCH_NMAX, false);
+}
+
+int ek_hip_sygv_ybatched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                         const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                         long long strideZ, int *info, double *seconds) {
+  if (itype < 1 || itype > 3) return -1;
+  return entry(UniformCall{1, itype, jobz, n, batch, (double *)A, lda, strideA, (double *)B, ldb, strideB, w, Z, ldz,
+                           strideZ, info, seconds, nullptr}, EK_HIP_YBATCH_NMAX, true);
 }
 
 // problems of different orders

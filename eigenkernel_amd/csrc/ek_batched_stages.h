@@ -1,6 +1,6 @@
 // ek_batched_stages.h -- what the two kernels of the batched solver share (not installed):
 //   ek_batched.hip    orders up to EK_HIP_BATCH_NMAX, the n x n image in LDS, classes NC = 32 / 64 / 128
-//   ek_batched_x.hip  orders up to EK_HIP_XBATCH_NMAX, the image in device memory, NC = 256
+//   ek_batched_x.hip  orders up to EK_HIP_YBATCH_NMAX, the image in device memory, NC = 256 / 512
 // One workgroup of 2 NC threads (NW waves) owns a problem; thread t is (row or column r = t % NC, half sub = t / NC).
 //      gdouble, cgdouble, block_reduce
 //   0  scan_a       the lower triangle of A is read once for NaN / Inf (info -5) and for max|a|

@@ -53,6 +53,11 @@
 // ek_hip_*_xvbatched*: the same kernel for problems of different orders.  A workgroup then finds its problem in entry
 // blockIdx.x of its launch's slice of the variable-order table (ek_batched.hip builds it) instead of at blockIdx.x *
 // stride; the image slot is blockIdx.x either way.
+//
+// ek_hip_eigenpairs_ybatched*, ek_hip_sygv_ybatched*: orders EK_HIP_XBATCH_NMAX + 1 .. EK_HIP_YBATCH_NMAX.  A second class
+// of the same kernel text, NC = 512, 1024 threads, leading dimension 513: the class is a template parameter (Class below)
+// and what is said above about 256, 257 and 512 threads reads 512, 513 and 1024 for it.  One workgroup of 16 waves per
+// compute unit, chunks of 256 problems in the same workspace, the Args form alone, CONG false and true.
 #include "ek_batched_stages.h"
 #include "ek_batched_window.h"
 
@@ -64,10 +69,19 @@ namespace batchedx {
 
 using namespace bstages;
 
-constexpr int NC = 256, T = 512, LD = NC + 1, P = T / NC, NW = T / 64;
-constexpr size_t kSlot = (size_t)NC * LD;           // doubles of one image
-constexpr int kChunk = 1024;                        // problems per launch: 1024 slots are 539 MB
-static_assert(P == 2 && NC == EK_HIP_XBATCH_NMAX, "two threads per row");
+// A class of this file: NC rows, T threads, the image's leading dimension, threads per row, waves, the doubles of one
+// image and the problems of one launch.  The kernel and its helpers take the class as a template parameter and name its
+// constants as they always did
+template <int NC_, int T_, int CHUNK_>
+struct Class {
+  static constexpr int NC = NC_, T = T_, LD = NC + 1, P = T / NC, NW = T / 64;
+  static constexpr size_t kSlot = (size_t)NC * LD;
+  static constexpr int kChunk = CHUNK_;
+  static_assert(P == 2, "two threads per row");
+};
+using ClassX = Class<256, 512, 1024>;               // orders 129 .. 256: 1024 slots are 539 MB
+using ClassY = Class<512, 1024, 256>;               // orders 257 .. 512 (ek_hip_*_ybatched*): 256 slots are 538 MB
+static_assert(ClassX::NC == EK_HIP_XBATCH_NMAX && ClassY::NC == EK_HIP_YBATCH_NMAX, "the classes' orders");
 
 struct Args {
   int problem, jobz, n;
@@ -122,21 +136,24 @@ struct Problem {
   gdouble *S;
   int *info;
 };
+template <typename C>
 __device__ __forceinline__ Problem locate(const Args &a) {
   const long long pb = blockIdx.x;
   return {a.n, (gdouble *)(a.A + pb * a.sA), a.lda, a.problem ? (gdouble *)(a.B + pb * a.sB) : nullptr, a.ldb,
           (gdouble *)(a.w + pb * a.n), nullptr, a.ldz,
-          (gdouble *)(a.ws + (size_t)pb * kSlot), a.info + pb};
+          (gdouble *)(a.ws + (size_t)pb * C::kSlot), a.info + pb};
 }
+template <typename C>
 __device__ __forceinline__ Problem locate(const XVArgs &a) {
   const Desc &d = a.table[blockIdx.x];
   return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz,
-          (gdouble *)(a.ws + (size_t)blockIdx.x * kSlot), a.info + d.index};
+          (gdouble *)(a.ws + (size_t)blockIdx.x * C::kSlot), a.info + d.index};
 }
+template <typename C>
 __device__ __forceinline__ Problem locate(const XVWArgs &a) {
   const Desc &d = a.table[blockIdx.x];
   return {d.n, (gdouble *)d.A, d.lda, (gdouble *)d.B, d.ldb, (gdouble *)d.w, (gdouble *)d.Z, d.ldz,
-          (gdouble *)(a.ws + (size_t)blockIdx.x * kSlot), a.info + d.index};
+          (gdouble *)(a.ws + (size_t)blockIdx.x * C::kSlot), a.info + d.index};
 }
 // the window of stage 4W: the call's, or the workgroup's own
 __device__ __forceinline__ const bwindow::Window &window(const XWArgs &a) { return a.win; }
@@ -190,9 +207,10 @@ __device__ __forceinline__ double img_dot(const gdouble *x, const double *l, int
 // pair take every other term, each in ascending order; the sum is half 0's part plus half 1's.  The parts of an even step
 // lie in e0 / e1 (half 0's, half 1's), those of an odd step in o0 / o1, so that a step costs one barrier.  Ends behind a
 // barrier.
-template <bool LOWER>
+template <typename C, bool LOWER>
 __device__ __forceinline__ void cong_pass(gdouble *S, const gdouble *B, int ldb, int n, int t, int r, int sub, bool row,
                                           double *sl, double *e0, double *e1, double *o0, double *o1) {
+  constexpr int NC = C::NC, LD = C::LD, P = C::P;
   if (t < n) sl[t] = B[t];                          // column 0 of L
   __syncthreads();
   const int last = LOWER ? r : n - 1;
@@ -217,9 +235,12 @@ __device__ __forceinline__ void cong_pass(gdouble *S, const gdouble *B, int ldb,
 // The table-and-window instantiations are held to four waves a SIMD, that is 128 vector registers and two workgroups on a
 // compute unit like the other three argument types: left alone, one of the two came out at 129.  The attribute's value for
 // the other types, 2, is what 512 threads imply anyway, and their code is unchanged by it
-template <bool CONG, typename ARGS = Args>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(std::is_same<ARGS, XVWArgs>::value ? 4 : 2)))
+// C: the class.  ClassY's 1024 threads are four waves a SIMD, which is the attribute's value for it too
+template <bool CONG, typename ARGS = Args, typename C = ClassX>
+__global__ __launch_bounds__(C::T)
+__attribute__((amdgpu_waves_per_eu(std::is_same<ARGS, XVWArgs>::value ? 4 : C::T / 256)))
 void xbatched_kernel(ARGS a) {
+  constexpr int NC = C::NC, LD = C::LD, P = C::P, NW = C::NW;
   constexpr bool VWIN = std::is_same<ARGS, XVWArgs>::value;
   constexpr bool WIN = VWIN || std::is_same<ARGS, XWArgs>::value;
   __shared__ double sd[NC], se[NC], st[NC];         // d, e, tau: alive from stage 3 to the end
@@ -230,7 +251,7 @@ void xbatched_kernel(ARGS a) {
   __shared__ int srank[NC];
   __shared__ int s_state, s_m, s_lo;
 
-  const Problem p = locate(a);
+  const Problem p = locate<C>(a);
   const int t = threadIdx.x, n = p.n;
   const int r = t % NC, sub = t / NC;
   const bool row = r < n;
@@ -279,7 +300,7 @@ void xbatched_kernel(ARGS a) {
   if (CONG) {
     __syncthreads();
     // Y = A L: the pair r owns row r of the full image
-    cong_pass<false>(S, B, ldb, n, t, r, sub, row, sl, sp, sp + NC, sv, sw);
+    cong_pass<C, false>(S, B, ldb, n, t, r, sub, row, sl, sp, sp + NC, sv, sw);
     // Y^T = L^T A (A is symmetric): the image transposed in place
     if (row)
       for (int j = sub; j < r; j += P) {
@@ -289,7 +310,7 @@ void xbatched_kernel(ARGS a) {
       }
     __syncthreads();
     // C = Y^T L, lower half: the pair r owns row r, columns 0 .. r
-    cong_pass<true>(S, B, ldb, n, t, r, sub, row, sl, sp, sp + NC, sv, sw);
+    cong_pass<C, true>(S, B, ldb, n, t, r, sub, row, sl, sp, sp + NC, sv, sw);
     if (row)
       for (int j = sub; j < r; j += P) S[j + r * LD] = S[r + j * LD];
   } else if (a.problem) {
@@ -666,20 +687,24 @@ void xbatched_kernel(ARGS a) {
   if (t == 0) *info = 0;
 }
 
-// the images: grown, never shrunk, released in ek_hip_finalize
+// the images: grown, never shrunk, released in ek_hip_finalize.  One allocation serves both classes, counted in doubles: a
+// launch of either holds g_mu, and every call ends with a synchronise, so no two launches ever share it
 static double *g_ws = nullptr;
-static size_t g_ws_slots = 0;
-static int g_chunk = kChunk;
+static size_t g_ws_doubles = 0;
+static int g_chunk = ClassX::kChunk, g_ychunk = ClassY::kChunk;
 
-static int ensure_images(size_t slots) {
-  if (slots <= g_ws_slots) return 0;
+// room for `slots` images of `slot` doubles each
+static int ensure_images(size_t slots, size_t slot = ClassX::kSlot) {
+  const size_t need = slots * slot;
+  if (need <= g_ws_doubles) return 0;
   if (g_ws) (void)hipFree(g_ws);
   g_ws = nullptr;
-  g_ws_slots = 0;
-  EK_HIP_CHECK(hipMalloc((void **)&g_ws, slots * kSlot * sizeof(double)));
-  g_ws_slots = slots;
+  g_ws_doubles = 0;
+  EK_HIP_CHECK(hipMalloc((void **)&g_ws, need * sizeof(double)));
+  g_ws_doubles = need;
   return 0;
 }
+static bool images_hold(int slots) { return (size_t)slots * ClassX::kSlot <= g_ws_doubles; }
 
 }  // namespace batchedx
 
@@ -689,7 +714,7 @@ void release_xbatched() {
   using namespace batchedx;
   if (g_ws) (void)hipFree(g_ws);
   g_ws = nullptr;
-  g_ws_slots = 0;
+  g_ws_doubles = 0;
 }
 
 // arguments checked (EK_HIP_BATCH_NMAX < n <= EK_HIP_XBATCH_NMAX, batch > 0), g_mu held; dinfo holds `batch` words
@@ -704,8 +729,31 @@ int xbatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int 
     Args a{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
            problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
            jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, dinfo + c0, g_ws, itype};
-    if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, Args>), dim3(count), dim3(T), 0, s, a);
-    else hipLaunchKernelGGL((xbatched_kernel<false, Args>), dim3(count), dim3(T), 0, s, a);
+    if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, Args>), dim3(count), dim3(ClassX::T), 0, s, a);
+    else hipLaunchKernelGGL((xbatched_kernel<false, Args>), dim3(count), dim3(ClassX::T), 0, s, a);
+    EK_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// ek_hip_*_ybatched*: arguments checked (EK_HIP_XBATCH_NMAX < n <= EK_HIP_YBATCH_NMAX, batch > 0), g_mu held; dinfo holds
+// `batch` words.  ClassY's two instantiations of the kernel: a workgroup of 1024 threads fills a compute unit, so a chunk
+// is one round of 256 workgroups; the chunks share the slots 0 .. K-1 in the order of the stream
+int ybatched_launch(hipStream_t s, int problem, int itype, int jobz, int n, int batch, double *dA, int lda,
+                    long long strideA, double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                    long long strideZ, int *dinfo) {
+  using namespace batchedx;
+  const int K = g_ychunk;
+  { int rc0 = ensure_images((size_t)std::min(batch, K), ClassY::kSlot); if (rc0) return rc0; }
+  for (int c0 = 0; c0 < batch; c0 += K) {
+    const int count = std::min(K, batch - c0);
+    Args a{problem, jobz, n, dA + (long long)c0 * strideA, lda, strideA,
+           problem ? dB + (long long)c0 * strideB : nullptr, ldb, strideB, dw + (long long)c0 * n,
+           jobz ? dZ + (long long)c0 * strideZ : nullptr, ldz, strideZ, dinfo + c0, g_ws, itype};
+    if (problem && itype != 1)
+      hipLaunchKernelGGL((xbatched_kernel<true, Args, ClassY>), dim3(count), dim3(ClassY::T), 0, s, a);
+    else
+      hipLaunchKernelGGL((xbatched_kernel<false, Args, ClassY>), dim3(count), dim3(ClassY::T), 0, s, a);
     EK_HIP_CHECK(hipGetLastError());
   }
   return 0;
@@ -732,12 +780,12 @@ int xwindow_launch(hipStream_t s, int problem, int itype, int jobz, int n, int c
                    long long strideZ, int *dinfo, int range, int il, int iu, int zcap, double vl, double vu, int *dm,
                    double *lu, int wcols) {
   using namespace batchedx;
-  if ((size_t)count > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
+  if (!images_hold(count)) return -1000 - (int)hipErrorInvalidValue;
   XWArgs a{{problem, jobz, n, dA, lda, strideA, problem ? dB : nullptr, ldb, strideB, dw, jobz ? dZ : nullptr, ldz,
             strideZ, dinfo, g_ws, itype},
            {range, il, iu, zcap, vl, vu, dm, lu, wcols}};
-  if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XWArgs>), dim3(count), dim3(T), 0, s, a);
-  else hipLaunchKernelGGL((xbatched_kernel<false, XWArgs>), dim3(count), dim3(T), 0, s, a);
+  if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XWArgs>), dim3(count), dim3(ClassX::T), 0, s, a);
+  else hipLaunchKernelGGL((xbatched_kernel<false, XWArgs>), dim3(count), dim3(ClassX::T), 0, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -749,10 +797,10 @@ int xwindow_launch(hipStream_t s, int problem, int itype, int jobz, int n, int c
 int xvwindow_launch(hipStream_t s, int problem, int itype, int jobz, int range, int count, const batched::Desc *table,
                     const batched::WDesc *wtable, int *dinfo, int *dm, double *lu) {
   using namespace batchedx;
-  if ((size_t)count > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
+  if (!images_hold(count)) return -1000 - (int)hipErrorInvalidValue;
   XVWArgs a{problem, jobz, table, wtable, dinfo, dm, g_ws, lu, range, itype};
-  if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XVWArgs>), dim3(count), dim3(T), 0, s, a);
-  else hipLaunchKernelGGL((xbatched_kernel<false, XVWArgs>), dim3(count), dim3(T), 0, s, a);
+  if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XVWArgs>), dim3(count), dim3(ClassX::T), 0, s, a);
+  else hipLaunchKernelGGL((xbatched_kernel<false, XVWArgs>), dim3(count), dim3(ClassX::T), 0, s, a);
   EK_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -764,12 +812,12 @@ int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count,
                      int *dinfo) {
   using namespace batchedx;
   const int K = g_chunk;
-  if ((size_t)std::min(count, K) > g_ws_slots) return -1000 - (int)hipErrorInvalidValue;
+  if (!images_hold(std::min(count, K))) return -1000 - (int)hipErrorInvalidValue;
   for (int c0 = 0; c0 < count; c0 += K) {
     const int chunk = std::min(K, count - c0);
     XVArgs a{problem, jobz, table + c0, dinfo, g_ws, itype};
-    if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XVArgs>), dim3(chunk), dim3(T), 0, s, a);
-    else hipLaunchKernelGGL((xbatched_kernel<false, XVArgs>), dim3(chunk), dim3(T), 0, s, a);
+    if (problem && itype != 1) hipLaunchKernelGGL((xbatched_kernel<true, XVArgs>), dim3(chunk), dim3(ClassX::T), 0, s, a);
+    else hipLaunchKernelGGL((xbatched_kernel<false, XVArgs>), dim3(chunk), dim3(ClassX::T), 0, s, a);
     EK_HIP_CHECK(hipGetLastError());
   }
   return 0;
@@ -781,6 +829,13 @@ int xvbatched_launch(hipStream_t s, int problem, int itype, int jobz, int count,
 extern "C" int ek_hip_debug_xbatched_chunk(int problems) {
   std::lock_guard<std::mutex> lk(ek::api::g_mu);
   const int before = ek::batchedx::g_chunk;
-  ek::batchedx::g_chunk = problems > 0 ? problems : ek::batchedx::kChunk;
+  ek::batchedx::g_chunk = problems > 0 ? problems : ek::batchedx::ClassX::kChunk;
+  return before;
+}
+
+extern "C" int ek_hip_debug_ybatched_chunk(int problems) {
+  std::lock_guard<std::mutex> lk(ek::api::g_mu);
+  const int before = ek::batchedx::g_ychunk;
+  ek::batchedx::g_ychunk = problems > 0 ? problems : ek::batchedx::ClassY::kChunk;
   return before;
 }

@@ -196,6 +196,15 @@ def load_library(path=None):
         "ek_hip_sygv_xbatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
                                          c_ll, _ip, _dp]),
         "ek_hip_debug_xbatched_chunk": (c_int, [c_int]),
+        "ek_hip_eigenpairs_ybatched_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp,
+                                                      vp, c_int, c_ll, _ip, _dp]),
+        "ek_hip_eigenpairs_ybatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp,
+                                               _dp, c_int, c_ll, _ip, _dp]),
+        "ek_hip_sygv_ybatched_device": (c_int, [c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp,
+                                                c_int, c_ll, _ip, _dp]),
+        "ek_hip_sygv_ybatched": (c_int, [c_int, c_int, c_int, c_int, _dp, c_int, c_ll, _dp, c_int, c_ll, _dp, _dp, c_int,
+                                         c_ll, _ip, _dp]),
+        "ek_hip_debug_ybatched_chunk": (c_int, [c_int]),
         "ek_hip_eigenpairs_window_batched_device": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int, c_int,
                                                             vp, c_int, c_ll, vp, c_int, c_ll, _ip, vp, vp, c_int, c_int,
                                                             c_ll, _ip, _dp]),
@@ -348,6 +357,8 @@ EXPORTED_SYMBOLS = (
     "ek_hip_check_sygv_window_xbatched_device", "ek_hip_check_sygv_window_xbatched",
     "ek_hip_check_window_xvbatched_device", "ek_hip_check_window_xvbatched",
     "ek_hip_check_sygv_window_xvbatched_device", "ek_hip_check_sygv_window_xvbatched",
+    "ek_hip_eigenpairs_ybatched_device", "ek_hip_eigenpairs_ybatched", "ek_hip_sygv_ybatched_device",
+    "ek_hip_sygv_ybatched", "ek_hip_debug_ybatched_chunk",
 )
 
 
@@ -1104,6 +1115,34 @@ def sygv_xbatched(A, B, itype=1, vectors=True, seconds=None):
     if B is None:
         raise ValueError("B is required")
     return _batched_call("ek_hip_sygv_xbatched", int(itype), A, B, vectors, seconds)
+
+
+YBATCH_NMAX = 512   # EK_HIP_YBATCH_NMAX
+
+
+def eigenpairs_ybatched(A, B=None, vectors=True, seconds=None):
+    """eigenpairs_xbatched for orders up to YBATCH_NMAX (ek_hip_eigenpairs_ybatched): the same arguments, returns and
+    errors.  Orders up to XBATCH_NMAX give eigenpairs_xbatched's bits; above it a class of 512 rows of the same kernel
+    runs, 256 problems a launch.  An order beyond YBATCH_NMAX raises SolverError with info -3."""
+    return _batched_call("ek_hip_eigenpairs_ybatched", 0 if B is None else 1, A, B, vectors, seconds)
+
+
+def sygv_ybatched(A, B, itype=1, vectors=True, seconds=None):
+    """sygv_xbatched for orders up to YBATCH_NMAX (ek_hip_sygv_ybatched): the same arguments, returns and errors.  Orders
+    up to XBATCH_NMAX give sygv_xbatched's bits; above it itype 1 is eigenpairs_ybatched(A, B) to the bit and types 2 and
+    3 run that kernel class with the reduction and the recovery of the type.  A missing B or an itype outside 1 .. 3
+    raises ValueError before the library is called; an order beyond YBATCH_NMAX raises SolverError with info -3."""
+    if itype not in (1, 2, 3):
+        raise ValueError("itype must be 1, 2 or 3")
+    if B is None:
+        raise ValueError("B is required")
+    return _batched_call("ek_hip_sygv_ybatched", int(itype), A, B, vectors, seconds)
+
+
+def ybatched_chunk(problems):
+    """Problems per launch of eigenpairs_ybatched and sygv_ybatched above XBATCH_NMAX (ek_hip_debug_ybatched_chunk): 0
+    restores the default of 256.  Returns the previous value.  No result depends on it."""
+    return int(load_library().ek_hip_debug_ybatched_chunk(int(problems)))
 
 
 def _vbatched_call(name, first, As, Bs, vectors, seconds):

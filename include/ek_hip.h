@@ -526,6 +526,43 @@ int ek_hip_sygv_xbatched(int itype, int jobz, int n, int batch, const double *A,
                          const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
                          long long strideZ, int *info, double *seconds);
 
+/* The same calls for orders up to EK_HIP_YBATCH_NMAX ("ybatched").  Argument for argument these are
+ * ek_hip_eigenpairs_xbatched* and ek_hip_sygv_xbatched* -- 16 arguments, the same argument-error codes decided before any
+ * device work and without dereferencing a data pointer, the first offending argument deciding (-1 for an itype outside
+ * 1 .. 3 before everything else, B always required in the sygv form) -- with one difference: -3 is for n < 0 or
+ * n > EK_HIP_YBATCH_NMAX.
+ *   0 <= n <= EK_HIP_XBATCH_NMAX : forwarded to the code behind the xbatched entries: the same bits in info, w, Z, dA, dB
+ *   EK_HIP_XBATCH_NMAX < n <= EK_HIP_YBATCH_NMAX : a second class of the xbatched kernel (512 rows, 1024 threads, two
+ *                   threads per row, the image with leading dimension 513 in the device workspace) runs the same stages
+ *                   with the same arithmetic rules and ownership maps; ek_hip_sygv_ybatched*(itype = 1) is
+ *                   ek_hip_eigenpairs_ybatched*(problem = 1) to the bit, types 2 and 3 run the instantiation with the
+ *                   reduction C = L^T A L
+ * The whole contract of ek_hip_eigenpairs_xbatched* and ek_hip_sygv_xbatched* holds at the new orders: the info codes;
+ * scaling taken from A alone; the device form IN PLACE (DSYTD2's lower layout in dA, L in dB); strictly upper triangles,
+ * rows n .. ld-1 and gaps never read or written; a failed problem touches only its own slots; the same bits alone, at any
+ * position of any batch, in any chunk, in the host and the device form; types 2 and 3 share w and dA bit for bit and
+ * Z3 = B Z2 to rounding; jobz = 0 returns the bits of jobz = 1 in w and dA.
+ * A batch of an order above EK_HIP_XBATCH_NMAX runs in chunks of at most 256 problems (one workgroup of 1024 threads per
+ * compute unit; ek_hip_debug_ybatched_chunk), launched one after the other on one stream without a host synchronise.
+ * Workspace: batch ints, and for orders above EK_HIP_XBATCH_NMAX min(batch, 256) images of 512 x 513 doubles (2 101 248
+ * bytes each, 538 MB for 256 problems or more) of device memory.  It is the allocation of ek_hip_eigenpairs_xbatched*,
+ * sized in bytes for whichever class asked for more: grown on demand, kept until ek_hip_finalize.
+ * The xbatched and batched entries keep answering -3 where they did.  Not at these orders: the variable-order form, the
+ * windows and the batched checks (ek_hip_check*, ek_hip_check_sygvx_device take any order, one problem a call). */
+#define EK_HIP_YBATCH_NMAX 512
+int ek_hip_eigenpairs_ybatched_device(int problem, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                      double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                      long long strideZ, int *info, double *seconds);
+int ek_hip_eigenpairs_ybatched(int problem, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                               const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                               long long strideZ, int *info, double *seconds);
+int ek_hip_sygv_ybatched_device(int itype, int jobz, int n, int batch, double *dA, int lda, long long strideA,
+                                double *dB, int ldb, long long strideB, double *dw, double *dZ, int ldz,
+                                long long strideZ, int *info, double *seconds);
+int ek_hip_sygv_ybatched(int itype, int jobz, int n, int batch, const double *A, int lda, long long strideA,
+                         const double *B, int ldb, long long strideB, double *w, double *Z, int ldz,
+                         long long strideZ, int *info, double *seconds);
+
 /* A WINDOW of eigenpairs of DSYGV's three problem types, per problem of a batch -- what itype is to rocSOLVER's
  * sygvdx_strided_batched, and what ek_hip_sygv_batched* are to ek_hip_eigenpairs_batched*, for
  * ek_hip_eigenpairs_window_batched* / ek_hip_eigenpairs_window_xbatched*.  The 23 arguments of those entries with problem

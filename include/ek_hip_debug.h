@@ -170,6 +170,10 @@ int ek_hip_debug_xvbatched_last(double *class_seconds, int *class_count);
    each chunk reusing the same image slots).  0 (or less) restores the default of 1024; returns the previous value.  A
    tuning and test hook: no result depends on it. */
 int ek_hip_debug_xbatched_chunk(int problems);
+/* ek_hip_eigenpairs_ybatched* and ek_hip_sygv_ybatched*, orders above EK_HIP_XBATCH_NMAX: problems per launch (a batch runs
+   in chunks of that many, each chunk reusing the same image slots).  0 (or less) restores the default of 256; returns the
+   previous value.  A tuning and test hook: no result depends on it. */
+int ek_hip_debug_ybatched_chunk(int problems);
 /* ek_hip_eigenpairs_window_batched*: problems per launch (a batch runs in chunks of that many, each chunk reusing the same
    slots of the inverse iteration's LU workspace).  0 (or less) restores the default of 1024; returns the previous value.
    A tuning and test hook: no result depends on it. */

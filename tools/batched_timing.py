@@ -6,7 +6,9 @@ loop over ek_hip_solve_device.  Device-resident arrays both ways, one process (t
                                                  --itype 2 / 3: the generalized rows solve A B x = l x / B A x = l x
                                                  through ek_hip_sygv_batched_device (the loop stays type 1's: a yardstick)
                                                  sizes above 128 (up to 256) time ek_hip_eigenpairs_xbatched_device
-                                                 (--itype 2 / 3: ek_hip_sygv_xbatched_device) against the same host loop
+                                                 (--itype 2 / 3: ek_hip_sygv_xbatched_device) against the same host loop;
+                                                 sizes above 256 (up to 512) ek_hip_eigenpairs_ybatched_device
+                                                 (ek_hip_sygv_ybatched_device); --check, --window and --mixed stop at 256
   python tools/batched_timing.py --once 64g      one batched call (256 generalized pairs of order 64 with vectors)
                                                  after a warm-up: what a kernel trace should look at
   python tools/batched_timing.py --mixed [--mixed-batch 2048] [--mixed-orders 8,128]
@@ -126,7 +128,11 @@ class Case:
         sec = ctypes.c_double(0.0)
         t0 = time.perf_counter()
         fn, first = self.lib.ek_hip_eigenpairs_batched_device, problem
-        if n > solver.BATCH_NMAX:                   # orders 129 .. 256: the image in device memory
+        if n > solver.XBATCH_NMAX:                  # orders 257 .. 512: the class of 512 rows
+            fn = self.lib.ek_hip_eigenpairs_ybatched_device
+            if problem and self.itype != 1:
+                fn, first = self.lib.ek_hip_sygv_ybatched_device, self.itype
+        elif n > solver.BATCH_NMAX:                 # orders 129 .. 256: the image in device memory
             fn = self.lib.ek_hip_eigenpairs_xbatched_device
             if problem and self.itype != 1:
                 fn, first = self.lib.ek_hip_sygv_xbatched_device, self.itype

@@ -3,7 +3,9 @@
 thread, __syncthreads() as a barrier and __shared__ as static storage; one problem per run (tools, not product).
 
   python tools/xbatched_host_emulation.py [--n 129] [--problem 1] [--itype 1|2|3] [--table] [--tsan] [--stop 0|1|2]
-                                          [--window IL,IU | --vl X --vu Y] [--case random|all_equal]
+                                          [--window IL,IU | --vl X --vu Y] [--case random|all_equal] [--class 256|512]
+      --class  512: the class of 512 rows and 1024 threads (ek_hip_*_ybatched*, orders 257 .. 512); it has
+               the uniform instantiations alone, so no --table and no window.  1024 OS threads: slow above order 300
       --window the window instantiation (ek_hip_eigenpairs_window_xbatched*): the pairs IL .. IU (1-based)
                by stage 4W -- bisection, inverse iteration on the rows of the image -- and stage 5 on those rows
       --vl, --vu  the same by value: the pairs in (vl, vu]; a missing bound is infinite
@@ -42,11 +44,14 @@ ap.add_argument("--window", default=None)
 ap.add_argument("--vl", type=float, default=None)
 ap.add_argument("--vu", type=float, default=None)
 ap.add_argument("--case", default="random", choices=("random", "all_equal"))
+ap.add_argument("--class", dest="cls", type=int, default=256, choices=(256, 512))
 args = ap.parse_args()
 by_value = args.vl is not None or args.vu is not None
 window = args.window is not None or by_value
 assert not (args.window and by_value), "--window or --vl / --vu"
 assert not window or not args.stop, "the window: --stop 0"
+assert args.cls == 256 or not (window or args.table), "--class 512: the uniform call alone"
+assert 0 < args.n <= args.cls, "--n within the class"
 assert args.itype == 1 or (args.problem == 1 and args.stop != 1), "--itype 2|3: problem 1, and --stop 0 or 2"
 CSRC = os.path.join(ROOT, "eigenkernel_amd", "csrc")
 src = open(os.path.join(CSRC, "ek_batched_x.hip")).read()
@@ -82,6 +87,7 @@ hdr = r'''
 #include <cstdint>
 #include <type_traits>
 #define EK_HIP_XBATCH_NMAX 256
+#define EK_HIP_YBATCH_NMAX 512
 #define __global__
 #define __device__
 #define __forceinline__ inline
@@ -91,7 +97,7 @@ hdr = r'''
 struct Idx { int x; };
 static thread_local Idx threadIdx, blockIdx;
 static std::barrier<> *g_bar;
-static double g_xch[512]; static int g_or;
+static double g_xch[1024]; static int g_or;
 static inline void __syncthreads() { g_bar->arrive_and_wait(); }
 static inline int __syncthreads_or(int v) { if (threadIdx.x == 0) g_or = 0; g_bar->arrive_and_wait(); if (v) __atomic_store_n(&g_or, 1, __ATOMIC_RELAXED); g_bar->arrive_and_wait(); int r = g_or; g_bar->arrive_and_wait(); return r; }
 static inline int __syncthreads_and(int v) { return !__syncthreads_or(!v); }
@@ -112,11 +118,12 @@ src += r'''
 }  // namespace batchedx
 }  // namespace ek
 using namespace ek::batchedx;
+using CL = @CLASS@;                                 // the class under test
 int main(int argc, char **argv) {
   const int n = argc > 1 ? atoi(argv[1]) : 129, problem = argc > 2 ? atoi(argv[2]) : 1;
   const int itype = argc > 3 ? atoi(argv[3]) : 1;
   const bool cong = problem && itype != 1;
-  std::vector<double> A((size_t)n * n), B((size_t)n * n), Z((size_t)n * n, -7.0), w(n, -7.0), ws(kSlot, NAN);
+  std::vector<double> A((size_t)n * n), B((size_t)n * n), Z((size_t)n * n, -7.0), w(n, -7.0), ws(CL::kSlot, NAN);
   unsigned long long s = 12345 + n;
   auto rnd = [&]() { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return ((double)(s >> 11) / 9007199254740992.0) * 2.0 - 1.0; };
   for (int j = 0; j < n; ++j)
@@ -146,11 +153,11 @@ int main(int argc, char **argv) {
     XVWArgs xvw{problem, 1, &wd, &ww, winfos, ms, ws.data(), lu.data(), range, itype};
     XWArgs xw{{problem, 1, n, A.data(), n, (long long)n * n, B.data(), n, (long long)n * n, w.data(), Z.data(), n, (long long)n * n, &winfo, ws.data(), itype},
               {range, il, iu, zcap, vl, vu, &m, lu.data(), zcap}};
-    std::barrier<> wbar(T);
+    std::barrier<> wbar(ClassX::T);
     g_bar = &wbar;
     for (int q = 0; q < 256; ++q) g_pair[q] = new std::barrier<>(2);
     std::vector<std::thread> wth;
-    for (int t = 0; t < T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (table) { if (cong) xbatched_kernel<true>(xvw); else xbatched_kernel<false>(xvw); } else if (cong) xbatched_kernel<true>(xw); else xbatched_kernel<false>(xw); });
+    for (int t = 0; t < ClassX::T; ++t) wth.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (table) { if (cong) xbatched_kernel<true>(xvw); else xbatched_kernel<false>(xvw); } else if (cong) xbatched_kernel<true>(xw); else xbatched_kernel<false>(xw); });
     for (auto &x : wth) x.join();
     if (table) {
       m = ms[2]; winfo = winfos[2];
@@ -214,10 +221,10 @@ int main(int argc, char **argv) {
   Desc d{A.data(), problem ? B.data() : nullptr, w.data(), Z.data(), n, n, n, n, 2, 0};
   XVArgs v{problem, 1, &d, infos, ws.data(), itype};
   g_stop2 = getenv("STOP2") ? atoi(getenv("STOP2")) : 0;
-  std::barrier<> bar(T);
+  std::barrier<> bar(CL::T);
   g_bar = &bar;
   std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) th.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (table) { if (cong) xbatched_kernel<true>(v); else xbatched_kernel<false>(v); } else if (cong) xbatched_kernel<true>(a); else xbatched_kernel<false>(a); });
+  for (int t = 0; t < CL::T; ++t) th.emplace_back([&, t]() { threadIdx.x = t; blockIdx.x = 0; if (table) { if (cong) xbatched_kernel<true>(v); else xbatched_kernel<false>(v); } else if (cong) xbatched_kernel<true, Args, CL>(a); else xbatched_kernel<false, Args, CL>(a); });
   for (auto &x : th) x.join();
   if (table && (infos[0] != 777 || infos[1] != 777)) { printf("a status word outside the entry's index was written\n"); return 1; }
   if (g_stop2) {
@@ -236,10 +243,10 @@ int main(int argc, char **argv) {
     if (g_stop2 == 1) for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) C[i + (size_t)j * n] = X[j + (size_t)i * n];
     }
     double worst = 0; int wi = -1, wj = -1, bad = 0;
-    for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) { if (g_stop2 == 2 && i < j) continue; double e = std::fabs(ws[i + (size_t)j * LD] - C[i + (size_t)j * n]); if (e != 0.0) ++bad; if (e > worst) { worst = e; wi = i; wj = j; } }
+    for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) { if (g_stop2 == 2 && i < j) continue; double e = std::fabs(ws[i + (size_t)j * CL::LD] - C[i + (size_t)j * n]); if (e != 0.0) ++bad; if (e > worst) { worst = e; wi = i; wj = j; } }
     printf("%s: worst |image - reference| = %.3e at (%d, %d), %d entries differ in their bits\n", g_stop2 == 1 ? "after X = L^-1 A (all entries, against X^T)" : cong ? "after stage 2 (lower triangle, against L^T A L)" : "after stage 2 (lower triangle, against C)", worst, wi, wj, bad);
     int shown = 0;
-    for (int j = 0; j < n && shown < 12; ++j) for (int i = 0; i < n && shown < 12; ++i) if (!(g_stop2 == 2 && i < j) && ws[i + (size_t)j * LD] != C[i + (size_t)j * n]) { printf("  (%d, %d): %.6e vs %.6e\n", i, j, ws[i + (size_t)j * LD], C[i + (size_t)j * n]); ++shown; }
+    for (int j = 0; j < n && shown < 12; ++j) for (int i = 0; i < n && shown < 12; ++i) if (!(g_stop2 == 2 && i < j) && ws[i + (size_t)j * CL::LD] != C[i + (size_t)j * n]) { printf("  (%d, %d): %.6e vs %.6e\n", i, j, ws[i + (size_t)j * CL::LD], C[i + (size_t)j * n]); ++shown; }
     return bad ? 1 : 0;
   }
   // residual and orthogonality on the host
@@ -293,7 +300,7 @@ int main(int argc, char **argv) {
 '''
 work = tempfile.mkdtemp(prefix="xbatched_emu_")
 cpp, exe = os.path.join(work, "emu.cpp"), os.path.join(work, "emu")
-open(cpp, "w").write(src)
+open(cpp, "w").write(src.replace("@CLASS@", "ClassX" if args.cls == 256 else "ClassY"))
 flags = ["-O1", "-g", "-fsanitize=thread"] if args.tsan else ["-O2"]
 subprocess.check_call(["g++", "-std=c++20", "-pthread", "-ffp-contract=off"] + flags + [cpp, "-o", exe])
 env = dict(os.environ)
