@@ -748,8 +748,14 @@ int ek_hip_residual_device(int problem, int n, int n_check, const double *dA, in
   if (problem != 0 && problem != 1) return -1;
   if (n < 0) return -2;
   if (n_check < 0 || n_check > n) return -3;
+  const int ldmin = n > 1 ? n : 1;
   if (n > 0 && !dA) return -4;
+  if (lda < ldmin) return -5;
   if (problem == 1 && n > 0 && !dB) return -6;
+  if (problem == 1 && ldb < ldmin) return -7;          // not for problem 0: callers pass any ldb beside a NULL B
+  if (n_check > 0 && !dw) return -8;
+  if (n_check > 0 && !dZ) return -9;
+  if (ldz < ldmin) return -10;
   int rc = ensure_init(); if (rc) return rc;
   if (n == 0 || n_check == 0) return 0;
   std::lock_guard<std::mutex> lk(g_mu);
@@ -775,6 +781,9 @@ int ek_hip_orthogonality_device(int problem, int n, int index1, int index2, cons
   if (index1 < 1 || index1 > n) return -3;
   if (index2 < index1 || index2 > n) return -4;
   if (problem == 1 && !dB) return -5;
+  if (problem == 1 && ldb < n) return -6;
+  if (!dZ) return -7;
+  if (ldz < n) return -8;                              // n >= 1 here
   int rc = ensure_init(); if (rc) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
   hipStream_t s = g_ctx.stream;
@@ -796,7 +805,11 @@ int ek_hip_ipratios_device(int problem, int n, int n_vec, const double *dB, int 
   if (problem != 0 && problem != 1) return -1;
   if (n < 0) return -2;
   if (n_vec < 0 || n_vec > n) return -3;
+  const int ldmin = n > 1 ? n : 1;
   if (problem == 1 && n > 0 && !dB) return -4;
+  if (problem == 1 && ldb < ldmin) return -5;
+  if (n_vec > 0 && !dZ) return -6;
+  if (ldz < ldmin) return -7;
   int rc = ensure_init(); if (rc) return rc;
   if (n == 0 || n_vec == 0) return 0;
   std::lock_guard<std::mutex> lk(g_mu);

@@ -39,20 +39,26 @@ __global__ void scale_cols_kernel(int m, int n, double *R, int ldr, const double
   for (int j = blockIdx.y; j < n; j += gridDim.y) R[(size_t)i + (size_t)j * ldr] *= -w[j];
 }
 
-// result[0] = sum, result[1] = max of sqrt(v[j]) over j < n; result[2] = sqrt(sum_j a[j])
+// result[0] = sum, result[1] = max of sqrt(v[j]) over j < n (a NaN is kept); result[2] = sqrt(sum_j a[j])
 __global__ __launch_bounds__(256) void finish_residual_kernel(int n, const double *__restrict__ colsq,
                                                               int na, const double *__restrict__ asq,
                                                               double *result) {
   __shared__ double red[4];
   __shared__ double mx[256];
   double s = 0.0, m = 0.0, a = 0.0;
-  for (int j = threadIdx.x; j < n; j += 256) { const double r = sqrt(colsq[j]); s += r; m = fmax(m, r); }
+  for (int j = threadIdx.x; j < n; j += 256) { const double r = sqrt(colsq[j]); s += r; m = (r > m || r != r) ? r : m; }
   for (int j = threadIdx.x; j < na; j += 256) a += asq[j];
   s = wg_sum(s, red);
   a = wg_sum(a, red);
   mx[threadIdx.x] = m;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) mx[threadIdx.x] = fmax(mx[threadIdx.x], mx[threadIdx.x + o]); __syncthreads(); }
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double y = mx[threadIdx.x + o], x = mx[threadIdx.x];
+      mx[threadIdx.x] = (y > x || y != y) ? y : x;
+    }
+    __syncthreads();
+  }
   if (threadIdx.x == 0) { result[0] = s; result[1] = mx[0]; result[2] = sqrt(a); }
 }
 

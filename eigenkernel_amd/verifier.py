@@ -7,7 +7,9 @@
 
 numpy on gathered arrays (1x1 grid); the normalisations are the reference's, including the
 quirk that the orthogonality check normalises by the computed G_jj instead of comparing
-with 1.
+with 1.  Products and sums of squares are float64, as the kernels form them; the square roots, reciprocals and
+divisions that follow them in eval_residual_norm and eval_orthogonality run in long double and are rounded once, so that
+on data whose sums are exact the mirror returns the correctly rounded value (tests/test_verify_cases_host.py).
 
 The *_sygv functions carry them over to DSYGV's types 2 (A B x = l x) and 3 (B A x = l x), as
 include/ek_hip.h defines them for ek_hip_check_sygv_*batched* and ek_hip_check_sygvx*; itype 1
@@ -16,15 +18,33 @@ forwards to the functions above.  A and B are symmetric by their lower triangles
 import numpy as np
 
 
+_L = np.longdouble      # the last square roots and divisions: one rounding to float64 at the very end
+
+
 def eval_residual_norm(A, values, V, B=None):
     A = np.asarray(A)
     V = np.asarray(V)
     n_check = V.shape[1]
-    a_norm = np.linalg.norm(A, "fro")
     R = (B @ V if B is not None else V.copy()) * (-np.asarray(values)[:n_check])
     R += A @ V
-    norms = np.linalg.norm(R, axis=0)
-    return a_norm, norms.sum() / a_norm / n_check, norms.max() / a_norm
+    # float64 products and sums of squares, as the kernels form them; what follows them in long double, so that on
+    # exact data the result is the correctly rounded value
+    a_norm = np.sqrt(_L((A * A).sum()))
+    norms = np.sqrt((R * R).sum(axis=0).astype(_L))
+    return np.float64(a_norm), np.float64(norms.sum() / a_norm / n_check), np.float64(norms.max() / a_norm)
+
+
+def _scaled_offdiagonal_norm(G):
+    """|| D^-1/2 G D^-1/2 with zero diagonal ||_F, D = diag(G): the scaling and the sum in long double, by column blocks"""
+    d = np.diag(G).astype(_L)
+    s = 1 / np.sqrt(d)
+    total = _L(0)
+    for c in range(0, G.shape[1], 256):
+        blk = G[:, c:c + 256].astype(_L) * s[:, None] * s[None, c:c + 256]
+        k = np.arange(c, c + blk.shape[1])
+        blk[k, k - c] = 0
+        total += (blk * blk).sum()
+    return np.float64(np.sqrt(total))
 
 
 def eval_orthogonality(V, B=None, index1=1, index2=None):
@@ -32,10 +52,7 @@ def eval_orthogonality(V, B=None, index1=1, index2=None):
     index2 = V.shape[1] if index2 is None else index2
     Vs = V[:, index1 - 1:index2]
     G = Vs.T @ (B @ Vs if B is not None else Vs)
-    s = 1.0 / np.sqrt(np.diag(G))
-    G = G * s[:, None] * s[None, :]
-    np.fill_diagonal(G, 0.0)
-    return np.linalg.norm(G, "fro")
+    return _scaled_offdiagonal_norm(G)
 
 
 def get_ipratios(V, S=None):

@@ -1223,7 +1223,22 @@ int ek_hip_synth_matrix_device(int n, unsigned long long seed, double *dM, int l
  *   residual      verifier.f90:75-204   A_norm = ||A||_F, res_ave = sum_j||A v_j - l_j B v_j||/A_norm/n_check,
  *                                       res_max = max_j ||.|| / A_norm   (first n_check columns)
  *   orthogonality verifier.f90:233-330  ||D^-1/2 (V^T B V) D^-1/2 - diag||_F over columns index1..index2 (1-based)
- *   ipratios      distribute_matrix.f90:18-78  sum_i v_ij^4 / (sum_i v_ij (S v)_ij)^2, j < n_vec (host output) */
+ *   ipratios      distribute_matrix.f90:18-78  sum_i v_ij^4 / (sum_i v_ij (S v)_ij)^2, j < n_vec (host output)
+ * Divisions are plain IEEE and the maximum keeps a NaN, as in the batched entries: NaN or Inf in w or in a column of Z
+ * that a call looks at shows in that call's outputs (a NaN in w[j]: res_ave AND res_max are NaN, the orthogonality and the
+ * IPRs are untouched; a zero column j of Z: the orthogonality and ipr[j] are NaN; A = 0: a_norm = 0, Inf or NaN in the
+ * residual slots), and the call still returns 0.  Never read: the strictly upper triangles of A and B and their rows
+ * n .. ld-1 (A and B are copied to compact symmetric images before any product), w from n_check on, the rows n .. ldz-1
+ * of Z, and the columns of Z outside the checked range (j >= n_check; outside index1 .. index2; j >= n_vec).  dB and ldb
+ * are not looked at for problem 0.  Every input is const.  Reductions have a fixed order: equal input, equal bits.
+ * Argument errors, -k for argument k of the prototype, decided before any device work, the first offender deciding:
+ *   residual       -1 problem, -2 n < 0, -3 n_check outside 0 .. n, -4 dA NULL (n > 0), -5 lda < max(1, n), -6 dB NULL and
+ *                  -7 ldb < max(1, n) (problem 1 only), -8 dw NULL and -9 dZ NULL (n_check > 0), -10 ldz < max(1, n)
+ *   orthogonality  -1 problem, -2 n < 0, -3 index1 outside 1 .. n (so n = 0 gives -3), -4 index2 outside index1 .. n,
+ *                  -5 dB NULL and -6 ldb < n (problem 1 only), -7 dZ NULL, -8 ldz < n
+ *   ipratios       -1 problem, -2 n < 0, -3 n_vec outside 0 .. n, -4 dB NULL and -5 ldb < max(1, n) (problem 1 only),
+ *                  -6 dZ NULL (n_vec > 0), -7 ldz < max(1, n)
+ * n = 0 (residual, ipratios) or a count of 0: 0, no output written. */
 int ek_hip_residual_device(int problem, int n, int n_check, const double *dA, int lda,
                            const double *dB, int ldb, const double *dw, const double *dZ, int ldz,
                            double *a_norm, double *res_ave, double *res_max);
